@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: TB evaluations/sec (profile x channel x angle) on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config 3|2]
+    python bench.py --gpus N --steps K --warmup W [--config 3|2] [--dump-outputs DIR] [--full]
 
 A step = one pass of the hot path (mwrt_tb_batch_device: absorption + optical depth + RTE, one
 fused HIP kernel) over one batch of synthetic radiosonde profiles already resident in HBM.
@@ -14,6 +14,11 @@ bucket's gather is exposed -- every batch is gathered inside the timed region, n
 torch.distributed.run; `python bench.py --gpus N` WITHOUT a launcher starts that launcher itself,
 in a child process, before anything here touches a GPU -- it never measures one GPU and calls it N.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up (W steps, then the --spinup launches), times the K steps and prints the line.
+--full adds what the headline does not need: the cold-start timing of the same K steps before the spin-up, the
+CPU baselines and the parity spot check against the C oracle.  --dump-outputs DIR writes the last timed step's
+results as DIR/<name>.npy (inputs are seeded: the same arguments give the same inputs on every run).
 """
 from __future__ import annotations
 
@@ -40,7 +45,14 @@ def parse():
                     help="3 = BASELINE.json configs[2] (7 elevations, default); 2 = configs[1] (zenith only)")
     ap.add_argument("--nprof", type=int, default=1000, help="profiles per GPU")
     ap.add_argument("--model", default="R24")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the cold-start timing (the K steps "
+                         "once more, before the spin-up), the CPU baselines and the parity spot check against the C oracle")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave out the CPU baselines and the parity spot check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(tb float64, valid as float64; at most 64 MB, a seeded sample of the profiles beyond that)")
     ap.add_argument("--per-launch-events", action="store_true",
                     help="bracket every launch with its own HIP event pair (the library's timing ring) instead of one pair "
                          "around the K launches: the pure kernel duration, at the price of ~8 us of event packets per step "
@@ -75,6 +87,26 @@ def usable_cores():
             quota = None
     used = n if quota is None else max(1, min(n, int(quota + 0.5)))
     return used, {"os_cpu_count": os.cpu_count(), "sched_affinity": n, "cgroup_cpu_quota": quota}
+
+
+DUMP_LIMIT_BYTES = 60_000_000        # below the 64 MB the dump may hold in all
+
+
+def dump_outputs(dirname, tb, valid):
+    """Write the last timed step's results: ``tb`` [..., nprof, nang, nf] float64 and ``valid`` [nprof] (0/1 as float64).
+    Past DUMP_LIMIT_BYTES a fixed, seeded sample of the profiles is written, with its indices as ``profile_index``."""
+    tb = np.asarray(tb, dtype=np.float64)
+    valid = np.asarray(valid).astype(np.float64)
+    nprof = valid.shape[0]
+    per_profile = tb.nbytes // max(nprof, 1) + valid.itemsize + 8
+    arrays = {"tb": tb, "valid": valid}
+    if nprof * per_profile > DUMP_LIMIT_BYTES:
+        rows = max(1, DUMP_LIMIT_BYTES // per_profile)
+        idx = np.sort(np.random.default_rng(0).choice(nprof, size=rows, replace=False))
+        arrays = {"tb": tb[..., idx, :, :], "valid": valid[idx], "profile_index": idx.astype(np.float64)}
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(tables, P, frq, ang, budget_s=20.0):
@@ -184,6 +216,8 @@ def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args.gpus))
     rank = int(os.environ.get("RANK", "0"))
@@ -287,9 +321,10 @@ def main():
             barrier()
         torch.cuda.synchronize()
         if args.spinup > 0:
-            # The state the driver's flags alone produce -- K steps right after the W warm-up steps, the GPU still
-            # on its way out of the idle power state -- is timed first and reported as "cold_start" beside the headline.
-            cold = timed_region()
+            if args.full:
+                # The state the driver's flags alone produce -- K steps right after the W warm-up steps, the GPU still
+                # on its way out of the idle power state -- is timed first and reported as "cold_start" beside the headline.
+                cold = timed_region()
             with _stdout_to_stderr():
                 run_steps(args.spinup)                      # clock spin-up: untimed, same launches as the timed steps
                 barrier()
@@ -355,9 +390,13 @@ def main():
                         f"{args.spinup} untimed spin-up launches (GPU still leaving its idle power state)",
                 "ms_per_step": cold_elapsed / K * 1e3, "value": evals_per_step * K / cold_elapsed,
                 "kernel_ms": ckms, "roofline_frac": aflops / (ckms * 1e-3) / 1e12 / roofline.FP64_VALU_PEAK_TFLOPS}
-        # parity spot check (not timed): HIP result of the last step vs the C oracle
+        # the last timed step's results: this rank's batch, and every rank's batch as the gather delivered it
         tb_gpu = out[(K - 1) % slots].cpu().numpy()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            tb_all = gathered[:, (K - 1) % slots].cpu().numpy() if use_dist else tb_gpu
+            dump_outputs(args.dump_outputs, tb_all, valid.cpu().numpy())
+        # parity spot check (not timed): HIP result of the last step vs the C oracle
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb, tb_cpu, n = cpu_baseline(tables, P, frq, ang)
             res["cpu_baseline"] = cb
             res["parity_check"] = {"max_abs_dev_K": float(np.abs(tb_gpu[:n] - tb_cpu).max()), "profiles": n,

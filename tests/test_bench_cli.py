@@ -65,3 +65,83 @@ def test_init_absmdl_r24_warns():
     rte = TbCloudRTE(z, 1000 * np.exp(-z / 8), 280 - 6 * z, 0.5 + 0 * z, np.array([22.24]), np.array([90.0]))
     with pytest.warns(UserWarning, match="R24 carried as R20SD"):
         rte.init_absmdl("R24")
+
+
+def test_plain_run_is_lean_and_full_is_opt_in(monkeypatch):
+    """A plain run times the headline only; the cold-start region, the CPU baselines and the parity spot check
+    sit behind --full, and --dump-outputs is off unless a directory is given."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "outdir"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "outdir"
+
+
+def test_zero_steps_is_an_error():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=120, cwd=ROOT)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
+def test_dump_outputs_are_float_and_bounded(tmp_path, monkeypatch):
+    """tb / valid as float64 .npy; past the size limit a seeded profile sample (the same one on every run)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    tb = rng.random((50, 7, 14))
+    valid = np.ones(50, dtype=np.uint8)
+    valid[3] = 0
+    bench.dump_outputs(str(tmp_path / "all"), tb, valid)
+    t, v = np.load(tmp_path / "all" / "tb.npy"), np.load(tmp_path / "all" / "valid.npy")
+    assert t.dtype == np.float64 and v.dtype == np.float64
+    assert np.array_equal(t, tb) and np.array_equal(v, valid.astype(np.float64))
+    assert not (tmp_path / "all" / "profile_index.npy").exists()
+    assert bench.DUMP_LIMIT_BYTES <= 64_000_000 - 4096          # .npy headers fit under 64 MB
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 20 * (7 * 14 * 8 * 2 + 16))
+    tb2 = rng.random((2, 50, 7, 14))                               # gathered form: [world, nprof, nang, nf]
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), tb2, valid)
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert files == ["profile_index.npy", "tb.npy", "valid.npy"]
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in files) <= bench.DUMP_LIMIT_BYTES + 3 * 256
+    idx = np.load(tmp_path / "s1" / "profile_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == 20 and np.all(np.diff(idx) > 0)
+    rows = idx.astype(int)
+    assert np.array_equal(np.load(tmp_path / "s1" / "tb.npy"), tb2[:, rows])
+    assert np.array_equal(np.load(tmp_path / "s1" / "valid.npy"), valid[rows].astype(np.float64))
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f))
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_timed_outputs(tmp_path):
+    """A plain run on the GPU: one JSON line with the headline fields and no --full extras; the dumped tb of the last
+    timed step agrees with the C oracle on the same seeded inputs."""
+    import json
+    import numpy as np
+    from mwr_fast_forward_operators_and_lbls_amd import profiles, spectroscopy
+    from oracle import c_oracle
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--spinup", "0", "--nprof", "8", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in res
+    assert res["steps"] == 3 and res["ms_per_step"] > 0 and res["dtype"] == "f64"
+    assert "cpu_baseline" not in res and "cold_start" not in res and "parity_check" not in res
+    tb, valid = np.load(out / "tb.npy"), np.load(out / "valid.npy")
+    assert tb.shape == (8, 7, 14) and tb.dtype == np.float64 and np.array_equal(valid, np.ones(8))
+    P = profiles.synthetic_profiles(8, config_id=3)
+    ref, _ = c_oracle.tb_batch(spectroscopy.get_model("R24"), P["z"][:2], P["p"][:2], P["t"][:2], P["rh"][:2],
+                               profiles.HATPRO_FRQS, profiles.BENCH_ELEVATIONS_7)
+    assert np.abs(tb[:2] - ref).max() < 1e-6
