@@ -79,6 +79,10 @@ SIGNATURES = {
                                                      _vp]),
     "mwrt_tb_jacobian_batch": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp,
                                               _vp, _vp]),
+    "mwrt_absorption_tl_batch_device": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
+                                                       _vp, _vp, _vp]),
+    "mwrt_tb_jacobian_batch_device": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp,
+                                                     _vp, _vp, _vp, _vp, _vp]),
     "mwrt_set_absorption_mode": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_set_chunk_width": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_selftest_math": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -381,6 +385,28 @@ class Context:
             self._handle, self.model(model), int(nprof), int(nlev), _ptr(d_p), _ptr(d_t), _ptr(d_rh),
             frq.size, _ptr(frq), _ptr(d_awet), _ptr(d_adry),
             _stream(stream)), "mwrt_absorption_batch_device")
+
+    @_serialised
+    def absorption_tl_batch_device(self, model, nprof, nlev, d_p, d_t, d_rh, frq, d_awet, d_adry, d_dawet_dt, d_dawet_de,
+                                   d_dadry_dt, d_dadry_de, stream=None):
+        """Tangent-linear absorption (include/mwrt.h mwrt_absorption_tl_batch_device): awet, adry [Np/km] and their partial
+        derivatives with respect to T at fixed e [Np/km/K] and e at fixed T [Np/km/hPa], each [nprof][nf][nlev]."""
+        frq = _f64(frq).ravel()
+        self._check(self._lib.mwrt_absorption_tl_batch_device(
+            self._handle, self.model(model), int(nprof), int(nlev), _ptr(d_p), _ptr(d_t), _ptr(d_rh), frq.size, _ptr(frq),
+            _ptr(d_awet), _ptr(d_adry), _ptr(d_dawet_dt), _ptr(d_dawet_de), _ptr(d_dadry_dt), _ptr(d_dadry_de),
+            _stream(stream)), "mwrt_absorption_tl_batch_device")
+
+    @_serialised
+    def tb_jacobian_batch_device(self, model, nprof, nlev, d_z, d_p, d_t, d_rh, frq, elev, d_tb, d_dtb_dt, d_dtb_de,
+                                 d_dtb_ddz, d_valid, stream=None):
+        """The K-matrix on device buffers (include/mwrt.h mwrt_tb_jacobian_batch_device): tb [nprof][nang][nf], dtb_dt,
+        dtb_de, dtb_ddz [nprof][nang][nf][nlev] and valid [nprof], as ``tb_jacobian_batch`` returns them."""
+        frq, elev = _f64(frq).ravel(), _f64(elev).ravel()
+        self._check(self._lib.mwrt_tb_jacobian_batch_device(
+            self._handle, self.model(model), int(nprof), int(nlev), _ptr(d_z), _ptr(d_p), _ptr(d_t), _ptr(d_rh),
+            frq.size, _ptr(frq), elev.size, _ptr(elev), _ptr(d_tb), _ptr(d_dtb_dt), _ptr(d_dtb_de), _ptr(d_dtb_ddz),
+            _ptr(d_valid), _stream(stream)), "mwrt_tb_jacobian_batch_device")
 
     def layer_tau_pitch(self, nf: int) -> int:
         """Doubles between consecutive levels of a layer-optical-depth array for nf frequencies (multiple of 16)."""

@@ -4,6 +4,7 @@
 // returns 0 and mwrt_create() fails with MWRT_ERR_NO_DEVICE.
 #define MWRT_HOST_TU 1      // this translation unit owns the non-template kernels
 #include "mwrt_inst.hip.h"
+#include "mwrt_tl.hip.h"
 
 #include <algorithm>
 #include <cmath>
@@ -114,6 +115,9 @@ struct mwrt_context {
   hipEvent_t ws_event = nullptr;
   hipStream_t ws_stream = nullptr;
   bool ws_used = false;
+  // device K-matrix path: the six tangent-linear absorption arrays + per-profile flags (grown only, never shrunk;
+  // handed over between streams like d_amf / d_alpha)
+  DevBuf d_jac;
   // staging for the host-buffer entry points
   DevBuf d_in, d_out, d_valid, d_ex;
   // timing: a ring of hipEvent pairs recorded around every kernel launch, on the launch stream
@@ -204,6 +208,13 @@ int workspace_release(mwrt_context* c, hipStream_t st) {
   c->ws_stream = st; c->ws_used = true;
   return MWRT_OK;
 }
+
+// Runs `fn` when the scope is left, whichever return path leaves it (C++17: the guard is never copied).
+template <class F> struct ScopeExit {
+  F fn;
+  ~ScopeExit() { fn(); }
+};
+template <class F> ScopeExit<F> on_scope_exit(F fn) { return ScopeExit<F>{fn}; }
 
 // `stream` argument of the *_device entry points: NULL = the context's own (non-blocking) stream,
 // MWRT_STREAM_LEGACY = the caller's legacy default stream (hipStream_t 0), else the handle itself
@@ -749,6 +760,7 @@ int mwrt_destroy(mwrt_context* c) {
   for (auto& e : c->mask_cache) (void)hipFree(e.d_masks);
   c->mask_cache.clear();
   c->frq_cache.release(); c->am_cache.release(); c->elev_cache.release(); c->d_amf.release(); c->d_duct.release(); c->d_alpha.release();
+  c->d_jac.release();
   c->d_in.release(); c->d_out.release();
   c->d_valid.release(); c->d_ex.release();
   for (hipEvent_t e : c->ev0) (void)hipEventDestroy(e);
@@ -1285,6 +1297,88 @@ int mwrt_tb_jacobian_batch(mwrt_context* c, const mwrt_model* m, int64_t nprof, 
     for (size_t k = 0; k < (size_t)nang * nf; ++k) tb[o + k] = qnan;
     for (size_t k = 0; k < (size_t)nang * nf * nlev; ++k) { dtb_dt[o * nlev + k] = qnan; dtb_de[o * nlev + k] = qnan; dtb_ddz[o * nlev + k] = qnan; }
   }
+  return MWRT_OK;
+}
+
+// Tangent-linear absorption (k_absorb_tl): alpha and d alpha / dT|e, d alpha / de|T.  DEVICE buffers, asynchronous.
+int mwrt_absorption_tl_batch_device(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
+                                    const double* d_p, const double* d_t, const double* d_rh, int32_t nf, const double* frq,
+                                    double* d_awet, double* d_adry, double* d_dawet_dt, double* d_dawet_de,
+                                    double* d_dadry_dt, double* d_dadry_de, void* stream) {
+  int rc = check_common(c, m, nprof, nlev, nf);
+  if (rc) return rc;
+  if (!d_p || !d_t || !d_rh || !frq || !d_awet || !d_adry || !d_dawet_dt || !d_dawet_de || !d_dadry_dt || !d_dadry_de)
+    return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
+  if (any_nan(frq, nf)) return fail(MWRT_ERR_INVALID_ARGUMENT, "NaN frequency");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = resolve_stream(c, stream);
+  if (nprof == 0) return MWRT_OK;
+  const double* dev_frq = nullptr;
+  rc = upload_small(c, c->frq_cache, frq, nf, &dev_frq); if (rc) return rc;
+  AbsorbTlArgs a{};
+  a.M = m->d_desc; a.p = d_p; a.t = d_t; a.rh = d_rh; a.frq = dev_frq;
+  a.awet = d_awet; a.adry = d_adry; a.dawet_dt = d_dawet_dt; a.dawet_de = d_dawet_de; a.dadry_dt = d_dadry_dt; a.dadry_de = d_dadry_de;
+  a.flags = nullptr; a.nlev = nlev; a.nf = nf; a.nslab = (nlev + WAVE - 1) / WAVE;
+  timing_begin(c, st);
+  const hipError_t e = launch_absorb_tl(a, nprof, st);
+  timing_end(c, st);
+  HIP_TRY(e);
+  return MWRT_OK;
+}
+
+// The K-matrix on caller-owned HBM: k_absorb_tl into the context's workspace, then k_jac_rte.  Asynchronous; after one
+// warm-up call with the same shapes and frequencies it neither allocates nor synchronises.
+int mwrt_tb_jacobian_batch_device(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
+                                  const double* d_z, const double* d_p, const double* d_t, const double* d_rh,
+                                  int32_t nf, const double* frq, int32_t nang, const double* elev,
+                                  double* d_tb, double* d_dtb_dt, double* d_dtb_de, double* d_dtb_ddz, uint8_t* d_valid,
+                                  void* stream) {
+  int rc = check_common(c, m, nprof, nlev, nf);
+  if (rc) return rc;
+  if (nang < 1 || nang > MWRT_MAX_ANGLES) return fail(MWRT_ERR_INVALID_ARGUMENT, "nang out of range");
+  if (!d_z || !d_p || !d_t || !d_rh || !frq || !elev || !d_tb || !d_dtb_dt || !d_dtb_de || !d_dtb_ddz || !d_valid)
+    return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
+  if (any_nan(frq, nf)) return fail(MWRT_ERR_INVALID_ARGUMENT, "NaN frequency");
+  if (nprof * nf > 2147483647LL) return fail(MWRT_ERR_UNSUPPORTED, "nprof x nf exceeds grid limit");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = resolve_stream(c, stream);
+  if (nprof == 0) return MWRT_OK;
+  std::vector<double> am;
+  rc = airmass_of(elev, nang, &am); if (rc) return rc;
+  const double *dev_frq = nullptr, *dev_am = nullptr;
+  rc = upload_small(c, c->frq_cache, frq, nf, &dev_frq); if (rc) return rc;
+  rc = upload_small(c, c->am_cache, am.data(), nang, &dev_am); if (rc) return rc;
+  const size_t nabs = (size_t)nprof * nf * nlev;
+  const size_t need = sizeof(double) * 6 * nabs + sizeof(unsigned) * (size_t)nprof;
+  if (need > c->d_jac.cap) {
+    HIP_TRY(hipDeviceSynchronize());                // queued launches may still read the old workspace
+    HIP_TRY(c->d_jac.reserve(need));
+  }
+  rc = workspace_acquire(c, st); if (rc) return rc;
+  auto handover = on_scope_exit([&] { (void)workspace_release(c, st); });    // on every return path from here on
+  double* w = c->d_jac.as<double>();
+  unsigned* flags = reinterpret_cast<unsigned*>(w + 6 * nabs);
+  HIP_TRY(hipMemsetAsync(flags, 0, sizeof(unsigned) * (size_t)nprof, st));
+  AbsorbTlArgs ta{};
+  ta.M = m->d_desc; ta.p = d_p; ta.t = d_t; ta.rh = d_rh; ta.frq = dev_frq;
+  ta.awet = w; ta.adry = w + nabs; ta.dawet_dt = w + 2 * nabs; ta.dawet_de = w + 3 * nabs;
+  ta.dadry_dt = w + 4 * nabs; ta.dadry_de = w + 5 * nabs;
+  ta.flags = flags; ta.nlev = nlev; ta.nf = nf; ta.nslab = (nlev + WAVE - 1) / WAVE;
+  timing_begin(c, st);
+  hipError_t e = launch_absorb_tl(ta, nprof, st);
+  timing_end(c, st);
+  HIP_TRY(e);
+  JacRteArgs ja{};
+  ja.M = m->d_desc; ja.z = d_z; ja.t = d_t;
+  ja.awet = ta.awet; ja.adry = ta.adry; ja.dawet_dt = ta.dawet_dt; ja.dawet_de = ta.dawet_de;
+  ja.dadry_dt = ta.dadry_dt; ja.dadry_de = ta.dadry_de; ja.flags = flags;
+  ja.frq = dev_frq; ja.airmass = dev_am;
+  ja.tb = d_tb; ja.dtb_dt = d_dtb_dt; ja.dtb_de = d_dtb_de; ja.dtb_ddz = d_dtb_ddz; ja.valid = d_valid;
+  ja.nlev = nlev; ja.nf = nf; ja.nang = nang;
+  timing_begin(c, st);
+  e = launch_jac_rte(ja, nprof, st);
+  timing_end(c, st);
+  HIP_TRY(e);
   return MWRT_OK;
 }
 

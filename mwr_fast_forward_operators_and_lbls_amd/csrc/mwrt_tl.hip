@@ -1,0 +1,455 @@
+// mwrt_tl.hip -- the device K-matrix path: tangent-linear absorption (k_absorb_tl) and the adjoint RTE that consumes it
+// (k_jac_rte).  Declarations and argument records: mwrt_tl.hip.h; entry points: mwrt_absorption_tl_batch_device and
+// mwrt_tb_jacobian_batch_device in mwrt.hip; the mathematics: DESIGN.md section 4.5.
+#include "mwrt_tl.hip.h"
+
+namespace mwrt {
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------
+// Forward-mode tangents in two directions: value, d/dT at fixed e, d/de at fixed T
+// ---------------------------------------------------------------------------------------------
+struct dd { double v, t, e; };
+__device__ __forceinline__ dd operator+(dd a, dd b) { return {a.v + b.v, a.t + b.t, a.e + b.e}; }
+__device__ __forceinline__ dd operator-(dd a, dd b) { return {a.v - b.v, a.t - b.t, a.e - b.e}; }
+__device__ __forceinline__ dd operator*(dd a, dd b) {
+  return {a.v * b.v, __builtin_fma(a.t, b.v, a.v * b.t), __builtin_fma(a.e, b.v, a.v * b.e)};
+}
+__device__ __forceinline__ dd operator*(double s, dd a) { return {s * a.v, s * a.t, s * a.e}; }
+__device__ __forceinline__ dd operator+(dd a, double s) { return {a.v + s, a.t, a.e}; }
+__device__ __forceinline__ dd operator+(double s, dd a) { return {a.v + s, a.t, a.e}; }
+__device__ __forceinline__ dd ddiv(dd a, dd b) {
+  const double r = fdiv(1.0, b.v), q = a.v * r;
+  return {q, (a.t - q * b.t) * r, (a.e - q * b.e) * r};
+}
+__device__ __forceinline__ dd dexp(dd a) { const double v = fexp(a.v); return {v, v * a.t, v * a.e}; }
+
+__device__ __forceinline__ cplx cscale(cplx a, double s) { return {a.re * s, a.im * s}; }
+__device__ __forceinline__ cplx csub(cplx a, cplx b) { return {a.re - b.re, a.im - b.im}; }
+__device__ __forceinline__ cplx caddc(cplx a, cplx b) { return {a.re + b.re, a.im + b.im}; }
+__device__ __forceinline__ double re_mul(cplx a, cplx b) { return __builtin_fma(a.re, b.re, -a.im * b.im); }
+
+// Hui, Armstrong & Wray's rational w ~ P(zh) / Q(zh) (dcerror_upper) and its derivative dw/dzh, zh = |y| - i x = the
+// principal square root the speed-dependent shape feeds it.  The tangent is that of the rational the values use (so
+// the K-matrix is the exact derivative of the computed absorption); the true function's w' = -2 z w + 2 i / sqrt(pi)
+// differs from it by the rational's own ~1e-6 error.
+__device__ __forceinline__ void hui_w_dw(cplx zh, cplx& w, cplx& dw) {
+  const double a[7] = {122.607931777104326, 214.382388694706425, 181.928533092181549, 93.155580458138441,
+                       30.180142196210589, 5.912626209773153, 0.564189583562615};
+  const double b[7] = {122.607931773875350, 352.730625110963558, 457.334478783897737, 348.703917719495792,
+                       170.354001821091472, 53.992906912940207, 10.479857114260399};
+  cplx p = {a[6], 0.0}, dp = {0.0, 0.0};
+#pragma unroll
+  for (int k = 5; k >= 0; --k) { dp = caddc(cmul(dp, zh), p); p = cadd(cmul(p, zh), a[k]); }
+  cplx q = {1.0, 0.0}, dq = {0.0, 0.0};
+#pragma unroll
+  for (int k = 6; k >= 0; --k) { dq = caddc(cmul(dq, zh), q); q = cadd(cmul(q, zh), b[k]); }
+  const cplx iq = crecip(q);
+  w = cmul(p, iq);
+  dw = cmul(csub(dp, cmul(w, dq)), iq);
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_absorb_tl: one wave = 64 levels of one profile x TL_NFC frequencies.  The per-(level, line) quantities and their
+// tangents (width, shift, strength, mixing, ...) are formed once per chunk; per frequency the line shape and its two
+// tangents are direct sums over every line.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64)
+k_absorb_tl(const AbsorbTlArgs A) {
+  constexpr int NFC = TL_NFC;
+  const int lane = threadIdx.x;
+  const int64_t prof = blockIdx.x / A.nslab;
+  const int lev = (int)(blockIdx.x - prof * A.nslab) * WAVE + lane;
+  const bool live = lev < A.nlev;
+  const int jbase = blockIdx.y * NFC;
+  const int nfc = min(NFC, A.nf - jbase);
+  const cmodel M = (cmodel)A.M;
+  const cdoubles cfrq = (cdoubles)A.frq;
+  const int64_t off = prof * A.nlev + (live ? lev : A.nlev - 1);
+  const double pin = A.p[off], tin = A.t[off], rhin = A.rh[off];
+  double fq[NFC];
+#pragma unroll
+  for (int j = 0; j < NFC; ++j) fq[j] = cfrq[jbase + min(j, nfc - 1)];
+
+  // RTEquation.vapor + the clearsky_absorption preamble, as the forward kernels evaluate it
+  const double e0 = goff_gratch_e(tin, rhin);
+  const LevelState L = level_state(pin, tin, e0);
+  const double inv_t = fdiv(1.0, L.t);
+  const double rvap = (0.01 * 8.314510) / 18.01528;
+  const dd t = {L.t, 1.0, 0.0};
+  const dd rho = {L.rho, -L.rho * inv_t, fdiv(1.0, rvap * L.t)};      // e / (rvap T)
+  const double P = L.p;                                                 // total pressure: independent of T and e
+
+  bool nan = isnan(pin) || isnan(tin) || isnan(rhin), neg = false;
+  // stores of one species' three arrays: lanes = consecutive levels of one row (coalesced)
+  auto store = [&](const dd (&a)[NFC], double* v, double* dt, double* de) {
+    if (!live) return;
+#pragma unroll
+    for (int j = 0; j < NFC; ++j) {
+      if (j < nfc) {
+        const int64_t o = (prof * A.nf + jbase + j) * A.nlev + lev;
+        v[o] = a[j].v; dt[o] = a[j].t; de[o] = a[j].e;
+        nan = nan || isnan(a[j].v);
+        neg = neg || a[j].v < 0.0;
+      }
+    }
+  };
+
+  // ---- H2O lines + continuum (H2OAbsModel.h2o_absorption [EXT]) ----
+  {
+    dd wsum[NFC];
+    const dd rt = rho * t;
+    const dd pvap = fdiv(1.0, M->h2o_pvap_div) * rt;
+    const dd pda = {P - pvap.v, -pvap.t, -pvap.e};
+    const dd den = M->h2o_den_coef * rho;
+    const dd lnc = {flog(fdiv(M->h2o_reftcon, L.t)), -inv_t, 0.0};
+    const dd con0 = (M->h2o_cf * pda * dexp(M->h2o_xcf * lnc) + M->h2o_cs * pvap * dexp(M->h2o_xcs * lnc)) * pvap;
+    const double tiv = fdiv(M->h2o_reftline, L.t);
+    const dd ti = {tiv, -tiv * inv_t, 0.0};
+    const dd tiln = {flog(tiv), -inv_t, 0.0};
+    const dd ti2 = dexp(2.5 * tiln);
+    const bool shifted = M->h2o_shift_mode != 0;
+    dd sum[NFC];
+#pragma unroll
+    for (int j = 0; j < NFC; ++j) sum[j] = {0.0, 0.0, 0.0};
+    for (int k = 0; k < M->n_h2o; ++k) {
+      const auto& R = M->h2or[k];
+      const dd w0 = R.w0 * pda * dexp(R.x * tiln) + R.w0s * pvap * dexp(R.xs * tiln);
+      dd c1 = {R.fl, 0.0, 0.0};
+      if (shifted) {
+        dd sf = R.sh * pda, ss = R.shs * pvap;
+        if (R.aair != 0.0) sf = sf * (1.0 + (-R.aair) * tiln);
+        if (R.aself != 0.0) ss = ss * (1.0 + (-R.aself) * tiln);
+        if (R.xh != 0.0) sf = sf * dexp(R.xh * tiln);
+        if (R.xhs != 0.0) ss = ss * dexp(R.xhs * tiln);
+        c1 = c1 + (sf + ss);
+      }
+      const dd wsq = w0 * w0;
+      const dd s = R.s1 * ti2 * dexp(R.b2 * (1.0 + (-1.0) * ti));    // S / fl^2: the f^2 is applied at the end
+      const dd base = ddiv(w0, wsq + 562500.0);
+      const dd sw = s * w0, sbase = s * base;
+      // speed-dependent resonant term (ABH2O_SD): per-(level, line) parts of Xc = A / B, A = w0 - 1.5 w2 + i (d1 + 1.5 delta2),
+      // B = w2 - i delta2, and their tangents (dA is frequency independent: d(d1) = -d(c1))
+      const bool sdline = M->h2o_w2[k] > 0.0;
+      double sdlim = -1.0;
+      cplx iB = {0.0, 0.0}, dA_t = {0.0, 0.0}, dA_e = {0.0, 0.0}, dB_t = {0.0, 0.0}, dB_e = {0.0, 0.0};
+      double xre = 0.0, xim0 = 0.0;
+      if (sdline) {
+        const dd w2 = M->h2o_w2[k] * pda * dexp(M->h2o_xw2[k] * tiln) + M->h2o_w2s[k] * pvap * dexp(M->h2o_xw2s[k] * tiln);
+        const dd d2 = M->h2o_d2[k] * pda + M->h2o_d2s[k] * pvap;
+        iB = crecip(cplx{w2.v, -d2.v});
+        sdlim = (w2.v > 0.0) ? 10.0 * w0.v : -1.0;
+        xre = w0.v - 1.5 * w2.v; xim0 = 1.5 * d2.v;
+        dA_t = {w0.t - 1.5 * w2.t, 1.5 * d2.t - c1.t}; dA_e = {w0.e - 1.5 * w2.e, 1.5 * d2.e - c1.e};
+        dB_t = {w2.t, -d2.t}; dB_e = {w2.e, -d2.e};
+      }
+#pragma unroll
+      for (int j = 0; j < NFC; ++j) {
+        const double f = fq[j];
+        const double d1 = f - c1.v, d2 = f + c1.v;
+        const double D1 = __builtin_fma(d1, d1, wsq.v), D2 = __builtin_fma(d2, d2, wsq.v);
+        const double D1t = __builtin_fma(-2.0 * d1, c1.t, wsq.t), D1e = __builtin_fma(-2.0 * d1, c1.e, wsq.e);
+        const double D2t = __builtin_fma(2.0 * d2, c1.t, wsq.t), D2e = __builtin_fma(2.0 * d2, c1.e, wsq.e);
+        const bool sd_in = fabs(d1) < sdlim;
+        const double m1 = (fabs(d1) < 750.0 && !sd_in) ? 1.0 : 0.0;    // 750-GHz cutoff; the SD shape replaces term 1
+        const double m2 = (fabs(d2) < 750.0) ? 1.0 : 0.0;
+        const double num = __builtin_fma(m1, D2, m2 * D1);
+        const double numt = __builtin_fma(m1, D2t, m2 * D1t), nume = __builtin_fma(m1, D2e, m2 * D1e);
+        const double den12 = D1 * D2;
+        const double dent = __builtin_fma(D1t, D2, D1 * D2t), dene = __builtin_fma(D1e, D2, D1 * D2e);
+        const double r = fdiv(1.0, den12);
+        const double q = num * r, qt = (numt - q * dent) * r, qe = (nume - q * dene) * r;
+        const double mm = m1 + m2;
+        sum[j].v = __builtin_fma(sw.v, q, __builtin_fma(-mm, sbase.v, sum[j].v));
+        sum[j].t = __builtin_fma(sw.t, q, __builtin_fma(sw.v, qt, __builtin_fma(-mm, sbase.t, sum[j].t)));
+        sum[j].e = __builtin_fma(sw.e, q, __builtin_fma(sw.v, qe, __builtin_fma(-mm, sbase.e, sum[j].e)));
+        if (sdline && wave_any(sd_in)) {
+          // Re SD and its tangents: with xrt = sqrt(Xc), pxw = sqrt(pi) xrt w(i xrt), SD = 2 (1 - pxw) / B,
+          //   dSD = CA dA + CB dB,  CA = -2 K h / B^2,  CB = -CA Xc - SD / B,  K = sqrt(pi) (w + xrt w'),  h = 1 / (2 xrt)
+          const cplx xc = cmul(cplx{xre, d1 + xim0}, iB);
+          const cplx xrt = csqrt_principal(xc);
+          cplx w, dw;
+          hui_w_dw(xrt, w, dw);
+          const double SQPI = 1.77245385090551603;
+          const cplx pxw = cmul(cscale(xrt, SQPI), w);
+          const cplx sdc = cmul(cplx{2.0 - 2.0 * pxw.re, -2.0 * pxw.im}, iB);
+          const cplx K = cscale(caddc(w, cmul(xrt, dw)), SQPI);
+          const cplx h = crecip(cscale(xrt, 2.0));
+          const cplx CA = cscale(cmul(cmul(K, h), cmul(iB, iB)), -2.0);
+          const cplx CB = csub(cplx{0.0, 0.0}, caddc(cmul(CA, xc), cmul(sdc, iB)));
+          const double sdt = re_mul(CA, dA_t) + re_mul(CB, dB_t), sde = re_mul(CA, dA_e) + re_mul(CB, dB_e);
+          const double r1 = sd_in ? sdc.re - base.v : 0.0;
+          const double r1t = sd_in ? sdt - base.t : 0.0, r1e = sd_in ? sde - base.e : 0.0;
+          sum[j].v = __builtin_fma(s.v, r1, sum[j].v);
+          sum[j].t = __builtin_fma(s.t, r1, __builtin_fma(s.v, r1t, sum[j].t));
+          sum[j].e = __builtin_fma(s.e, r1, __builtin_fma(s.v, r1e, sum[j].e));
+        }
+      }
+    }
+    const bool dry = !(L.rho > 0.0);
+    const dd cden = 3.183e-05 * den;
+#pragma unroll
+    for (int j = 0; j < NFC; ++j) {
+      const double f2 = fq[j] * fq[j];
+      dd a = f2 * (cden * sum[j] + con0);
+      if (dry) a.v = 0.0;          // the value is zeroed at rho <= 0; the tangent is the right-sided one (continuous there)
+      wsum[j] = a;
+    }
+    store(wsum, A.awet, A.dawet_dt, A.dawet_de);
+  }
+
+  // ---- O2 lines + non-resonant term + N2 continuum (O2AbsModel.o2_absorption / N2AbsModel [EXT]) ----
+  {
+    dd dsum[NFC];
+    const double thv = fdiv(300.0, L.t);
+    const dd th = {thv, -thv * inv_t, 0.0};
+    const dd th1 = th + (-1.0);
+    const dd lnth = {flog(thv), -inv_t, 0.0};
+    const dd b = dexp(M->o2_x * lnth);
+    const dd preswv = fdiv(1.0, M->o2_pvap_div) * (rho * t);
+    const dd presda = {P - preswv.v, -preswv.t, -preswv.e};
+    const dd den = 0.001 * (presda * b + M->o2_wv_factor * preswv * th);
+    const dd dens = 0.001 * ((presda + M->o2_wv_factor * preswv) * th);
+    const dd dfnr = M->o2_wb300 * den;
+    const dd pe2 = den * den;
+    const bool second = M->o2_mix_mode != 0;
+    const dd ymul = second ? den : (0.001 * P) * b;
+    const bool line1_dens = !second && M->o2_line1_dens;
+    dd sum[NFC];
+#pragma unroll
+    for (int j = 0; j < NFC; ++j) sum[j] = {0.0, 0.0, 0.0};
+    for (int k = 0; k < M->n_o2; ++k) {
+      const auto& R = M->o2r[k];
+      const dd y = ymul * (R.y1 * th1 + R.y0);
+      dd dnu = {0.0, 0.0, 0.0}, gfac = {1.0, 0.0, 0.0};
+      if (second) {
+        dnu = pe2 * (R.dnu1 * th1 + R.dnu0);
+        gfac = 1.0 + pe2 * (R.g1 * th1 + R.g0);
+      }
+      const dd df = R.w300 * ((k == 0 && line1_dens) ? dens : den);
+      const dd str = R.s300rf2 * dexp(-R.be * th1);                   // S300 / F^2: the f^2 is applied at the end
+      // n1 / D1 + n2 / D2 = (f^2 Pp + Qq) / (D1 D2),  Pp = 2 (a + c b), Qq = 2 (c^2 + w^2)(a - c b)  (the 2 is in scale2)
+      const dd c1 = dnu + R.f;
+      const dd df2 = df * df;
+      const dd a = str * df * gfac;
+      const dd cb = c1 * (str * y);
+      const dd cc = c1 * c1 + df2;
+      const dd Pp = a + cb, Qq = cc * (a - cb);
+#pragma unroll
+      for (int j = 0; j < NFC; ++j) {
+        const double f = fq[j], f2 = f * f;
+        const double d1 = f - c1.v, d2 = f + c1.v;
+        const double D1 = __builtin_fma(d1, d1, df2.v), D2 = __builtin_fma(d2, d2, df2.v);
+        const double D1t = __builtin_fma(-2.0 * d1, c1.t, df2.t), D1e = __builtin_fma(-2.0 * d1, c1.e, df2.e);
+        const double D2t = __builtin_fma(2.0 * d2, c1.t, df2.t), D2e = __builtin_fma(2.0 * d2, c1.e, df2.e);
+        const double den12 = D1 * D2;
+        const double dent = __builtin_fma(D1t, D2, D1 * D2t), dene = __builtin_fma(D1e, D2, D1 * D2e);
+        const double r = fdiv(1.0, den12);
+        const double q = __builtin_fma(f2, Pp.v, Qq.v) * r;
+        sum[j].v += q;
+        sum[j].t = __builtin_fma(__builtin_fma(f2, Pp.t, Qq.t) - q * dent, r, sum[j].t);
+        sum[j].e = __builtin_fma(__builtin_fma(f2, Pp.e, Qq.e) - q * dene, r, sum[j].e);
+      }
+    }
+    const dd scale2 = (2.0 * M->o2_coef) * (presda * (th * th * th));
+    const dd pn2 = M->n2_ptot ? dd{P, 0.0, 0.0} : dd{L.pdry, 0.0, -1.0};
+    const dd n2c = (M->n2_n * M->n2_l) * (pn2 * pn2 * dexp(M->n2_m * lnth));
+    const dd nr0 = (0.5 * M->o2_nonres) * dfnr;
+    const dd dfnr2 = dfnr * dfnr;
+#pragma unroll
+    for (int j = 0; j < NFC; ++j) {
+      const double f = fq[j], f2 = f * f;
+      double fdep = 1.0;
+      if (M->n2_fdep) { const double qq = f * (1.0 / 450.0); fdep = 0.5 + fdiv(0.5, 1.0 + qq * qq); }
+      const dd hnonres = ddiv(f2 * nr0, th * (dfnr2 + f2));
+      dd o2 = scale2 * (f2 * sum[j] + hnonres);
+      if (!(o2.v > 0.0)) o2 = {0.0, 0.0, 0.0};                       // max(o2abs, 0): no slope where it clamps
+      dsum[j] = o2 + (fdep * f2) * n2c;
+    }
+    store(dsum, A.adry, A.dadry_dt, A.dadry_de);
+  }
+
+  if (A.flags) {
+    const unsigned fl = (wave_any(live && nan) ? 1u : 0u) | (wave_any(live && neg) ? 2u : 0u);
+    if (fl && lane == 0) atomicOr(A.flags + prof, fl);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_jac_rte: one workgroup per (profile, frequency), one lane per level.  Per frequency the layer values, their partial
+// derivatives, the Planck terms and the zenith optical-depth prefix are formed once; per elevation the transmittances,
+// one workgroup prefix sum (S_l = sum_{m <= l} c_m T_{m-1}) and a neighbour exchange give every level's three
+// derivatives, which the lanes store as one contiguous row (level fastest: coalesced).
+// ---------------------------------------------------------------------------------------------
+
+// log-mean layer value and its two partial derivatives, branch for branch as layer_value<true>
+__device__ __forceinline__ double layer_value_tl(double x1, double x0, double& d1, double& d0, bool& neg) {
+  if (x0 < 0.0 || x1 < 0.0) { neg = true; d1 = d0 = 0.0; return 0.0; }
+  const double d = x1 - x0;
+  if (fabs(d) < 1e-09) { d1 = 1.0; d0 = 0.0; return x1; }
+  if (x0 == 0.0 || x1 == 0.0) { d1 = d0 = 0.5; return 0.5 * (x1 + x0); }
+  const double sm = x1 + x0, ism = fdiv(1.0, sm), s = d * ism;
+  if (fabs(s) <= LOGMEAN_SMALL_S) {
+    // L = sm/2 q(z), q = s/atanh(s), z = s^2:  dL/dx1 = q/2 + 2 s q'(z) x0/sm,  dL/dx0 = q/2 - 2 s q'(z) x1/sm
+    const double z = s * s;
+    const double c[10] = {-3.3333333333333333333e-01, -8.8888888888888888889e-02, -4.6560846560846560847e-02,
+                          -3.0194003527336860670e-02, -2.1796804019026241248e-02, -1.6787551856334925118e-02,
+                          -1.3502765051265933100e-02, -1.1203745637718733130e-02, -9.5160731945278989134e-03,
+                          -8.2312065673505011548e-03};
+    double q = 0.0, qp = 0.0;
+#pragma unroll
+    for (int k = 9; k >= 0; --k) { qp = __builtin_fma(qp, z, (k + 1) * c[k]); q = (q + c[k]) * z; }
+    q += 1.0;
+    const double u = 2.0 * s * qp * ism;
+    d1 = __builtin_fma(u, x0, 0.5 * q);
+    d0 = __builtin_fma(-u, x1, 0.5 * q);
+    return 0.5 * sm * q;
+  }
+  const double ln = flog(fdiv(x1, x0)), iln = fdiv(1.0, ln), L = d * iln;
+  d1 = (1.0 - fdiv(L, x1)) * iln;
+  d0 = (fdiv(L, x0) - 1.0) * iln;
+  return L;
+}
+
+// inclusive prefix sum over the workgroup (lanes by shuffles, then the waves in index order: deterministic)
+__device__ __forceinline__ double block_scan(double v, double* wsum, int tid, int nwaves, double& total) {
+  const int lane = tid & (WAVE - 1), wave = tid / WAVE;
+#pragma unroll
+  for (int o = 1; o < WAVE; o <<= 1) {
+    const double u = __shfl_up(v, o, WAVE);
+    if (lane >= o) v += u;
+  }
+  __syncthreads();
+  if (lane == WAVE - 1) wsum[wave] = v;
+  __syncthreads();
+  double off = 0.0, tot = 0.0;
+  for (int w = 0; w < nwaves; ++w) {
+    const double x = wsum[w];
+    off += (w < wave) ? x : 0.0;
+    tot += x;
+  }
+  total = tot;
+  return v + off;
+}
+
+__global__ void __launch_bounds__(1024)
+k_jac_rte(const JacRteArgs A) {
+  extern __shared__ double smem[];
+  const int tid = threadIdx.x, nthr = blockDim.x, nwaves = nthr / WAVE;
+  const int nlev = A.nlev, nf = A.nf, nang = A.nang;
+  const int64_t prof = blockIdx.x / nf;
+  const int j = (int)(blockIdx.x - prof * nf);
+  double* s0 = smem;
+  double* s1 = smem + nthr;
+  double* s2 = smem + 2 * nthr;
+  double* wsum = smem + 3 * nthr;
+  const cmodel M = (cmodel)A.M;
+  const bool live = tid < nlev;
+  const int l = live ? tid : nlev - 1;
+  const int64_t lo = prof * nlev + l, ao = (prof * nf + j) * nlev + l;
+  const double qnan = __builtin_nan("");
+
+  const double zl = A.z[lo], tl = A.t[lo];
+  const unsigned fl = A.flags[prof];
+  const bool bad_nan = __syncthreads_or(live && (isnan(zl) || isnan(tl))) || (fl & 1u);
+  const bool bad = bad_nan || (fl & 2u);
+  if (j == 0 && tid == 0) A.valid[prof] = bad_nan ? 0 : (bad ? 2 : 1);
+  if (bad) {                           // NaN in the profile (0) or negative absorption (2): the whole profile is NaN
+    for (int a = 0; a < nang; ++a) {
+      const int64_t row = (prof * nang + a) * nf + j;
+      if (live) { A.dtb_dt[row * nlev + tid] = qnan; A.dtb_de[row * nlev + tid] = qnan; A.dtb_ddz[row * nlev + tid] = qnan; }
+      if (tid == 0) A.tb[row] = qnan;
+    }
+    return;
+  }
+  const double aw = A.awet[ao], ad = A.adry[ao];
+  const double awT = A.dawet_dt[ao], awE = A.dawet_de[ao], adT = A.dadry_dt[ao], adE = A.dadry_de[ao];
+  const double hvk = A.frq[j] * (1e9 * M->planck_h / M->boltzmann_k);
+  const double x = fdiv(hvk, tl);
+  const double b = planck_b(x, fdiv(tl, hvk));
+  const double dbdT = fdiv(b * (b + 1.0) * x, tl);                       // db/dT = b (b + 1) hvk / T^2
+
+  // ---- per frequency: layer l (between levels l-1 and l) lives on lane l ----
+  s0[tid] = aw; s1[tid] = ad; s2[tid] = b;
+  __syncthreads();
+  const bool lay = live && tid > 0;
+  double Lw = 0.0, w1 = 0.0, w0 = 0.0, Ld = 0.0, d1 = 0.0, d0 = 0.0, dz = 0.0, bm = 0.0;
+  if (lay) {
+    bool neg = false;                  // (negative values are flagged by k_absorb_tl already)
+    Lw = layer_value_tl(aw, s0[tid - 1], w1, w0, neg);
+    Ld = layer_value_tl(ad, s1[tid - 1], d1, d0, neg);
+    const double z0 = A.z[prof * nlev];
+    dz = (zl - z0) - (A.z[lo - 1] - z0);
+    bm = s2[tid - 1];
+  }
+  const double tauz = lay ? Lw * dz + Ld * dz : 0.0;                   // zenith optical depth of layer l
+  __syncthreads();
+  s0[tid] = w0; s1[tid] = d0;          // the lower-end partials of layer l, for level l-1
+  __syncthreads();
+  const bool has_up = tid + 1 < nlev;
+  const double w0n = has_up ? s0[tid + 1] : 0.0, d0n = has_up ? s1[tid + 1] : 0.0;
+  double tau_tot;
+  const double cum_in = block_scan(tauz, wsum, tid, nwaves, tau_tot);
+  const double cum_ex = cum_in - tauz;                                   // zenith optical depth below layer l
+  const double bbg = fdiv(1.0, fexp(fdiv(hvk, M->t_cosmic)) - 1.0);
+
+  for (int a = 0; a < nang; ++a) {
+    const double am = A.airmass[a];
+    const int64_t row = (prof * nang + a) * nf + j;
+    double* o_t = A.dtb_dt + row * nlev;
+    double* o_e = A.dtb_de + row * nlev;
+    double* o_z = A.dtb_ddz + row * nlev;
+    if (isnan(am)) {                   // a NaN elevation: its rows are NaN, the profile stays valid
+      if (live) { o_t[tid] = qnan; o_e[tid] = qnan; o_z[tid] = qnan; }
+      if (tid == 0) A.tb[row] = qnan;
+      continue;
+    }
+    const double tau = am * tauz;
+    const double E = fexp(-tau);
+    const double th = (tau <= EXP_SMALL_X) ? ftanh_half_small(tau) : fdiv(1.0 - E, 1.0 + E);   // (1 - E) / (1 + E)
+    const double Tm1 = fexp(-am * cum_ex);                               // transmittance below layer l
+    const double Tl = Tm1 * E;
+    const double Pc = lay ? (bm + b * E) * th * Tm1 : 0.0;
+    double Bsum;
+    const double S = block_scan(Pc, wsum, tid, nwaves, Bsum);
+    const double Ttop = fexp(-am * tau_tot);
+    const double Btot = (Ttop > TRANS_MIN) ? __builtin_fma(bbg, Ttop, Bsum) : Bsum;
+    const double Lg = flog(1.0 + fdiv(1.0, Btot));
+    const double dTB_dB = fdiv(hvk, Lg * Lg * Btot * (Btot + 1.0));
+    const double opE = 1.0 + E;
+    const double dc_dtau = fdiv(E * (2.0 * bm + 2.0 * b * E - b + b * E * E), opE * opE);
+    const double g = lay ? dTB_dB * (Tm1 * dc_dtau - (Btot - S)) : 0.0;  // dTB / dtau_l (everything above l is dimmed)
+    const double gk = g * am * dz;
+    s0[tid] = gk; s1[tid] = th;
+    __syncthreads();
+    const double gkn = has_up ? s0[tid + 1] : 0.0, thn = has_up ? s1[tid + 1] : 0.0;
+    const double btl = dTB_dB * dbdT;
+    double ct = gk * (w1 * awT + d1 * adT) + btl * Tm1 * (E * th);        // level l as the upper end of layer l
+    double ce = gk * (w1 * awE + d1 * adE);
+    ct += gkn * (w0n * awT + d0n * adT) + btl * Tl * thn;                 // ... and as the lower end of layer l+1
+    ce += gkn * (w0n * awE + d0n * adE);
+    if (live) {
+      o_t[tid] = ct; o_e[tid] = ce;
+      o_z[tid] = (lay && dz != 0.0) ? g * am * (Lw + Ld) : 0.0;          // dTB / d(thickness of layer l) [K/km]
+    }
+    if (tid == 0) A.tb[row] = fdiv(hvk, Lg);
+  }
+}
+
+}  // namespace
+
+hipError_t launch_absorb_tl(const AbsorbTlArgs& a, int64_t nprof, hipStream_t st) {
+  const dim3 grid((unsigned)(nprof * a.nslab), (unsigned)((a.nf + TL_NFC - 1) / TL_NFC));
+  hipLaunchKernelGGL(k_absorb_tl, grid, dim3(WAVE), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_jac_rte(const JacRteArgs& a, int64_t nprof, hipStream_t st) {
+  const int threads = ((a.nlev + WAVE - 1) / WAVE) * WAVE;
+  const size_t lds = sizeof(double) * (3 * (size_t)threads + 16);
+  hipLaunchKernelGGL(k_jac_rte, dim3((unsigned)(nprof * a.nf)), dim3(threads), lds, st, a);
+  return hipGetLastError();
+}
+
+}  // namespace mwrt

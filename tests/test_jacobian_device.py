@@ -1,0 +1,320 @@
+"""The device K-matrix path: tangent-linear absorption (mwrt_absorption_tl_batch_device), the device K-matrix
+(mwrt_tb_jacobian_batch_device) and the torch autograd op on top of it (autodiff.brightness_temperature).
+
+CPU tests: the ABI surface, and the op's chain rule with the native call replaced by an oracle stand-in.
+GPU tests (-m gpu): values and derivatives against the forward absorption, the host K-matrix and oracle differences;
+NaN rules, streams and memory; gradients on the device."""
+import dataclasses
+
+import numpy as np
+import pytest
+
+from mwr_fast_forward_operators_and_lbls_amd import _native, profiles as pr, spectroscopy as sp
+from oracle import c_oracle, lbl_oracle as lo
+
+NEW_SYMBOLS = ("mwrt_absorption_tl_batch_device", "mwrt_tb_jacobian_batch_device")
+
+
+# ---- oracle helpers (small profiles only: one C oracle run per perturbed state) -----------------------------------
+def oracle_tb(tables, z, p, t, rh, frq, ang):
+    return c_oracle.tb_profile(tables, z, p, t, rh, frq, ang)["tbtotal"].reshape(len(ang), len(frq))
+
+
+def oracle_k_matrix(tables, z, p, t, rh, frq, ang):
+    """The operator's partial derivatives (T at fixed e, e, layer thickness) by central differences of the oracle TB:
+    what mwrt_tb_jacobian_batch_device returns for one profile.  -> tb [nang][nf], {dtb_dt, dtb_de, dtb_ddz} [nang][nf][nlev]"""
+    nlev = len(z)
+    es = lo.vapor(t, np.ones(nlev))[0]
+    e = rh * es
+    jac = {k: np.zeros((len(ang), len(frq), nlev)) for k in ("dtb_dt", "dtb_de", "dtb_ddz")}
+    for l in range(nlev):
+        dT, de, dz = 0.01, max(1e-4 * e[l], 1e-7), 1e-4
+        tp, tm, rp, rm = t.copy(), t.copy(), rh.copy(), rh.copy()
+        tp[l] += dT; tm[l] -= dT
+        rp[l] = e[l] / lo.vapor(tp[l:l + 1], np.ones(1))[0][0]; rm[l] = e[l] / lo.vapor(tm[l:l + 1], np.ones(1))[0][0]
+        jac["dtb_dt"][..., l] = (oracle_tb(tables, z, p, tp, rp, frq, ang) - oracle_tb(tables, z, p, tm, rm, frq, ang)) / (2 * dT)
+        rp, rm = rh.copy(), rh.copy()
+        rp[l] = (e[l] + de) / es[l]; rm[l] = (e[l] - de) / es[l]
+        jac["dtb_de"][..., l] = (oracle_tb(tables, z, p, t, rp, frq, ang) - oracle_tb(tables, z, p, t, rm, frq, ang)) / (2 * de)
+        if l > 0:                                  # the layer below level l: everything from l up moves
+            zp, zm = z.copy(), z.copy(); zp[l:] += dz; zm[l:] -= dz
+            jac["dtb_ddz"][..., l] = (oracle_tb(tables, zp, p, t, rh, frq, ang) - oracle_tb(tables, zm, p, t, rh, frq, ang)) / (2 * dz)
+    return oracle_tb(tables, z, p, t, rh, frq, ang), jac
+
+
+def oracle_direct_gradients(tables, z, p, t, rh, frq, ang):
+    """d TB / d t (at fixed rh), d rh, d z_i (one level moves) by central differences: [nang][nf][nlev] each."""
+    nlev = len(z)
+    out = {k: np.zeros((len(ang), len(frq), nlev)) for k in ("t", "rh", "z")}
+    for l in range(nlev):
+        for k, x, h in (("t", t, 0.01), ("rh", rh, max(1e-4 * rh[l], 1e-7)), ("z", z, 1e-4)):
+            xp, xm = x.copy(), x.copy(); xp[l] += h; xm[l] -= h
+            args = {"z": z, "t": t, "rh": rh}
+            hi = oracle_tb(tables, **{**args, k: xp}, p=p, frq=frq, ang=ang)
+            lo_ = oracle_tb(tables, **{**args, k: xm}, p=p, frq=frq, ang=ang)
+            out[k][..., l] = (hi - lo_) / (2 * h)
+    return out
+
+
+SMALL_FRQ = pr.HATPRO_FRQS[[0, 6, 9]]
+SMALL_ANG = np.array([90.0, 19.2])
+
+
+# ---- CPU ---------------------------------------------------------------------------------------------------------
+def test_device_k_matrix_symbols_exported(native_lib):
+    for s in NEW_SYMBOLS:
+        assert hasattr(native_lib, s), s
+        assert s in _native.SIGNATURES, s
+    assert native_lib.mwrt_version() == 301
+
+
+def test_autograd_chain_rule_against_oracle(monkeypatch):
+    """The op's backward (contraction + chain rule to t, rh, z) with the native call replaced by oracle differences of the
+    operator's own variables, against direct oracle differences with respect to t, rh and z."""
+    torch = pytest.importorskip("torch")
+    from mwr_fast_forward_operators_and_lbls_amd import autodiff
+    tables = sp.get_model("R17")
+    P = pr.synthetic_profiles(1, 31, nlev=30)
+    z, p, t, rh = (P[k][0] for k in ("z", "p", "t", "rh"))
+
+    def stand_in(model, z_, p_, t_, rh_, frq, elev, stream):
+        tb, jac = oracle_k_matrix(tables, *(x[0].numpy() for x in (z_, p_, t_, rh_)), frq, elev)
+        as_t = lambda a: torch.from_numpy(np.ascontiguousarray(a))[None]          # noqa: E731
+        return as_t(tb), torch.ones(1, dtype=torch.uint8), as_t(jac["dtb_dt"]), as_t(jac["dtb_de"]), as_t(jac["dtb_ddz"])
+    monkeypatch.setattr(autodiff, "_native_jacobian", stand_in)
+
+    zt, pt, tt, rht = (torch.tensor(x[None], dtype=torch.float64) for x in (z, p, t, rh))
+    direct = oracle_direct_gradients(tables, z, p, t, rh, SMALL_FRQ, SMALL_ANG)
+    for a in range(len(SMALL_ANG)):
+        for j in range(len(SMALL_FRQ)):
+            xs = [x.clone().requires_grad_(True) for x in (zt, tt, rht)]
+            tb, valid = autodiff.brightness_temperature(tables, xs[0], pt, xs[1], xs[2], SMALL_FRQ, SMALL_ANG)
+            assert tb.shape == (1, 2, 3) and valid.tolist() == [1]
+            tb[0, a, j].backward()
+            for x, k in zip(xs, ("z", "t", "rh")):
+                got, want = x.grad[0].numpy(), direct[k][a, j]
+                assert np.abs(got - want).max() <= 1e-4 * np.abs(want).max(), (k, a, j)
+    with pytest.raises(NotImplementedError):
+        autodiff.brightness_temperature(tables, zt, pt.clone().requires_grad_(True), tt, rht, SMALL_FRQ, SMALL_ANG)
+
+
+# ---- GPU ---------------------------------------------------------------------------------------------------------
+def _torch_cuda():
+    torch = pytest.importorskip("torch")
+    if not torch.cuda.is_available():
+        pytest.fail("gpu-marked test started without a GPU visible to torch")
+    return torch
+
+
+def _dev(torch, P, keys=("z", "p", "t", "rh")):
+    return [torch.tensor(np.ascontiguousarray(P[k]), dtype=torch.float64, device="cuda") for k in keys]
+
+
+def _cur(torch):
+    """torch's current stream: native calls on it are ordered with torch's allocations and frees"""
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _k_matrix_device(gpu_ctx, torch, model, P, frq, ang):
+    z, p, t, rh = _dev(torch, P)
+    nprof, nlev = z.shape
+    opts = dict(dtype=torch.float64, device="cuda")
+    tb = torch.empty((nprof, len(ang), len(frq)), **opts)
+    jac = {k: torch.empty((nprof, len(ang), len(frq), nlev), **opts) for k in ("dtb_dt", "dtb_de", "dtb_ddz")}
+    valid = torch.empty(nprof, dtype=torch.uint8, device="cuda")
+    gpu_ctx.tb_jacobian_batch_device(model, nprof, nlev, z.data_ptr(), p.data_ptr(), t.data_ptr(), rh.data_ptr(), frq, ang,
+                                     tb.data_ptr(), jac["dtb_dt"].data_ptr(), jac["dtb_de"].data_ptr(),
+                                     jac["dtb_ddz"].data_ptr(), valid.data_ptr(), stream=_cur(torch))
+    return tb, valid, jac
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["R98", "R17", "R20", "R20SD"])
+def test_tl_absorption_values_and_derivatives(gpu_ctx, name):
+    torch = _torch_cuda()
+    frq = np.append(pr.HATPRO_FRQS, 183.31)
+    P = pr.synthetic_profiles(3, 41, nlev=40)
+    P["rh"][0, 6] = 0.0                                          # a dry level
+    P["t"][2, 9] = np.nan                                        # a NaN profile
+    p, t, rh = _dev(torch, P, ("p", "t", "rh"))
+    nprof, nlev = p.shape
+    out = [torch.empty((nprof, len(frq), nlev), dtype=torch.float64, device="cuda") for _ in range(6)]
+    gpu_ctx.absorption_tl_batch_device(name, nprof, nlev, p.data_ptr(), t.data_ptr(), rh.data_ptr(), frq,
+                                       *[o.data_ptr() for o in out], stream=_cur(torch))
+    ref = [torch.empty_like(out[0]) for _ in range(2)]
+    gpu_ctx.set_absorption_mode(1)
+    try:
+        gpu_ctx.absorption_batch_device(name, nprof, nlev, p.data_ptr(), t.data_ptr(), rh.data_ptr(), frq,
+                                        ref[0].data_ptr(), ref[1].data_ptr(), stream=_cur(torch))
+    finally:
+        gpu_ctx.set_absorption_mode(0)
+    torch.cuda.synchronize()
+    aw, ad, dwt, dwe, ddt, dde = (o.cpu().numpy() for o in out)
+    for got, want in ((aw, ref[0].cpu().numpy()), (ad, ref[1].cpu().numpy())):
+        assert np.array_equal(np.isnan(got), np.isnan(want))
+        scale = np.nanmax(np.abs(want), axis=-1, keepdims=True)
+        assert (np.nan_to_num(np.abs(got - want)) <= 1e-9 * np.abs(np.nan_to_num(want)) + 1e-13 * scale).all()
+    assert all(np.isnan(x[2, :, 9]).all() for x in (ad, dwt, dwe, ddt, dde))     # (awet is 0 there, as in the forward)
+    # derivatives against central differences of the oracle's clearsky_absorption
+    m = sp.get_model(name)
+    for i in range(2):
+        e = lo.vapor(P["t"][i], P["rh"][i])[0]
+        for j, f in enumerate(frq):
+            def ab(tk, ee):
+                return lo.clearsky_absorption(m, P["p"][i], tk, ee, f)
+            base = ab(P["t"][i], e)
+            hT = 1e-3
+            fd = {}
+            up, dn = ab(P["t"][i] + hT, e), ab(P["t"][i] - hT, e)
+            fd["t"] = [((up[s] - dn[s]) / (2 * hT), (up[s] - base[s]) / hT, (base[s] - dn[s]) / hT) for s in (0, 1)]
+            fd["e"] = []
+            for s in (0, 1):
+                # e +- 1e-5 e for the wet term (it scales with e); the dry term barely depends on e, and a relative step at
+                # the top of the profile (e ~ 1e-4 hPa) would leave the oracle's rounding larger than the derivative, so it
+                # takes an absolute step of 1e-5 of the profile's largest e (one-sided where e is smaller than that)
+                he = np.where(e > 0, 1e-5 * e, 1e-6) if s == 0 else np.full_like(e, 1e-5 * e.max())
+                two = e > he
+                up, dn = ab(P["t"][i], e + he), ab(P["t"][i], np.where(two, e - he, e))
+                fwd = (up[s] - base[s]) / he
+                bwd = np.where(two, (base[s] - dn[s]) / he, fwd)
+                fd["e"].append((np.where(two, (up[s] - dn[s]) / (2 * he), fwd), fwd, bwd))
+            for (var, s), got in ((("t", 0), dwt), (("e", 0), dwe), (("t", 1), ddt), (("e", 1), dde)):
+                c, fwd, bwd = fd[var][s]
+                g = got[i, j]
+                scale = np.abs(c).max()
+                if scale == 0.0:
+                    assert np.abs(g).max() <= 1e-12, (name, var, s, f)
+                    continue
+                # a point whose +- evaluations straddle a branch (SD switch, 750-GHz cutoff, O2 clamp) has no derivative
+                # to compare against: its one-sided differences disagree by far more than the curvature term (~1e-5)
+                smooth = np.abs(fwd - bwd) <= 1e-4 * scale
+                assert smooth.mean() > 0.9, (name, var, s, f)
+                err = np.abs(g - c)[smooth]
+                assert err.max() <= 1e-6 * scale, (name, var, s, f, err.max() / scale)
+
+
+@pytest.mark.gpu
+def test_device_k_matrix_against_host_k_matrix(gpu_ctx):
+    torch = _torch_cuda()
+    frq, ang = pr.HATPRO_FRQS, pr.BENCH_ELEVATIONS_7
+    P = pr.synthetic_profiles(200, 2)
+    tb, valid, jac = _k_matrix_device(gpu_ctx, torch, "R24", P, frq, ang)
+    z, p, t, rh = _dev(torch, P)
+    fwd = torch.empty_like(tb)
+    fv = torch.empty_like(valid)
+    gpu_ctx.tb_batch_device("R24", 200, 180, z.data_ptr(), p.data_ptr(), t.data_ptr(), rh.data_ptr(), frq, ang,
+                            fwd.data_ptr(), fv.data_ptr(), stream=_cur(torch))
+    torch.cuda.synchronize()
+    tb, valid, fwd = tb.cpu().numpy(), valid.cpu().numpy(), fwd.cpu().numpy()
+    jac = {k: v.cpu().numpy() for k, v in jac.items()}
+    assert (valid == 1).all()
+    assert np.abs(tb - fwd).max() <= 1e-8
+    htb, hvalid, hjac = gpu_ctx.tb_jacobian_batch("R24", P["z"], P["p"], P["t"], P["rh"], frq, ang)
+    assert (hvalid == 1).all() and np.abs(htb - tb).max() <= 1e-8
+    # thickness derivatives: both analytic
+    scale = np.abs(hjac["dtb_ddz"]).max(axis=-1, keepdims=True)
+    assert (np.abs(jac["dtb_ddz"] - hjac["dtb_ddz"]) <= 1e-8 * scale).all()
+    # T and e: the host differences its absorption (T +- 0.01 K, e (1 +- 1e-4)); the device is exact
+    m = sp.get_model("R24")
+    for k in ("dtb_dt", "dtb_de"):
+        scale = np.abs(hjac[k]).max(axis=-1, keepdims=True)
+        rel = np.abs(jac[k] - hjac[k]) / np.maximum(scale, 1e-300)
+        if k == "dtb_de":
+            assert np.abs(jac[k] - hjac[k]).max() <= 2e-5 * np.abs(hjac[k]).max()
+            # at the top of the profiles the host's step is 1e-7 hPa and its difference carries the forward absorption's
+            # regrouping rounding (~1e-12 relative): the repository's row-by-row finite-difference floor
+            assert (rel <= 1e-3).all(), (k, rel.max())
+            continue
+        # ... and where the host's +- 0.01 K straddles a branch of the absorption (the speed-dependent switch at ten
+        # half-widths), its central difference is meaningless: every other entry agrees to 2e-5 of its row
+        off = np.argwhere(rel > 2e-5)
+        assert len(off) <= 1e-4 * rel.size, len(off)
+        for i, j, l in {(i, j, l) for i, _, j, l in off}:
+            e = lo.vapor(P["t"][i][l:l + 1], P["rh"][i][l:l + 1])[0]
+            ab = [lo.clearsky_absorption(m, P["p"][i][l:l + 1], P["t"][i][l:l + 1] + d, e, frq[j]) for d in (-0.01, 0.0, 0.01)]
+            kink = max(abs((ab[2][s][0] - ab[1][s][0]) - (ab[1][s][0] - ab[0][s][0])) / abs(ab[2][s][0] - ab[0][s][0]) for s in (0, 1))
+            assert kink > 1e-2, (i, j, l, kink)
+    # one 180-level profile against oracle differences
+    i = 7
+    _, ref = oracle_k_matrix(sp.get_model("R24"), *(P[k][i] for k in ("z", "p", "t", "rh")), frq, ang)
+    for k in ("dtb_dt", "dtb_de", "dtb_ddz"):
+        assert np.abs(jac[k][i] - ref[k]).max() <= 2e-5 * np.abs(ref[k]).max(), k
+
+
+@pytest.mark.gpu
+def test_device_k_matrix_nan_rules(gpu_ctx):
+    torch = _torch_cuda()
+    frq = pr.HATPRO_FRQS[[0, 3, 7, 13]]
+    ang = np.array([90.0, np.nan, 30.0])
+    P = pr.synthetic_profiles(3, 5, nlev=50)
+    P["rh"][1, 20] = np.nan
+    tb, valid, jac = _k_matrix_device(gpu_ctx, torch, "R98", P, frq, ang)
+    torch.cuda.synchronize()
+    tb, valid = tb.cpu().numpy(), valid.cpu().numpy()
+    jac = {k: v.cpu().numpy() for k, v in jac.items()}
+    assert valid.tolist() == [1, 0, 1]
+    assert np.isnan(tb[1]).all() and all(np.isnan(v[1]).all() for v in jac.values())
+    for i in (0, 2):                     # the NaN elevation blanks its own rows only
+        assert np.isnan(tb[i, 1]).all() and all(np.isnan(v[i, 1]).all() for v in jac.values())
+        assert np.isfinite(tb[i, [0, 2]]).all() and all(np.isfinite(v[i, [0, 2]]).all() for v in jac.values())
+    bad = dataclasses.replace(sp.get_model("R98"), name="R98_negcont_jac", h2o_cf=-1e-6)
+    tb, valid, jac = _k_matrix_device(gpu_ctx, torch, bad, P, frq, np.array([90.0]))
+    torch.cuda.synchronize()
+    assert valid.cpu().tolist() == [2, 0, 2]
+    assert torch.isnan(tb).all() and all(torch.isnan(v).all() for v in jac.values())
+
+
+@pytest.mark.gpu
+def test_device_k_matrix_streams_and_memory(gpu_ctx):
+    torch = _torch_cuda()
+    frq, ang = pr.HATPRO_FRQS, pr.BENCH_ELEVATIONS_7
+    P = pr.synthetic_profiles(64, 3)
+    ref = _k_matrix_device(gpu_ctx, torch, "R24", P, frq, ang)
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        got = _k_matrix_device(gpu_ctx, torch, "R24", P, frq, ang)          # on s: torch's current stream there
+    s.synchronize()
+    assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1])
+    assert all(torch.equal(got[2][k], ref[2][k]) for k in ref[2])
+    # ten identical calls after a warm-up allocate nothing (the workspace at this size is 121 MB)
+    Q = pr.synthetic_profiles(1000, 2)
+    z, p, t, rh = _dev(torch, Q)
+    opts = dict(dtype=torch.float64, device="cuda")
+    tb = torch.empty((1000, 7, 14), **opts)
+    jac = [torch.empty((1000, 7, 14, 180), **opts) for _ in range(3)]
+    valid = torch.empty(1000, dtype=torch.uint8, device="cuda")
+    args = ("R24", 1000, 180, z.data_ptr(), p.data_ptr(), t.data_ptr(), rh.data_ptr(), frq, ang, tb.data_ptr(),
+            *[j.data_ptr() for j in jac], valid.data_ptr())
+    gpu_ctx.tb_jacobian_batch_device(*args, stream=_cur(torch))
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    for _ in range(10):
+        gpu_ctx.tb_jacobian_batch_device(*args, stream=_cur(torch))
+    torch.cuda.synchronize()
+    free1 = torch.cuda.mem_get_info()[0]
+    assert free0 - free1 < 64 << 20
+    assert (valid == 1).all()
+
+
+@pytest.mark.gpu
+def test_autograd_on_device_against_oracle(gpu_ctx):
+    torch = _torch_cuda()
+    from mwr_fast_forward_operators_and_lbls_amd import autodiff
+    tables = sp.get_model("R24")
+    P = pr.synthetic_profiles(1, 13, nlev=30)
+    z, p, t, rh = _dev(torch, P)
+    xs = [x.clone().requires_grad_(True) for x in (z, t, rh)]
+    tb, valid = autodiff.brightness_temperature(tables, xs[0], p, xs[1], xs[2], SMALL_FRQ, SMALL_ANG)
+    tb.sum().backward()
+    assert valid.cpu().tolist() == [1]
+    direct = oracle_direct_gradients(tables, *(P[k][0] for k in ("z", "p", "t", "rh")), SMALL_FRQ, SMALL_ANG)
+    for x, k in zip(xs, ("z", "t", "rh")):
+        got, want = x.grad[0].cpu().numpy(), direct[k].sum(axis=(0, 1))
+        assert np.abs(got - want).max() <= 1e-4 * np.abs(want).max(), k
+    # without grad: the forward call alone, same TBs
+    with torch.no_grad():
+        tb0, _ = autodiff.brightness_temperature(tables, z, p, t, rh, SMALL_FRQ, SMALL_ANG)
+    assert (tb0 - tb.detach()).abs().max().item() <= 1e-8
+    with pytest.raises(NotImplementedError):
+        autodiff.brightness_temperature(tables, z, p.clone().requires_grad_(True), t, rh, SMALL_FRQ, SMALL_ANG)
