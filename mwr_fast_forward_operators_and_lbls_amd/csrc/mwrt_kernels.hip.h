@@ -2561,7 +2561,9 @@ k_tb_jacobian(const JacArgs A) {
       const double tau = (layer_value_grad(aw[l], aw[l - 1], g1, g0, neg) * dz + layer_value_grad(ad[l], ad[l - 1], g1, g0, neg) * dz) * am;
       const double E = exp(-tau);
       const double bl = 1.0 / (exp(hvk / t[l]) - 1.0);
-      Btot += (bprev + bl * E) / (1.0 + E) * T * (1.0 - E);
+      const double c = (bprev + bl * E) / (1.0 + E) * T * (1.0 - E);
+      Btot += c;
+      o_z[l] = c;                                                 // (scratch until walk 2: c_l T_{l-1})
       T *= E;
       bprev = bl;
     }
@@ -2574,13 +2576,18 @@ k_tb_jacobian(const JacArgs A) {
   A.tb[orow] = hvk / Lg;
   const double dTB_dB = hvk / (Lg * Lg * Btot * (Btot + 1.0));
   if (isnan(am)) { blank(1); return; }                          // a NaN elevation: its rows are NaN, the profile stays valid
+  // the radiance reaching the antenna from above each layer, sum_{m > l} c_m T_{m-1} + the cosmic term, summed from the
+  // top down into o_z[l] (B_tot - S_l would cancel to ~eps B_tot where it is tiny, at levels an opaque path hides)
+  {
+    double above = with_bg ? bbg * T : 0.0;
+    for (int l = nlev - 1; l >= 1; --l) { const double c = o_z[l]; o_z[l] = above; above += c; }
+  }
   // ---- walk 2: derivatives ----
   const double inv2dT = 0.5 / A.dT;
   auto dA = [&](int species, int lvl, bool wrt_e) {             // d(absorption)/dT or /de at a level, central difference
     const double hi = A.a[wrt_e ? 3 : 1][species][arow + lvl], lo = A.a[wrt_e ? 4 : 2][species][arow + lvl];
     return wrt_e ? (hi - lo) / (2.0 * A.de[prof * nlev + lvl]) : (hi - lo) * inv2dT;
   };
-  double S = 0.0;                                               // sum_{m <= l} c_m T_{m-1}
   double Tm = 1.0;
   double b0 = 1.0 / (exp(hvk / t[0]) - 1.0);
   double acc_t = 0.0, acc_e = 0.0;                              // contributions to level l-1 collected so far
@@ -2593,11 +2600,9 @@ k_tb_jacobian(const JacArgs A) {
     const double E = exp(-tau);
     const double b1 = 1.0 / (exp(hvk / t[l]) - 1.0);
     const double opE = 1.0 + E, omE = 1.0 - E;
-    const double c = (b0 + b1 * E) / opE * omE;
-    S += c * Tm;
     const double dc_dtau = E * (2.0 * b0 + 2.0 * b1 * E - b1 + b1 * E * E) / (opE * opE);
-    // everything above layer l (later layers and the cosmic term) is dimmed by E_l
-    const double g = dTB_dB * (Tm * dc_dtau - (Btot - S));                       // dTB/dtau_l
+    // everything above layer l (later layers and the cosmic term, o_z[l] from the top-down sum) is dimmed by E_l
+    const double g = dTB_dB * (Tm * dc_dtau - o_z[l]);                          // dTB/dtau_l
     const double gk = g * am * dz;
     // level l-1 (lower end of the layer) and level l (upper end)
     acc_t += gk * (w0 * dA(0, l - 1, false) + d0 * dA(1, l - 1, false)) + dTB_dB * Tm * (omE / opE) * (b0 * (b0 + 1.0) * hvk / (t[l - 1] * t[l - 1]));
@@ -2605,7 +2610,8 @@ k_tb_jacobian(const JacArgs A) {
     o_t[l - 1] = acc_t; o_e[l - 1] = acc_e;
     acc_t = gk * (w1 * dA(0, l, false) + d1 * dA(1, l, false)) + dTB_dB * Tm * (E * omE / opE) * (b1 * (b1 + 1.0) * hvk / (t[l] * t[l]));
     acc_e = gk * (w1 * dA(0, l, true) + d1 * dA(1, l, true));
-    o_z[l] = (dz != 0.0) ? g * tau / dz : 0.0;                                  // dTB / d(thickness of layer l) [K/km]
+    // dTB / d(thickness of layer l) [K/km]: tau_l = m (Lw + Ld) dz_l is linear in dz_l, so this holds at dz_l = 0 too
+    o_z[l] = g * am * (Lw + Ld);
     Tm *= E;
     b0 = b1;
   }

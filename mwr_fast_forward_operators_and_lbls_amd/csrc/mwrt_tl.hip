@@ -333,6 +333,25 @@ __device__ __forceinline__ double block_scan(double v, double* wsum, int tid, in
   return v + off;
 }
 
+// exclusive suffix sum over the workgroup: the sum of v over the lanes above tid (lanes by shuffles, then the waves
+// above in a fixed order: deterministic).  Summed from the top down, never as a total minus a prefix: where the terms
+// above are tiny (levels an opaque path hides) the result keeps its relative accuracy.
+__device__ __forceinline__ double block_suffix_excl(double v, double* wsum, int tid, int nwaves) {
+  const int lane = tid & (WAVE - 1), wave = tid / WAVE;
+#pragma unroll
+  for (int o = 1; o < WAVE; o <<= 1) {
+    const double u = __shfl_down(v, o, WAVE);
+    if (lane + o < WAVE) v += u;
+  }
+  __syncthreads();                     // (wsum may still be read by a previous scan)
+  if (lane == 0) wsum[wave] = v;       // the wave's total
+  __syncthreads();
+  const double nxt = __shfl_down(v, 1, WAVE);
+  double off = 0.0;
+  for (int w = nwaves - 1; w > wave; --w) off += wsum[w];
+  return ((lane + 1 < WAVE) ? nxt : 0.0) + off;
+}
+
 __global__ void __launch_bounds__(1024)
 k_jac_rte(const JacRteArgs A) {
   extern __shared__ double smem[];
@@ -412,14 +431,17 @@ k_jac_rte(const JacRteArgs A) {
     const double Tl = Tm1 * E;
     const double Pc = lay ? (bm + b * E) * th * Tm1 : 0.0;
     double Bsum;
-    const double S = block_scan(Pc, wsum, tid, nwaves, Bsum);
+    (void)block_scan(Pc, wsum, tid, nwaves, Bsum);
     const double Ttop = fexp(-am * tau_tot);
     const double Btot = (Ttop > TRANS_MIN) ? __builtin_fma(bbg, Ttop, Bsum) : Bsum;
+    // radiance reaching the antenna from above layer l (sum_{m > l} c_m T_{m-1} + the cosmic term), summed directly:
+    // B_tot - S_l would cancel to ~eps B_tot where it is tiny
+    const double above = block_suffix_excl(Pc, wsum, tid, nwaves) + ((Ttop > TRANS_MIN) ? bbg * Ttop : 0.0);
     const double Lg = flog(1.0 + fdiv(1.0, Btot));
     const double dTB_dB = fdiv(hvk, Lg * Lg * Btot * (Btot + 1.0));
     const double opE = 1.0 + E;
     const double dc_dtau = fdiv(E * (2.0 * bm + 2.0 * b * E - b + b * E * E), opE * opE);
-    const double g = lay ? dTB_dB * (Tm1 * dc_dtau - (Btot - S)) : 0.0;  // dTB / dtau_l (everything above l is dimmed)
+    const double g = lay ? dTB_dB * (Tm1 * dc_dtau - above) : 0.0;       // dTB / dtau_l (everything above l is dimmed)
     const double gk = g * am * dz;
     s0[tid] = gk; s1[tid] = th;
     __syncthreads();
@@ -431,7 +453,8 @@ k_jac_rte(const JacRteArgs A) {
     ce += gkn * (w0n * awE + d0n * adE);
     if (live) {
       o_t[tid] = ct; o_e[tid] = ce;
-      o_z[tid] = (lay && dz != 0.0) ? g * am * (Lw + Ld) : 0.0;          // dTB / d(thickness of layer l) [K/km]
+      // dTB / d(thickness of layer l) [K/km]: tau_l = m (Lw + Ld) dz_l is linear in dz_l, so this holds at dz_l = 0 too
+      o_z[tid] = lay ? g * am * (Lw + Ld) : 0.0;
     }
     if (tid == 0) A.tb[row] = fdiv(hvk, Lg);
   }
