@@ -45,3 +45,16 @@ if __name__ == "__main__":
     print("liquid water path %.0f g m-2; ray tracing cools the 4.2-degree K-band TBs by %.1f ... %.1f K"
           % (float(np.sum(0.5 * (denliq[1:] + denliq[:-1]) * np.diff(z))) * 1000.0,
              (base - rows["clear, ray tracing"])[3, :7].min(), (base - rows["clear, ray tracing"])[3, :7].max()))
+
+    # dTB/dLWP per channel from the device K-matrix under cloud: scale the cloud column uniformly (denliq -> (1 + s)
+    # denliq, so LWP -> (1 + s) LWP) and contract dtb_dliq [K per g m-3] with it: dTB/dLWP = sum_i dtb_dliq_i denliq_i / LWP
+    import torch
+    from mwr_fast_forward_operators_and_lbls_amd import autodiff
+    dev = [torch.tensor(x[None], dtype=torch.float64, device="cuda") for x in (z, p, t, rh, denliq)]
+    dl = dev[4].clone().requires_grad_(True)
+    lwp = float(np.sum(0.5 * (denliq[1:] + denliq[:-1]) * np.diff(z))) * 1000.0
+    print("dTB/dLWP [K per 100 g m-2] at the zenith, per channel:")
+    for j, f in enumerate(frqs):
+        tb, _ = autodiff.brightness_temperature("R17", dev[0], dev[1], dev[2], dev[3], frqs[j:j + 1], ang[:1], denliq=dl)
+        (g,) = torch.autograd.grad(tb.sum(), dl)
+        print(f"  {f:6.2f} GHz  {100.0 * float((g * dl).sum()) / lwp:7.3f}")

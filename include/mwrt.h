@@ -315,7 +315,8 @@ int mwrt_tb_jacobian_batch(mwrt_context* ctx, const mwrt_model* model,
                            int32_t nf, const double* frq_ghz, int32_t nang, const double* elev_deg,
                            double* tb_out, double* dtb_dt, double* dtb_de, double* dtb_ddz, uint8_t* valid_out);
 
-/* The device K-matrix path.  Clear sky, plane-parallel.  Both entries are independent of
+/* The device K-matrix path.  Plane-parallel; clear sky, or cloud liquid / ice through
+ * mwrt_tb_jacobian_batch_opt_device.  All entries are independent of
  * mwrt_set_absorption_mode and mwrt_set_chunk_width: the absorption is summed over every line at every frequency.
  *
  * mwrt_absorption_tl_batch_device: clearsky_absorption and its exact partial derivatives (tangent-linear, not finite
@@ -345,6 +346,44 @@ int mwrt_tb_jacobian_batch_device(mwrt_context* ctx, const mwrt_model* model, in
                                   int32_t nf, const double* frq_ghz, int32_t nang, const double* elev_deg,
                                   double* d_tb, double* d_dtb_dt, double* d_dtb_de, double* d_dtb_ddz, uint8_t* d_valid,
                                   void* stream);
+
+/* mwrt_tb_jacobian_batch_device under cloud: the K-matrix of the operator mwrt_tb_batch_opt_device computes with
+ * d_options->denliq / denice (DEVICE pointers [nprof][nlev], g m-3; either may be NULL), and two more Jacobians,
+ *   d_dtb_dliq  K per g m-3   d TB / d denliq_i        d_dtb_dice  K per g m-3   d TB / d denice_i
+ * [nprof][nang][nf][nlev] each; either may be NULL (not wanted).  The T, e and thickness Jacobians carry the cloud's
+ * optical depth.  All cloud work happens inside k_jac_rte: no further launch and no further workspace.
+ * (MWRT_VERSION stays 301, as it did when the clear-sky device K-matrix was added: the symbol is an addition.)
+ *   Refused: options->ray_tracing != 0 or options->o3n != NULL -> MWRT_ERR_UNSUPPORTED (the adjoint is plane-parallel and
+ *   has no ozone tangent); d_dtb_dliq without denliq, or d_dtb_dice without denice -> MWRT_ERR_INVALID_ARGUMENT.
+ *   Clear sky: d_options NULL, or both cloud pointers NULL, is mwrt_tb_jacobian_batch_device itself (which calls this
+ *   entry), bit for bit; so is a call whose cloud arrays hold no positive entry (its cloud rows are all 0).  Streams,
+ *   workspace, NaN-frequency handling and the no-allocation / no-synchronisation claim after one warm-up call are the clear entry's.
+ *   Flags: a NaN in denliq / denice -> valid 0, every row of the profile NaN, as the forward kernel.  A negative cloud
+ *   absorption coefficient -> valid 2; it can arise only per frequency (a negative frequency under ice, or a temperature
+ *   far outside the liquid model's range), and the rows of the frequencies where it arises are NaN.
+ * Derivative conventions -- the derivative of the branch the forward takes, as for the clear rows:
+ *   aliq_i = denliq_i * kappa(T_i, f) for denliq_i > 0, else 0: d aliq / d denliq = kappa, d aliq / dT = denliq * d kappa / dT
+ *     (kappa: LiqAbsModel.liquid_water_absorption per g m-3, either liq_mode, differentiated exactly);
+ *   aice_i = k_ice * f * denice_i for denice_i > 0, else 0: no T tangent;
+ *   a density <= 0 is "no cloud": its derivative is 0;
+ *   the layer rule is exponential_integration(zeroflg = False): a layer with a zero end value has the value 0 and the
+ *     partials (0, 0).  (The log-mean's own one-sided slope at a zero end is infinite: a forward difference of 1e-4 g m-3
+ *     there gives 4e3 - 1.5e4 K per g m-3 and grows as the step shrinks.)  So an ISOLATED cloudy level -- both
+ *     neighbours without cloud -- contributes nothing to the TBs and its row entries are all 0; cloud shows from two
+ *     adjacent cloudy levels on;
+ *   |x1 - x0| < 1e-9 gives the value x1 and the partials (1, 0); otherwise the log-mean partials of the clear rows;
+ *   dtb_dt (fixed e) gains the liquid term; dtb_ddz is g m (Lw + Ld + Ll + Li); dtb_de keeps its form;
+ *   a layer's optical depth is summed as the forward does, ((wet + dry) + ice) + liquid, so the TBs equal
+ *     mwrt_tb_batch_opt_device's to 1e-8 K.
+ * Not yet timed on a GPU (DESIGN.md 4.5.2 says what has been measured); k_jac_rte keeps the occupancy (5 waves/SIMD) and
+ * the 0 bytes of scratch it had before the cloud path. */
+int mwrt_tb_jacobian_batch_opt_device(mwrt_context* ctx, const mwrt_model* model, int64_t nprof, int32_t nlev,
+                                      const double* d_z_km, const double* d_p_hpa, const double* d_t_k,
+                                      const double* d_rh_frac,
+                                      int32_t nf, const double* frq_ghz, int32_t nang, const double* elev_deg,
+                                      double* d_tb, double* d_dtb_dt, double* d_dtb_de, double* d_dtb_ddz,
+                                      double* d_dtb_dliq, double* d_dtb_dice, uint8_t* d_valid,
+                                      const mwrt_tb_options* d_options, void* stream);
 
 /* Diagnostic: evaluates the kernels' own exp / log / division helpers (fexp, flog, fdiv, fdiv1) on
  * host arrays x[n], y_pos[n] (y > 0), so their accuracy can be checked against libm. */

@@ -83,6 +83,9 @@ SIGNATURES = {
                                                        _vp, _vp, _vp]),
     "mwrt_tb_jacobian_batch_device": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp,
                                                      _vp, _vp, _vp, _vp, _vp]),
+    "mwrt_tb_jacobian_batch_opt_device": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp,
+                                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(MwrtTbOptions),
+                                                         _vp]),
     "mwrt_set_absorption_mode": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_set_chunk_width": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_selftest_math": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -407,6 +410,27 @@ class Context:
             self._handle, self.model(model), int(nprof), int(nlev), _ptr(d_z), _ptr(d_p), _ptr(d_t), _ptr(d_rh),
             frq.size, _ptr(frq), elev.size, _ptr(elev), _ptr(d_tb), _ptr(d_dtb_dt), _ptr(d_dtb_de), _ptr(d_dtb_ddz),
             _ptr(d_valid), _stream(stream)), "mwrt_tb_jacobian_batch_device")
+
+    @_serialised
+    def tb_jacobian_batch_opt_device(self, model, nprof, nlev, d_z, d_p, d_t, d_rh, frq, elev, d_tb, d_dtb_dt, d_dtb_de,
+                                     d_dtb_ddz, d_valid, d_denliq=None, d_denice=None, d_dtb_dliq=None, d_dtb_dice=None,
+                                     stream=None, ray_tracing=False, d_o3n=None):
+        """The K-matrix under cloud liquid / ice (include/mwrt.h mwrt_tb_jacobian_batch_opt_device): as
+        ``tb_jacobian_batch_device`` with ``d_denliq`` / ``d_denice`` [nprof][nlev] (g m-3) as inputs and ``d_dtb_dliq`` /
+        ``d_dtb_dice`` [nprof][nang][nf][nlev] (K per g m-3) as further outputs; each may be None.  ``ray_tracing`` and
+        ``d_o3n`` exist to be refused (MWRT_ERR_UNSUPPORTED)."""
+        frq, elev = _f64(frq).ravel(), _f64(elev).ravel()
+        opts = None
+        if d_denliq is not None or d_denice is not None or ray_tracing or d_o3n is not None:
+            opts = MwrtTbOptions(int(d_denliq) if d_denliq is not None else None,
+                                 int(d_denice) if d_denice is not None else None, int(bool(ray_tracing)), 0,
+                                 int(d_o3n) if d_o3n is not None else None)
+        self._check(self._lib.mwrt_tb_jacobian_batch_opt_device(
+            self._handle, self.model(model), int(nprof), int(nlev), _ptr(d_z), _ptr(d_p), _ptr(d_t), _ptr(d_rh),
+            frq.size, _ptr(frq), elev.size, _ptr(elev), _ptr(d_tb), _ptr(d_dtb_dt), _ptr(d_dtb_de), _ptr(d_dtb_ddz),
+            _ptr(d_dtb_dliq) if d_dtb_dliq is not None else None, _ptr(d_dtb_dice) if d_dtb_dice is not None else None,
+            _ptr(d_valid), ctypes.byref(opts) if opts is not None else None, _stream(stream)),
+            "mwrt_tb_jacobian_batch_opt_device")
 
     def layer_tau_pitch(self, nf: int) -> int:
         """Doubles between consecutive levels of a layer-optical-depth array for nf frequencies (multiple of 16)."""

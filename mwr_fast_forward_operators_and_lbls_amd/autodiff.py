@@ -13,6 +13,8 @@ the incoming gradient on the device and applies the chain rule to the op's own v
     dTB/dt|rh = dtb_dt + dtb_de * rh * des/dT,   dTB/drh = dtb_de * es(T),   dTB/dz_i = dtb_ddz_i - dtb_ddz_{i+1}
 
 (es: Goff-Gratch over water, as RTEquation.vapor; level i is the top of one layer and the bottom of the next).
+With ``denliq`` / ``denice`` (cloud liquid / ice, g m-3) the same holds through ``mwrt_tb_batch_opt_device`` and
+``mwrt_tb_jacobian_batch_opt_device``; two more saved Jacobians give ``grad_denliq = sum_{ang, f} g * dtb_dliq`` (ice alike).
 No pressure derivative is computed: ``p.requires_grad`` raises NotImplementedError.  A profile flagged invalid
 (valid 0: NaN input, 2: negative absorption) gets NaN gradients -- NaN in, NaN out.
 """
@@ -54,8 +56,41 @@ def _native_jacobian(model, z, p, t, rh, frq, elev, stream):
     return (tb, valid, *jac)
 
 
-def _check_device(z, p, t, rh):
-    for name, x in (("z", z), ("p", p), ("t", t), ("rh", rh)):
+def _native_tb_cloudy(model, z, p, t, rh, denliq, denice, frq, elev, stream):
+    """TBs only under cloud: one ``mwrt_tb_batch_opt_device`` call.  Returns (tb, valid)."""
+    nprof, nlev = _check_device(z, p, t, rh, denliq=denliq, denice=denice)
+    tb = torch.empty((nprof, elev.size, frq.size), dtype=torch.float64, device=z.device)
+    valid = torch.empty(nprof, dtype=torch.uint8, device=z.device)
+    _native.default_context(z.device.index or 0).tb_batch_device(
+        model, nprof, nlev, z.data_ptr(), p.data_ptr(), t.data_ptr(), rh.data_ptr(), frq, elev, tb.data_ptr(),
+        valid.data_ptr(), stream=_stream_of(z, stream),
+        d_denliq=None if denliq is None else denliq.data_ptr(), d_denice=None if denice is None else denice.data_ptr())
+    return tb, valid
+
+
+def _native_jacobian_cloudy(model, z, p, t, rh, denliq, denice, frq, elev, stream):
+    """The K-matrix under cloud: one ``mwrt_tb_jacobian_batch_opt_device`` call.  Returns (tb, valid, dtb_dt, dtb_de,
+    dtb_ddz, dtb_dliq, dtb_dice); a cloud Jacobian is None where its input is.
+
+    The single place the cloudy op reaches the native library: CPU tests substitute a reference stand-in here."""
+    nprof, nlev = _check_device(z, p, t, rh, denliq=denliq, denice=denice)
+    opts = dict(dtype=torch.float64, device=z.device)
+    tb = torch.empty((nprof, elev.size, frq.size), **opts)
+    jac = [torch.empty((nprof, elev.size, frq.size, nlev), **opts) for _ in range(3)]
+    jl = None if denliq is None else torch.empty((nprof, elev.size, frq.size, nlev), **opts)
+    ji = None if denice is None else torch.empty((nprof, elev.size, frq.size, nlev), **opts)
+    valid = torch.empty(nprof, dtype=torch.uint8, device=z.device)
+    _native.default_context(z.device.index or 0).tb_jacobian_batch_opt_device(
+        model, nprof, nlev, z.data_ptr(), p.data_ptr(), t.data_ptr(), rh.data_ptr(), frq, elev, tb.data_ptr(),
+        jac[0].data_ptr(), jac[1].data_ptr(), jac[2].data_ptr(), valid.data_ptr(),
+        d_denliq=None if denliq is None else denliq.data_ptr(), d_denice=None if denice is None else denice.data_ptr(),
+        d_dtb_dliq=None if jl is None else jl.data_ptr(), d_dtb_dice=None if ji is None else ji.data_ptr(),
+        stream=_stream_of(z, stream))
+    return (tb, valid, *jac, jl, ji)
+
+
+def _check_device(z, p, t, rh, **cloud):
+    for name, x in (("z", z), ("p", p), ("t", t), ("rh", rh), *((k, v) for k, v in cloud.items() if v is not None)):
         if not x.is_cuda or x.dtype != torch.float64 or x.dim() != 2 or not x.is_contiguous():
             raise ValueError(f"{name}: expected a contiguous float64 [nprof][nlev] CUDA tensor")
         if x.shape != z.shape or x.device != z.device:
@@ -110,16 +145,62 @@ class _BrightnessTemperature(torch.autograd.Function):
                 grad_rh if ctx.needs_input_grad[2] else None, None, None, None, None, None)
 
 
-def brightness_temperature(model, z, p, t, rh, frq, elev, stream=None):
-    """Clear-sky plane-parallel downwelling TBs, differentiable with respect to z, t and rh.
+class _BrightnessTemperatureCloudy(torch.autograd.Function):
+    """The op under cloud liquid / ice: the clear op's backward plus grad_denliq = sum_{ang, f} g * dtb_dliq (ice alike)."""
+
+    @staticmethod
+    def forward(ctx, z, t, rh, denliq, denice, p, model, frq, elev, stream):
+        tb, valid, dtb_dt, dtb_de, dtb_ddz, dtb_dliq, dtb_dice = _native_jacobian_cloudy(
+            model, z, p, t, rh, denliq, denice, frq, elev, stream)
+        ctx.has_liq, ctx.has_ice = dtb_dliq is not None, dtb_dice is not None
+        ctx.save_for_backward(t, rh, valid, dtb_dt, dtb_de, dtb_ddz, *(x for x in (dtb_dliq, dtb_dice) if x is not None))
+        ctx.mark_non_differentiable(valid)
+        return tb, valid
+
+    @staticmethod
+    def backward(ctx, grad_tb, _grad_valid):
+        t, rh, valid, dtb_dt, dtb_de, dtb_ddz, *cloud = ctx.saved_tensors
+        dtb_dliq = cloud.pop(0) if ctx.has_liq else None
+        dtb_dice = cloud.pop(0) if ctx.has_ice else None
+        g = grad_tb.unsqueeze(-1)
+        keep = g != 0
+
+        def contract(j):
+            return torch.where(keep, j * g, torch.zeros((), dtype=j.dtype, device=j.device)).sum(dim=(1, 2))
+
+        gt, ge, gdz = contract(dtb_dt), contract(dtb_de), contract(dtb_ddz)
+        es, des_dt = goff_gratch_es(t)
+        grads = [gdz - torch.nn.functional.pad(gdz[:, 1:], (0, 1)), gt + ge * rh * des_dt, ge * es,
+                 contract(dtb_dliq) if dtb_dliq is not None else None,
+                 contract(dtb_dice) if dtb_dice is not None else None]
+        bad = (valid != 1).unsqueeze(-1)
+        nan = torch.full((), float("nan"), dtype=gt.dtype, device=gt.device)
+        grads = [torch.where(bad, nan, x) if x is not None and ctx.needs_input_grad[k] else None
+                 for k, x in enumerate(grads)]
+        return (*grads, None, None, None, None, None)
+
+
+def brightness_temperature(model, z, p, t, rh, frq, elev, stream=None, denliq=None, denice=None):
+    """Plane-parallel downwelling TBs, differentiable with respect to z, t and rh -- and, under cloud, with respect to
+    ``denliq`` / ``denice`` (cloud liquid / ice water content, g m-3, float64 [nprof][nlev] CUDA tensors; include/mwrt.h
+    ``mwrt_tb_jacobian_batch_opt_device`` states the derivative conventions: an isolated cloudy level has none).
 
     model: a model name or ModelTables record; z [km], p [hPa], t [K], rh [fraction]: float64 [nprof][nlev] CUDA tensors,
     ground -> top; frq [GHz] and elev [deg] host arrays.  ``stream``: a hipStream_t handle (default: torch's current
-    stream).  Returns ``tb [nprof][nang][nf]`` and ``valid [nprof]`` (uint8, include/mwrt.h)."""
+    stream).  Returns ``tb [nprof][nang][nf]`` and ``valid [nprof]`` (uint8, include/mwrt.h).  With both cloud arguments
+    None this is the clear-sky op; otherwise the forward is one ``mwrt_tb_batch_opt_device`` call without grad and one
+    ``mwrt_tb_jacobian_batch_opt_device`` call with."""
     if p.requires_grad:
         raise NotImplementedError("brightness_temperature: no derivative with respect to pressure is computed")
     frq = np.ascontiguousarray(frq, dtype=np.float64).ravel()
     elev = np.ascontiguousarray(elev, dtype=np.float64).ravel()
+    if denliq is not None or denice is not None:
+        cloud = [x for x in (denliq, denice) if x is not None]
+        if torch.is_grad_enabled() and any(x.requires_grad for x in (z, t, rh, *cloud)):
+            return _BrightnessTemperatureCloudy.apply(z, t, rh, denliq, denice, p, model, frq, elev, stream)
+        return _native_tb_cloudy(model, z.detach(), p, t.detach(), rh.detach(),
+                                 None if denliq is None else denliq.detach(),
+                                 None if denice is None else denice.detach(), frq, elev, stream)
     if torch.is_grad_enabled() and any(x.requires_grad for x in (z, t, rh)):
         return _BrightnessTemperature.apply(z, t, rh, p, model, frq, elev, stream)
     return _native_tb(model, z.detach(), p, t.detach(), rh.detach(), frq, elev, stream)

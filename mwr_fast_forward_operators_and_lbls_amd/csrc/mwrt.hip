@@ -1333,8 +1333,26 @@ int mwrt_tb_jacobian_batch_device(mwrt_context* c, const mwrt_model* m, int64_t 
                                   int32_t nf, const double* frq, int32_t nang, const double* elev,
                                   double* d_tb, double* d_dtb_dt, double* d_dtb_de, double* d_dtb_ddz, uint8_t* d_valid,
                                   void* stream) {
+  return mwrt_tb_jacobian_batch_opt_device(c, m, nprof, nlev, d_z, d_p, d_t, d_rh, nf, frq, nang, elev, d_tb, d_dtb_dt,
+                                           d_dtb_de, d_dtb_ddz, nullptr, nullptr, d_valid, nullptr, stream);
+}
+
+// The same with cloud liquid / ice (mwrt_tb_options.denliq / denice, device pointers): k_jac_rte forms the cloud
+// absorption and its tangents itself, so the workspace and the launches are those of the clear call.
+int mwrt_tb_jacobian_batch_opt_device(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
+                                      const double* d_z, const double* d_p, const double* d_t, const double* d_rh,
+                                      int32_t nf, const double* frq, int32_t nang, const double* elev,
+                                      double* d_tb, double* d_dtb_dt, double* d_dtb_de, double* d_dtb_ddz,
+                                      double* d_dtb_dliq, double* d_dtb_dice, uint8_t* d_valid,
+                                      const mwrt_tb_options* opt, void* stream) {
   int rc = check_common(c, m, nprof, nlev, nf);
   if (rc) return rc;
+  if (opt && opt->ray_tracing != 0) return fail(MWRT_ERR_UNSUPPORTED, "the K-matrix is plane-parallel: ray_tracing is not supported");
+  if (opt && opt->o3n) return fail(MWRT_ERR_UNSUPPORTED, "the K-matrix has no ozone tangent: o3n is not supported");
+  const double* d_denliq = opt ? opt->denliq : nullptr;
+  const double* d_denice = opt ? opt->denice : nullptr;
+  if (d_dtb_dliq && !d_denliq) return fail(MWRT_ERR_INVALID_ARGUMENT, "d_dtb_dliq given without options->denliq");
+  if (d_dtb_dice && !d_denice) return fail(MWRT_ERR_INVALID_ARGUMENT, "d_dtb_dice given without options->denice");
   if (nang < 1 || nang > MWRT_MAX_ANGLES) return fail(MWRT_ERR_INVALID_ARGUMENT, "nang out of range");
   if (!d_z || !d_p || !d_t || !d_rh || !frq || !elev || !d_tb || !d_dtb_dt || !d_dtb_de || !d_dtb_ddz || !d_valid)
     return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
@@ -1375,6 +1393,9 @@ int mwrt_tb_jacobian_batch_device(mwrt_context* c, const mwrt_model* m, int64_t 
   ja.frq = dev_frq; ja.airmass = dev_am;
   ja.tb = d_tb; ja.dtb_dt = d_dtb_dt; ja.dtb_de = d_dtb_de; ja.dtb_ddz = d_dtb_ddz; ja.valid = d_valid;
   ja.nlev = nlev; ja.nf = nf; ja.nang = nang;
+  ja.denliq = d_denliq; ja.denice = d_denice; ja.dtb_dliq = d_dtb_dliq; ja.dtb_dice = d_dtb_dice;
+  // with cloud arrays the kernel only lowers valid (k_jac_rte): preset it
+  if (d_denliq || d_denice) HIP_TRY(hipMemsetAsync(d_valid, 1, (size_t)nprof, st));
   timing_begin(c, st);
   e = launch_jac_rte(ja, nprof, st);
   timing_end(c, st);

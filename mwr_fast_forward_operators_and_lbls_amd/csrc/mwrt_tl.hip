@@ -1,6 +1,7 @@
 // mwrt_tl.hip -- the device K-matrix path: tangent-linear absorption (k_absorb_tl) and the adjoint RTE that consumes it
-// (k_jac_rte).  Declarations and argument records: mwrt_tl.hip.h; entry points: mwrt_absorption_tl_batch_device and
-// mwrt_tb_jacobian_batch_device in mwrt.hip; the mathematics: DESIGN.md section 4.5.
+// (k_jac_rte).  Declarations and argument records: mwrt_tl.hip.h; entry points: mwrt_absorption_tl_batch_device,
+// mwrt_tb_jacobian_batch_device and mwrt_tb_jacobian_batch_opt_device (cloud liquid / ice) in mwrt.hip; the
+// mathematics: DESIGN.md sections 4.5 - 4.5.2.
 #include "mwrt_tl.hip.h"
 
 namespace mwrt {
@@ -283,12 +284,15 @@ k_absorb_tl(const AbsorbTlArgs A) {
 // derivatives, which the lanes store as one contiguous row (level fastest: coalesced).
 // ---------------------------------------------------------------------------------------------
 
-// log-mean layer value and its two partial derivatives, branch for branch as layer_value<true>
+// log-mean layer value and its two partial derivatives, branch for branch as layer_value<ZEROFLG>.  ZEROFLG = false
+// (cloud liquid and ice): a layer with a zero end has the value 0 and the partials (0, 0) -- the derivative of the branch
+// taken; the log-mean's own one-sided slope at a zero end is infinite
+template <bool ZEROFLG = true>
 __device__ __forceinline__ double layer_value_tl(double x1, double x0, double& d1, double& d0, bool& neg) {
   if (x0 < 0.0 || x1 < 0.0) { neg = true; d1 = d0 = 0.0; return 0.0; }
   const double d = x1 - x0;
   if (fabs(d) < 1e-09) { d1 = 1.0; d0 = 0.0; return x1; }
-  if (x0 == 0.0 || x1 == 0.0) { d1 = d0 = 0.5; return 0.5 * (x1 + x0); }
+  if (x0 == 0.0 || x1 == 0.0) { d1 = d0 = ZEROFLG ? 0.5 : 0.0; return ZEROFLG ? 0.5 * (x1 + x0) : 0.0; }
   const double sm = x1 + x0, ism = fdiv(1.0, sm), s = d * ism;
   if (fabs(s) <= LOGMEAN_SMALL_S) {
     // L = sm/2 q(z), q = s/atanh(s), z = s^2:  dL/dx1 = q/2 + 2 s q'(z) x0/sm,  dL/dx0 = q/2 - 2 s q'(z) x1/sm
@@ -311,6 +315,77 @@ __device__ __forceinline__ double layer_value_tl(double x1, double x0, double& d
   d0 = (fdiv(L, x0) - 1.0) * iln;
   return L;
 }
+
+// nothing is scheduled across this point (keeps independent chains from being interleaved where that costs registers)
+#define MWRT_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
+
+// Cloud liquid absorption per unit water content and its exact T-derivative: kap = liquid_abs(cloud_level(M, tk), f, 1)
+// [Np/km per g m-3] as the forward kernels compute it, kapT = d kap / dT of those formulas (both liq_modes).  The complex
+// logarithms' values are clog_'s; their derivatives are quotients (d log w = dw / w), so nothing here differentiates atan2.
+__device__ __forceinline__ void liquid_abs_tl(cmodel M, double tk, double f, double& kap, double& kapT) {
+  cplx eps, deps;
+  if (M->liq_mode == 0) {
+    const double eps2 = 3.52;
+    const double thr = fdiv(300.0, tk), theta1 = 1.0 - thr, dth = fdiv(thr, tk);
+    const double eps0 = 77.66 - 103.3 * theta1, deps0 = -103.3 * dth;
+    const double a = 0.0671 * eps0, da = 0.0671 * deps0;
+    const double fp = (316.0 * theta1 + 146.4) * theta1 + 20.2, dfp = (632.0 * theta1 + 146.4) * dth;
+    const double b = fdiv(1.0, fp), db = -dfp * b * b;
+    const double c = fdiv(1.0, 39.8 * fp), dc = -39.8 * dfp * c * c;
+    // t = A r, r = 1 / (1 + i f b):  dt = dA r - t r (i f db)
+    const cplx r1 = crecip(cplx{1.0, f * b}), r2 = crecip(cplx{1.0, f * c});
+    const cplx t1 = cscale(r1, eps0 - a), t2 = cscale(r2, a - eps2);
+    const cplx dt1 = csub(cscale(r1, deps0 - da), cmul(cmul(t1, r1), cplx{0.0, f * db}));
+    const cplx dt2 = csub(cscale(r2, da), cmul(cmul(t2, r2), cplx{0.0, f * dc}));
+    eps = cplx{t1.re + t2.re + eps2, t1.im + t2.im};
+    deps = caddc(dt1, dt2);
+  } else {
+    const double tc = tk - 273.15;
+    const double lth = flog(fdiv(300.0, tk)), dlth = -fdiv(1.0, tk);
+    const double e1 = -43.7527 * fexp(0.05 * lth), e2 = 299.504 * fexp(1.47 * lth), e3 = -399.364 * fexp(2.11 * lth),
+                 e4 = 221.327 * fexp(2.31 * lth);
+    const double eps0 = e1 + e2 + e3 + e4;
+    const double deps0 = (0.05 * e1 + 1.47 * e2 + 2.11 * e3 + 2.31 * e4) * dlth;
+    const double a = 80.69715 * fexp(-tc * (1.0 / 226.45)), da = -a * (1.0 / 226.45);                // delta
+    const double qs = fdiv(1.0, tc + 133.07);
+    const double b = 1164.023 * fexp(fdiv(-651.4728, tc + 133.07)), db = b * 651.4728 * qs * qs;      // sd
+    const double c = 4.008724 * fexp(-tc * (1.0 / 103.05)), dc = -c * (1.0 / 103.05);                // delta_B
+    const double f1 = 10.46012 + tc * (0.1454962 + tc * (0.063267156 + tc * 0.00093786645));
+    const double df1 = 0.1454962 + tc * (2.0 * 0.063267156 + tc * (3.0 * 0.00093786645));
+    const cplx z1 = {-0.75 * f1, f1}, dz1 = {-0.75 * df1, df1};
+    // cnorm = log(z2 / z1), z1 = (-0.75 + i) f1:  d cnorm = -df1 / f1 (real), d (1 / cnorm) = (df1 / f1) / cnorm^2
+    // (the three complex logarithms one after the other: interleaved, their atan2 chains would set the kernel's register count)
+    const cplx icn = crecip(clog_(cdiv(cplx{-4500.0, 2000.0}, z1)));
+    MWRT_SCHED_FENCE();
+    const cplx dicn = cscale(cmul(icn, icn), fdiv(df1, f1));
+    const cplx icj = {icn.re, -icn.im}, dicj = {dicn.re, -dicn.im};
+    // kap0 = -delta z / (sd + z), z = i f
+    const cplx rb = crecip(cplx{b, f});
+    const cplx kap0 = cmul(cplx{0.0, -a * f}, rb);
+    const cplx dkap0 = csub(cmul(cplx{0.0, -da * f}, rb), cscale(cmul(kap0, rb), db));
+    // log((z - z2) / (z - z1)) and its conjugate-pole twin: d log = dz1 / (z - z1)
+    const cplx zp = {-z1.re, f - z1.im}, zj = {-z1.re, f + z1.im};
+    const cplx lp = clog_(cdiv(cplx{4500.0, f - 2000.0}, zp));
+    MWRT_SCHED_FENCE();
+    const cplx lj = clog_(cdiv(cplx{4500.0, f + 2000.0}, zj));
+    MWRT_SCHED_FENCE();
+    const cplx dlp = cdiv(dz1, zp), dlj = cdiv(cplx{dz1.re, -dz1.im}, zj);
+    const double hd = 0.5 * c, dhd = 0.5 * dc;
+    const cplx hlp = cscale(lp, hd), hlj = cscale(lj, hd);
+    const cplx chip = cmul(hlp, icn), chij = cmul(hlj, icj);
+    const cplx dchip = caddc(cmul(caddc(cscale(lp, dhd), cscale(dlp, hd)), icn), cmul(hlp, dicn));
+    const cplx dchij = caddc(cmul(caddc(cscale(lj, dhd), cscale(dlj, hd)), icj), cmul(hlj, dicj));
+    eps = cplx{eps0 + (kap0.re + (chip.re + chij.re - c)), kap0.im + (chip.im + chij.im)};
+    deps = cplx{deps0 + (dkap0.re + (dchip.re + dchij.re - dc)), dkap0.im + (dchip.im + dchij.im)};
+  }
+  // re = (eps - 1) / (eps + 2):  d re = 3 d eps / (eps + 2)^2
+  const cplx ie2 = crecip(cplx{eps.re + 2.0, eps.im});
+  const cplx re = cmul(cplx{eps.re - 1.0, eps.im}, ie2);
+  const cplx dre = cscale(cmul(deps, cmul(ie2, ie2)), 3.0);
+  kap = -0.06286 * re.im * f;
+  kapT = -0.06286 * dre.im * f;
+}
+#undef MWRT_SCHED_FENCE
 
 // inclusive prefix sum over the workgroup (lanes by shuffles, then the waves in index order: deterministic)
 __device__ __forceinline__ double block_scan(double v, double* wsum, int tid, int nwaves, double& total) {
@@ -371,16 +446,77 @@ k_jac_rte(const JacRteArgs A) {
 
   const double zl = A.z[lo], tl = A.t[lo];
   const unsigned fl = A.flags[prof];
-  const bool bad_nan = __syncthreads_or(live && (isnan(zl) || isnan(tl))) || (fl & 1u);
+  // cloud liquid / ice: every branch on it is uniform across the workgroup, and a call without cloud
+  // arrays executes the clear-sky arithmetic alone
+  const bool cloud_call = A.denliq != nullptr || A.denice != nullptr;
+  double denl = 0.0, deni = 0.0;
+  bool nan_here = live && (isnan(zl) || isnan(tl));
+  if (cloud_call) {
+    if (A.denliq) denl = A.denliq[lo];
+    if (A.denice) deni = A.denice[lo];
+    nan_here = nan_here || (live && (isnan(denl) || isnan(deni)));
+  }
+  const bool bad_nan = __syncthreads_or(nan_here) || (fl & 1u);
   const bool bad = bad_nan || (fl & 2u);
-  if (j == 0 && tid == 0) A.valid[prof] = bad_nan ? 0 : (bad ? 2 : 1);
-  if (bad) {                           // NaN in the profile (0) or negative absorption (2): the whole profile is NaN
+  // a cloudy call's valid array is preset to 1 by the entry point and only ever lowered here (the cloud terms are
+  // checked per frequency, further down); a clear call writes all three values
+  if (j == 0 && tid == 0 && (bad || !cloud_call)) A.valid[prof] = bad_nan ? 0 : (bad ? 2 : 1);
+  auto blank_profile = [&]() {
     for (int a = 0; a < nang; ++a) {
       const int64_t row = (prof * nang + a) * nf + j;
-      if (live) { A.dtb_dt[row * nlev + tid] = qnan; A.dtb_de[row * nlev + tid] = qnan; A.dtb_ddz[row * nlev + tid] = qnan; }
+      if (live) {
+        A.dtb_dt[row * nlev + tid] = qnan; A.dtb_de[row * nlev + tid] = qnan; A.dtb_ddz[row * nlev + tid] = qnan;
+        if (A.dtb_dliq) A.dtb_dliq[row * nlev + tid] = qnan;
+        if (A.dtb_dice) A.dtb_dice[row * nlev + tid] = qnan;
+      }
       if (tid == 0) A.tb[row] = qnan;
     }
+  };
+  if (bad) {                           // NaN in the profile (0) or negative absorption (2): the whole profile is NaN
+    blank_profile();
     return;
+  }
+  // skipped for a profile that holds no cloud at all (workgroup vote), as in the forward kernel
+  const bool cloudy = cloud_call && __syncthreads_or(live && (denl > 0.0 || deni > 0.0));
+  // ---- cloud: aliq = denl kap(T, f) (denl > 0, else 0), aice = CLOUD_KICE f deni (deni > 0, else 0), the zeroflg = false
+  // layer rule and the neighbour exchange through the LDS rows, before the clear-sky operands are loaded (few registers
+  // are live here).  What the elevation loop needs per level goes to seven LDS rows of a cloudy launch, each lane reading
+  // back its own entries, so the loop holds no more registers than the clear one:
+  //   Lc = Ll + Li;  ql1, ql0 = the partials of layers l and l+1 towards aliq_l, times kap (d aliq / d denl);
+  //   tl1, tl0 the same times denl dkap/dT (d aliq / dT);  qi1, qi0 those of the ice layers times d aice / d deni
+  const bool lay = live && tid > 0;
+  const bool has_up = tid + 1 < nlev;
+  double* cst = smem + 3 * nthr + 16 + tid;
+  double tci = 0.0, tli = 0.0;         // ice and liquid zenith optical depth of layer l
+  if (cloudy) {
+    double kap = 0.0, kapT = 0.0;
+    if (denl > 0.0) liquid_abs_tl(M, tl, A.frq[j], kap, kapT);
+    const double kice = (deni > 0.0) ? CLOUD_KICE * A.frq[j] : 0.0;
+    const double al = kap * denl, ai = kice * deni;
+    s0[tid] = al; s1[tid] = ai;
+    __syncthreads();
+    double Ll = 0.0, l1 = 0.0, l0 = 0.0, Li = 0.0, i1 = 0.0, i0 = 0.0;
+    bool neg = false;
+    if (lay) {
+      Ll = layer_value_tl<false>(al, s0[tid - 1], l1, l0, neg);
+      Li = layer_value_tl<false>(ai, s1[tid - 1], i1, i0, neg);
+      const double z0 = A.z[prof * nlev];
+      const double dzc = (zl - z0) - (A.z[lo - 1] - z0);
+      tci = Li * dzc; tli = Ll * dzc;
+    }
+    if (__syncthreads_or(neg)) {       // a negative cloud coefficient: flag 2 (the rows of this frequency are NaN)
+      if (tid == 0) A.valid[prof] = 2;
+      blank_profile();
+      return;
+    }
+    s0[tid] = l0; s1[tid] = i0;
+    __syncthreads();
+    const double l0n = has_up ? s0[tid + 1] : 0.0, i0n = has_up ? s1[tid + 1] : 0.0;
+    cst[0] = Ll + Li;
+    cst[nthr] = l1 * kap; cst[2 * nthr] = l0n * kap;
+    cst[3 * nthr] = l1 * (denl * kapT); cst[4 * nthr] = l0n * (denl * kapT);
+    cst[5 * nthr] = i1 * kice; cst[6 * nthr] = i0n * kice;
+    __syncthreads();                   // s0 / s1 are about to hold the clear-sky rows
   }
   const double aw = A.awet[ao], ad = A.adry[ao];
   const double awT = A.dawet_dt[ao], awE = A.dawet_de[ao], adT = A.dadry_dt[ao], adE = A.dadry_de[ao];
@@ -392,7 +528,6 @@ k_jac_rte(const JacRteArgs A) {
   // ---- per frequency: layer l (between levels l-1 and l) lives on lane l ----
   s0[tid] = aw; s1[tid] = ad; s2[tid] = b;
   __syncthreads();
-  const bool lay = live && tid > 0;
   double Lw = 0.0, w1 = 0.0, w0 = 0.0, Ld = 0.0, d1 = 0.0, d0 = 0.0, dz = 0.0, bm = 0.0;
   if (lay) {
     bool neg = false;                  // (negative values are flagged by k_absorb_tl already)
@@ -402,12 +537,12 @@ k_jac_rte(const JacRteArgs A) {
     dz = (zl - z0) - (A.z[lo - 1] - z0);
     bm = s2[tid - 1];
   }
-  const double tauz = lay ? Lw * dz + Ld * dz : 0.0;                   // zenith optical depth of layer l
+  double tauz = lay ? Lw * dz + Ld * dz : 0.0;                         // zenith optical depth of layer l
   __syncthreads();
   s0[tid] = w0; s1[tid] = d0;          // the lower-end partials of layer l, for level l-1
   __syncthreads();
-  const bool has_up = tid + 1 < nlev;
   const double w0n = has_up ? s0[tid + 1] : 0.0, d0n = has_up ? s1[tid + 1] : 0.0;
+  if (cloudy) tauz = (tauz + tci) + tli;                              // the forward's order: ((wet + dry) + ice) + liquid
   double tau_tot;
   const double cum_in = block_scan(tauz, wsum, tid, nwaves, tau_tot);
   const double cum_ex = cum_in - tauz;                                   // zenith optical depth below layer l
@@ -419,8 +554,10 @@ k_jac_rte(const JacRteArgs A) {
     double* o_t = A.dtb_dt + row * nlev;
     double* o_e = A.dtb_de + row * nlev;
     double* o_z = A.dtb_ddz + row * nlev;
+    double* o_l = A.dtb_dliq ? A.dtb_dliq + row * nlev : nullptr;
+    double* o_i = A.dtb_dice ? A.dtb_dice + row * nlev : nullptr;
     if (isnan(am)) {                   // a NaN elevation: its rows are NaN, the profile stays valid
-      if (live) { o_t[tid] = qnan; o_e[tid] = qnan; o_z[tid] = qnan; }
+      if (live) { o_t[tid] = qnan; o_e[tid] = qnan; o_z[tid] = qnan; if (o_l) o_l[tid] = qnan; if (o_i) o_i[tid] = qnan; }
       if (tid == 0) A.tb[row] = qnan;
       continue;
     }
@@ -452,10 +589,21 @@ k_jac_rte(const JacRteArgs A) {
     ct += gkn * (w0n * awT + d0n * adT) + btl * Tl * thn;                 // ... and as the lower end of layer l+1
     ce += gkn * (w0n * awE + d0n * adE);
     if (live) {
-      o_t[tid] = ct; o_e[tid] = ce;
-      // dTB / d(thickness of layer l) [K/km]: tau_l = m (Lw + Ld) dz_l is linear in dz_l, so this holds at dz_l = 0 too
-      o_z[tid] = lay ? g * am * (Lw + Ld) : 0.0;
+      o_e[tid] = ce;
+      // dTB / d(thickness of layer l) [K/km]: tau_l = m (Lw + Ld + Ll + Li) dz_l is linear in dz_l, so this holds at
+      // dz_l = 0 too
+      o_z[tid] = lay ? g * am * (cloudy ? (Lw + Ld) + cst[0] : Lw + Ld) : 0.0;
     }
+    if (cloud_call) {                  // two more rows; a profile without cloud in a cloudy call has all-zero rows
+      double rl = 0.0, ri = 0.0;
+      if (cloudy) {
+        rl = gk * cst[nthr] + gkn * cst[2 * nthr];
+        ri = gk * cst[5 * nthr] + gkn * cst[6 * nthr];
+        ct += gk * cst[3 * nthr] + gkn * cst[4 * nthr];     // the liquid term of dTB/dT at fixed e (ice has no T tangent)
+      }
+      if (live) { if (o_l) o_l[tid] = rl; if (o_i) o_i[tid] = ri; }
+    }
+    if (live) o_t[tid] = ct;
     if (tid == 0) A.tb[row] = fdiv(hvk, Lg);
   }
 }
@@ -470,7 +618,13 @@ hipError_t launch_absorb_tl(const AbsorbTlArgs& a, int64_t nprof, hipStream_t st
 
 hipError_t launch_jac_rte(const JacRteArgs& a, int64_t nprof, hipStream_t st) {
   const int threads = ((a.nlev + WAVE - 1) / WAVE) * WAVE;
-  const size_t lds = sizeof(double) * (3 * (size_t)threads + 16);
+  const bool cloud_call = a.denliq || a.denice;                    // seven more rows: the per-level cloud terms
+  const size_t lds = sizeof(double) * ((cloud_call ? 10 : 3) * (size_t)threads + 16);
+  if (lds > 64 * 1024) {               // (cloudy launches above 818 levels: beyond the default dynamic LDS limit)
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_jac_rte),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
   hipLaunchKernelGGL(k_jac_rte, dim3((unsigned)(nprof * a.nf)), dim3(threads), lds, st, a);
   return hipGetLastError();
 }

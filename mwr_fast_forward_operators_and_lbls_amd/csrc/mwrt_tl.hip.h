@@ -3,7 +3,8 @@
 // Two kernels, each in this one translation unit (built by build.py next to the chunk-width units):
 //   k_absorb_tl  clearsky_absorption and its exact partial derivatives with respect to T (at fixed e) and e (at
 //                fixed T) for every level and frequency: every line at every frequency, no far-line forms, no windows
-//   k_jac_rte    the layer rule + Planck-space RTE + bright and their adjoint, fed by those six arrays
+//   k_jac_rte    the layer rule + Planck-space RTE + bright and their adjoint, fed by those six arrays;
+//                with cloud liquid / ice it forms their absorption and its tangents itself
 #pragma once
 #include "mwrt_kernels.hip.h"
 
@@ -27,9 +28,11 @@ struct JacRteArgs {
   const double* awet; const double* adry;                     // [nprof][nf][nlev] as k_absorb_tl writes them
   const double* dawet_dt; const double* dawet_de; const double* dadry_dt; const double* dadry_de;
   const unsigned* flags;                                      // [nprof] from k_absorb_tl
+  const double* denliq; const double* denice;                 // [nprof][nlev] g m-3, either may be null (both: clear sky)
   const double* frq; const double* airmass;                   // [nf], [nang] device copies
   double* tb;                                                 // [nprof][nang][nf]
   double* dtb_dt; double* dtb_de; double* dtb_ddz;            // [nprof][nang][nf][nlev]
+  double* dtb_dliq; double* dtb_dice;                         // the same layout, K per g m-3; null = not wanted
   uint8_t* valid;                                             // [nprof]
   int nlev, nf, nang;
 };

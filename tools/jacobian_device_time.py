@@ -1,5 +1,6 @@
 """Device time of the device K-matrix path next to the forward call, one process, one stream, HIP events
-(mwrt_set_timing): mwrt_tb_jacobian_batch_device (k_absorb_tl + k_jac_rte), mwrt_absorption_tl_batch_device (k_absorb_tl
+(mwrt_set_timing): mwrt_tb_jacobian_batch_device (k_absorb_tl + k_jac_rte), mwrt_tb_jacobian_batch_opt_device with a cloud in
+every profile (skipped on a library without it), mwrt_absorption_tl_batch_device (k_absorb_tl
 alone) and mwrt_tb_batch_device (the fused forward kernel), at 1000 profiles x 14 channels (HATPRO) x 7 elevations x 180
 levels, R24.  Usage: python tools/jacobian_device_time.py [--reps N] [--out FILE.json]"""
 import argparse
@@ -30,11 +31,21 @@ def main():
     jac = [torch.empty((nprof, nang, nf, nlev), **f64) for _ in range(3)]
     absn = [torch.empty((nprof, nf, nlev), **f64) for _ in range(6)]
     valid = torch.empty(nprof, dtype=torch.uint8, device="cuda")
+    # a cloud in every profile: liquid over levels 20-39, ice over levels 60-79
+    cloud = np.zeros((2, nprof, nlev))
+    cloud[0, :, 20:40] = np.linspace(0.1, 0.3, 20)
+    cloud[1, :, 60:80] = np.linspace(0.02, 0.08, 20)
+    denl, deni = (torch.tensor(c, **f64) for c in cloud)
+    cjac = [torch.empty((nprof, nang, nf, nlev), **f64) for _ in range(2)]
     torch.cuda.synchronize()
     calls = {
         "tb_jacobian_batch_device": lambda: ctx.tb_jacobian_batch_device(
             "R24", nprof, nlev, z.data_ptr(), p.data_ptr(), t.data_ptr(), rh.data_ptr(), frq, ang, tb.data_ptr(),
             *[j.data_ptr() for j in jac], valid.data_ptr()),
+        "tb_jacobian_batch_opt_device_cloudy": lambda: ctx.tb_jacobian_batch_opt_device(
+            "R24", nprof, nlev, z.data_ptr(), p.data_ptr(), t.data_ptr(), rh.data_ptr(), frq, ang, tb.data_ptr(),
+            *[j.data_ptr() for j in jac], valid.data_ptr(), d_denliq=denl.data_ptr(), d_denice=deni.data_ptr(),
+            d_dtb_dliq=cjac[0].data_ptr(), d_dtb_dice=cjac[1].data_ptr()),
         "absorption_tl_batch_device": lambda: ctx.absorption_tl_batch_device(
             "R24", nprof, nlev, p.data_ptr(), t.data_ptr(), rh.data_ptr(), frq, *[x.data_ptr() for x in absn]),
         "tb_batch_device": lambda: ctx.tb_batch_device(
@@ -42,6 +53,8 @@ def main():
             valid.data_ptr()),
     }
     res = {"shape": {"nprof": nprof, "nf": nf, "nang": nang, "nlev": nlev, "model": "R24"}, "reps": a.reps}
+    if not hasattr(ctx._lib, "mwrt_tb_jacobian_batch_opt_device") or "mwrt_tb_jacobian_batch_opt_device" not in nat.SIGNATURES:
+        del calls["tb_jacobian_batch_opt_device_cloudy"]
     for name, fn in calls.items():
         for _ in range(3):
             fn()                                       # warm-up: workspace, frequency / air-mass copies, code objects
@@ -56,6 +69,9 @@ def main():
         ms = np.array(ms)
         res[name] = {"median_ms": float(np.median(ms)), "min_ms": float(ms.min()), "max_ms": float(ms.max()),
                      "p10_ms": float(np.percentile(ms, 10)), "p90_ms": float(np.percentile(ms, 90)), "launches": launches}
+    if "tb_jacobian_batch_opt_device_cloudy" in res:
+        res["ratio_cloudy_jacobian_over_clear"] = (res["tb_jacobian_batch_opt_device_cloudy"]["median_ms"]
+                                                   / res["tb_jacobian_batch_device"]["median_ms"])
     res["ratio_jacobian_over_forward"] = res["tb_jacobian_batch_device"]["median_ms"] / res["tb_batch_device"]["median_ms"]
     res["ratio_tl_absorption_over_forward"] = res["absorption_tl_batch_device"]["median_ms"] / res["tb_batch_device"]["median_ms"]
     txt = json.dumps(res, indent=1)
