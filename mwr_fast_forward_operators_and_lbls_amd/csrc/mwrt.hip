@@ -6,7 +6,6 @@
 #include "mwrt_inst.hip.h"
 #include "mwrt_tl.hip.h"
 
-#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -47,42 +46,68 @@ struct DevBuf {
   template <class T> T* as() { return static_cast<T*>(p); }
 };
 
-// Content-keyed, immutable device copies of small host arrays.
-struct ParamCache {
-  struct Entry { std::vector<double> host; double* dev = nullptr; unsigned long stamp = 0; };
-  std::vector<Entry> entries;
-  unsigned long clock = 0;
-  static constexpr size_t MAX_ENTRIES = 32;
-  // device pointer holding exactly src[0..n); uploads through `copy_stream` (never a capturing stream)
-  hipError_t get(const double* src, int n, hipStream_t copy_stream, const double** out) {
-    for (Entry& e : entries)
-      if ((int)e.host.size() == n && std::memcmp(e.host.data(), src, sizeof(double) * (size_t)n) == 0) {
-        e.stamp = ++clock; *out = e.dev; return hipSuccess;
+// Content-keyed, immutable device blobs: the small per-call parameter arrays (frq, air mass, elevations), the line
+// masks of a frequency list and its window tables.  The key is (model id or 0, a small integer tag, doubles).  A blob is
+// never overwritten or freed while the context lives (bar LRU eviction behind a device-wide drain), so launches still
+// queued on ANY stream and captured hipGraphs keep reading valid memory.
+class DeviceCache {
+ public:
+  struct Blob { const char* dev = nullptr; int count = 0; };     // count: what the builder returned (records in the blob)
+  explicit DeviceCache(size_t capacity) : capacity_(capacity) {}
+  // The blob of (model, tag, key[0..n)).  A hit is one linear memcmp scan: it never evicts or synchronises.  On a miss
+  // `build(std::vector<char>* host)` fills the host bytes and returns the count; uploads go through `copy_stream`
+  // (never a capturing stream).
+  template <class Build>
+  hipError_t get(uint64_t model, int tag, const double* key, int n, hipStream_t copy_stream, Build build, Blob* out) {
+    for (Entry& e : entries_)
+      if (e.model == model && e.tag == tag && (int)e.key.size() == n &&
+          std::memcmp(e.key.data(), key, sizeof(double) * (size_t)n) == 0) {
+        // least recently USED goes first: a hit is stamped anew, so a warm-up call keeps what it touched (a later miss of the
+        // same sequence must not evict it -- the eviction drains the device, which a capturing stream refuses)
+        e.stamp = ++clock_;
+        *out = Blob{e.dev, e.count};
+        return hipSuccess;
       }
-    if (entries.size() >= MAX_ENTRIES) {
-      // evict the least recently used copy -- only after everything queued on the device has drained
+    std::vector<char> host;
+    const int count = build(&host);
+    return insert(model, tag, key, n, host, count, copy_stream, out);
+  }
+  void release() { for (Entry& e : entries_) (void)hipFree(e.dev); entries_.clear(); }
+  // the caller has drained the device: launches on any stream may still read the blobs
+  void drop_model(uint64_t model) {
+    for (size_t i = entries_.size(); i-- > 0;)
+      if (entries_[i].model == model) { (void)hipFree(entries_[i].dev); entries_.erase(entries_.begin() + (long)i); }
+  }
+
+ private:
+  struct Entry { uint64_t model; int tag; std::vector<double> key; char* dev; int count; unsigned long stamp; };
+  hipError_t insert(uint64_t model, int tag, const double* key, int n, const std::vector<char>& host, int count,
+                    hipStream_t copy_stream, Blob* out) {
+    if (entries_.size() >= capacity_) {
+      // bounded: evict the least recently used blob -- only after everything queued on the device has drained
       hipError_t e = hipDeviceSynchronize();
       if (e != hipSuccess) return e;
       size_t lru = 0;
-      for (size_t i = 1; i < entries.size(); ++i) if (entries[i].stamp < entries[lru].stamp) lru = i;
-      (void)hipFree(entries[lru].dev);
-      entries.erase(entries.begin() + (long)lru);
+      for (size_t i = 1; i < entries_.size(); ++i) if (entries_[i].stamp < entries_[lru].stamp) lru = i;
+      (void)hipFree(entries_[lru].dev);
+      entries_.erase(entries_.begin() + (long)lru);
     }
-    Entry ne;
-    ne.host.assign(src, src + n);
-    hipError_t e = hipMalloc((void**)&ne.dev, sizeof(double) * (size_t)(n > 0 ? n : 1));
+    Entry ne{model, tag, std::vector<double>(key, key + n), nullptr, count, 0};
+    hipError_t e = hipMalloc((void**)&ne.dev, host.empty() ? 1 : host.size());
     if (e != hipSuccess) return e;
     // a fresh buffer nobody reads yet: copy on the context's own stream and wait for it, so the
     // bytes are in HBM before any stream (the caller's included) can launch a reader
-    e = hipMemcpyAsync(ne.dev, ne.host.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, copy_stream);
+    e = hipMemcpyAsync(ne.dev, host.data(), host.size(), hipMemcpyHostToDevice, copy_stream);
     if (e == hipSuccess) e = hipStreamSynchronize(copy_stream);
     if (e != hipSuccess) { (void)hipFree(ne.dev); return e; }
-    ne.stamp = ++clock;
-    entries.push_back(std::move(ne));
-    *out = entries.back().dev;
+    ne.stamp = ++clock_;
+    entries_.push_back(std::move(ne));
+    *out = Blob{entries_.back().dev, count};
     return hipSuccess;
   }
-  void release() { for (Entry& e : entries) (void)hipFree(e.dev); entries.clear(); }
+  std::vector<Entry> entries_;
+  size_t capacity_;
+  unsigned long clock_ = 0;
 };
 
 }  // namespace
@@ -92,19 +117,15 @@ struct mwrt_context {
   hipStream_t stream = nullptr;
   int lds_max = 65536;
   int num_cus = 256;            // compute units of the device (MI355X: 256)
-  // small per-call parameter arrays (frq, airmass): content-keyed device copies.  A copy is never
-  // overwritten or freed while the context lives (bar LRU eviction behind a device-wide drain), so
-  // launches still queued on ANY stream and captured hipGraphs keep reading valid memory.
-  ParamCache frq_cache, am_cache, elev_cache;
-  // fine-grid absorption: window descriptors + Lagrange matrices per (model, frequency list), immutable like ParamCache
+  // small per-call parameter arrays (frq, airmass, elevations): content-keyed device copies
+  DeviceCache frq_cache{32}, am_cache{32}, elev_cache{32};
   int absorption_mode = 0;      // 0 auto, 1 direct, 2 windowed
   int chunk_width = 0;          // 0 auto, 8 / 14 / 16: frequencies per workgroup of the fused TB kernel (mwrt_set_chunk_width)
-  struct WinEntry { uint64_t model_id; std::vector<double> frq; char* d_blob; size_t off_lag, off_lagh, off_lagsd; int nwin; };
-  std::vector<WinEntry> win_cache;
+  // fine-grid absorption: window descriptors + Lagrange matrices per (model, frequency list)
+  DeviceCache win_cache{16};
   // line classification of every frequency chunk (LineMasks), per (model, frequency list, chunk width): depends on the
   // frequencies and the table only, so the host computes it once instead of every workgroup voting on it
-  struct MaskEntry { uint64_t model_id; int nfc; std::vector<double> frq; LineMasks* d_masks; };
-  std::vector<MaskEntry> mask_cache;
+  DeviceCache mask_cache{64};
   // ray-tracing workspace: path factors [nprof][nang][nlev] and the per-profile ducting flag
   DevBuf d_amf, d_duct;
   // fine-grid two-kernel path: materialised absorption of one profile batch (awet | adry)
@@ -135,65 +156,28 @@ struct mwrt_model {
 
 namespace {
 
-// K2 work split: items = pairs x nseg over `threads` lanes; cost ~ rounds x seglen (+ combine)
-// segments per (frequency, angle) pair for one K2 pass of `npairs` pairs: fill the workgroup in one round
-int plan_k2_pass(int nlev, int npairs, int threads) {
-  const int layers = nlev - 1;
-  int best = 1; long best_cost = -1;
-  for (int ns = 1; ns <= 64 && ns <= (layers > 0 ? layers : 1); ++ns) {
-    const int sl = (layers + ns - 1) / ns;
-    const long rounds = ((long)npairs * ns + threads - 1) / threads;
-    const long cost = rounds * (sl * 8L + 4) + ns;      // 8 ~ relative cost of a layer step vs a combine step
-    if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = ns; }
-  }
-  return best;
+int upload_small(mwrt_context* c, DeviceCache& cache, const double* src, int n, const double** dev) {
+  DeviceCache::Blob b;
+  const hipError_t e = cache.get(0, 0, src, n, c->stream, [&](std::vector<char>* host) {
+    host->assign((const char*)src, (const char*)(src + n));
+    return n;
+  }, &b);
+  HIP_TRY(e);
+  *dev = (const double*)b.dev;
+  return MWRT_OK;
 }
 
-// rows kept in LDS per K2 pass; a 14-wide chunk runs as passes of 8 and 6 rows, each with its own split
-int nfk_of(int /*nfc*/) { return 8; }
-
-unsigned magic_of(int d) { return d <= 1 ? 0u : (unsigned)((((uint64_t)1 << 32) + (uint64_t)d - 1) / (uint64_t)d); }
-void set_magics(LaunchGeom* g, int nang) {
-  g->magic_nseg[0] = magic_of(g->nseg[0]);
-  g->magic_nseg[1] = magic_of(g->nseg[1]);
-  g->magic_nang = magic_of(nang);
-}
-
-void set_pass(LaunchGeom* g, int h, int nlev, int ns) {
-  g->nseg[h] = ns < 1 ? 1 : ns;
-  g->seglen[h] = (nlev - 1 + g->nseg[h] - 1) / g->nseg[h];
-  if (g->seglen[h] < 1) g->seglen[h] = 1;
-}
-
-LaunchGeom plan_k2(int nlev, int nfc, int nf, int nang, int threads) {
-  LaunchGeom g;
-  const int nfk = nfk_of(nfc);
-  const int rows0 = std::min(nfk, std::min(nfc, nf));
-  const int rows1 = std::max(0, std::min(nfc, nf) - nfk);
-  set_pass(&g, 0, nlev, plan_k2_pass(nlev, rows0 * nang, threads));
-  set_pass(&g, 1, nlev, rows1 > 0 ? plan_k2_pass(nlev, rows1 * nang, threads) : 1);
-  g.npart = 2 * nang * std::max(rows0 * g.nseg[0], rows1 * g.nseg[1]);
-  set_magics(&g, nang);
-  // row stride in doubles: odd multiple of 2 dwords keeps ds_read_b64 rows on distinct banks
-  int ld = nlev + 1;
-  if ((ld & 1) == 0) ld += 1;
-  g.ldrow = ld;
-  return g;
-}
-
-size_t fused_lds_bytes(int nfc, const LaunchGeom& g, int /*nang*/, int threads) {
-  const int nfk = nfk_of(nfc);
-  // float gmax[nfk][threads/16], int wcnt[nwaves], int perm[threads]
-  const size_t sort_doubles = ((size_t)nfk * (threads / 16) + (threads / WAVE) + threads + 1) / 2;
-  return sizeof(double) * ((size_t)2 * nfk * g.ldrow + (size_t)g.npart + 16 +
-                           (size_t)(threads / WAVE) * 2 * nfc + sort_doubles);
-}
-
-// K2 split for a chunk width, shrunk until the workgroup's LDS fits; false if it cannot
-bool plan_fused(const mwrt_context* c, int nfc, int nlev, int nf, int nang, LaunchGeom* g, size_t* lds, int threads = 0);
-
-int upload_small(mwrt_context* c, ParamCache& cache, const double* src, int n, const double** dev) {
-  HIP_TRY(cache.get(src, n, c->stream, dev));
+// device copy of chunk_masks(...) for chunks of `nfc` frequencies
+int get_masks(mwrt_context* c, const mwrt_model* m, const double* frq, int nf, int nfc, const LineMasks** out) {
+  DeviceCache::Blob b;
+  const hipError_t e = c->mask_cache.get(m->id, nfc, frq, nf, c->stream, [&](std::vector<char>* host) {
+    std::vector<LineMasks> masks;
+    chunk_masks(m->h_desc, frq, nf, nfc, &masks);
+    host->assign((const char*)masks.data(), (const char*)(masks.data() + masks.size()));
+    return (int)masks.size();
+  }, &b);
+  HIP_TRY(e);
+  *out = (const LineMasks*)b.dev;
   return MWRT_OK;
 }
 
@@ -233,423 +217,109 @@ int check_common(const mwrt_context* c, const mwrt_model* m, int64_t nprof, int3
   return MWRT_OK;
 }
 
-bool any_nan(const double* x, int n) {
-  for (int i = 0; i < n; ++i) if (std::isnan(x[i])) return true;
-  return false;
+// Grows a workspace that consecutive calls share (never shrinks it): launches queued on any stream may still read
+// the old allocation, so the device drains first
+hipError_t grow_behind_drain(DevBuf& b, size_t bytes) {
+  if (bytes <= b.cap) return hipSuccess;
+  const hipError_t e = hipDeviceSynchronize();
+  return e != hipSuccess ? e : b.reserve(bytes);
 }
 
-void timing_begin(mwrt_context* c, hipStream_t st) {
+// one kernel launch (`launch()` -> hipError_t), between a pair of the ring's events when timing is on
+template <class F> int timed(mwrt_context* c, hipStream_t st, F launch) {
   if (c->timing) (void)hipEventRecord(c->ev0[c->ev_count % TIMING_RING], st);
-}
-void timing_end(mwrt_context* c, hipStream_t st) {
+  const hipError_t e = launch();
   if (c->timing) { (void)hipEventRecord(c->ev1[c->ev_count % TIMING_RING], st); c->ev_count++; }
+  HIP_TRY(e);
+  return MWRT_OK;
 }
+
+#if MWRT_PHASE_CLOCK
+// diagnostic build: stamps of the LAST launch go to $MWRT_PHASE_DUMP as raw int64 [nprof][4][10] (100-MHz wall clock; slots 8, 9 = HW_ID, XCC_ID)
+long long* g_phase = nullptr;
+size_t g_phase_cap = 0;
+int phase_attach(FusedArgs* a, int64_t nprof, int nchunks, hipStream_t st) {
+  const size_t phase_n = (size_t)nprof * 4 * 10;
+  a->phase = nullptr;
+  if (!std::getenv("MWRT_PHASE_DUMP") || nchunks != 1) return MWRT_OK;
+  if (g_phase_cap < phase_n) { if (g_phase) (void)hipFree(g_phase); HIP_TRY(hipMalloc((void**)&g_phase, phase_n * 8)); g_phase_cap = phase_n; }
+  HIP_TRY(hipMemsetAsync(g_phase, 0, phase_n * 8, st));
+  a->phase = g_phase;
+  return MWRT_OK;
+}
+int phase_dump(const FusedArgs& a, int64_t nprof, hipStream_t st) {
+  if (!a.phase) return MWRT_OK;
+  const size_t phase_n = (size_t)nprof * 4 * 10;
+  std::vector<long long> h(phase_n);
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpy(h.data(), g_phase, phase_n * 8, hipMemcpyDeviceToHost));
+  if (FILE* f = std::fopen(std::getenv("MWRT_PHASE_DUMP"), "wb")) { std::fwrite(h.data(), 8, phase_n, f); std::fclose(f); }
+  return MWRT_OK;
+}
+#else
+int phase_attach(FusedArgs*, int64_t, int, hipStream_t) { return MWRT_OK; }
+int phase_dump(const FusedArgs&, int64_t, hipStream_t) { return MWRT_OK; }
+#endif
 
 int launch_fused(mwrt_context* c, int nfc, FusedArgs a, int64_t nprof, hipStream_t st, int variant) {
-  int threads = ((a.nlev + WAVE - 1) / WAVE) * WAVE;
+  int threads = lanes_for(a.nlev);
   // The RTE-from-absorption kernel is light on registers (4 waves per SIMD fit): a fourth wave that holds no
   // level still takes its share of the (frequency, angle, segment) items, 90 serial layer steps instead of 120
   if (variant == FUSED_FROM_ALPHA && threads < 256 && a.nang > 1) threads = 256;
   const int nchunks = (a.nf + nfc - 1) / nfc;
   size_t lds = 0;
-  if (!plan_fused(c, nfc, a.nlev, a.nf, a.nang, &a.g, &lds, threads))
+  if (!plan_fused(c->lds_max, nfc, a.nlev, a.nf, a.nang, &a.g, &lds, threads))
     return fail(MWRT_ERR_UNSUPPORTED, "LDS budget exceeded (nlev x nang too large)");
   dim3 grid((unsigned)nprof /* = nmodels x profiles */, (unsigned)nchunks), block(threads);
   // valid[] = 1 is written by the kernel itself when one workgroup owns the profile; with several
   // frequency chunks per profile the flags are preset here and the kernel only lowers/raises them
   a.write_valid = nchunks == 1;
   if (!a.write_valid) HIP_TRY(hipMemsetAsync(a.valid, 1, (size_t)nprof, st));
-#if MWRT_PHASE_CLOCK
-  // diagnostic build: stamps of the LAST launch go to $MWRT_PHASE_DUMP as raw int64 [nprof][4][10] (100-MHz wall clock; slots 8, 9 = HW_ID, XCC_ID)
-  static long long* d_phase = nullptr; static size_t phase_cap = 0;
-  const char* dump = std::getenv("MWRT_PHASE_DUMP");
-  const size_t phase_n = (size_t)nprof * 4 * 10;
-  a.phase = nullptr;
-  if (dump && nchunks == 1) {
-    if (phase_cap < phase_n) { if (d_phase) (void)hipFree(d_phase); HIP_TRY(hipMalloc((void**)&d_phase, phase_n * 8)); phase_cap = phase_n; }
-    HIP_TRY(hipMemsetAsync(d_phase, 0, phase_n * 8, st));
-    a.phase = d_phase;
-  }
-#endif
-  timing_begin(c, st);
-  hipError_t e;
-  switch (nfc) {                                    // one translation unit per chunk width (csrc/mwrt_inst.hip)
-    case 8: e = launch_fused_nfc8(a, grid, block, lds, st, variant); break;
-    case 14: e = launch_fused_nfc14(a, grid, block, lds, st, variant); break;
-    default: e = launch_fused_nfc16(a, grid, block, lds, st, variant); break;
-  }
-  timing_end(c, st);
-  HIP_TRY(e);
-#if MWRT_PHASE_CLOCK
-  if (a.phase) {
-    std::vector<long long> h(phase_n);
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(h.data(), d_phase, phase_n * 8, hipMemcpyDeviceToHost));
-    if (FILE* f = std::fopen(dump, "wb")) { std::fwrite(h.data(), 8, phase_n, f); std::fclose(f); }
-  }
-#endif
-  return MWRT_OK;
+  int rc = phase_attach(&a, nprof, nchunks, st); if (rc) return rc;
+  rc = timed(c, st, [&] {
+    switch (nfc) {                                    // one translation unit per chunk width (csrc/mwrt_inst.hip)
+      case 8: return launch_fused_nfc8(a, grid, block, lds, st, variant);
+      case 14: return launch_fused_nfc14(a, grid, block, lds, st, variant);
+      default: return launch_fused_nfc16(a, grid, block, lds, st, variant);
+    }
+  });
+  return rc ? rc : phase_dump(a, nprof, st);
 }
 
 int launch_absorb(mwrt_context* c, int nfc, const AbsorbArgs& a, int64_t nprof, hipStream_t st) {
-  const int threads = ((a.nlev + WAVE - 1) / WAVE) * WAVE;
   const int nchunks = (a.nf + nfc - 1) / nfc;
-  dim3 grid((unsigned)nprof, (unsigned)nchunks), block(threads);
-  timing_begin(c, st);
-  hipError_t e;
-  switch (nfc) {
-    case 8: e = launch_absorb_nfc8(a, grid, block, st); break;
-    case 14: e = launch_absorb_nfc14(a, grid, block, st); break;
-    default: e = launch_absorb_nfc16(a, grid, block, st); break;
-  }
-  timing_end(c, st);
+  dim3 grid((unsigned)nprof, (unsigned)nchunks), block(lanes_for(a.nlev));
+  return timed(c, st, [&] {
+    switch (nfc) {
+      case 8: return launch_absorb_nfc8(a, grid, block, st);
+      case 14: return launch_absorb_nfc14(a, grid, block, st);
+      default: return launch_absorb_nfc16(a, grid, block, st);
+    }
+  });
+}
+
+// the windowed absorption kernel on a list absorption_route() gave it: absorption coefficients, or with `T` the layer
+// optical depths.  Its tables are the device copy of build_windows(...) in pack_windows' layout and the WIN_NFC masks.
+int launch_windowed_absorption(mwrt_context* c, const mwrt_model* m, int64_t nprof, int nlev, const double* d_p, const double* d_t,
+                               const double* d_rh, int nf, const double* frq, const double* dev_frq, double* d_awet,
+                               double* d_adry, const TauOut* T, int threads, hipStream_t st) {
+  DeviceCache::Blob b;
+  const hipError_t e = c->win_cache.get(m->id, 0, frq, nf, c->stream, [&](std::vector<char>* host) {
+    WindowSet ws;
+    build_windows(m->h_desc, frq, nf, &ws);
+    pack_windows(ws, nf, host);
+    return (int)ws.wins.size();
+  }, &b);
   HIP_TRY(e);
-  return MWRT_OK;
-}
-
-bool plan_fused(const mwrt_context* c, int nfc, int nlev, int nf, int nang, LaunchGeom* g, size_t* lds, int threads) {
-  if (threads <= 0) threads = ((nlev + WAVE - 1) / WAVE) * WAVE;
-  *g = plan_k2(nlev, nfc, nf, nang, threads);
-  *lds = fused_lds_bytes(nfc, *g, nang, threads);
-  while (*lds > (size_t)c->lds_max && (g->nseg[0] > 1 || g->nseg[1] > 1)) {     // shrink the partials if LDS is short
-    const int nfk = nfk_of(nfc);
-    const int rows0 = std::min(nfk, std::min(nfc, nf)), rows1 = std::max(0, std::min(nfc, nf) - nfk);
-    set_pass(g, 0, nlev, (g->nseg[0] + 1) / 2);
-    set_pass(g, 1, nlev, (g->nseg[1] + 1) / 2);
-    g->npart = 2 * nang * std::max(rows0 * g->nseg[0], rows1 * g->nseg[1]);
-    set_magics(g, nang);
-    *lds = fused_lds_bytes(nfc, *g, nang, threads);
-  }
-  return *lds <= (size_t)c->lds_max;
-}
-
-// frequency-chunk width: 14 HATPRO channels fit one chunk exactly; other counts use 16 / 8
-int pick_nfc(int nf) {
-  if (nf % 14 == 0 || nf <= 14) return (nf <= 8) ? 8 : 14;
-  return 16;
-}
-
-// ... unless the caller fixed the width (mwrt_set_chunk_width: 8 splits a 14-channel profile over two workgroups, each with
-// the full per-(level, line) set-up but half the line-frequency work -- one profile 58 instead of 75 us, 256 profiles 61
-// instead of 76, 512 profiles 77 instead of 83 at seven elevations; not the default because results would then depend, in the
-// 13th digit, on how a caller batches its profiles) or the profile is so tall that the wide chunk's LDS rows do not fit: then 8
-int pick_nfc_fused(const mwrt_context* c, int nlev, int nf, int nang) {
-  int nfc = c->chunk_width ? c->chunk_width : pick_nfc(nf);
-  LaunchGeom g; size_t lds;
-  if (!plan_fused(c, nfc, nlev, nf, nang, &g, &lds)) nfc = 8;
-  return nfc;
-}
-
-// ---- fine-grid absorption: windows of WIN_CHUNKS chunks, Chebyshev nodes, Lagrange matrices ----
-constexpr double WIN_MARGIN_GHZ = 4.0;       // an O2 line is window-far when its centre is this far beyond the window (16 nodes)
-constexpr double WIN_H2O_MARGIN_GHZ = 30.0;  // an H2O line: this far (8 nodes; the H2O table is sparse, few lines come closer)
-constexpr double WIN_MAX_SPAN_GHZ = 6.0;     // widest window the 16-node interpolation is used on
-constexpr double WIN_CUTOFF_GUARD_GHZ = 5.0; // the H2O 750-GHz cutoff must be this clearly in or out (pressure shifts < 1 GHz)
-
-bool windows_eligible(const double* frq, int nf) {
-  if (nf < WIN_CHUNKS * WIN_NFC) return false;
-  for (int j = 1; j < nf; ++j) if (!(frq[j] > frq[j - 1])) return false;
-  const int per = WIN_CHUNKS * WIN_NFC;
-  for (int b = 0; b < nf; b += per) {
-    const int e = std::min(nf, b + per) - 1;
-    if (e == b) return false;                              // a one-frequency window has no span to put nodes on
-    if (frq[e] - frq[b] > WIN_MAX_SPAN_GHZ) return false;
-  }
-  return true;
-}
-
-// upper bound of a speed-dependent H2O line's half width anywhere in an atmosphere (dry air <= 1100 hPa, vapour
-// <= 150 hPa, T >= 148 K): the host may put such a line in a window's far set only where 10 half-widths cannot
-// reach the window; the kernel re-checks per level and takes the line back if they can
-double sd_halfwidth_bound(const mwrt_model_desc& t, int k) {
-  return t.h2o_w0[k] * 1100.0 * std::pow(2.0, std::max(t.h2o_x[k], 0.0)) +
-         t.h2o_w0s[k] * 150.0 * std::pow(2.0, std::max(t.h2o_xs[k], 0.0));
-}
-
-// line_masks of every chunk of `nfc` frequencies (what the kernels' line loops are steered by; mwrt_kernels.hip.h LineMasks)
-void chunk_masks(const mwrt_model_desc& t, const double* frq, int nf, int nfc, std::vector<LineMasks>* out) {
-  const int nchunks = (nf + nfc - 1) / nfc;
-  out->assign(nchunks, LineMasks{});
-  for (int ch = 0; ch < nchunks; ++ch) {
-    const int j0 = ch * nfc, j1 = std::min(nf, j0 + nfc);
-    LineMasks& lm = (*out)[ch];
-    // very far lines (vfar_add): poles of the line's term in u = f^2, u ~ c^2 -+ 2 i c w, at >= 1/VF_RATIO_MAX half ranges
-    // from the middle of the chunk's f^2 values -- with 2 GHz of allowance for pressure shifts and 10 GHz for the half width
-    double ulo = 1e300, uhi = 0.0;
-    for (int j = j0; j < j1; ++j) { ulo = std::min(ulo, frq[j] * frq[j]); uhi = std::max(uhi, frq[j] * frq[j]); }
-    lm.vf_u0 = 0.5 * (ulo + uhi);
-    lm.vf_h = std::max(0.5 * (uhi - ulo), 1.0);
-    lm.vf_invh = 1.0 / lm.vf_h;
-    auto very_far = [&](double c) {
-      const double cl = std::max(c - 2.0, 0.0), ch = c + 2.0;
-      const double plo = cl * cl - 100.0, phi = ch * ch;             // real part of the poles lies in [plo, phi]
-      const double dist = (lm.vf_u0 < plo) ? plo - lm.vf_u0 : ((lm.vf_u0 > phi) ? lm.vf_u0 - phi : 0.0);
-      return lm.vf_h <= VF_RATIO_MAX * dist;
-    };
-    // (a line costs ~40 instructions in the polynomial against 7 per frequency directly: not worth it under 7 frequencies)
-    static const bool no_vfar_env = std::getenv("MWRT_NO_VFAR") != nullptr;               // diagnostic: time the direct sums
-    const bool no_vfar = no_vfar_env || (j1 - j0) < VF_MIN_FREQS;
-    for (int k = 0; k < t.n_o2; ++k) {
-      double dmin = 1e300;
-      for (int j = j0; j < j1; ++j) dmin = std::min(dmin, std::fabs(frq[j] - t.o2_f[k]));
-      if (dmin >= FAR_MIN_GHZ + FAR_SHIFT_GHZ) lm.o2_far |= 1ull << k;
-      if (!no_vfar && very_far(t.o2_f[k])) lm.o2_vfar |= 1ull << k;
-    }
-    if (__builtin_popcountll(lm.o2_vfar) < VF_MIN_LINES) lm.o2_vfar = 0;
-    for (int k = 0; k < t.n_h2o; ++k) {
-      double dmin = 1e300, smin = 1e300;
-      for (int j = j0; j < j1; ++j) { dmin = std::min(dmin, std::fabs(frq[j] - t.h2o_fl[k])); smin = std::min(smin, std::fabs(frq[j] + t.h2o_fl[k])); }
-      if (dmin >= FAR_H2O_GHZ) lm.h2o_far |= 1u << k;
-      if (!no_vfar && very_far(t.h2o_fl[k])) lm.h2o_vfar |= 1u << k;
-      if (dmin >= 750.0 + FAR_H2O_GHZ && smin >= 750.0 + FAR_H2O_GHZ) lm.h2o_none |= 1u << k;
-      if (smin >= 750.0 + FAR_H2O_GHZ) lm.h2o_res |= 1u << k;
-      if (t.h2o_w2[k] > 0.0) {
-        lm.h2o_sd |= 1u << k;
-        if (10.0 * sd_halfwidth_bound(t, k) < dmin - 1.0) lm.h2o_sdfar |= 1u << k;       // its special shape cannot reach the chunk
-        // half-sampled shape: a full 16-frequency chunk of increasing frequencies, >= 3 GHz and 5 spans from the centre
-        bool inc = nfc == 16 && j1 - j0 == 16;
-        for (int j = j0 + 1; inc && j < j1; ++j) inc = frq[j] > frq[j - 1];
-        static const bool no_half = std::getenv("MWRT_NO_SD_HALF") != nullptr;            // diagnostic: time the full sampling
-        if (inc && !no_half && dmin >= 3.0 && dmin >= 5.0 * (frq[j1 - 1] - frq[j0])) lm.h2o_sdint |= 1u << k;
-      }
-    }
-    if (__builtin_popcount(lm.h2o_vfar) < VF_MIN_LINES) lm.h2o_vfar = 0;
-  }
-}
-
-// device copy of chunk_masks(...), immutable and cached like the window descriptors
-int get_masks(mwrt_context* c, const mwrt_model* m, const double* frq, int nf, int nfc, const LineMasks** out) {
-  for (size_t i = 0; i < c->mask_cache.size(); ++i) {
-    auto& e = c->mask_cache[i];
-    if (e.model_id == m->id && e.nfc == nfc && (int)e.frq.size() == nf && std::memcmp(e.frq.data(), frq, sizeof(double) * nf) == 0) {
-      *out = e.d_masks;
-      // least recently USED goes first: a hit moves to the back, so a warm-up call keeps what it touched (a later miss of the
-      // same sequence must not evict it -- the eviction drains the device, which a capturing stream refuses)
-      std::rotate(c->mask_cache.begin() + (long)i, c->mask_cache.begin() + (long)i + 1, c->mask_cache.end());
-      return MWRT_OK;
-    }
-  }
-  if (c->mask_cache.size() >= 64) {                     // bounded: drop the least recently used entry behind a device-wide drain
-    HIP_TRY(hipDeviceSynchronize());
-    (void)hipFree(c->mask_cache.front().d_masks);
-    c->mask_cache.erase(c->mask_cache.begin());
-  }
-  std::vector<LineMasks> host;
-  chunk_masks(m->h_desc, frq, nf, nfc, &host);
-  mwrt_context::MaskEntry e{m->id, nfc, std::vector<double>(frq, frq + nf), nullptr};
-  HIP_TRY(hipMalloc((void**)&e.d_masks, sizeof(LineMasks) * host.size()));
-  hipError_t err = hipMemcpyAsync(e.d_masks, host.data(), sizeof(LineMasks) * host.size(), hipMemcpyHostToDevice, c->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
-  if (err != hipSuccess) { (void)hipFree(e.d_masks); HIP_TRY(err); }
-  c->mask_cache.push_back(std::move(e));
-  *out = c->mask_cache.back().d_masks;
-  return MWRT_OK;
-}
-
-// Chebyshev nodes of [flo, fhi] and the barycentric Lagrange weights of every target frequency of the window,
-// stored [chunk][node][target]; targets past the last frequency repeat it (their results are discarded)
-template <int NNODES>
-void window_nodes(const double* frq, int b, int e, int nchunks, double* fnode, double* blk_base) {
-  const int per = nchunks * WIN_NFC;
-  const double flo = frq[b], fhi = frq[e];
-  long double x[NNODES], bw[NNODES];
-  for (int m = 0; m < NNODES; ++m)
-    fnode[m] = (double)(0.5L * (flo + fhi) + 0.5L * (fhi - flo) * cosl(M_PIl * (2 * m + 1) / (2.0L * NNODES)));
-  for (int m = 0; m < NNODES; ++m) x[m] = fnode[m];                // weights for the nodes as the kernel sees them
-  for (int m = 0; m < NNODES; ++m) {
-    long double prod = 1.0L;
-    for (int k = 0; k < NNODES; ++k) if (k != m) prod *= (x[m] - x[k]);
-    bw[m] = 1.0L / prod;
-  }
-  for (int r = 0; r < per; ++r) {
-    const long double f = frq[std::min(b + r, e)];
-    const int cidx = r / WIN_NFC, j = r % WIN_NFC;
-    double* blk = blk_base + (size_t)cidx * NNODES * WIN_NFC;
-    int hit = -1;
-    for (int m = 0; m < NNODES; ++m) if (f == x[m]) hit = m;
-    if (hit >= 0) { blk[hit * WIN_NFC + j] = 1.0; continue; }
-    long double q[NNODES], sum = 0.0L;
-    for (int m = 0; m < NNODES; ++m) { q[m] = bw[m] / (f - x[m]); sum += q[m]; }
-    for (int m = 0; m < NNODES; ++m) blk[m * WIN_NFC + j] = (double)(q[m] / sum);
-  }
-}
-
-struct WindowSet {
-  std::vector<WinDesc> wins;
-  std::vector<double> lag, lag_h;       // [nwin][WIN_CHUNKS_MAX][nodes][WIN_NFC]
-  std::vector<double> lag_sd;           // [nchunks][SD_TARGETS][SD_NODES]: odd slots of a chunk from slots 0, 2, ..., 14, 15
-};
-
-// far-line sets of a window [flo, fhi]: an O2 line is far beyond max(4 GHz, 1.6 half-spans), an H2O line beyond
-// max(30 GHz, 11.8 half-spans) -- the distance-to-half-span ratios the 16- and 8-node interpolations were sized for
-void window_far_sets(const mwrt_model_desc& t, double flo, double fhi, WinDesc* d) {
-  const double half = 0.5 * (fhi - flo);
-  const double mo = std::max(WIN_MARGIN_GHZ, 1.6 * half), mh = std::max(WIN_H2O_MARGIN_GHZ, 11.8 * half);
-  d->o2_far = 0; d->h2o_far_both = 0; d->h2o_far_res = 0;
-  for (int k = 0; k < t.n_o2; ++k) {
-    const double c = t.o2_f[k];
-    if (c < flo - mo || c > fhi + mo) d->o2_far |= 1ull << k;
-  }
-  for (int k = 0; k < t.n_h2o; ++k) {
-    const double c = t.h2o_fl[k];
-    if (!(c < flo - mh || c > fhi + mh)) continue;
-    // a speed-dependent line stays direct wherever its special shape (inside 10 half-widths) could reach the window
-    if (t.h2o_w2[k] > 0.0 && !(10.0 * sd_halfwidth_bound(t, k) < std::min(std::fabs(c - flo), std::fabs(c - fhi)) - 1.0)) continue;
-    const double g = WIN_CUTOFF_GUARD_GHZ;
-    const bool d1_in = std::fabs(flo - c) < 750.0 - g && std::fabs(fhi - c) < 750.0 - g;
-    const bool d2_in = fhi + c < 750.0 - g;
-    const bool d2_out = flo + c >= 750.0 + g;
-    if (d1_in && d2_in) d->h2o_far_both |= 1u << k;
-    else if (d1_in && d2_out) d->h2o_far_res |= 1u << k;
-    // anything else (a cutoff crossing the window, or both terms out) is left to the per-chunk loops
-  }
-}
-
-void build_windows(const mwrt_model_desc& t, const double* frq, int nf, WindowSet* ws) {
-  const int per = WIN_CHUNKS * WIN_NFC;
-  const int nchunks = (nf + WIN_NFC - 1) / WIN_NFC;
-  const int nbase = (nf + per - 1) / per;
-  // base windows of WIN_CHUNKS chunks; two neighbours are MERGED (one node phase for both) when the merged window
-  // keeps every O2 line far and loses no H2O line from the far set: the out-of-band stretches of a spectrum
-  struct Span { int c0, nch; };
-  std::vector<Span> spans;
-  auto bounds = [&](const Span& sp, int* b, int* e) { *b = sp.c0 * WIN_NFC; *e = std::min(nf, (sp.c0 + sp.nch) * WIN_NFC) - 1; };
-  for (int w = 0; w < nbase; ++w) spans.push_back({w * WIN_CHUNKS, std::min(WIN_CHUNKS, nchunks - w * WIN_CHUNKS)});
-  const bool merge = std::getenv("MWRT_WIN_NOMERGE") == nullptr;                       // diagnostic: time the unmerged windows
-  for (size_t i = 0; i + 1 < spans.size();) {
-    const Span m{spans[i].c0, spans[i].nch + spans[i + 1].nch};
-    bool ok = merge && spans[i].nch == WIN_CHUNKS && m.nch <= WIN_CHUNKS_MAX;
-    if (ok) {
-      int b, e; bounds(m, &b, &e);
-      WinDesc dm{}, d0{}, d1{};
-      window_far_sets(t, frq[b], frq[e], &dm);
-      int b0, e0, b1, e1; bounds(spans[i], &b0, &e0); bounds(spans[i + 1], &b1, &e1);
-      window_far_sets(t, frq[b0], frq[e0], &d0);
-      window_far_sets(t, frq[b1], frq[e1], &d1);
-      const unsigned long long all_o2 = t.n_o2 >= 64 ? ~0ull : ((1ull << t.n_o2) - 1ull);
-      ok = dm.o2_far == all_o2 &&                                                     // no O2 line anywhere near
-           (dm.h2o_far_both | dm.h2o_far_res) == ((d0.h2o_far_both | d0.h2o_far_res) & (d1.h2o_far_both | d1.h2o_far_res));
-    }
-    if (ok) { spans[i] = m; spans.erase(spans.begin() + (long)i + 1); ++i; }           // (a merged window is not merged again)
-    else ++i;
-  }
-  // Workgroups are dispatched in grid order (profiles fastest, then windows): the EXPENSIVE windows go first, so that the
-  // last, partly filled round of the launch is made of cheap ones (the oxygen band sits at the end of a 20-60 GHz grid).
-  // Cost per frequency, roughly, in instructions: a floor, 12 per oxygen line evaluated directly, the speed-dependent shape
-  // where some level can be inside its 10 half-widths.
-  if (std::getenv("MWRT_WIN_GRID_ORDER") == nullptr) {                                   // (diagnostic: keep the grid order)
-    auto cost = [&](const Span& sp) {
-      int b, e; bounds(sp, &b, &e);
-      WinDesc d{};
-      window_far_sets(t, frq[b], frq[e], &d);
-      const unsigned long long all_o2 = t.n_o2 >= 64 ? ~0ull : ((1ull << t.n_o2) - 1ull);
-      double per_f = 150.0 + 12.0 * __builtin_popcountll(~d.o2_far & all_o2);
-      for (int k = 0; k < t.n_h2o; ++k) {
-        if (!(t.h2o_w2[k] > 0.0)) continue;
-        const double c = t.h2o_fl[k];
-        const double dist = (c < frq[b]) ? frq[b] - c : ((c > frq[e]) ? c - frq[e] : 0.0);
-        per_f += 50.0 * std::max(0.0, 1.0 - dist / (10.0 * sd_halfwidth_bound(t, k)));
-      }
-      return per_f * (e - b + 1);
-    };
-    std::stable_sort(spans.begin(), spans.end(), [&](const Span& x, const Span& y) { return cost(x) > cost(y); });
-  }
-  // Lagrange weights of the half-sampled speed-dependent shape, per chunk (zero for a partial last chunk: never used)
-  ws->lag_sd.assign((size_t)nchunks * SD_TARGETS * SD_NODES, 0.0);
-  for (int ch = 0; ch < nchunks; ++ch) {
-    if ((ch + 1) * WIN_NFC > nf) continue;
-    const double* f = frq + (size_t)ch * WIN_NFC;
-    for (int i = 0; i < SD_TARGETS; ++i) {
-      const long double x = f[2 * i + 1];
-      for (int n = 0; n < SD_NODES; ++n) {
-        long double w = 1.0L;
-        for (int q = 0; q < SD_NODES; ++q)
-          if (q != n) w *= (x - (long double)f[sd_node_slot(q)]) / ((long double)f[sd_node_slot(n)] - (long double)f[sd_node_slot(q)]);
-        ws->lag_sd[((size_t)ch * SD_TARGETS + i) * SD_NODES + n] = (double)w;
-      }
-    }
-  }
-  const int nwin = (int)spans.size();
-  const int perm = WIN_CHUNKS_MAX * WIN_NFC;
-  ws->wins.assign(nwin, WinDesc{});
-  ws->lag.assign((size_t)nwin * perm * WIN_NODES, 0.0);
-  ws->lag_h.assign((size_t)nwin * perm * WIN_NODES_H, 0.0);
-  for (int w = 0; w < nwin; ++w) {
-    WinDesc& d = ws->wins[w];
-    int b, e; bounds(spans[w], &b, &e);
-    d.flo = frq[b]; d.fhi = frq[e];
-    d.first_chunk = spans[w].c0;
-    d.nchunks = spans[w].nch;
-    window_nodes<WIN_NODES>(frq, b, e, d.nchunks, d.fnode, ws->lag.data() + (size_t)w * perm * WIN_NODES);
-    window_nodes<WIN_NODES_H>(frq, b, e, d.nchunks, d.fnode_h, ws->lag_h.data() + (size_t)w * perm * WIN_NODES_H);
-    window_far_sets(t, d.flo, d.fhi, &d);
-  }
-}
-
-struct WinPtrs { const WinDesc* win; const double* lag; const double* lag_h; const double* lag_sd; const LineMasks* masks; int nwin; };   // masks: get_masks(.., WIN_NFC)
-
-int get_windows(mwrt_context* c, const mwrt_model* m, const double* frq, int nf, WinPtrs* out) {
-  for (size_t i = 0; i < c->win_cache.size(); ++i) {
-    auto& e = c->win_cache[i];
-    if (e.model_id == m->id && (int)e.frq.size() == nf && std::memcmp(e.frq.data(), frq, sizeof(double) * nf) == 0) {
-      *out = WinPtrs{(const WinDesc*)e.d_blob, (const double*)(e.d_blob + e.off_lag), (const double*)(e.d_blob + e.off_lagh),
-                     (const double*)(e.d_blob + e.off_lagsd), nullptr, e.nwin};
-      std::rotate(c->win_cache.begin() + (long)i, c->win_cache.begin() + (long)i + 1, c->win_cache.end());   // least recently used first
-      return get_masks(c, m, frq, nf, WIN_NFC, &out->masks);
-    }
-  }
-  if (c->win_cache.size() >= 16) {                      // bounded: drop the least recently used entry behind a device-wide drain
-    HIP_TRY(hipDeviceSynchronize());
-    (void)hipFree(c->win_cache.front().d_blob);
-    c->win_cache.erase(c->win_cache.begin());
-  }
-  WindowSet ws;
-  build_windows(m->h_desc, frq, nf, &ws);
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  mwrt_context::WinEntry e{m->id, std::vector<double>(frq, frq + nf), nullptr, 0, 0, 0, (int)ws.wins.size()};
-  e.off_lag = up(sizeof(WinDesc) * ws.wins.size());
-  e.off_lagh = e.off_lag + up(sizeof(double) * ws.lag.size());
-  e.off_lagsd = e.off_lagh + up(sizeof(double) * ws.lag_h.size());
-  const size_t total = e.off_lagsd + up(sizeof(double) * ws.lag_sd.size());
-  std::vector<char> host(total, 0);
-  std::memcpy(host.data(), ws.wins.data(), sizeof(WinDesc) * ws.wins.size());
-  std::memcpy(host.data() + e.off_lag, ws.lag.data(), sizeof(double) * ws.lag.size());
-  std::memcpy(host.data() + e.off_lagh, ws.lag_h.data(), sizeof(double) * ws.lag_h.size());
-  std::memcpy(host.data() + e.off_lagsd, ws.lag_sd.data(), sizeof(double) * ws.lag_sd.size());
-  HIP_TRY(hipMalloc((void**)&e.d_blob, total));
-  hipError_t err = hipMemcpyAsync(e.d_blob, host.data(), total, hipMemcpyHostToDevice, c->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
-  if (err != hipSuccess) { (void)hipFree(e.d_blob); HIP_TRY(err); }
-  c->win_cache.push_back(std::move(e));
-  const auto& k = c->win_cache.back();
-  *out = WinPtrs{(const WinDesc*)k.d_blob, (const double*)(k.d_blob + k.off_lag), (const double*)(k.d_blob + k.off_lagh),
-                 (const double*)(k.d_blob + k.off_lagsd), nullptr, k.nwin};
-  return get_masks(c, m, frq, nf, WIN_NFC, &out->masks);
-}
-
-// plane-parallel air mass 1 / sin(elev) per elevation (NaN elevation -> NaN air mass: that angle's rows come out NaN)
-int airmass_of(const double* elev, int nang, std::vector<double>* am) {
-  am->resize(nang);
-  for (int a = 0; a < nang; ++a) {
-    // The wrapper tests ang = [elevation_k] per k (PyRTlib_processing.py:106, :117) and skips only that
-    // k: a NaN elevation blanks its own [:, k, :] rows and nothing else.  Its air mass is NaN, which
-    // the slant-path integration carries into every output of that angle; valid[] is about the
-    // profile's own data and stays 1.
-    if (std::isnan(elev[a])) { (*am)[a] = std::nan(""); continue; }
-    // a path at or below the horizon has no plane-parallel air mass
-    if (!(elev[a] > 0.0 && elev[a] < 180.0))
-      return fail(MWRT_ERR_INVALID_ARGUMENT, "elevation angles must lie in (0, 180) degrees");
-    (*am)[a] = 1.0 / std::sin(elev[a] * M_PI / 180.0);
-  }
-  return MWRT_OK;
-}
-
-// ---- fine-grid two-kernel form: K1 + layer step -> zenith layer optical depth in HBM -> RTE ----
-int tau_pitch_of(int nf) { return ((nf + TAU_NFC - 1) / TAU_NFC) * TAU_NFC; }
-
-// can the windowed absorption kernel serve this call (frequency list, level count, LDS)?
-bool windowed_ok(const mwrt_context* c, const double* frq, int nf, int threads) {
-  return windows_eligible(frq, nf) && threads <= 512 && absorb_win_lds_bytes(threads) <= (size_t)c->lds_max;
+  const WindowLayout l = window_layout(b.count, nf);
+  AbsorbWinArgs w{};
+  w.M = m->d_desc; w.p = d_p; w.t = d_t; w.rh = d_rh; w.frq = dev_frq;
+  w.win = (const WinDesc*)b.dev; w.lagrange = (const double*)(b.dev + l.off_lag);
+  w.lagrange_h = (const double*)(b.dev + l.off_lagh); w.lag_sd = (const double*)(b.dev + l.off_lagsd);
+  int rc = get_masks(c, m, frq, nf, WIN_NFC, &w.masks); if (rc) return rc;
+  w.awet = d_awet; w.adry = d_adry; w.nlev = nlev; w.nf = nf;
+  if (T) w.T = *T;
+  return timed(c, st, [&] { return launch_absorb_win(w, dim3((unsigned)nprof, (unsigned)b.count), dim3(threads), st, T != nullptr); });
 }
 
 // K1 (+ layer step): d_tau [nprof][nlev][fpitch], d_valid [nprof].  Windowed kernel when the list qualifies
@@ -659,33 +329,20 @@ int layer_tau_launch(mwrt_context* c, const mwrt_model* m, int64_t nprof, int nl
                      double* d_tau, int fpitch, uint8_t* d_valid, hipStream_t st) {
   const int threads = tau_threads(nlev);
   if (threads > 1024) return fail(MWRT_ERR_UNSUPPORTED, "layer optical depths: nlev > 1009");
-  const bool eligible = windowed_ok(c, frq, nf, threads);
-  if (c->absorption_mode == 2 && !eligible)
+  const AbsorbRoute route = absorption_route(c->absorption_mode, c->lds_max, frq, nf, threads);
+  if (route == AbsorbRoute::refused)
     return fail(MWRT_ERR_UNSUPPORTED, "windowed absorption needs >= 128 strictly increasing frequencies in windows <= 6 GHz wide, "
                                       "<= 505 levels");
   HIP_TRY(hipMemsetAsync(d_valid, 1, (size_t)nprof, st));
-  TauOut T{d_z, d_tau, d_valid, fpitch};
-  if (eligible && c->absorption_mode != 1) {
-    WinPtrs wp{};
-    int rc = get_windows(c, m, frq, nf, &wp); if (rc) return rc;
-    AbsorbWinArgs w{};
-    w.M = m->d_desc; w.p = d_p; w.t = d_t; w.rh = d_rh; w.frq = dev_frq;
-    w.win = wp.win; w.lagrange = wp.lag; w.lagrange_h = wp.lag_h; w.masks = wp.masks; w.lag_sd = wp.lag_sd;
-    w.nlev = nlev; w.nf = nf; w.T = T;
-    timing_begin(c, st);
-    hipError_t e = launch_absorb_win(w, dim3((unsigned)nprof, (unsigned)wp.nwin), dim3(threads), st, true);
-    timing_end(c, st);
-    HIP_TRY(e);
-    return MWRT_OK;
-  }
+  const TauOut T{d_z, d_tau, d_valid, fpitch};
+  if (route == AbsorbRoute::windowed)
+    return launch_windowed_absorption(c, m, nprof, nlev, d_p, d_t, d_rh, nf, frq, dev_frq, nullptr, nullptr, &T, threads, st);
   AbsorbArgs a{};
   a.M = m->d_desc; a.p = d_p; a.t = d_t; a.rh = d_rh; a.frq = dev_frq; a.nlev = nlev; a.nf = nf; a.T = T;
   { int rc = get_masks(c, m, frq, nf, TAU_NFC, &a.masks); if (rc) return rc; }
-  timing_begin(c, st);
-  hipError_t e = launch_absorb_tau(a, dim3((unsigned)nprof, (unsigned)((nf + TAU_NFC - 1) / TAU_NFC)), dim3(threads), st);
-  timing_end(c, st);
-  HIP_TRY(e);
-  return MWRT_OK;
+  return timed(c, st, [&] {
+    return launch_absorb_tau(a, dim3((unsigned)nprof, (unsigned)((nf + TAU_NFC - 1) / TAU_NFC)), dim3(threads), st);
+  });
 }
 
 // K2: TBs from layer optical depths; the elevations go through in groups of <= 8 (or 10) per launch
@@ -698,15 +355,92 @@ int rte_tau_launch(mwrt_context* c, const mwrt_model* m, int64_t nprof, int nlev
   const dim3 grid((unsigned)nprof, (unsigned)((nf + RTE_THREADS - 1) / RTE_THREADS));
   const size_t lds = sizeof(double) * 2 * (size_t)nlev;
   for (int a0 = 0; a0 < nang;) {
-    const int rem = nang - a0;
-    const int na = rem <= 8 ? rem : (rem == 10 ? 10 : (rem == 9 ? 5 : 8));
+    const int na = rte_tau_angles(nang - a0);
     r.a0 = a0;
-    timing_begin(c, st);
-    hipError_t e = launch_rte_tau(r, grid, lds, st, na);
-    timing_end(c, st);
-    HIP_TRY(e);
+    const int rc = timed(c, st, [&] { return launch_rte_tau(r, grid, lds, st, na); });
+    if (rc) return rc;
     a0 += na;
   }
+  return MWRT_OK;
+}
+
+// ---- the preamble the entry points share ----
+// An entry's own check, evaluated by the entry and reported in its place among the shared ones (the tests pin which
+// status comes out when several checks would fire)
+struct Check { int code; const char* msg; };
+constexpr Check PASS{MWRT_OK, nullptr};
+
+enum : unsigned {
+  CALL_ANGLES = 1,       // the entry takes elevations: nang is range-checked, the air masses are uploaded
+  CALL_HOST = 2,         // host-buffer entry: the context's own stream; nprof == 0 returns before hipSetDevice, not after
+  CALL_STAGES = 4,       // ... that hands its staged buffers to a device entry: no NaN check and no uploads of its own
+  CALL_NAN_BLANKS = 8    // tb_launch: a NaN frequency or all-NaN elevations is reported in Call::blank instead of failing
+};
+
+struct CallSpec {
+  unsigned flags;
+  int64_t nprof; int nlev, nf; const double* frq;
+  int nang; const double* elev;            // (0, nullptr without CALL_ANGLES)
+  void* stream;                            // the entry's `stream` argument (device entries)
+  bool buffers_ok;                         // every pointer argument the entry requires is given
+  Check after_common = PASS, after_buffers = PASS, before_device = PASS;
+};
+
+struct Call {
+  hipStream_t st = nullptr;
+  const double* dev_frq = nullptr;
+  const double* dev_am = nullptr;
+  bool empty = false;                      // nprof == 0: nothing to do
+  bool blank = false;                      // CALL_NAN_BLANKS
+};
+
+int begin_call(mwrt_context* c, const mwrt_model* const* ms, int nmodels, const CallSpec& s, Call* call) {
+  for (int i = 0; i < nmodels; ++i) {
+    int rc = check_common(c, ms[i], s.nprof, s.nlev, s.nf);
+    if (rc) return rc;
+  }
+  if (s.after_common.code) return fail(s.after_common.code, s.after_common.msg);
+  const bool angles = s.flags & CALL_ANGLES, stages = s.flags & CALL_STAGES, blanks = s.flags & CALL_NAN_BLANKS;
+  if (angles && (s.nang < 1 || s.nang > MWRT_MAX_ANGLES)) return fail(MWRT_ERR_INVALID_ARGUMENT, "nang out of range");
+  if (!s.buffers_ok) return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
+  if (s.after_buffers.code) return fail(s.after_buffers.code, s.after_buffers.msg);
+  if (!stages && !blanks && any_nan(s.frq, s.nf)) return fail(MWRT_ERR_INVALID_ARGUMENT, "NaN frequency");
+  if (s.before_device.code) return fail(s.before_device.code, s.before_device.msg);
+  call->empty = s.nprof == 0;
+  if ((s.flags & CALL_HOST) && call->empty) return MWRT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  call->st = (s.flags & CALL_HOST) ? c->stream : resolve_stream(c, s.stream);
+  if (call->empty || stages) return MWRT_OK;
+  // check_for_nans covers frqs and ang too (PyRTlib_processing.py:77-78): a NaN frequency (the
+  // wrapper's frqs array is shared by every call) leaves everything NaN, valid = 0
+  call->blank = blanks && (any_nan(s.frq, s.nf) || all_nan(s.elev, s.nang));
+  if (call->blank) return MWRT_OK;
+  if (angles) {
+    std::vector<double> am;
+    if (!airmass_of(s.elev, s.nang, &am)) return fail(MWRT_ERR_INVALID_ARGUMENT, "elevation angles must lie in (0, 180) degrees");
+    int rc = upload_small(c, c->frq_cache, s.frq, s.nf, &call->dev_frq); if (rc) return rc;
+    return upload_small(c, c->am_cache, am.data(), s.nang, &call->dev_am);
+  }
+  return upload_small(c, c->frq_cache, s.frq, s.nf, &call->dev_frq);
+}
+
+// The seven optional output columns (mwrt_tb_extras): taulay holds a value per (frequency, level), the others per
+// (elevation, frequency)
+struct ExtraSlot {
+  double* mwrt_tb_extras::*col;
+  bool per_level;
+  size_t row(int nlev, int nf, int nang) const { return per_level ? (size_t)nf * nlev : (size_t)nang * nf; }   // doubles per profile
+};
+constexpr ExtraSlot EXTRA_SLOTS[] = {{&mwrt_tb_extras::tbatm, false},  {&mwrt_tb_extras::tmr, false},    {&mwrt_tb_extras::tauwet, false},
+                                     {&mwrt_tb_extras::taudry, false}, {&mwrt_tb_extras::taulay, true},  {&mwrt_tb_extras::tauliq, false},
+                                     {&mwrt_tb_extras::tauice, false}};
+constexpr int NEX = sizeof(EXTRA_SLOTS) / sizeof(EXTRA_SLOTS[0]);
+
+// host-buffer entries: the k input arrays of `n` doubles each, side by side in d_in
+int stage_in(mwrt_context* c, hipStream_t st, size_t n, const double* const* src, int k) {
+  HIP_TRY(c->d_in.reserve((size_t)k * n * sizeof(double)));
+  for (int i = 0; i < k; ++i)
+    HIP_TRY(hipMemcpyAsync(c->d_in.as<double>() + (size_t)i * n, src[i], n * sizeof(double), hipMemcpyHostToDevice, st));
   return MWRT_OK;
 }
 
@@ -755,10 +489,7 @@ int mwrt_destroy(mwrt_context* c) {
   if (!c) return MWRT_OK;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
-  for (auto& e : c->win_cache) (void)hipFree(e.d_blob);
-  c->win_cache.clear();
-  for (auto& e : c->mask_cache) (void)hipFree(e.d_masks);
-  c->mask_cache.clear();
+  c->win_cache.release(); c->mask_cache.release();
   c->frq_cache.release(); c->am_cache.release(); c->elev_cache.release(); c->d_amf.release(); c->d_duct.release(); c->d_alpha.release();
   c->d_jac.release();
   c->d_in.release(); c->d_out.release();
@@ -813,16 +544,8 @@ int mwrt_model_destroy(mwrt_context* c, mwrt_model* m) {
   if (c) {
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();                       // launches on any stream may still read the tables / windows
-    for (size_t i = c->win_cache.size(); i-- > 0;)      // window descriptors are keyed by the model: drop this one's
-      if (c->win_cache[i].model_id == m->id) {
-        (void)hipFree(c->win_cache[i].d_blob);
-        c->win_cache.erase(c->win_cache.begin() + (long)i);
-      }
-    for (size_t i = c->mask_cache.size(); i-- > 0;)
-      if (c->mask_cache[i].model_id == m->id) {
-        (void)hipFree(c->mask_cache[i].d_masks);
-        c->mask_cache.erase(c->mask_cache.begin() + (long)i);
-      }
+    c->win_cache.drop_model(m->id);                     // window descriptors and masks are keyed by the model: drop this one's
+    c->mask_cache.drop_model(m->id);
   }
   if (m->d_desc) (void)hipFree(m->d_desc);
   delete m;
@@ -844,43 +567,23 @@ static int tb_launch(mwrt_context* c, int nmodels, const mwrt_model* const* ms, 
     for (int i = 0; i < nmodels; ++i)
       if (ms[i] && ms[i]->h_desc.n_x <= 0)
         return fail(MWRT_ERR_UNSUPPORTED, "o3n given but the model carries no extra-species line table (mwrt_model_desc.n_x = 0)");
-  for (int i = 0; i < nmodels; ++i) {
-    int rc = check_common(c, ms[i], nprof, nlev, nf);
-    if (rc) return rc;
-  }
-  if (nang < 1 || nang > MWRT_MAX_ANGLES) return fail(MWRT_ERR_INVALID_ARGUMENT, "nang out of range");
   const bool from_alpha = d_awet != nullptr;
-  if (!d_z || !d_t || !frq || !elev || !d_tb || !d_valid || (!from_alpha && (!d_p || !d_rh)) || (from_alpha && !d_adry))
-    return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
   const int64_t rows = nprof * nmodels;
-  if (rows > 2147483647LL) return fail(MWRT_ERR_UNSUPPORTED, "nmodels x nprof exceeds grid limit");
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = resolve_stream(c, stream);
-  if (nprof == 0) return MWRT_OK;
-  const size_t nout = (size_t)rows * nang * nf;
-  bool all_elev_nan = true;
-  for (int a = 0; a < nang; ++a) all_elev_nan = all_elev_nan && std::isnan(elev[a]);
-  if (any_nan(frq, nf) || all_elev_nan) {
-    // check_for_nans covers frqs and ang too (PyRTlib_processing.py:77-78): a NaN frequency (the
-    // wrapper's frqs array is shared by every call) leaves everything NaN, valid = 0
-    HIP_TRY(hipMemsetAsync(d_tb, 0xFF, nout * sizeof(double), st));
+  CallSpec s{CALL_ANGLES | CALL_NAN_BLANKS, nprof, nlev, nf, frq, nang, elev, stream};
+  s.buffers_ok = d_z && d_t && frq && elev && d_tb && d_valid && (from_alpha ? d_adry != nullptr : d_p && d_rh);
+  if (rows > 2147483647LL) s.after_buffers = Check{MWRT_ERR_UNSUPPORTED, "nmodels x nprof exceeds grid limit"};
+  Call call;
+  int rc = begin_call(c, ms, nmodels, s, &call);
+  if (rc || call.empty) return rc;
+  hipStream_t st = call.st;
+  if (call.blank) {                                   // the one place where NaN inputs blank the outputs instead of failing
+    HIP_TRY(hipMemsetAsync(d_tb, 0xFF, (size_t)rows * nang * nf * sizeof(double), st));
     HIP_TRY(hipMemsetAsync(d_valid, 0, (size_t)rows, st));
-    if (ex) {
-      if (ex->tbatm) HIP_TRY(hipMemsetAsync(ex->tbatm, 0xFF, nout * sizeof(double), st));
-      if (ex->tmr) HIP_TRY(hipMemsetAsync(ex->tmr, 0xFF, nout * sizeof(double), st));
-      if (ex->tauwet) HIP_TRY(hipMemsetAsync(ex->tauwet, 0xFF, nout * sizeof(double), st));
-      if (ex->taudry) HIP_TRY(hipMemsetAsync(ex->taudry, 0xFF, nout * sizeof(double), st));
-      if (ex->taulay) HIP_TRY(hipMemsetAsync(ex->taulay, 0xFF, (size_t)rows * nf * nlev * sizeof(double), st));
-      if (ex->tauliq) HIP_TRY(hipMemsetAsync(ex->tauliq, 0xFF, nout * sizeof(double), st));
-      if (ex->tauice) HIP_TRY(hipMemsetAsync(ex->tauice, 0xFF, nout * sizeof(double), st));
-    }
+    for (const ExtraSlot& x : EXTRA_SLOTS)
+      if (ex && ex->*x.col) HIP_TRY(hipMemsetAsync(ex->*x.col, 0xFF, (size_t)rows * x.row(nlev, nf, nang) * sizeof(double), st));
     return MWRT_OK;
   }
-  std::vector<double> am;
-  int rc = airmass_of(elev, nang, &am); if (rc) return rc;
-  const double *dev_frq = nullptr, *dev_am = nullptr;
-  rc = upload_small(c, c->frq_cache, frq, nf, &dev_frq); if (rc) return rc;
-  rc = upload_small(c, c->am_cache, am.data(), nang, &dev_am); if (rc) return rc;
+  const double *dev_frq = call.dev_frq, *dev_am = call.dev_am;
 
   FusedArgs a{};
   for (int i = 0; i < nmodels; ++i) a.Ms[i] = ms[i]->d_desc;
@@ -895,27 +598,26 @@ static int tb_launch(mwrt_context* c, int nmodels, const mwrt_model* const* ms, 
   // and NaN elevations, like every other column)
   if (cloudy) { a.denliq = opt->denliq; a.denice = opt->denice; }
   if (ozone) a.o3n = opt->o3n;
+  bool ws_held = false;                               // a shared workspace is in use: handed over on every return path
+  auto handover = on_scope_exit([&] { if (ws_held) (void)workspace_release(c, st); });
   if (rays) {
     // RTEquation.refractivity + ray_tracing [EXT] as a pre-kernel on the same stream: path factor ds/dz per
     // (profile, angle, layer) into the context's workspace (grown only, never shrunk)
     const double* dev_elev = nullptr;
     rc = upload_small(c, c->elev_cache, elev, nang, &dev_elev); if (rc) return rc;
-    const size_t need = (size_t)nprof * nang * nlev * sizeof(double);
-    if (need > c->d_amf.cap || (size_t)nprof > c->d_duct.cap) {
-      HIP_TRY(hipDeviceSynchronize());                // queued launches may still read the old workspace
-      HIP_TRY(c->d_amf.reserve(need));
-      HIP_TRY(c->d_duct.reserve((size_t)nprof));
-    }
+    HIP_TRY(grow_behind_drain(c->d_amf, (size_t)nprof * nang * nlev * sizeof(double)));
+    HIP_TRY(grow_behind_drain(c->d_duct, (size_t)nprof));
     rc = workspace_acquire(c, st); if (rc) return rc;
+    ws_held = true;
     HIP_TRY(hipMemsetAsync(c->d_duct.p, 0, (size_t)nprof, st));
-    const int rthreads = ((nlev + WAVE - 1) / WAVE) * WAVE;
-    hipLaunchKernelGGL(k_ray_paths, dim3((unsigned)nprof), dim3(rthreads), 0, st, d_z, d_p, d_t, d_rh, (int)nlev, dev_elev,
+    hipLaunchKernelGGL(k_ray_paths, dim3((unsigned)nprof), dim3(lanes_for(nlev)), 0, st, d_z, d_p, d_t, d_rh, (int)nlev, dev_elev,
                        (int)nang, c->d_amf.as<double>(), c->d_duct.as<uint8_t>());
     HIP_TRY(hipGetLastError());
     a.amf = c->d_amf.as<double>();
     a.duct = c->d_duct.as<uint8_t>();
   }
-  const bool extras = ex && (ex->tbatm || ex->tmr || ex->tauwet || ex->taudry || ex->taulay || ex->tauliq || ex->tauice);
+  bool extras = false;
+  for (const ExtraSlot& x : EXTRA_SLOTS) extras = extras || (ex && ex->*x.col);
   int variant = extras ? FUSED_FULL : (use_opt ? FUSED_OPT : FUSED_TB_ONLY);
   if (from_alpha) {
     if (extras || use_opt || nmodels != 1)
@@ -927,19 +629,17 @@ static int tb_launch(mwrt_context* c, int nmodels, const mwrt_model* const* ms, 
   // ~1.8x the fused kernel's K1 on such grids and ends each chunk with the layer step, so what crosses HBM is the
   // zenith layer optical depth: 8 B per (profile, level, frequency), written once, read once by k_rte_tau
   // (lane = frequency).  Profile batches of <= alpha_batch_bytes, both kernels on the caller's stream.
-  if (variant == FUSED_TB_ONLY && nmodels == 1 && c->absorption_mode != 1 && windowed_ok(c, frq, nf, tau_threads(nlev))) {
+  if (variant == FUSED_TB_ONLY && nmodels == 1 &&
+      absorption_route(c->absorption_mode, c->lds_max, frq, nf, tau_threads(nlev)) == AbsorbRoute::windowed) {
     const int fpitch = tau_pitch_of(nf);
     const size_t per_prof = (size_t)nlev * fpitch * sizeof(double);
     const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(nprof, (int64_t)(c->alpha_batch_bytes / per_prof)));
-    bool have_ws = true;
-    if ((size_t)batch * per_prof > c->d_alpha.cap) {
-      HIP_TRY(hipDeviceSynchronize());                // queued launches may still read the old workspace
-      const hipError_t e = c->d_alpha.reserve((size_t)batch * per_prof);
-      if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); have_ws = false; }   // no room for tau: the fused kernel
-      else HIP_TRY(e);                                                              // needs no workspace at all
-    }
-    if (have_ws) {
+    const hipError_t e = grow_behind_drain(c->d_alpha, (size_t)batch * per_prof);
+    if (e == hipErrorOutOfMemory) (void)hipGetLastError();          // no room for tau: the fused kernel needs no workspace at all
+    else {
+      HIP_TRY(e);
       rc = workspace_acquire(c, st); if (rc) return rc;
+      ws_held = true;
       for (int64_t b0 = 0; b0 < nprof; b0 += batch) {
         const int64_t nb = std::min(batch, nprof - b0);
         double* d_tau = c->d_alpha.as<double>();
@@ -950,15 +650,13 @@ static int tb_launch(mwrt_context* c, int nmodels, const mwrt_model* const* ms, 
                             d_tb + (size_t)b0 * nang * nf, d_valid + b0, st);
         if (rc) return rc;
       }
-      return workspace_release(c, st);
+      return MWRT_OK;
     }
   }
-  const int nfc_main = pick_nfc_fused(c, nlev, nf, nang);
+  const int nfc_main = pick_nfc_fused(c->chunk_width, c->lds_max, nlev, nf, nang);
   if (variant != FUSED_FROM_ALPHA)
     for (int i = 0; i < nmodels; ++i) { rc = get_masks(c, ms[i], frq, nf, nfc_main, &a.masks[i]); if (rc) return rc; }
-  rc = launch_fused(c, nfc_main, a, rows, st, variant);
-  if (rc == MWRT_OK && rays) rc = workspace_release(c, st);
-  return rc;
+  return launch_fused(c, nfc_main, a, rows, st, variant);
 }
 
 int mwrt_tb_batch_device(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
@@ -997,6 +695,55 @@ int mwrt_tb_batch_multi_device(mwrt_context* c, int32_t nmodels, const mwrt_mode
                    stream);
 }
 
+// the host-buffer TB entries behind their checks: the profiles cross PCIe once (for all models), one tb_launch, the
+// results come back and flagged rows are blanked
+static int tb_host(mwrt_context* c, hipStream_t st, int nmodels, const mwrt_model* const* ms, int64_t nprof, int32_t nlev,
+                   const double* z, const double* p, const double* t, const double* rh, int32_t nf, const double* frq,
+                   int32_t nang, const double* elev, double* tb, uint8_t* valid, const mwrt_tb_extras* ex,
+                   const mwrt_tb_options* opt) {
+  const size_t nin = (size_t)nprof * nlev, rows = (size_t)nprof * nmodels, nout = rows * nang * nf;
+  // inputs: z p t rh, then whichever of denliq denice o3n the options carry
+  const double* src[7] = {z, p, t, rh};
+  int nsrc = 4;
+  mwrt_tb_options dopt{};
+  const double** dopt_in[3] = {&dopt.denliq, &dopt.denice, &dopt.o3n};
+  const double* opt_in[3] = {opt ? opt->denliq : nullptr, opt ? opt->denice : nullptr, opt ? opt->o3n : nullptr};
+  int where[3];
+  for (int k = 0; k < 3; ++k) if (opt_in[k]) { where[k] = nsrc; src[nsrc++] = opt_in[k]; }
+  int rc = stage_in(c, st, nin, src, nsrc); if (rc) return rc;
+  HIP_TRY(c->d_out.reserve(nout * sizeof(double)));
+  HIP_TRY(c->d_valid.reserve(rows));
+  const double* din = c->d_in.as<double>();
+  for (int k = 0; k < 3; ++k) if (opt_in[k]) *dopt_in[k] = din + (size_t)where[k] * nin;
+  if (opt) dopt.ray_tracing = opt->ray_tracing;
+  mwrt_tb_extras dex{};
+  if (ex) {
+    size_t need = 0;
+    for (const ExtraSlot& x : EXTRA_SLOTS) if (ex->*x.col) need += rows * x.row(nlev, nf, nang);
+    HIP_TRY(c->d_ex.reserve(need * sizeof(double) + 8));
+    double* q = c->d_ex.as<double>();
+    for (const ExtraSlot& x : EXTRA_SLOTS) if (ex->*x.col) { dex.*x.col = q; q += rows * x.row(nlev, nf, nang); }
+  }
+  rc = tb_launch(c, nmodels, ms, nprof, nlev, din, din + nin, din + 2 * nin, din + 3 * nin, nf, frq, nang, elev,
+                 c->d_out.as<double>(), c->d_valid.as<uint8_t>(), ex ? &dex : nullptr, st, opt ? &dopt : nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(tb, c->d_out.p, nout * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(valid, c->d_valid.p, rows, hipMemcpyDeviceToHost, st));
+  // a profile flagged 2 (negative absorption: pyrtlib raises for the whole execute()) is blanked
+  // as a whole, whichever frequency chunk met it
+  RowArray out[1 + NEX] = {{tb, (size_t)nang * nf}};
+  int nout_arrays = 1;
+  for (const ExtraSlot& x : EXTRA_SLOTS) {
+    if (!ex || !(ex->*x.col)) continue;
+    const size_t per = x.row(nlev, nf, nang);
+    HIP_TRY(hipMemcpyAsync(ex->*x.col, dex.*x.col, rows * per * sizeof(double), hipMemcpyDeviceToHost, st));
+    out[nout_arrays++] = RowArray{ex->*x.col, per};
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  blank_rows(valid, (int64_t)rows, false, out, nout_arrays);
+  return MWRT_OK;
+}
+
 int mwrt_tb_batch_multi(mwrt_context* c, int32_t nmodels, const mwrt_model* const* models, int64_t nprof, int32_t nlev,
                         const double* z, const double* p, const double* t, const double* rh,
                         int32_t nf, const double* frq, int32_t nang, const double* elev,
@@ -1006,25 +753,7 @@ int mwrt_tb_batch_multi(mwrt_context* c, int32_t nmodels, const mwrt_model* cons
   if (nprof < 0 || nlev < 2 || nf < 1 || nang < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "bad sizes");
   if (nprof == 0) return MWRT_OK;
   HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  const size_t nin = (size_t)nprof * nlev, rows = (size_t)nprof * nmodels, nout = rows * nang * nf;
-  HIP_TRY(c->d_in.reserve(4 * nin * sizeof(double)));
-  HIP_TRY(c->d_out.reserve(nout * sizeof(double)));
-  HIP_TRY(c->d_valid.reserve(rows));
-  double* din = c->d_in.as<double>();
-  const double* src[4] = {z, p, t, rh};
-  for (int k = 0; k < 4; ++k)                        // the profiles cross PCIe once for all models
-    HIP_TRY(hipMemcpyAsync(din + k * nin, src[k], nin * sizeof(double), hipMemcpyHostToDevice, st));
-  int rc = tb_launch(c, nmodels, models, nprof, nlev, din, din + nin, din + 2 * nin, din + 3 * nin, nf, frq, nang, elev,
-                     c->d_out.as<double>(), c->d_valid.as<uint8_t>(), nullptr, st);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(tb, c->d_out.p, nout * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(valid, c->d_valid.p, rows, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const double qnan = std::nan("");
-  for (size_t i = 0; i < rows; ++i)
-    if (valid[i] == 2) for (size_t o = 0; o < (size_t)nang * nf; ++o) tb[i * nang * nf + o] = qnan;
-  return MWRT_OK;
+  return tb_host(c, c->stream, nmodels, models, nprof, nlev, z, p, t, rh, nf, frq, nang, elev, tb, valid, nullptr, nullptr);
 }
 
 int mwrt_tb_batch(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
@@ -1038,123 +767,50 @@ int mwrt_tb_batch_opt(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32
                       const double* z, const double* p, const double* t, const double* rh,
                       int32_t nf, const double* frq, int32_t nang, const double* elev,
                       double* tb, uint8_t* valid, const mwrt_tb_extras* ex, const mwrt_tb_options* opt) {
-  int rc = check_common(c, m, nprof, nlev, nf);
-  if (rc) return rc;
-  if (nang < 1 || nang > MWRT_MAX_ANGLES) return fail(MWRT_ERR_INVALID_ARGUMENT, "nang out of range");
-  if (!z || !p || !t || !rh || !frq || !elev || !tb || !valid) return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
-  if (nprof == 0) return MWRT_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  const size_t nin = (size_t)nprof * nlev, nout = (size_t)nprof * nang * nf;
-  const size_t nlay = (size_t)nprof * nf * nlev;
-  const bool has_liq = opt && opt->denliq, has_ice = opt && opt->denice, has_o3 = opt && opt->o3n;
-  HIP_TRY(c->d_in.reserve((4 + (has_liq ? 1 : 0) + (has_ice ? 1 : 0) + (has_o3 ? 1 : 0)) * nin * sizeof(double)));
-  HIP_TRY(c->d_out.reserve(nout * sizeof(double)));
-  HIP_TRY(c->d_valid.reserve((size_t)nprof));
-  double* din = c->d_in.as<double>();
-  const double* src[4] = {z, p, t, rh};
-  for (int k = 0; k < 4; ++k)
-    HIP_TRY(hipMemcpyAsync(din + k * nin, src[k], nin * sizeof(double), hipMemcpyHostToDevice, st));
-  mwrt_tb_options dopt{};
-  if (opt) {
-    double* q = din + 4 * nin;
-    if (has_liq) { HIP_TRY(hipMemcpyAsync(q, opt->denliq, nin * sizeof(double), hipMemcpyHostToDevice, st)); dopt.denliq = q; q += nin; }
-    if (has_ice) { HIP_TRY(hipMemcpyAsync(q, opt->denice, nin * sizeof(double), hipMemcpyHostToDevice, st)); dopt.denice = q; q += nin; }
-    if (has_o3) { HIP_TRY(hipMemcpyAsync(q, opt->o3n, nin * sizeof(double), hipMemcpyHostToDevice, st)); dopt.o3n = q; }
-    dopt.ray_tracing = opt->ray_tracing;
-  }
-  constexpr int NEX = 7;                               // tbatm tmr tauwet taudry taulay tauliq tauice
-  mwrt_tb_extras dex{};
-  double* host_ex[NEX] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  double** slots[NEX] = {&dex.tbatm, &dex.tmr, &dex.tauwet, &dex.taudry, &dex.taulay, &dex.tauliq, &dex.tauice};
-  auto exlen = [&](int k) { return k == 4 ? nlay : nout; };
-  if (ex) {
-    host_ex[0] = ex->tbatm; host_ex[1] = ex->tmr; host_ex[2] = ex->tauwet; host_ex[3] = ex->taudry; host_ex[4] = ex->taulay;
-    host_ex[5] = ex->tauliq; host_ex[6] = ex->tauice;
-    size_t need = 0;
-    for (int k = 0; k < NEX; ++k) if (host_ex[k]) need += exlen(k);
-    HIP_TRY(c->d_ex.reserve(need * sizeof(double) + 8));
-    double* q = c->d_ex.as<double>();
-    for (int k = 0; k < NEX; ++k) if (host_ex[k]) { *slots[k] = q; q += exlen(k); }
-  }
-  rc = mwrt_tb_batch_opt_device(c, m, nprof, nlev, din, din + nin, din + 2 * nin, din + 3 * nin, nf, frq, nang, elev,
-                                c->d_out.as<double>(), c->d_valid.as<uint8_t>(), ex ? &dex : nullptr, opt ? &dopt : nullptr,
-                                st);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(tb, c->d_out.p, nout * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(valid, c->d_valid.p, (size_t)nprof, hipMemcpyDeviceToHost, st));
-  if (ex) {
-    for (int k = 0; k < NEX; ++k)
-      if (host_ex[k]) HIP_TRY(hipMemcpyAsync(host_ex[k], *slots[k], exlen(k) * sizeof(double), hipMemcpyDeviceToHost, st));
-  }
-  HIP_TRY(hipStreamSynchronize(st));
-  // a profile flagged 2 (negative absorption: pyrtlib raises for the whole execute()) is blanked
-  // as a whole, whichever frequency chunk met it
-  const double qnan = std::nan("");
-  for (int64_t i = 0; i < nprof; ++i) {
-    if (valid[i] != 2) continue;
-    for (size_t o = 0; o < (size_t)nang * nf; ++o) tb[(size_t)i * nang * nf + o] = qnan;
-    for (int k = 0; k < NEX; ++k) {
-      if (!host_ex[k]) continue;
-      const size_t per = k == 4 ? (size_t)nf * nlev : (size_t)nang * nf;
-      for (size_t o = 0; o < per; ++o) host_ex[k][(size_t)i * per + o] = qnan;
-    }
-  }
-  return MWRT_OK;
+  CallSpec s{CALL_ANGLES | CALL_HOST | CALL_STAGES, nprof, nlev, nf, frq, nang, elev, nullptr};
+  s.buffers_ok = z && p && t && rh && frq && elev && tb && valid;
+  Call call;
+  const int rc = begin_call(c, &m, 1, s, &call);
+  if (rc || call.empty) return rc;
+  return tb_host(c, call.st, 1, &m, nprof, nlev, z, p, t, rh, nf, frq, nang, elev, tb, valid, ex, opt);
 }
 
 int mwrt_absorption_batch_device(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
                                  const double* d_p, const double* d_t, const double* d_rh,
                                  int32_t nf, const double* frq, double* d_awet, double* d_adry, void* stream) {
-  int rc = check_common(c, m, nprof, nlev, nf);
-  if (rc) return rc;
-  if (!d_p || !d_t || !d_rh || !frq || !d_awet || !d_adry) return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
-  if (any_nan(frq, nf)) return fail(MWRT_ERR_INVALID_ARGUMENT, "NaN frequency");
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = resolve_stream(c, stream);
-  if (nprof == 0) return MWRT_OK;
-  const double* dev_frq = nullptr;
-  rc = upload_small(c, c->frq_cache, frq, nf, &dev_frq); if (rc) return rc;
-  const int wthreads = ((nlev + WAVE - 1) / WAVE) * WAVE;
-  const bool eligible = windowed_ok(c, frq, nf, wthreads);            // node sums in LDS: 2 x 16 doubles per thread
-  if (c->absorption_mode == 2 && !eligible)
+  CallSpec s{0, nprof, nlev, nf, frq, 0, nullptr, stream};
+  s.buffers_ok = d_p && d_t && d_rh && frq && d_awet && d_adry;
+  Call call;
+  int rc = begin_call(c, &m, 1, s, &call);
+  if (rc || call.empty) return rc;
+  const int wthreads = lanes_for(nlev);                 // node sums in LDS: 2 x 16 doubles per thread
+  const AbsorbRoute route = absorption_route(c->absorption_mode, c->lds_max, frq, nf, wthreads);
+  if (route == AbsorbRoute::refused)
     return fail(MWRT_ERR_UNSUPPORTED, "windowed absorption needs >= 128 strictly increasing frequencies in windows <= 6 GHz wide");
-  if (eligible && c->absorption_mode != 1) {
-    WinPtrs wp{};
-    rc = get_windows(c, m, frq, nf, &wp); if (rc) return rc;
-    AbsorbWinArgs w{};
-    w.M = m->d_desc; w.p = d_p; w.t = d_t; w.rh = d_rh; w.frq = dev_frq;
-    w.win = wp.win; w.lagrange = wp.lag; w.lagrange_h = wp.lag_h; w.masks = wp.masks; w.lag_sd = wp.lag_sd;
-    w.awet = d_awet; w.adry = d_adry; w.nlev = nlev; w.nf = nf;
-    timing_begin(c, st);
-    hipError_t e = launch_absorb_win(w, dim3((unsigned)nprof, (unsigned)wp.nwin), dim3(wthreads), st, false);
-    timing_end(c, st);
-    HIP_TRY(e);
-    return MWRT_OK;
-  }
+  if (route == AbsorbRoute::windowed)
+    return launch_windowed_absorption(c, m, nprof, nlev, d_p, d_t, d_rh, nf, frq, call.dev_frq, d_awet, d_adry, nullptr, wthreads,
+                                      call.st);
   AbsorbArgs a{};
-  a.M = m->d_desc; a.p = d_p; a.t = d_t; a.rh = d_rh; a.frq = dev_frq;
+  a.M = m->d_desc; a.p = d_p; a.t = d_t; a.rh = d_rh; a.frq = call.dev_frq;
   a.awet = d_awet; a.adry = d_adry; a.nlev = nlev; a.nf = nf;
   rc = get_masks(c, m, frq, nf, pick_nfc(nf), &a.masks); if (rc) return rc;
-  return launch_absorb(c, pick_nfc(nf), a, nprof, st);
+  return launch_absorb(c, pick_nfc(nf), a, nprof, call.st);
 }
 
 int mwrt_absorption_batch(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
                           const double* p, const double* t, const double* rh,
                           int32_t nf, const double* frq, double* awet, double* adry) {
-  int rc = check_common(c, m, nprof, nlev, nf);
-  if (rc) return rc;
-  if (!p || !t || !rh || !frq || !awet || !adry) return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
-  if (nprof == 0) return MWRT_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = c->stream;
+  CallSpec s{CALL_HOST | CALL_STAGES, nprof, nlev, nf, frq, 0, nullptr, nullptr};
+  s.buffers_ok = p && t && rh && frq && awet && adry;
+  Call call;
+  int rc = begin_call(c, &m, 1, s, &call);
+  if (rc || call.empty) return rc;
+  hipStream_t st = call.st;
   const size_t nin = (size_t)nprof * nlev, nout = (size_t)nprof * nf * nlev;
-  HIP_TRY(c->d_in.reserve(3 * nin * sizeof(double)));
-  HIP_TRY(c->d_out.reserve(2 * nout * sizeof(double)));
-  double* din = c->d_in.as<double>();
   const double* src[3] = {p, t, rh};
-  for (int k = 0; k < 3; ++k)
-    HIP_TRY(hipMemcpyAsync(din + k * nin, src[k], nin * sizeof(double), hipMemcpyHostToDevice, st));
+  rc = stage_in(c, st, nin, src, 3); if (rc) return rc;
+  HIP_TRY(c->d_out.reserve(2 * nout * sizeof(double)));
+  const double* din = c->d_in.as<double>();
   double* dout = c->d_out.as<double>();
   rc = mwrt_absorption_batch_device(c, m, nprof, nlev, din, din + nin, din + 2 * nin, nf, frq, dout, dout + nout, st);
   if (rc) return rc;
@@ -1170,39 +826,27 @@ int mwrt_layer_tau_batch_device(mwrt_context* c, const mwrt_model* m, int64_t np
                                 const double* d_z, const double* d_p, const double* d_t, const double* d_rh,
                                 int32_t nf, const double* frq, double* d_tau, int32_t tau_pitch, uint8_t* d_valid,
                                 void* stream) {
-  int rc = check_common(c, m, nprof, nlev, nf);
-  if (rc) return rc;
-  if (!d_z || !d_p || !d_t || !d_rh || !frq || !d_tau || !d_valid) return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
+  CallSpec s{0, nprof, nlev, nf, frq, 0, nullptr, stream};
+  s.buffers_ok = d_z && d_p && d_t && d_rh && frq && d_tau && d_valid;
   if (tau_pitch < tau_pitch_of(nf) || tau_pitch % TAU_NFC != 0)
-    return fail(MWRT_ERR_INVALID_ARGUMENT, "tau_pitch must be a multiple of 16 and >= mwrt_layer_tau_pitch(nf)");
-  if (any_nan(frq, nf)) return fail(MWRT_ERR_INVALID_ARGUMENT, "NaN frequency");
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = resolve_stream(c, stream);
-  if (nprof == 0) return MWRT_OK;
-  const double* dev_frq = nullptr;
-  rc = upload_small(c, c->frq_cache, frq, nf, &dev_frq); if (rc) return rc;
-  return layer_tau_launch(c, m, nprof, nlev, d_z, d_p, d_t, d_rh, nf, frq, dev_frq, d_tau, tau_pitch, d_valid, st);
+    s.after_buffers = Check{MWRT_ERR_INVALID_ARGUMENT, "tau_pitch must be a multiple of 16 and >= mwrt_layer_tau_pitch(nf)"};
+  Call call;
+  int rc = begin_call(c, &m, 1, s, &call);
+  if (rc || call.empty) return rc;
+  return layer_tau_launch(c, m, nprof, nlev, d_z, d_p, d_t, d_rh, nf, frq, call.dev_frq, d_tau, tau_pitch, d_valid, call.st);
 }
 
 int mwrt_tb_from_layer_tau_device(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
                                   const double* d_tau, int32_t tau_pitch, const double* d_t,
                                   int32_t nf, const double* frq, int32_t nang, const double* elev,
                                   const uint8_t* d_valid, double* d_tb, void* stream) {
-  int rc = check_common(c, m, nprof, nlev, nf);
-  if (rc) return rc;
-  if (nang < 1 || nang > MWRT_MAX_ANGLES) return fail(MWRT_ERR_INVALID_ARGUMENT, "nang out of range");
-  if (!d_tau || !d_t || !frq || !elev || !d_valid || !d_tb) return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
-  if (tau_pitch < nf) return fail(MWRT_ERR_INVALID_ARGUMENT, "tau_pitch < nf");
-  if (any_nan(frq, nf)) return fail(MWRT_ERR_INVALID_ARGUMENT, "NaN frequency");
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = resolve_stream(c, stream);
-  if (nprof == 0) return MWRT_OK;
-  std::vector<double> am;
-  rc = airmass_of(elev, nang, &am); if (rc) return rc;
-  const double *dev_frq = nullptr, *dev_am = nullptr;
-  rc = upload_small(c, c->frq_cache, frq, nf, &dev_frq); if (rc) return rc;
-  rc = upload_small(c, c->am_cache, am.data(), nang, &dev_am); if (rc) return rc;
-  return rte_tau_launch(c, m, nprof, nlev, d_tau, tau_pitch, d_t, nf, dev_frq, nang, dev_am, d_tb, d_valid, st);
+  CallSpec s{CALL_ANGLES, nprof, nlev, nf, frq, nang, elev, stream};
+  s.buffers_ok = d_tau && d_t && frq && elev && d_valid && d_tb;
+  if (tau_pitch < nf) s.after_buffers = Check{MWRT_ERR_INVALID_ARGUMENT, "tau_pitch < nf"};
+  Call call;
+  int rc = begin_call(c, &m, 1, s, &call);
+  if (rc || call.empty) return rc;
+  return rte_tau_launch(c, m, nprof, nlev, d_tau, tau_pitch, d_t, nf, call.dev_frq, nang, call.dev_am, d_tb, d_valid, call.st);
 }
 
 // K-matrix (dTB/dT, dTB/de, dTB/d thickness per level) -- see k_tb_jacobian.  HOST buffers, synchronous.
@@ -1210,20 +854,13 @@ int mwrt_tb_jacobian_batch(mwrt_context* c, const mwrt_model* m, int64_t nprof, 
                            const double* z, const double* p, const double* t, const double* rh,
                            int32_t nf, const double* frq, int32_t nang, const double* elev,
                            double* tb, double* dtb_dt, double* dtb_de, double* dtb_ddz, uint8_t* valid) {
-  int rc = check_common(c, m, nprof, nlev, nf);
-  if (rc) return rc;
-  if (nang < 1 || nang > MWRT_MAX_ANGLES) return fail(MWRT_ERR_INVALID_ARGUMENT, "nang out of range");
-  if (!z || !p || !t || !rh || !frq || !elev || !tb || !dtb_dt || !dtb_de || !dtb_ddz || !valid)
-    return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
-  if (any_nan(frq, nf)) return fail(MWRT_ERR_INVALID_ARGUMENT, "NaN frequency");
-  if (nprof == 0) return MWRT_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  std::vector<double> am;
-  rc = airmass_of(elev, nang, &am); if (rc) return rc;
-  const double *dev_frq = nullptr, *dev_am = nullptr;
-  rc = upload_small(c, c->frq_cache, frq, nf, &dev_frq); if (rc) return rc;
-  rc = upload_small(c, c->am_cache, am.data(), nang, &dev_am); if (rc) return rc;
+  CallSpec s{CALL_ANGLES | CALL_HOST, nprof, nlev, nf, frq, nang, elev, nullptr};
+  s.buffers_ok = z && p && t && rh && frq && elev && tb && dtb_dt && dtb_de && dtb_ddz && valid;
+  Call call;
+  int rc = begin_call(c, &m, 1, s, &call);
+  if (rc || call.empty) return rc;
+  hipStream_t st = call.st;
+  const double *dev_frq = call.dev_frq, *dev_am = call.dev_am;
   constexpr double DT = 0.01, REL_E = 1e-4, MIN_DE = 1e-7;       // local steps of the absorption derivatives
   // Goff-Gratch over water, as RTEquation.vapor [EXT] (host copy: only used to keep e fixed while T moves)
   auto es_of = [](double tk) {
@@ -1276,10 +913,11 @@ int mwrt_tb_jacobian_batch(mwrt_context* c, const mwrt_model* m, int64_t nprof, 
     a.nprof = nb; a.nlev = nlev; a.nf = nf; a.nang = nang;
     HIP_TRY(hipMemsetAsync(d_valid, 1, (size_t)nb, st));
     const int64_t nthreads = nb * nf * nang;
-    timing_begin(c, st);
-    hipLaunchKernelGGL(k_tb_jacobian, dim3((unsigned)((nthreads + 63) / 64)), dim3(64), 0, st, a);
-    timing_end(c, st);
-    HIP_TRY(hipGetLastError());
+    rc = timed(c, st, [&] {
+      hipLaunchKernelGGL(k_tb_jacobian, dim3((unsigned)((nthreads + 63) / 64)), dim3(64), 0, st, a);
+      return hipGetLastError();
+    });
+    if (rc) return rc;
     const size_t o = (size_t)b0 * nang * nf;
     HIP_TRY(hipMemcpyAsync(tb + o, d_tb, sizeof(double) * ntb, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(dtb_dt + o * nlev, a.dtb_dt, sizeof(double) * njac, hipMemcpyDeviceToHost, st));
@@ -1290,13 +928,9 @@ int mwrt_tb_jacobian_batch(mwrt_context* c, const mwrt_model* m, int64_t nprof, 
   }
   ws.release();
   // a profile flagged 0 / 2 is blanked as a whole, whichever thread met it
-  const double qnan = std::nan("");
-  for (int64_t i = 0; i < nprof; ++i) {
-    if (valid[i] == 1) continue;
-    const size_t o = (size_t)i * nang * nf;
-    for (size_t k = 0; k < (size_t)nang * nf; ++k) tb[o + k] = qnan;
-    for (size_t k = 0; k < (size_t)nang * nf * nlev; ++k) { dtb_dt[o * nlev + k] = qnan; dtb_de[o * nlev + k] = qnan; dtb_ddz[o * nlev + k] = qnan; }
-  }
+  const size_t ntb = (size_t)nang * nf;
+  const RowArray out[4] = {{tb, ntb}, {dtb_dt, ntb * nlev}, {dtb_de, ntb * nlev}, {dtb_ddz, ntb * nlev}};
+  blank_rows(valid, nprof, true, out, 4);
   return MWRT_OK;
 }
 
@@ -1305,25 +939,16 @@ int mwrt_absorption_tl_batch_device(mwrt_context* c, const mwrt_model* m, int64_
                                     const double* d_p, const double* d_t, const double* d_rh, int32_t nf, const double* frq,
                                     double* d_awet, double* d_adry, double* d_dawet_dt, double* d_dawet_de,
                                     double* d_dadry_dt, double* d_dadry_de, void* stream) {
-  int rc = check_common(c, m, nprof, nlev, nf);
-  if (rc) return rc;
-  if (!d_p || !d_t || !d_rh || !frq || !d_awet || !d_adry || !d_dawet_dt || !d_dawet_de || !d_dadry_dt || !d_dadry_de)
-    return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
-  if (any_nan(frq, nf)) return fail(MWRT_ERR_INVALID_ARGUMENT, "NaN frequency");
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = resolve_stream(c, stream);
-  if (nprof == 0) return MWRT_OK;
-  const double* dev_frq = nullptr;
-  rc = upload_small(c, c->frq_cache, frq, nf, &dev_frq); if (rc) return rc;
+  CallSpec s{0, nprof, nlev, nf, frq, 0, nullptr, stream};
+  s.buffers_ok = d_p && d_t && d_rh && frq && d_awet && d_adry && d_dawet_dt && d_dawet_de && d_dadry_dt && d_dadry_de;
+  Call call;
+  int rc = begin_call(c, &m, 1, s, &call);
+  if (rc || call.empty) return rc;
   AbsorbTlArgs a{};
-  a.M = m->d_desc; a.p = d_p; a.t = d_t; a.rh = d_rh; a.frq = dev_frq;
+  a.M = m->d_desc; a.p = d_p; a.t = d_t; a.rh = d_rh; a.frq = call.dev_frq;
   a.awet = d_awet; a.adry = d_adry; a.dawet_dt = d_dawet_dt; a.dawet_de = d_dawet_de; a.dadry_dt = d_dadry_dt; a.dadry_de = d_dadry_de;
   a.flags = nullptr; a.nlev = nlev; a.nf = nf; a.nslab = (nlev + WAVE - 1) / WAVE;
-  timing_begin(c, st);
-  const hipError_t e = launch_absorb_tl(a, nprof, st);
-  timing_end(c, st);
-  HIP_TRY(e);
-  return MWRT_OK;
+  return timed(c, call.st, [&] { return launch_absorb_tl(a, nprof, call.st); });
 }
 
 // The K-matrix on caller-owned HBM: k_absorb_tl into the context's workspace, then k_jac_rte.  Asynchronous; after one
@@ -1345,33 +970,22 @@ int mwrt_tb_jacobian_batch_opt_device(mwrt_context* c, const mwrt_model* m, int6
                                       double* d_tb, double* d_dtb_dt, double* d_dtb_de, double* d_dtb_ddz,
                                       double* d_dtb_dliq, double* d_dtb_dice, uint8_t* d_valid,
                                       const mwrt_tb_options* opt, void* stream) {
-  int rc = check_common(c, m, nprof, nlev, nf);
-  if (rc) return rc;
-  if (opt && opt->ray_tracing != 0) return fail(MWRT_ERR_UNSUPPORTED, "the K-matrix is plane-parallel: ray_tracing is not supported");
-  if (opt && opt->o3n) return fail(MWRT_ERR_UNSUPPORTED, "the K-matrix has no ozone tangent: o3n is not supported");
   const double* d_denliq = opt ? opt->denliq : nullptr;
   const double* d_denice = opt ? opt->denice : nullptr;
-  if (d_dtb_dliq && !d_denliq) return fail(MWRT_ERR_INVALID_ARGUMENT, "d_dtb_dliq given without options->denliq");
-  if (d_dtb_dice && !d_denice) return fail(MWRT_ERR_INVALID_ARGUMENT, "d_dtb_dice given without options->denice");
-  if (nang < 1 || nang > MWRT_MAX_ANGLES) return fail(MWRT_ERR_INVALID_ARGUMENT, "nang out of range");
-  if (!d_z || !d_p || !d_t || !d_rh || !frq || !elev || !d_tb || !d_dtb_dt || !d_dtb_de || !d_dtb_ddz || !d_valid)
-    return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
-  if (any_nan(frq, nf)) return fail(MWRT_ERR_INVALID_ARGUMENT, "NaN frequency");
-  if (nprof * nf > 2147483647LL) return fail(MWRT_ERR_UNSUPPORTED, "nprof x nf exceeds grid limit");
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = resolve_stream(c, stream);
-  if (nprof == 0) return MWRT_OK;
-  std::vector<double> am;
-  rc = airmass_of(elev, nang, &am); if (rc) return rc;
-  const double *dev_frq = nullptr, *dev_am = nullptr;
-  rc = upload_small(c, c->frq_cache, frq, nf, &dev_frq); if (rc) return rc;
-  rc = upload_small(c, c->am_cache, am.data(), nang, &dev_am); if (rc) return rc;
+  CallSpec s{CALL_ANGLES, nprof, nlev, nf, frq, nang, elev, stream};
+  if (opt && opt->ray_tracing != 0) s.after_common = Check{MWRT_ERR_UNSUPPORTED, "the K-matrix is plane-parallel: ray_tracing is not supported"};
+  else if (opt && opt->o3n) s.after_common = Check{MWRT_ERR_UNSUPPORTED, "the K-matrix has no ozone tangent: o3n is not supported"};
+  else if (d_dtb_dliq && !d_denliq) s.after_common = Check{MWRT_ERR_INVALID_ARGUMENT, "d_dtb_dliq given without options->denliq"};
+  else if (d_dtb_dice && !d_denice) s.after_common = Check{MWRT_ERR_INVALID_ARGUMENT, "d_dtb_dice given without options->denice"};
+  s.buffers_ok = d_z && d_p && d_t && d_rh && frq && elev && d_tb && d_dtb_dt && d_dtb_de && d_dtb_ddz && d_valid;
+  if (nprof * nf > 2147483647LL) s.before_device = Check{MWRT_ERR_UNSUPPORTED, "nprof x nf exceeds grid limit"};
+  Call call;
+  int rc = begin_call(c, &m, 1, s, &call);
+  if (rc || call.empty) return rc;
+  hipStream_t st = call.st;
+  const double *dev_frq = call.dev_frq, *dev_am = call.dev_am;
   const size_t nabs = (size_t)nprof * nf * nlev;
-  const size_t need = sizeof(double) * 6 * nabs + sizeof(unsigned) * (size_t)nprof;
-  if (need > c->d_jac.cap) {
-    HIP_TRY(hipDeviceSynchronize());                // queued launches may still read the old workspace
-    HIP_TRY(c->d_jac.reserve(need));
-  }
+  HIP_TRY(grow_behind_drain(c->d_jac, sizeof(double) * 6 * nabs + sizeof(unsigned) * (size_t)nprof));
   rc = workspace_acquire(c, st); if (rc) return rc;
   auto handover = on_scope_exit([&] { (void)workspace_release(c, st); });    // on every return path from here on
   double* w = c->d_jac.as<double>();
@@ -1382,10 +996,8 @@ int mwrt_tb_jacobian_batch_opt_device(mwrt_context* c, const mwrt_model* m, int6
   ta.awet = w; ta.adry = w + nabs; ta.dawet_dt = w + 2 * nabs; ta.dawet_de = w + 3 * nabs;
   ta.dadry_dt = w + 4 * nabs; ta.dadry_de = w + 5 * nabs;
   ta.flags = flags; ta.nlev = nlev; ta.nf = nf; ta.nslab = (nlev + WAVE - 1) / WAVE;
-  timing_begin(c, st);
-  hipError_t e = launch_absorb_tl(ta, nprof, st);
-  timing_end(c, st);
-  HIP_TRY(e);
+  rc = timed(c, st, [&] { return launch_absorb_tl(ta, nprof, st); });
+  if (rc) return rc;
   JacRteArgs ja{};
   ja.M = m->d_desc; ja.z = d_z; ja.t = d_t;
   ja.awet = ta.awet; ja.adry = ta.adry; ja.dawet_dt = ta.dawet_dt; ja.dawet_de = ta.dawet_de;
@@ -1396,11 +1008,7 @@ int mwrt_tb_jacobian_batch_opt_device(mwrt_context* c, const mwrt_model* m, int6
   ja.denliq = d_denliq; ja.denice = d_denice; ja.dtb_dliq = d_dtb_dliq; ja.dtb_dice = d_dtb_dice;
   // with cloud arrays the kernel only lowers valid (k_jac_rte): preset it
   if (d_denliq || d_denice) HIP_TRY(hipMemsetAsync(d_valid, 1, (size_t)nprof, st));
-  timing_begin(c, st);
-  e = launch_jac_rte(ja, nprof, st);
-  timing_end(c, st);
-  HIP_TRY(e);
-  return MWRT_OK;
+  return timed(c, st, [&] { return launch_jac_rte(ja, nprof, st); });
 }
 
 int mwrt_set_chunk_width(mwrt_context* c, int width) {
@@ -1423,12 +1031,11 @@ int mwrt_selftest_math(mwrt_context* c, int32_t n, const double* x, const double
   if (n == 0) return MWRT_OK;
   HIP_TRY(hipSetDevice(c->device));
   const size_t b = sizeof(double) * (size_t)n;
-  HIP_TRY(c->d_in.reserve(2 * b));
+  const double* src[2] = {x, y_pos};
+  int rc = stage_in(c, c->stream, (size_t)n, src, 2); if (rc) return rc;
   HIP_TRY(c->d_out.reserve(4 * b));
   double* din = c->d_in.as<double>();
   double* dout = c->d_out.as<double>();
-  HIP_TRY(hipMemcpyAsync(din, x, b, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(din + n, y_pos, b, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_selftest_math, dim3((n + 255) / 256), dim3(256), 0, c->stream, din, din + n, dout, dout + n,
                      dout + 2 * (size_t)n, dout + 3 * (size_t)n, n);
   HIP_TRY(hipGetLastError());

@@ -16,10 +16,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/mwrt.h"
+#include "mwrt_plan.h"      // the plain records and constants shared with the host's planning unit
 
 namespace mwrt {
 
-constexpr int WAVE = 64;
 constexpr double TAUMAX = 125.0;
 constexpr double TRANS_MIN = 5.1664206328378610e-55;   // exp(-TAUMAX)
 
@@ -39,15 +39,6 @@ struct ModelFlat : mwrt_model_desc {
 };
 typedef const __attribute__((address_space(4))) ModelFlat* cmodel;
 typedef const __attribute__((address_space(4))) double* cdoubles;
-
-struct LaunchGeom {          // host-computed K2 work split (see plan_k2 in mwrt.hip), per K2 pass
-  int nseg[2];               // level segments per (freq, angle) pair
-  int seglen[2];             // layers per segment
-  int npart;                 // doubles of segment partials (B, T) the largest pass needs
-  int ldrow;                 // padded LDS row length (doubles) of tau/boft: conflict-free for b64
-  unsigned magic_nseg[2];    // ceil(2^32 / nseg), ceil(2^32 / nang): n / d = umulhi(n, magic) for n < 65536, 1 < d <= 1024
-  unsigned magic_nang;       // (the work-item index splits cost two integer divisions per item otherwise)
-};
 
 // n / d for the small operands of the K2 work split (see LaunchGeom): one v_mul_hi_u32
 __device__ __forceinline__ int div_small(int n, int d, unsigned magic) {
@@ -287,31 +278,8 @@ __device__ __forceinline__ double fdiv1(double x, double d) {
 // top of each side it keeps the branch a branch.
 #define KEEP_BRANCH() asm volatile("")
 
-// "Far" lines: every frequency of the chunk is at least FAR_MIN_GHZ (+ the shift allowance) away
-// from the line centre, so D1*D2 may be formed as a polynomial in f^2 without harmful cancellation.
-constexpr double FAR_MIN_GHZ = 0.2;
-constexpr double FAR_SHIFT_GHZ = 0.05;     // O2: |dnu| allowance, checked per line by wave vote
-constexpr double FAR_H2O_GHZ = 5.0;        // H2O: covers any pressure shift (< 1 GHz) with margin
-
-// Wave-uniform bit sets over line indices (line k of the table against the chunk's frequencies).  They steer the line
-// loops: each loop walks ONE set with ONE loop body, so the NFC accumulators never cross a
-// control-flow join between differently allocated variants (the v_mov copies that cost).
-struct LineMasks {
-  unsigned long long o2_far;   // every chunk frequency >= FAR_MIN_GHZ + FAR_SHIFT_GHZ from the line centre
-  unsigned h2o_far;            // ... >= FAR_H2O_GHZ from the line centre
-  unsigned h2o_none;           // both Lorentz terms beyond the 750-GHz cutoff for every frequency (FAR_H2O_GHZ margin)
-  unsigned h2o_res;            // negative-frequency term beyond the cutoff for every frequency (e.g. 752 GHz from 22 GHz)
-  unsigned h2o_sd;             // speed-dependent lines (W2 > 0)
-  unsigned h2o_sdfar;          // ... of those, the ones whose special shape (inside 10 half-widths) cannot reach any frequency of
-                               // the chunk by the host's bound: treated as plain lines, re-checked per level (wave vote)
-  unsigned h2o_sdint;          // speed-dependent lines far enough from the chunk (>= 3 GHz and 5 spans) for the half-sampled shape
-  unsigned h2o_vfar;           // "very far" lines: summed as ONE Taylor polynomial in f^2 about the chunk's middle (vfar_add)
-  unsigned long long o2_vfar;
-  double vf_u0, vf_h, vf_invh; // middle and half range of the chunk's f^2 values [GHz^2] (vf_h >= 1), 1 / vf_h
-};
-
 // The sets depend on the chunk's frequencies and the table only: the host computes them once per (model, frequency
-// list, chunk width) -- csrc/mwrt.hip chunk_masks() -- and the kernels fetch their chunk's record through the scalar
+// list, chunk width) -- csrc/mwrt_plan.cpp chunk_masks() -- and the kernels fetch their chunk's record through the scalar
 // cache (round 2 had every workgroup derive them: ~180 VALU per lane and chunk).
 typedef const __attribute__((address_space(4))) LineMasks* cmasks;
 __device__ __forceinline__ LineMasks load_masks(const LineMasks* table, int chunk) {
@@ -556,10 +524,7 @@ __device__ __forceinline__ void far_quad_accumulate(const double* sfq, const Far
 // one Horner evaluation per frequency.  Truncation after x^7: sum_{j>=8} (j+1) r^j <= 4e-14 of the line's own term at
 // r = VF_RATIO_MAX (the poles' distance ratio), and such a line is a few percent of the absorption at most; the host picks
 // the lines (chunk_masks) with the shift / width allowances.
-constexpr int VF_TERMS = 8;
-constexpr double VF_RATIO_MAX = 0.016;
-constexpr int VF_MIN_FREQS = 7;              // ... and chunks with fewer frequencies than this are served directly
-constexpr int VF_MIN_LINES = 4;              // fewer lines than this do not pay for the Horner pass (8 per frequency)
+constexpr int VF_TERMS = 8;                  // (VF_RATIO_MAX, VF_MIN_FREQS, VF_MIN_LINES: mwrt_plan.h)
 __device__ __forceinline__ void vfar_add(const FarLine& fl, double u0, double h, double (&acc)[VF_TERMS]) {
   const double d0 = __builtin_fma(u0, u0 + fl.A2, fl.Bc);
   const double d1h = __builtin_fma(fl.A2, h, (2.0 * u0) * h);
@@ -629,8 +594,7 @@ __device__ __forceinline__ unsigned long long lowest_bits(unsigned long long m, 
 // interpolated to the other 7 with host-computed Lagrange weights: error <= 4e-12 of the line's Lorentzian
 // (probe on the oracle's formulas), against the 1e-10 the windowed path works to.  Where a lane is inside 10
 // half-widths the odd slots then get Lorentzian + interpolated difference; outside, the plain Lorentzian as always.
-constexpr int SD_NODES = 9, SD_TARGETS = 7;
-__host__ __device__ constexpr int sd_node_slot(int n) { return n < 8 ? 2 * n : 15; }
+// (SD_NODES, SD_TARGETS, sd_node_slot: mwrt_plan.h)
 
 // Window mode (k_absorb_win, fine spectral grids).  The lines far from a whole WINDOW of chunks are summed at a few
 // Chebyshev nodes of the window (NODES = true: raw line sums out, no continuum, no SD lines; a line whose per-lane
@@ -1440,8 +1404,6 @@ k_ray_paths(const double* __restrict__ z, const double* __restrict__ p, const do
 // ---------------------------------------------------------------------------------------------
 // fused kernel: profile in -> TB out
 // ---------------------------------------------------------------------------------------------
-constexpr int MAX_MULTI = 8;   // absorption models evaluated by one launch (the wrapper runs four)
-
 struct FusedArgs {
   // blockIdx.x enumerates (model, profile): outputs are [nmodels][nprof]..., inputs [nprof]...
   const ModelFlat* Ms[MAX_MULTI];
@@ -1966,9 +1928,7 @@ k_tb_fused(const FusedArgs A) {
 // 3 waves cover 190 levels (the reference's 180), and the waves of a workgroup never wait for each other inside
 // the frequency loop.
 // ---------------------------------------------------------------------------------------------
-constexpr int TAU_NFC = 16;                   // tau rows are written in 16-frequency (128-byte) pieces
-__host__ __device__ constexpr int tau_threads(int nlev) { return ((nlev - 1 + (WAVE - 2)) / (WAVE - 1)) * WAVE; }
-
+// (TAU_NFC and tau_threads, the workgroup size that follows from this mapping: mwrt_plan.h)
 struct TauOut {
   const double* z;         // [nprof][nlev] km (layer thickness)
   double* tau;             // [nprof][nlev][fpitch]; row 0 (the ground level) is 0
@@ -2138,23 +2098,6 @@ k_absorb(const AbsorbArgs A) {
 // TAU = true: the chunk ends with the layer step (see k_absorb) and writes the zenith layer optical depth,
 // [level][frequency], 8 B per point; the fine-grid TB path is this kernel followed by k_rte_tau.
 // ---------------------------------------------------------------------------------------------
-constexpr int WIN_NODES = 16;          // O2: lines from WIN_MARGIN_GHZ beyond the window
-constexpr int WIN_NODES_H = 8;         // H2O: lines from WIN_H2O_MARGIN_GHZ beyond it -- so smooth across the window that 8
-                                       // nodes do (convergence ~ 25^-n); a third less LDS = a fourth workgroup per CU
-constexpr int WIN_CHUNKS = 8;          // chunks of a base window
-constexpr int WIN_CHUNKS_MAX = 16;     // ... of a merged one (two neighbours with no line near either: one node phase for both)
-constexpr int WIN_NFC = 16;
-
-struct WinDesc {                       // one per window, built by the host (csrc/mwrt.hip: build_windows)
-  double fnode[WIN_NODES];             // Chebyshev nodes of [f_lo, f_hi], GHz
-  double fnode_h[WIN_NODES_H];
-  double flo, fhi;                     // the window itself
-  unsigned long long o2_far;           // O2 lines >= WIN_MARGIN_GHZ beyond the window
-  unsigned h2o_far_both, h2o_far_res;  // H2O lines >= WIN_H2O_MARGIN_GHZ beyond the window with a cutoff state uniform across it
-  int first_chunk, nchunks;            // chunks [first_chunk, first_chunk + nchunks) of the frequency list
-  int pad0, pad1;
-};
-
 struct AbsorbWinArgs {
   const ModelFlat* M;
   const double* p; const double* t; const double* rh;
@@ -2359,7 +2302,6 @@ struct RteTauArgs {
   int nlev, nf, nang, fpitch, a0;
 };
 
-constexpr int RTE_THREADS = 256;
 constexpr int RTE_PF = 8;        // levels in flight per lane
 
 template <int NA>

@@ -8,6 +8,8 @@ picks exactly one per stage from the frequency count (chunk width 8 / 14 / 16), 
 CPU part (unmarked): ``kernel_inventory`` lists the kernels of the built library with ``nm``; ``expected_kernels``
 restates the routing in a few lines of Python; the union over the case table ``CASES`` must equal the inventory, in both
 directions, so a new instantiation without a covering case, or a case claiming a kernel that does not exist, fails here.
+The restatement is held to the library's own planning code: ``tests/plan_dump.cpp`` links ``csrc/mwrt_plan.cpp`` as is
+(a host-only unit), is built with the host compiler under ASan + UBSan and answers every seam and every case.
 
 GPU part (each test marked ``gpu``): every case runs through its entry point and is compared with the C oracle
 (TBs to 1e-6 K, optical depths and absorption to 1e-9 relative), with oracle-free checks on the tall classes against
@@ -19,6 +21,7 @@ import dataclasses
 import json
 import os
 import re
+import shutil
 import subprocess
 
 import numpy as np
@@ -30,13 +33,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mwr_fast_forward_operators_and_lbls_amd", "csrc")
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the routing, restated (constants: csrc/mwrt_kernels.hip.h and csrc/mwrt.hip; test_mirror_constants_match_the_source)
+# the routing, restated (the planning code itself: csrc/mwrt_plan.h, csrc/mwrt_plan.cpp; test_mirror_matches_the_planning_code)
 # ---------------------------------------------------------------------------------------------------------------------
 WAVE = 64
 MAX_LEVELS = 1024
 TAU_NFC = 16
 WIN_CHUNKS, WIN_NFC, WIN_NODES, WIN_NODES_H = 8, 16, 16, 8
 WIN_MAX_SPAN_GHZ = 6.0
+NFK, WIN_CHUNKS_MAX, RTE_THREADS, MAX_MULTI, MAX_ANGLES = 8, 16, 256, 8, 64
 LDS_MAX = 160 * 1024          # hipDeviceAttributeMaxSharedMemoryPerBlock on gfx950 (test_lds_budget_as_mirrored)
 ERR_UNSUPPORTED = -5
 
@@ -62,7 +66,7 @@ def pick_nfc(nf):
 
 def fused_lds_bytes_min(nfc, nlev, nf, nang, threads):
     """fused_lds_bytes at one segment per pass: where plan_fused's shrink loop ends, so plan_fused fails iff this does not fit"""
-    nfk = 8                                                        # nfk_of
+    nfk = NFK
     rows0, rows1 = min(nfk, nfc, nf), max(0, min(nfc, nf) - nfk)
     ldrow = nlev + 1 + ((nlev + 1) % 2 == 0)                       # plan_k2: odd row stride
     npart = 2 * nang * max(rows0, rows1)
@@ -85,7 +89,7 @@ def fused_threads(nlev, nang, variant):
 
 
 def tau_threads(nlev):
-    """tau_threads (mwrt_kernels.hip.h): 63 levels per wave plus one repeated level"""
+    """tau_threads (mwrt_plan.h): 63 levels per wave plus one repeated level"""
     return -(-(nlev - 1) // (WAVE - 1)) * WAVE
 
 
@@ -102,18 +106,18 @@ def windows_eligible(frq):
 
 
 def absorb_win_lds_bytes(threads):
-    """absorb_win_lds_bytes (mwrt_inst.hip)"""
+    """absorb_win_lds_bytes"""
     maxt = 256 if threads <= 256 else 512
     return 8 * ((WIN_NODES + WIN_NODES_H) * threads + (3 * WIN_NFC + 2) * (1 + maxt // WAVE) + (3 * WIN_NODES_H + 2)) + 64
 
 
 def windowed_ok(frq, threads, lds_max):
-    """windowed_ok"""
+    """absorption_route: can the windowed kernel serve the call"""
     return windows_eligible(frq) and threads <= 512 and absorb_win_lds_bytes(threads) <= lds_max
 
 
 def rte_tau_split(nang):
-    """rte_tau_launch: elevations per k_rte_tau<NA> launch -- up to 8, 10 whole, 9 as 5 + 4"""
+    """rte_tau_angles, as rte_tau_launch walks it: elevations per k_rte_tau<NA> launch -- up to 8, 10 whole, 9 as 5 + 4"""
     out, rem = [], nang
     while rem > 0:
         na = rem if rem <= 8 else (10 if rem == 10 else (5 if rem == 9 else 8))
@@ -171,7 +175,8 @@ def tb_variant(options):
 
 
 def route(c, lds_max=LDS_MAX):
-    """-> (kernel names the call launches, return code): the host routing of csrc/mwrt.hip and csrc/mwrt_inst.hip"""
+    """-> (kernel names the call launches, return code): the host routing of csrc/mwrt.hip, csrc/mwrt_plan.cpp and
+    csrc/mwrt_inst.hip"""
     frq = FREQS[c.frq]
     nf = len(frq)
     if c.entry == "selftest":
@@ -315,24 +320,101 @@ def test_case_table_covers_every_compiled_kernel(native_lib):
     assert not claimed - inventory, "cases claim kernels that are not compiled: %s" % sorted(claimed - inventory)
 
 
-def test_mirror_constants_match_the_source():
-    src = "".join(open(os.path.join(CSRC, f)).read() for f in ("mwrt_kernels.hip.h", "mwrt.hip", "mwrt_inst.hip"))
+# what test_routing_mirror_at_its_seams pins, as inputs: the planning code is asked the same questions
+SEAM_NLEV = (2, 64, 65, 253, 254, 505, 506, 1009, 1010)
+SEAM_NANG = (1, 6, 8, 9, 10, 14, 64)
+SEAM_NF = (1, 8, 9, 14, 15, 16, 28, 33, 42, 512)
 
-    def const(name):
-        m = re.search(r"constexpr (?:int|double) %s = ([0-9.]+);" % name, src)
-        assert m, name
-        return float(m.group(1))
-    for name, val in (("WAVE", WAVE), ("TAU_NFC", TAU_NFC), ("WIN_CHUNKS", WIN_CHUNKS), ("WIN_NFC", WIN_NFC),
-                      ("WIN_NODES", WIN_NODES), ("WIN_NODES_H", WIN_NODES_H), ("WIN_MAX_SPAN_GHZ", WIN_MAX_SPAN_GHZ)):
-        assert const(name) == val, name
+
+def seam_frequency_lists():
+    f = FREQS["fine"]
+    return [f, f[:127], f[::-1], np.linspace(20.0, 26.1, 128), np.linspace(20.0, 26.0, 128), f[:129]]
+
+
+@pytest.fixture(scope="module")
+def plan_dump(tmp_path_factory):
+    """tests/plan_dump.cpp + csrc/mwrt_plan.cpp, built with the host C++ compiler under ASan + UBSan; returns
+    ask(request lines) -> one parsed JSON answer per line.  A sanitiser report ends the child with a non-zero status."""
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path_factory.mktemp("plan_dump") / "plan_dump")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(ROOT, "tests", "plan_dump.cpp"), os.path.join(CSRC, "mwrt_plan.cpp"), "-o", exe], check=True)
+
+    def ask(lines):
+        r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True)
+        assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-4000:])
+        out = [json.loads(x) for x in r.stdout.splitlines()]
+        assert len(out) == len(lines)
+        return out
+    return ask
+
+
+def test_mirror_matches_the_planning_code(plan_dump, tmp_path):
+    """The Python restatement above against csrc/mwrt_plan.cpp itself, at every seam of test_routing_mirror_at_its_seams and
+    for every Call of CASES; the same sanitised run takes the frequency lists through chunk_masks and build_windows"""
+    line = lambda *a: " ".join(repr(float(x)) if isinstance(x, (float, np.floating)) else str(x) for x in a)
+    want, asked = [], []
+
+    def ask(request, expect):
+        asked.append(request)
+        want.append(expect)
+
+    ask("constants", dict(WAVE=WAVE, NFK=NFK, TAU_NFC=TAU_NFC, WIN_CHUNKS=WIN_CHUNKS, WIN_CHUNKS_MAX=WIN_CHUNKS_MAX, WIN_NFC=WIN_NFC,
+                          WIN_NODES=WIN_NODES, WIN_NODES_H=WIN_NODES_H, WIN_MAX_SPAN_GHZ=WIN_MAX_SPAN_GHZ, RTE_THREADS=RTE_THREADS,
+                          MAX_MULTI=MAX_MULTI, MAX_LEVELS=MAX_LEVELS, MAX_ANGLES=MAX_ANGLES, ERR_UNSUPPORTED=ERR_UNSUPPORTED))
+
+    def fused(nlev, nf, nang, width, lds_max, threads):
+        nfc = pick_nfc_fused(nlev, nf, nang, width, lds_max)
+        ask(line("fused", nlev, nf, nang, width, lds_max, threads),
+            dict(pick_nfc=pick_nfc(nf), nfc=nfc, fits=fused_lds_bytes_min(nfc, nlev, nf, nang, threads) <= lds_max,
+                 lds_min_wide=fused_lds_bytes_min(width or pick_nfc(nf), nlev, nf, nang, threads)))
+
+    def levels(nlev):
+        ask(line("tau", nlev), dict(tau_threads=tau_threads(nlev), lanes_for=roundup(nlev)))
+
+    for nlev in SEAM_NLEV:
+        levels(nlev)
+    for threads in range(WAVE, MAX_LEVELS + 2 * WAVE, WAVE):
+        ask(line("winlds", threads), dict(absorb_win_lds_bytes=absorb_win_lds_bytes(threads)))
+    for nang in SEAM_NANG + tuple(range(1, MAX_ANGLES + 1)):
+        ask(line("split", nang), dict(split=rte_tau_split(nang)))
+    for nf in SEAM_NF:
+        fused(180, nf, 3, 0, LDS_MAX, roundup(180))
+    for lds_max in (64 * 1024, LDS_MAX):
+        fused(1024, 33, 64, 0, lds_max, 1024)
+    for f in seam_frequency_lists():
+        ask(line("eligible", *f), dict(eligible=windows_eligible(f)))
+    for c in CASES:
+        frq = FREQS[c.frq]
+        variant = ALPHA if c.entry == "alpha" else tb_variant(c.options)
+        levels(c.nlev)
+        ask(line("split", c.nang), dict(split=rte_tau_split(c.nang)))
+        ask(line("eligible", *frq), dict(eligible=windows_eligible(frq)))
+        for lds_max in (64 * 1024, LDS_MAX):
+            fused(c.nlev, len(frq), c.nang, c.chunk_width, lds_max, fused_threads(c.nlev, c.nang, variant))
+    # chunk_masks / build_windows / pack_windows under the sanitisers: every table family x four frequency lists
+    fine = FREQS["fine"]
+    for family in FAMILIES:
+        path = tmp_path / (family + ".desc")
+        path.write_bytes(bytes(sp.get_model(family).to_c()))
+        ask(line("tables", path), {})
+        for f in (FREQS["hatpro"], fine, fine[:129], fine[:16]):
+            nchunks = [-(-len(f) // w) for w in (8, 14, 16)]
+            ask(line("blobs", *f), dict(nchunks=nchunks, window_chunks=nchunks[2]))
+    got = plan_dump(asked)
+    assert got[0]["sizeof_desc"] == len(bytes(sp.get_model("R24").to_c()))
+    for request, g, w in zip(asked, got, want):
+        assert {k: g[k] for k in w} == w, (request[:80], g, w)
+        if request.startswith("blobs"):
+            off = g["layout"]
+            assert g["nwin"] >= 1 and g["blob_bytes"] == off[3] and all(o % 256 == 0 for o in off) and 0 < off[0] < off[1] < off[2] < off[3]
+            assert g["flo"] in [float(x) for x in request.split()[1:]]
     assert "#define MWRT_MAX_LEVELS %d" % MAX_LEVELS in open(os.path.join(ROOT, "include", "mwrt.h")).read()
-    assert "return ((nlev - 1 + (WAVE - 2)) / (WAVE - 1)) * WAVE;" in src          # tau_threads
-    assert "rem <= 8 ? rem : (rem == 10 ? 10 : (rem == 9 ? 5 : 8))" in src           # rte_tau_launch
 
 
 def test_routing_mirror_at_its_seams():
-    assert [tau_threads(n) for n in (2, 64, 65, 253, 254, 505, 506, 1009, 1010)] == [64, 64, 128, 256, 320, 512, 576, 1024,
-                                                                                     1088]
+    assert [tau_threads(n) for n in SEAM_NLEV] == [64, 64, 128, 256, 320, 512, 576, 1024, 1088]
     assert [size_class(tau_threads(n)) for n in (253, 254, 505, 506, 1009)] == [256, 512, 512, 1024, 1024]
     fine = lambda nlev, **kw: Call("x", "layer_tau", nlev, frq="fine", nang=2, **kw)
     assert route(fine(1009, absorption_mode=1)) == ({"k_absorb<16, 1024, true>", "k_rte_tau<2>"}, 0)
@@ -340,8 +422,8 @@ def test_routing_mirror_at_its_seams():
     assert route(fine(505)) == ({"k_absorb_win<512, true>", "k_rte_tau<2>"}, 0)
     assert route(fine(506)) == ({"k_absorb<16, 1024, true>", "k_rte_tau<2>"}, 0)      # too tall for the windows
     assert route(fine(506, absorption_mode=2))[1] == ERR_UNSUPPORTED
-    assert [rte_tau_split(n) for n in (1, 6, 8, 9, 10, 14, 64)] == [[1], [6], [8], [5, 4], [10], [8, 6], [8] * 8]
-    assert [pick_nfc(n) for n in (1, 8, 9, 14, 15, 16, 28, 33, 42, 512)] == [8, 8, 14, 14, 16, 16, 14, 16, 14, 16]
+    assert [rte_tau_split(n) for n in SEAM_NANG] == [[1], [6], [8], [5, 4], [10], [8, 6], [8] * 8]
+    assert [pick_nfc(n) for n in SEAM_NF] == [8, 8, 14, 14, 16, 16, 14, 16, 14, 16]
     assert [fused_threads(n, 2, ALPHA) for n in (2, 64, 65, 128, 129, 192, 193, 600)] == [256] * 7 + [640]
     assert [fused_threads(n, 1, ALPHA) for n in (2, 64, 65, 193)] == [64, 64, 128, 256]
     assert fused_threads(64, 2, TB_ONLY) == 64
