@@ -385,6 +385,55 @@ int mwrt_tb_jacobian_batch_opt_device(mwrt_context* ctx, const mwrt_model* model
                                       double* d_dtb_dliq, double* d_dtb_dice, uint8_t* d_valid,
                                       const mwrt_tb_options* d_options, void* stream);
 
+/* The device K-matrix in the variables a retrieval works in or a data set stores.  The INPUTS are
+ * those of mwrt_tb_jacobian_batch_opt_device -- z, p, T, rh, and denliq / denice in g m-3 through the options; only the
+ * variables of the returned derivatives change.  k_jac_rte changes them while each row element is still in a register:
+ * no further launch, no further workspace, no second pass over the rows. */
+typedef struct mwrt_jac_variables {
+  int32_t humidity;  /* 0 e [hPa] (the dtb_de row); 1 rh [fraction]; 2 ppmv (e = ppmv * p / 1e6) */
+  int32_t cloud;     /* 0 density [g m-3] (the dtb_dliq / dtb_dice rows); 1 mass mixing ratio [kg/kg]: den = q * 1000 * rho, rho = 100 p / (287.06 T) */
+  int32_t heights;   /* 0 fixed: thickness row as it is; 1 hydrostatic: thickness folded into the T and humidity rows */
+  int32_t reserved;  /* must be 0 */
+} mwrt_jac_variables;
+
+/* mwrt_tb_jacobian_batch_opt_device with `vars`.  With i the level index (0 = ground), e = rh * es(T) (Goff-Gratch) and
+ * the RAW rows of that entry A_T = dtb_dt, A_e = dtb_de, Z = dtb_ddz, R_l = dtb_dliq, R_i = dtb_dice, the rows returned
+ * are, applied in this order:
+ *   heights = 1 (hydrostatic): the heights follow dz_i = (287.04 / 9.80665) * (Tv_i + Tv_{i-1}) / 2 * ln(p_{i-1} / p_i) / 1000 km,
+ *     Tv = T (1 + 0.608 q), q = 0.622 e / (p - 0.378 e).  With c_i = (287.04 / (2 * 9.80665)) * ln(p_{i-1} / p_i) / 1000 for
+ *     i >= 1, c_0 = 0, and G_i = Z_i c_i + Z_{i+1} c_{i+1} (nothing above the top level):
+ *       A_T += G * (1 + 0.608 q)        A_e += G * 0.608 * T * 0.622 p / (p - 0.378 e)^2
+ *     The derivative is taken at the z passed in: exact when that z obeys the rule.
+ *   humidity h:  d_dtb_dh = A_e * de/dh, de/dh = 1 (e), es(T) (rh), p / 1e6 (ppmv);
+ *                d_dtb_dt = A_T + A_e * (de/dT at fixed h), which is 0 for e and ppmv and rh * es'(T) for rh;
+ *   cloud = 1 (kg/kg):  d_dtb_dliq = R_l * 1000 rho, d_dtb_dice = R_i * 1000 rho, and
+ *                d_dtb_dt -= (R_l * denliq + R_i * denice) / T  (density falls with T at fixed mixing ratio).
+ * Units: d_dtb_dt K/K at fixed h and mixing ratio / density; d_dtb_dh K/hPa, K per unit rh, or K/ppmv; cloud rows K per
+ * g m-3 or K per kg/kg.
+ *   d_dtb_ddz may be NULL in any mode; given, it is always the raw thickness row Z.
+ *   A mode out of range, or reserved != 0 -> MWRT_ERR_INVALID_ARGUMENT.
+ *   vars NULL or all zero is mwrt_tb_jacobian_batch_opt_device (which calls into this entry's implementation) bit for bit.
+ *   Everything else -- refusals, NaN and valid rules (a NaN in p or rh is valid 0 as well), streams, workspace, no
+ *   allocation and no synchronisation after one warm-up call -- is that entry's.  Dynamic LDS: 9 more rows of one double
+ *   per lane when a mode is set (152 KiB for a cloudy call at 1024 levels).  (MWRT_VERSION stays 301: additions.) */
+int mwrt_tb_jacobian_batch_vars_device(mwrt_context* ctx, const mwrt_model* model, int64_t nprof, int32_t nlev,
+                                       const double* d_z_km, const double* d_p_hpa, const double* d_t_k,
+                                       const double* d_rh_frac,
+                                       int32_t nf, const double* frq_ghz, int32_t nang, const double* elev_deg,
+                                       double* d_tb, double* d_dtb_dt, double* d_dtb_dh, double* d_dtb_ddz,
+                                       double* d_dtb_dliq, double* d_dtb_dice, uint8_t* d_valid,
+                                       const mwrt_tb_options* d_options, const mwrt_jac_variables* vars, void* stream);
+
+/* The same on HOST buffers, synchronous (options->denliq / denice are host pointers): the arrays are staged through
+ * device buffers of the call's own, which are freed on every return path, and the results are those of the device entry
+ * bit for bit.  dtb_ddz, dtb_dliq and dtb_dice may be NULL. */
+int mwrt_tb_jacobian_batch_vars(mwrt_context* ctx, const mwrt_model* model, int64_t nprof, int32_t nlev,
+                                const double* z_km, const double* p_hpa, const double* t_k, const double* rh_frac,
+                                int32_t nf, const double* frq_ghz, int32_t nang, const double* elev_deg,
+                                double* tb, double* dtb_dt, double* dtb_dh, double* dtb_ddz, double* dtb_dliq,
+                                double* dtb_dice, uint8_t* valid, const mwrt_tb_options* options,
+                                const mwrt_jac_variables* vars);
+
 /* Diagnostic: evaluates the kernels' own exp / log / division helpers (fexp, flog, fdiv, fdiv1) on
  * host arrays x[n], y_pos[n] (y > 0), so their accuracy can be checked against libm. */
 int mwrt_selftest_math(mwrt_context* ctx, int32_t n, const double* x, const double* y_pos,

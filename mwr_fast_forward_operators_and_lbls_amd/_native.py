@@ -42,6 +42,22 @@ class MwrtTbOptions(ctypes.Structure):
                 ("reserved0", ctypes.c_int32), ("o3n", ctypes.c_void_p)]
 
 
+class JacVariables(ctypes.Structure):
+    """include/mwrt.h mwrt_jac_variables: the variables the device K-matrix is returned in."""
+    _fields_ = [("humidity", ctypes.c_int32), ("cloud", ctypes.c_int32), ("heights", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+    HUMIDITY = {"e": 0, "rh": 1, "ppmv": 2}
+    CLOUD = {"density": 0, "kg/kg": 1}
+    HEIGHTS = {"fixed": 0, "hydrostatic": 1}
+
+    @classmethod
+    def of(cls, humidity="e", cloud="density", heights="fixed", reserved=0):
+        """Names (or the ABI's integers, passed through unchecked: the library refuses what is out of range)."""
+        pick = lambda table, x: table[x] if isinstance(x, str) else int(x)   # noqa: E731
+        return cls(pick(cls.HUMIDITY, humidity), pick(cls.CLOUD, cloud), pick(cls.HEIGHTS, heights), int(reserved))
+
+
 MWRT_VERSION = 301
 
 
@@ -86,6 +102,12 @@ SIGNATURES = {
     "mwrt_tb_jacobian_batch_opt_device": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp,
                                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(MwrtTbOptions),
                                                          _vp]),
+    "mwrt_tb_jacobian_batch_vars_device": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp,
+                                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(MwrtTbOptions),
+                                                          ctypes.POINTER(JacVariables), _vp]),
+    "mwrt_tb_jacobian_batch_vars": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp,
+                                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(MwrtTbOptions),
+                                                   ctypes.POINTER(JacVariables)]),
     "mwrt_set_absorption_mode": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_set_chunk_width": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_selftest_math": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -431,6 +453,59 @@ class Context:
             _ptr(d_dtb_dliq) if d_dtb_dliq is not None else None, _ptr(d_dtb_dice) if d_dtb_dice is not None else None,
             _ptr(d_valid), ctypes.byref(opts) if opts is not None else None, _stream(stream)),
             "mwrt_tb_jacobian_batch_opt_device")
+
+    @_serialised
+    def tb_jacobian_batch_vars_device(self, model, nprof, nlev, d_z, d_p, d_t, d_rh, frq, elev, d_tb, d_dtb_dt, d_dtb_dh,
+                                      d_valid, d_dtb_ddz=None, d_denliq=None, d_denice=None, d_dtb_dliq=None,
+                                      d_dtb_dice=None, variables=None, stream=None, ray_tracing=False, d_o3n=None):
+        """The device K-matrix in retrieval variables (include/mwrt.h mwrt_tb_jacobian_batch_vars_device): as
+        ``tb_jacobian_batch_opt_device`` with ``variables`` a ``JacVariables`` (None: the raw rows) and ``d_dtb_ddz``
+        optional in every mode.  ``d_dtb_dh`` receives the humidity row in the variable asked for."""
+        frq, elev = _f64(frq).ravel(), _f64(elev).ravel()
+        opts = None
+        if d_denliq is not None or d_denice is not None or ray_tracing or d_o3n is not None:
+            opts = MwrtTbOptions(int(d_denliq) if d_denliq is not None else None,
+                                 int(d_denice) if d_denice is not None else None, int(bool(ray_tracing)), 0,
+                                 int(d_o3n) if d_o3n is not None else None)
+        opt_ptr = lambda x: _ptr(x) if x is not None else None   # noqa: E731
+        self._check(self._lib.mwrt_tb_jacobian_batch_vars_device(
+            self._handle, self.model(model), int(nprof), int(nlev), _ptr(d_z), _ptr(d_p), _ptr(d_t), _ptr(d_rh),
+            frq.size, _ptr(frq), elev.size, _ptr(elev), _ptr(d_tb), _ptr(d_dtb_dt), _ptr(d_dtb_dh), opt_ptr(d_dtb_ddz),
+            opt_ptr(d_dtb_dliq), opt_ptr(d_dtb_dice), _ptr(d_valid), ctypes.byref(opts) if opts is not None else None,
+            ctypes.byref(variables) if variables is not None else None, _stream(stream)),
+            "mwrt_tb_jacobian_batch_vars_device")
+
+    @_serialised
+    def tb_jacobian_batch_vars(self, model, z, p, t, rh, frq, elev, denliq=None, denice=None, variables=None,
+                               thickness=True):
+        """The same on NumPy arrays, synchronous (include/mwrt.h mwrt_tb_jacobian_batch_vars): returns ``tb
+        [nprof][nang][nf]``, ``valid [nprof]`` and a dict of ``dtb_dt``, ``dtb_dh`` (the humidity row in the variable
+        asked for), ``dtb_ddz`` (the raw thickness row; absent with ``thickness=False``) and, for each cloud array given,
+        ``dtb_dliq`` / ``dtb_dice``, each ``[nprof][nang][nf][nlev]`` (levels ground -> top)."""
+        z = _f64(z)
+        if z.ndim != 2:
+            raise ValueError("profiles must be [nprof][nlev]")
+        nprof, nlev = z.shape
+        p, t, rh = _f64(p, z.shape, "p"), _f64(t, z.shape, "t"), _f64(rh, z.shape, "rh")
+        frq, elev = _f64(frq).ravel(), _f64(elev).ravel()
+        nf, nang = frq.size, elev.size
+        dl = None if denliq is None else _f64(denliq, z.shape, "denliq")
+        di = None if denice is None else _f64(denice, z.shape, "denice")
+        opts = None
+        if dl is not None or di is not None:
+            opts = MwrtTbOptions(dl.ctypes.data if dl is not None else None, di.ctypes.data if di is not None else None,
+                                 0, 0, None)
+        keys = ["dtb_dt", "dtb_dh"] + (["dtb_ddz"] if thickness else []) + (["dtb_dliq"] if dl is not None else []) + \
+               (["dtb_dice"] if di is not None else [])
+        tb = np.empty((nprof, nang, nf))
+        jac = {k: np.empty((nprof, nang, nf, nlev)) for k in keys}
+        valid = np.empty(nprof, dtype=np.uint8)
+        out = [_ptr(jac[k]) if k in jac else None for k in ("dtb_dt", "dtb_dh", "dtb_ddz", "dtb_dliq", "dtb_dice")]
+        self._check(self._lib.mwrt_tb_jacobian_batch_vars(
+            self._handle, self.model(model), nprof, nlev, _ptr(z), _ptr(p), _ptr(t), _ptr(rh), nf, _ptr(frq), nang, _ptr(elev),
+            _ptr(tb), *out, _ptr(valid), ctypes.byref(opts) if opts is not None else None,
+            ctypes.byref(variables) if variables is not None else None), "mwrt_tb_jacobian_batch_vars")
+        return tb, valid, jac
 
     def layer_tau_pitch(self, nf: int) -> int:
         """Doubles between consecutive levels of a layer-optical-depth array for nf frequencies (multiple of 16)."""

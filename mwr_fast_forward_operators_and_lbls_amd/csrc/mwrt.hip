@@ -444,6 +444,60 @@ int stage_in(mwrt_context* c, hipStream_t st, size_t n, const double* const* src
   return MWRT_OK;
 }
 
+// The device K-matrix behind its three entries (clear, cloud, retrieval variables): k_absorb_tl into the context's
+// workspace, then k_jac_rte.  `ddz_required`: the entries without mwrt_jac_variables have no optional thickness row.
+int jacobian_vars_device(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
+                         const double* d_z, const double* d_p, const double* d_t, const double* d_rh,
+                         int32_t nf, const double* frq, int32_t nang, const double* elev,
+                         double* d_tb, double* d_dtb_dt, double* d_dtb_dh, double* d_dtb_ddz,
+                         double* d_dtb_dliq, double* d_dtb_dice, uint8_t* d_valid,
+                         const mwrt_tb_options* opt, const mwrt_jac_variables* vars, bool ddz_required, void* stream) {
+  const double* d_denliq = opt ? opt->denliq : nullptr;
+  const double* d_denice = opt ? opt->denice : nullptr;
+  CallSpec s{CALL_ANGLES, nprof, nlev, nf, frq, nang, elev, stream};
+  if (opt && opt->ray_tracing != 0) s.after_common = Check{MWRT_ERR_UNSUPPORTED, "the K-matrix is plane-parallel: ray_tracing is not supported"};
+  else if (opt && opt->o3n) s.after_common = Check{MWRT_ERR_UNSUPPORTED, "the K-matrix has no ozone tangent: o3n is not supported"};
+  else if (d_dtb_dliq && !d_denliq) s.after_common = Check{MWRT_ERR_INVALID_ARGUMENT, "d_dtb_dliq given without options->denliq"};
+  else if (d_dtb_dice && !d_denice) s.after_common = Check{MWRT_ERR_INVALID_ARGUMENT, "d_dtb_dice given without options->denice"};
+  else if (vars && (vars->humidity < 0 || vars->humidity > 2 || vars->cloud < 0 || vars->cloud > 1 || vars->heights < 0 ||
+                    vars->heights > 1 || vars->reserved != 0))
+    s.after_common = Check{MWRT_ERR_INVALID_ARGUMENT, "mwrt_jac_variables: a mode out of range, or reserved != 0"};
+  s.buffers_ok = d_z && d_p && d_t && d_rh && frq && elev && d_tb && d_dtb_dt && d_dtb_dh && (d_dtb_ddz || !ddz_required) && d_valid;
+  if (nprof * nf > 2147483647LL) s.before_device = Check{MWRT_ERR_UNSUPPORTED, "nprof x nf exceeds grid limit"};
+  Call call;
+  int rc = begin_call(c, &m, 1, s, &call);
+  if (rc || call.empty) return rc;
+  hipStream_t st = call.st;
+  const double *dev_frq = call.dev_frq, *dev_am = call.dev_am;
+  const size_t nabs = (size_t)nprof * nf * nlev;
+  HIP_TRY(grow_behind_drain(c->d_jac, sizeof(double) * 6 * nabs + sizeof(unsigned) * (size_t)nprof));
+  rc = workspace_acquire(c, st); if (rc) return rc;
+  auto handover = on_scope_exit([&] { (void)workspace_release(c, st); });    // on every return path from here on
+  double* w = c->d_jac.as<double>();
+  unsigned* flags = reinterpret_cast<unsigned*>(w + 6 * nabs);
+  HIP_TRY(hipMemsetAsync(flags, 0, sizeof(unsigned) * (size_t)nprof, st));
+  AbsorbTlArgs ta{};
+  ta.M = m->d_desc; ta.p = d_p; ta.t = d_t; ta.rh = d_rh; ta.frq = dev_frq;
+  ta.awet = w; ta.adry = w + nabs; ta.dawet_dt = w + 2 * nabs; ta.dawet_de = w + 3 * nabs;
+  ta.dadry_dt = w + 4 * nabs; ta.dadry_de = w + 5 * nabs;
+  ta.flags = flags; ta.nlev = nlev; ta.nf = nf; ta.nslab = (nlev + WAVE - 1) / WAVE;
+  rc = timed(c, st, [&] { return launch_absorb_tl(ta, nprof, st); });
+  if (rc) return rc;
+  JacRteArgs ja{};
+  ja.M = m->d_desc; ja.z = d_z; ja.t = d_t;
+  ja.awet = ta.awet; ja.adry = ta.adry; ja.dawet_dt = ta.dawet_dt; ja.dawet_de = ta.dawet_de;
+  ja.dadry_dt = ta.dadry_dt; ja.dadry_de = ta.dadry_de; ja.flags = flags;
+  ja.frq = dev_frq; ja.airmass = dev_am;
+  ja.tb = d_tb; ja.dtb_dt = d_dtb_dt; ja.dtb_de = d_dtb_dh; ja.dtb_ddz = d_dtb_ddz; ja.valid = d_valid;
+  ja.nlev = nlev; ja.nf = nf; ja.nang = nang;
+  ja.denliq = d_denliq; ja.denice = d_denice; ja.dtb_dliq = d_dtb_dliq; ja.dtb_dice = d_dtb_dice;
+  ja.p = d_p; ja.rh = d_rh;
+  if (vars) { ja.humidity = vars->humidity; ja.cloud = vars->cloud; ja.heights = vars->heights; }
+  // with cloud arrays the kernel only lowers valid (k_jac_rte): preset it
+  if (d_denliq || d_denice) HIP_TRY(hipMemsetAsync(d_valid, 1, (size_t)nprof, st));
+  return timed(c, st, [&] { return launch_jac_rte(ja, nprof, st); });
+}
+
 }  // namespace
 
 extern "C" {
@@ -970,45 +1024,68 @@ int mwrt_tb_jacobian_batch_opt_device(mwrt_context* c, const mwrt_model* m, int6
                                       double* d_tb, double* d_dtb_dt, double* d_dtb_de, double* d_dtb_ddz,
                                       double* d_dtb_dliq, double* d_dtb_dice, uint8_t* d_valid,
                                       const mwrt_tb_options* opt, void* stream) {
-  const double* d_denliq = opt ? opt->denliq : nullptr;
-  const double* d_denice = opt ? opt->denice : nullptr;
-  CallSpec s{CALL_ANGLES, nprof, nlev, nf, frq, nang, elev, stream};
-  if (opt && opt->ray_tracing != 0) s.after_common = Check{MWRT_ERR_UNSUPPORTED, "the K-matrix is plane-parallel: ray_tracing is not supported"};
-  else if (opt && opt->o3n) s.after_common = Check{MWRT_ERR_UNSUPPORTED, "the K-matrix has no ozone tangent: o3n is not supported"};
-  else if (d_dtb_dliq && !d_denliq) s.after_common = Check{MWRT_ERR_INVALID_ARGUMENT, "d_dtb_dliq given without options->denliq"};
-  else if (d_dtb_dice && !d_denice) s.after_common = Check{MWRT_ERR_INVALID_ARGUMENT, "d_dtb_dice given without options->denice"};
-  s.buffers_ok = d_z && d_p && d_t && d_rh && frq && elev && d_tb && d_dtb_dt && d_dtb_de && d_dtb_ddz && d_valid;
-  if (nprof * nf > 2147483647LL) s.before_device = Check{MWRT_ERR_UNSUPPORTED, "nprof x nf exceeds grid limit"};
+  // (this entry has no optional thickness row: the check sits where its "null buffer" check always sat)
+  return jacobian_vars_device(c, m, nprof, nlev, d_z, d_p, d_t, d_rh, nf, frq, nang, elev, d_tb, d_dtb_dt, d_dtb_de, d_dtb_ddz,
+                              d_dtb_dliq, d_dtb_dice, d_valid, opt, nullptr, /*ddz_required=*/true, stream);
+}
+
+// The same in the caller's retrieval variables (mwrt_jac_variables): k_jac_rte changes the variables of each row element
+// before it stores it, so there is no further launch, no further workspace and no second pass over the rows.
+int mwrt_tb_jacobian_batch_vars_device(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
+                                       const double* d_z, const double* d_p, const double* d_t, const double* d_rh,
+                                       int32_t nf, const double* frq, int32_t nang, const double* elev,
+                                       double* d_tb, double* d_dtb_dt, double* d_dtb_dh, double* d_dtb_ddz,
+                                       double* d_dtb_dliq, double* d_dtb_dice, uint8_t* d_valid,
+                                       const mwrt_tb_options* opt, const mwrt_jac_variables* vars, void* stream) {
+  return jacobian_vars_device(c, m, nprof, nlev, d_z, d_p, d_t, d_rh, nf, frq, nang, elev, d_tb, d_dtb_dt, d_dtb_dh, d_dtb_ddz,
+                              d_dtb_dliq, d_dtb_dice, d_valid, opt, vars, /*ddz_required=*/false, stream);
+}
+
+// ... and on HOST buffers, synchronous: staged through device buffers of this call's own (freed on every return path),
+// one mwrt_tb_jacobian_batch_vars_device call on the context's stream -- which makes every check and every decision
+// (valid, NaN rows) -- and the results copied back as they are.
+int mwrt_tb_jacobian_batch_vars(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
+                                const double* z, const double* p, const double* t, const double* rh,
+                                int32_t nf, const double* frq, int32_t nang, const double* elev,
+                                double* tb, double* dtb_dt, double* dtb_dh, double* dtb_ddz, double* dtb_dliq, double* dtb_dice,
+                                uint8_t* valid, const mwrt_tb_options* opt, const mwrt_jac_variables* vars) {
+  CallSpec s{CALL_ANGLES | CALL_HOST | CALL_STAGES, nprof, nlev, nf, frq, nang, elev, nullptr};
+  s.buffers_ok = z && p && t && rh && frq && elev && tb && dtb_dt && dtb_dh && valid;
   Call call;
   int rc = begin_call(c, &m, 1, s, &call);
   if (rc || call.empty) return rc;
   hipStream_t st = call.st;
-  const double *dev_frq = call.dev_frq, *dev_am = call.dev_am;
-  const size_t nabs = (size_t)nprof * nf * nlev;
-  HIP_TRY(grow_behind_drain(c->d_jac, sizeof(double) * 6 * nabs + sizeof(unsigned) * (size_t)nprof));
-  rc = workspace_acquire(c, st); if (rc) return rc;
-  auto handover = on_scope_exit([&] { (void)workspace_release(c, st); });    // on every return path from here on
-  double* w = c->d_jac.as<double>();
-  unsigned* flags = reinterpret_cast<unsigned*>(w + 6 * nabs);
-  HIP_TRY(hipMemsetAsync(flags, 0, sizeof(unsigned) * (size_t)nprof, st));
-  AbsorbTlArgs ta{};
-  ta.M = m->d_desc; ta.p = d_p; ta.t = d_t; ta.rh = d_rh; ta.frq = dev_frq;
-  ta.awet = w; ta.adry = w + nabs; ta.dawet_dt = w + 2 * nabs; ta.dawet_de = w + 3 * nabs;
-  ta.dadry_dt = w + 4 * nabs; ta.dadry_de = w + 5 * nabs;
-  ta.flags = flags; ta.nlev = nlev; ta.nf = nf; ta.nslab = (nlev + WAVE - 1) / WAVE;
-  rc = timed(c, st, [&] { return launch_absorb_tl(ta, nprof, st); });
+  const size_t nin = (size_t)nprof * nlev, ntb = (size_t)nprof * nang * nf, njac = ntb * nlev;
+  const double* in[6] = {z, p, t, rh, opt ? opt->denliq : nullptr, opt ? opt->denice : nullptr};
+  double* out[5] = {dtb_dt, dtb_dh, dtb_ddz, dtb_dliq, dtb_dice};
+  size_t nsrc = 0, nrows = 0;
+  for (const double* x : in) nsrc += x != nullptr;
+  for (const double* x : out) nrows += x != nullptr;
+  DevBuf buf;                                                     // this call's own: inputs | tb | rows | valid
+  auto free_buf = on_scope_exit([&] { buf.release(); });
+  HIP_TRY(buf.reserve(sizeof(double) * (nsrc * nin + ntb + nrows * njac) + (size_t)nprof));
+  double* q = buf.as<double>();
+  const double* din[6] = {};
+  for (int k = 0; k < 6; ++k)
+    if (in[k]) {
+      HIP_TRY(hipMemcpyAsync(q, in[k], sizeof(double) * nin, hipMemcpyHostToDevice, st));
+      din[k] = q; q += nin;
+    }
+  double* d_tb = q; q += ntb;
+  double* dout[5] = {};
+  for (int k = 0; k < 5; ++k) if (out[k]) { dout[k] = q; q += njac; }
+  uint8_t* d_valid = reinterpret_cast<uint8_t*>(q);
+  mwrt_tb_options dopt{};
+  if (opt) { dopt = *opt; dopt.denliq = din[4]; dopt.denice = din[5]; }
+  rc = mwrt_tb_jacobian_batch_vars_device(c, m, nprof, nlev, din[0], din[1], din[2], din[3], nf, frq, nang, elev, d_tb, dout[0],
+                                          dout[1], dout[2], dout[3], dout[4], d_valid, opt ? &dopt : nullptr, vars, nullptr);
   if (rc) return rc;
-  JacRteArgs ja{};
-  ja.M = m->d_desc; ja.z = d_z; ja.t = d_t;
-  ja.awet = ta.awet; ja.adry = ta.adry; ja.dawet_dt = ta.dawet_dt; ja.dawet_de = ta.dawet_de;
-  ja.dadry_dt = ta.dadry_dt; ja.dadry_de = ta.dadry_de; ja.flags = flags;
-  ja.frq = dev_frq; ja.airmass = dev_am;
-  ja.tb = d_tb; ja.dtb_dt = d_dtb_dt; ja.dtb_de = d_dtb_de; ja.dtb_ddz = d_dtb_ddz; ja.valid = d_valid;
-  ja.nlev = nlev; ja.nf = nf; ja.nang = nang;
-  ja.denliq = d_denliq; ja.denice = d_denice; ja.dtb_dliq = d_dtb_dliq; ja.dtb_dice = d_dtb_dice;
-  // with cloud arrays the kernel only lowers valid (k_jac_rte): preset it
-  if (d_denliq || d_denice) HIP_TRY(hipMemsetAsync(d_valid, 1, (size_t)nprof, st));
-  return timed(c, st, [&] { return launch_jac_rte(ja, nprof, st); });
+  HIP_TRY(hipMemcpyAsync(tb, d_tb, sizeof(double) * ntb, hipMemcpyDeviceToHost, st));
+  for (int k = 0; k < 5; ++k)
+    if (out[k]) HIP_TRY(hipMemcpyAsync(out[k], dout[k], sizeof(double) * njac, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(valid, d_valid, (size_t)nprof, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return MWRT_OK;
 }
 
 int mwrt_set_chunk_width(mwrt_context* c, int width) {

@@ -1,7 +1,7 @@
 // mwrt_tl.hip -- the device K-matrix path: tangent-linear absorption (k_absorb_tl) and the adjoint RTE that consumes it
 // (k_jac_rte).  Declarations and argument records: mwrt_tl.hip.h; entry points: mwrt_absorption_tl_batch_device,
-// mwrt_tb_jacobian_batch_device and mwrt_tb_jacobian_batch_opt_device (cloud liquid / ice) in mwrt.hip; the
-// mathematics: DESIGN.md sections 4.5 - 4.5.2.
+// mwrt_tb_jacobian_batch_device, mwrt_tb_jacobian_batch_opt_device (cloud liquid / ice) and
+// mwrt_tb_jacobian_batch_vars_device (retrieval variables) in mwrt.hip; the mathematics: DESIGN.md sections 4.5 - 4.5.3.
 #include "mwrt_tl.hip.h"
 
 namespace mwrt {
@@ -387,6 +387,21 @@ __device__ __forceinline__ void liquid_abs_tl(cmodel M, double tk, double f, dou
 }
 #undef MWRT_SCHED_FENCE
 
+// Goff-Gratch saturation vapour pressure over water and its T-derivative, in goff_gratch_e's own form:
+// es = 10^g(y), y = 373.16 / T, so d es / dT = es ln10 g'(y) (-y / T)
+__device__ __forceinline__ void goff_gratch_es_tl(double tk, double& es, double& des) {
+  const double LN10 = 2.302585092994045684;
+  const double INV_LN10 = 0.434294481903251828;
+  const double y = 373.16 / tk;
+  const double a = fexp(LN10 * (11.344 * (1.0 - (1.0 / y)))), b = fexp(LN10 * (-3.49149 * (y - 1.0)));
+  const double g = -7.90298 * (y - 1.0) + 5.02808 * (flog(y) * INV_LN10) - 1.3816e-07 * (a - 1.0) + 0.0081328 * (b - 1.0) +
+                   3.0057148979490314 /*log10(1013.246)*/;
+  const double gy = -7.90298 + fdiv(5.02808 * INV_LN10, y) - (1.3816e-07 * 11.344 * LN10) * fdiv(a, y * y) -
+                    (0.0081328 * 3.49149 * LN10) * b;
+  es = fexp(LN10 * g);
+  des = es * LN10 * gy * -fdiv(y, tk);
+}
+
 // inclusive prefix sum over the workgroup (lanes by shuffles, then the waves in index order: deterministic)
 __device__ __forceinline__ double block_scan(double v, double* wsum, int tid, int nwaves, double& total) {
   const int lane = tid & (WAVE - 1), wave = tid / WAVE;
@@ -465,7 +480,8 @@ k_jac_rte(const JacRteArgs A) {
     for (int a = 0; a < nang; ++a) {
       const int64_t row = (prof * nang + a) * nf + j;
       if (live) {
-        A.dtb_dt[row * nlev + tid] = qnan; A.dtb_de[row * nlev + tid] = qnan; A.dtb_ddz[row * nlev + tid] = qnan;
+        A.dtb_dt[row * nlev + tid] = qnan; A.dtb_de[row * nlev + tid] = qnan;
+        if (A.dtb_ddz) A.dtb_ddz[row * nlev + tid] = qnan;
         if (A.dtb_dliq) A.dtb_dliq[row * nlev + tid] = qnan;
         if (A.dtb_dice) A.dtb_dice[row * nlev + tid] = qnan;
       }
@@ -518,6 +534,36 @@ k_jac_rte(const JacRteArgs A) {
     cst[5 * nthr] = i1 * kice; cst[6 * nthr] = i0n * kice;
     __syncthreads();                   // s0 / s1 are about to hold the clear-sky rows
   }
+  // ---- retrieval variables: the per-level factors of the change of variables, formed once and parked in
+  // nine LDS rows behind the cloud rows, each lane reading back its own entries inside the elevation loop.  Every branch
+  // on a mode is uniform across the workgroup, and a call with all three modes 0 executes none of this.
+  //   hydrostatic heights: dz_l = c_l (Tv_l + Tv_{l-1}), c_l = (287.04 / (2 g)) ln(p_{l-1} / p_l) / 1000 (c_0 = 0), so the
+  //   thickness rows Z_l and Z_{l+1} reach level l through kT = dTv/dT|e = 1 + 0.608 q and kE = dTv/de|T =
+  //   0.608 T 0.622 p / (p - 0.378 e)^2, q = 0.622 e / (p - 0.378 e):  v0 = c_l kT, v1 = c_{l+1} kT, v2 = c_l kE, v3 = c_{l+1} kE
+  //   humidity h: v4 = de/dh (es(T) for rh, p / 1e6 for ppmv), v5 = de/dT at fixed h (rh es'(T) for rh, else 0)
+  //   cloud as kg/kg: v6 = 1000 rho_air = 1e5 p / (287.06 T), v7 = denliq / T, v8 = denice / T
+  const bool vars_call = (A.humidity | A.cloud | A.heights) != 0;
+  double* vst = smem + (cloud_call ? 10 : 3) * nthr + 16 + tid;
+  if (vars_call) {
+    const double pl = A.p[lo], rhl = A.rh[lo];
+    double es = 0.0, des = 0.0;
+    if (A.heights || A.humidity == 1) goff_gratch_es_tl(tl, es, des);
+    double v[4] = {0.0, 0.0, 0.0, 0.0};
+    if (A.heights) {
+      const double e = rhl * es, ipe = fdiv(1.0, pl - 0.378 * e);
+      const double kT = 1.0 + 0.608 * (0.622 * e * ipe), kE = 0.608 * tl * (0.622 * pl) * (ipe * ipe);
+      const double RG = 287.04 / (2.0 * 9.80665) / 1000.0;
+      const double cl = lay ? RG * flog(fdiv(A.p[lo - 1], pl)) : 0.0;
+      const double cn = has_up ? RG * flog(fdiv(pl, A.p[lo + 1])) : 0.0;
+      v[0] = cl * kT; v[1] = cn * kT; v[2] = cl * kE; v[3] = cn * kE;
+    }
+    vst[0] = v[0]; vst[nthr] = v[1]; vst[2 * nthr] = v[2]; vst[3 * nthr] = v[3];
+    vst[4 * nthr] = (A.humidity == 1) ? es : (A.humidity == 2) ? pl * 1e-6 : 1.0;
+    vst[5 * nthr] = (A.humidity == 1) ? rhl * des : 0.0;
+    const double it = fdiv(1.0, tl);
+    vst[6 * nthr] = (1e5 / 287.06) * pl * it;
+    vst[7 * nthr] = denl * it; vst[8 * nthr] = deni * it;
+  }
   const double aw = A.awet[ao], ad = A.adry[ao];
   const double awT = A.dawet_dt[ao], awE = A.dawet_de[ao], adT = A.dadry_dt[ao], adE = A.dadry_de[ao];
   const double hvk = A.frq[j] * (1e9 * M->planck_h / M->boltzmann_k);
@@ -553,11 +599,11 @@ k_jac_rte(const JacRteArgs A) {
     const int64_t row = (prof * nang + a) * nf + j;
     double* o_t = A.dtb_dt + row * nlev;
     double* o_e = A.dtb_de + row * nlev;
-    double* o_z = A.dtb_ddz + row * nlev;
+    double* o_z = A.dtb_ddz ? A.dtb_ddz + row * nlev : nullptr;
     double* o_l = A.dtb_dliq ? A.dtb_dliq + row * nlev : nullptr;
     double* o_i = A.dtb_dice ? A.dtb_dice + row * nlev : nullptr;
     if (isnan(am)) {                   // a NaN elevation: its rows are NaN, the profile stays valid
-      if (live) { o_t[tid] = qnan; o_e[tid] = qnan; o_z[tid] = qnan; if (o_l) o_l[tid] = qnan; if (o_i) o_i[tid] = qnan; }
+      if (live) { o_t[tid] = qnan; o_e[tid] = qnan; if (o_z) o_z[tid] = qnan; if (o_l) o_l[tid] = qnan; if (o_i) o_i[tid] = qnan; }
       if (tid == 0) A.tb[row] = qnan;
       continue;
     }
@@ -580,7 +626,11 @@ k_jac_rte(const JacRteArgs A) {
     const double dc_dtau = fdiv(E * (2.0 * bm + 2.0 * b * E - b + b * E * E), opE * opE);
     const double g = lay ? dTB_dB * (Tm1 * dc_dtau - above) : 0.0;       // dTB / dtau_l (everything above l is dimmed)
     const double gk = g * am * dz;
+    // dTB / d(thickness of layer l) [K/km]: tau_l = m (Lw + Ld + Ll + Li) dz_l is linear in dz_l, so this holds at
+    // dz_l = 0 too
+    const double zr = lay ? g * am * (cloudy ? (Lw + Ld) + cst[0] : Lw + Ld) : 0.0;
     s0[tid] = gk; s1[tid] = th;
+    if (A.heights) s2[tid] = zr;       // (s2 is free inside the loop) level l needs the row of the layer above it too
     __syncthreads();
     const double gkn = has_up ? s0[tid + 1] : 0.0, thn = has_up ? s1[tid + 1] : 0.0;
     const double btl = dTB_dB * dbdT;
@@ -588,22 +638,30 @@ k_jac_rte(const JacRteArgs A) {
     double ce = gk * (w1 * awE + d1 * adE);
     ct += gkn * (w0n * awT + d0n * adT) + btl * Tl * thn;                 // ... and as the lower end of layer l+1
     ce += gkn * (w0n * awE + d0n * adE);
+    double rl = 0.0, ri = 0.0;         // two more rows of a cloudy call; a profile without cloud in it has all-zero rows
+    if (cloudy) {
+      rl = gk * cst[nthr] + gkn * cst[2 * nthr];
+      ri = gk * cst[5 * nthr] + gkn * cst[6 * nthr];
+      ct += gk * cst[3 * nthr] + gkn * cst[4 * nthr];       // the liquid term of dTB/dT at fixed e (ice has no T tangent)
+    }
+    if (vars_call) {                   // the rows in the caller's variables, each element still in its register
+      if (A.heights) {                 // thickness follows Tv of its two ends: folded into the T and humidity rows
+        const double zn = has_up ? s2[tid + 1] : 0.0;
+        ct += zr * vst[0] + zn * vst[nthr];
+        ce += zr * vst[2 * nthr] + zn * vst[3 * nthr];
+      }
+      if (A.humidity) { ct += ce * vst[5 * nthr]; ce *= vst[4 * nthr]; }
+      if (A.cloud && cloudy) {         // density falls with T at fixed mixing ratio
+        ct -= rl * vst[7 * nthr] + ri * vst[8 * nthr];
+        rl *= vst[6 * nthr]; ri *= vst[6 * nthr];
+      }
+    }
     if (live) {
       o_e[tid] = ce;
-      // dTB / d(thickness of layer l) [K/km]: tau_l = m (Lw + Ld + Ll + Li) dz_l is linear in dz_l, so this holds at
-      // dz_l = 0 too
-      o_z[tid] = lay ? g * am * (cloudy ? (Lw + Ld) + cst[0] : Lw + Ld) : 0.0;
+      if (o_z) o_z[tid] = zr;
+      if (cloud_call) { if (o_l) o_l[tid] = rl; if (o_i) o_i[tid] = ri; }
+      o_t[tid] = ct;
     }
-    if (cloud_call) {                  // two more rows; a profile without cloud in a cloudy call has all-zero rows
-      double rl = 0.0, ri = 0.0;
-      if (cloudy) {
-        rl = gk * cst[nthr] + gkn * cst[2 * nthr];
-        ri = gk * cst[5 * nthr] + gkn * cst[6 * nthr];
-        ct += gk * cst[3 * nthr] + gkn * cst[4 * nthr];     // the liquid term of dTB/dT at fixed e (ice has no T tangent)
-      }
-      if (live) { if (o_l) o_l[tid] = rl; if (o_i) o_i[tid] = ri; }
-    }
-    if (live) o_t[tid] = ct;
     if (tid == 0) A.tb[row] = fdiv(hvk, Lg);
   }
 }
@@ -619,8 +677,12 @@ hipError_t launch_absorb_tl(const AbsorbTlArgs& a, int64_t nprof, hipStream_t st
 hipError_t launch_jac_rte(const JacRteArgs& a, int64_t nprof, hipStream_t st) {
   const int threads = ((a.nlev + WAVE - 1) / WAVE) * WAVE;
   const bool cloud_call = a.denliq || a.denice;                    // seven more rows: the per-level cloud terms
-  const size_t lds = sizeof(double) * ((cloud_call ? 10 : 3) * (size_t)threads + 16);
-  if (lds > 64 * 1024) {               // (cloudy launches above 818 levels: beyond the default dynamic LDS limit)
+  const bool vars_call = a.humidity || a.cloud || a.heights;       // nine more: the factors of the change of variables
+  const size_t rows = (cloud_call ? 10 : 3) + (vars_call ? JAC_VARS_ROWS : 0);
+  const size_t lds = sizeof(double) * (rows * (size_t)threads + 16);
+  // beyond the default dynamic LDS limit: cloudy launches above 768 levels; with retrieval variables clear launches above
+  // 640 levels (12 rows) and cloudy ones above 384 (19 rows: 152 KiB at 1024 levels, inside the 160 KiB of a workgroup)
+  if (lds > 64 * 1024) {
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_jac_rte),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;

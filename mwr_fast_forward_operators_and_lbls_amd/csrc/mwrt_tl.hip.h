@@ -4,7 +4,8 @@
 //   k_absorb_tl  clearsky_absorption and its exact partial derivatives with respect to T (at fixed e) and e (at
 //                fixed T) for every level and frequency: every line at every frequency, no far-line forms, no windows
 //   k_jac_rte    the layer rule + Planck-space RTE + bright and their adjoint, fed by those six arrays;
-//                with cloud liquid / ice it forms their absorption and its tangents itself
+//                with cloud liquid / ice it forms their absorption and its tangents itself; with retrieval
+//                variables it changes the rows' variables before it stores them
 #pragma once
 #include "mwrt_kernels.hip.h"
 
@@ -35,7 +36,13 @@ struct JacRteArgs {
   double* dtb_dliq; double* dtb_dice;                         // the same layout, K per g m-3; null = not wanted
   uint8_t* valid;                                             // [nprof]
   int nlev, nf, nang;
+  // retrieval variables (mwrt_jac_variables); all three 0: the rows above as they are.  dtb_ddz may then
+  // be null (the raw thickness row is not wanted); dtb_de holds the humidity row, dtb_dliq / dtb_dice K per kg/kg
+  const double* p; const double* rh;                          // [nprof][nlev], read only when a mode is set
+  int humidity, cloud, heights;
 };
+
+constexpr int JAC_VARS_ROWS = 9;   // LDS rows of a launch with a retrieval-variable mode set, behind the cloud rows
 
 hipError_t launch_absorb_tl(const AbsorbTlArgs& a, int64_t nprof, hipStream_t st);
 hipError_t launch_jac_rte(const JacRteArgs& a, int64_t nprof, hipStream_t st);

@@ -183,6 +183,55 @@ def derive_TBs4PyRTlib(ds, args=None, cloudy=None, ray_tracing=None):
     return ds
 
 
+def _native_k_matrix_vars(tables, z, p, t, rh, frqs, elev, denliq, denice, variables):
+    """The single contact point of ``derive_jacobians4PyRTlib`` with the native library: ``(tb, valid, rows)`` of
+    ``Context.tb_jacobian_batch_vars`` without the thickness row."""
+    return _native.default_context().tb_jacobian_batch_vars(tables, z, p, t, rh, frqs, elev, denliq=denliq, denice=denice,
+                                                            variables=variables, thickness=False)
+
+
+def derive_jacobians4PyRTlib(ds, model="R24", cloudy=False):
+    """The K-matrix of one model for the whole data set, in the variables and the layout the reference stores its
+    RTTOV-gb sensitivities in (RTTOV_gb_processing.py:408-433): ``Jacobian_T_PyRTlib_<model>`` [K K-1, at fixed ppmv],
+    ``Jacobian_ppmv_PyRTlib_<model>`` [K ppmv-1] and, with ``cloudy``, ``Jacobian_liq_PyRTlib_<model>`` /
+    ``Jacobian_ice_PyRTlib_<model>`` [K kg kg-1], dims ``(time, N_Levels, N_Channels, elevation, Crop)``, level index
+    0 = top.  One device K-matrix call (``mwrt_tb_jacobian_batch_vars``: ppmv, kg/kg) for all (time, Crop) profiles and
+    all elevations; heights are fixed (``Level_z`` is data).  A profile with a NaN input keeps NaN; a negative absorption
+    coefficient raises, as ``derive_TBs4PyRTlib`` does."""
+    frqs = np.array([22.24, 23.04, 23.84, 25.44, 26.24, 27.84, 31.4, 51.26, 52.28,
+                     53.86, 54.94, 56.66, 57.3, 58.])
+    nf = len(frqs)
+    ang = np.asarray(ds["elevation"].values, dtype=np.float64)
+    nang = len(ang)
+    z, p, t, rh, ntime, ncrop = pack_profiles(ds)
+    nlev = z.shape[1]
+    tables = spectroscopy.get_model(model)
+    denliq = denice = None
+    if cloudy:
+        # the producer marks "no cloud information" with NaN (preprocessing4all.py:656-657): treat as no cloud
+        denliq, denice = (np.nan_to_num(x, nan=0.0) for x in pack_clouds(ds, p, t))
+    variables = _native.JacVariables.of(humidity="ppmv", cloud="kg/kg", heights="fixed")
+    _, valid, jac = _native_k_matrix_vars(tables, z, p, t, rh, frqs, ang, denliq, denice, variables)
+    bad = np.nonzero(valid == 2)[0]
+    if bad.size:
+        raise ValueError(f"Error encountered in exponential_integration (profile index {int(bad[0])}, model {model})")
+    what = [("T", "dtb_dt", "K K-1", "temperature"), ("ppmv", "dtb_dh", "K ppmv-1", "WV")]
+    if cloudy:
+        what += [("liq", "dtb_dliq", "K kg kg-1", "liquid water content"), ("ice", "dtb_dice", "K kg kg-1", "ice water content")]
+    for tag, key, units, long in what:
+        # [nprof][nang][nf][nlev] ground -> top  ->  (time, N_Levels top -> ground, nf, nang, Crop); time-major, Crop-minor
+        out = jac[key].reshape(ntime, ncrop, nang, nf, nlev).transpose(0, 4, 3, 2, 1)[:, ::-1]
+        name = f"Jacobian_{tag}_PyRTlib_{model}"
+        ds[name] = (('time', 'N_Levels', 'N_Channels', 'elevation', 'Crop'), np.ascontiguousarray(out))
+        ds[name].attrs = {
+            "units": units,
+            "long_name": f"TB Level Sensitivities to {long} by channel from PyRTlib {model}",
+            "description": "Sensitivities were derived with the line-by-line adjoint from radiosonde profiles.",
+            "tables_provenance": tables.provenance,
+        }
+    return ds
+
+
 def open_dataset(path: str):
     """``xr.open_dataset`` when xarray is importable (:205); without it NetCDF-4 files are read through
     libhdf5 (netcdf4_io), NetCDF-3 through scipy, and ``.npz`` is the exchange format."""

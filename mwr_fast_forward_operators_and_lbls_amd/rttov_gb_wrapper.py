@@ -16,9 +16,10 @@ RTTOV-gb profiles carry no geometric height: it is rebuilt hydrostatically from 
 the station height, and humidity converts as e = ppmv * p / 1e6 (the reference's own
 ``rh2ppmv`` / ``ppmv2rh``, preprocessing4all.py:124-136) with pyrtlib's Goff-Gratch e_s.
 The K-matrix block the reference also parses (:286-300: per channel a header of three lines, then one row
-``level p dTB/dT dTB/dppmv dTB/dliq`` per level) is produced by ``jacobians`` (one call of the operator's
-adjoint, ``mwrt_tb_jacobian_batch``; central / forward differences through the batched operator for the liquid column) and
-written / read by ``format_jacobians`` / ``parse_jacobians``.  Liquid water
+``level p dTB/dT dTB/dppmv dTB/dliq`` per level) is produced for any number of profiles by ``jacobians_batch`` (the device
+K-matrix in these variables, liquid column included, ``mwrt_tb_jacobian_batch_vars``) and for one profile by ``jacobians``
+(one call of the host adjoint, ``mwrt_tb_jacobian_batch``; central / forward differences through the batched operator for
+the liquid column), and written / read by ``format_jacobians`` / ``parse_jacobians``.  Liquid water
 enters through the cloud-liquid opt-in of the LBL operator (``clear_sky=False``; the reference itself runs RTTOV-gb
 with ``clear_sky_bool=True``, :82-86, so the default here is clear sky too).
 """
@@ -175,6 +176,46 @@ def jacobians_adjoint(profile: dict, model: str = "R24", frqs=HATPRO_FRQS):
     d_t = jac["dtb_dt"][0, 0] + dtb_dtv * dtv_dt[None, :]
     d_q = (jac["dtb_de"][0, 0] + dtb_dtv * (dtv_dq * dq_de)[None, :]) * de_dppmv[None, :]
     return d_t.T[::-1].copy(), d_q.T[::-1].copy()
+
+
+def _native_k_matrix_vars(tables, z, p, t, rh, frqs, elev, denliq, denice, variables):
+    """The single contact point of ``jacobians_batch`` with the native library: ``(tb, valid, rows)`` of
+    ``Context.tb_jacobian_batch_vars`` without the thickness row."""
+    return _native.default_context().tb_jacobian_batch_vars(tables, z, p, t, rh, frqs, elev, denliq=denliq, denice=denice,
+                                                            variables=variables, thickness=False)
+
+
+def jacobians_batch(profiles: List[dict], model: str = "R24", frqs=HATPRO_FRQS, liquid: bool = False):
+    """RTTOV-gb's K run for any number of parsed profiles: the device K-matrix (``mwrt_tb_jacobian_batch_vars``) in this
+    surface's own variables -- T at fixed ppmv, ppmv, liquid as kg/kg -- with the hydrostatic heights ``to_lbl_inputs``
+    rebuilds folded into the T and ppmv columns inside the kernel.  One call per distinct elevation, as ``simulate``
+    groups them; no finite differences anywhere (the liquid column is the adjoint's, too).
+
+    Returns ``(dTB_dT [nprof][nlev][nchan] K/K, dTB_dq [nprof][nlev][nchan] K/ppmv)`` and with ``liquid=True`` a third
+    array ``dTB_dliq`` in K per kg/kg, levels TOP -> GROUND; ``liquid=True`` also takes the T and ppmv columns in the
+    presence of each profile's ``liquid`` column, like ``jacobians``.  ``format_jacobians(p, dT[i], dq[i], dl[i])`` writes
+    profile i's block.  A profile with a NaN input has NaN columns; a negative absorption coefficient raises, as
+    ``jacobians`` does for a rejected profile."""
+    z, p, t, rh, elev = to_lbl_inputs(profiles)
+    nprof, nlev = z.shape
+    frqs = np.asarray(frqs, dtype=float)
+    tables = spectroscopy.get_model(model)
+    variables = _native.JacVariables.of(humidity="ppmv", cloud="kg/kg", heights="hydrostatic")
+    denliq = None
+    if liquid:
+        from .pyrtlib_processing import cloud_density_g_m3
+        q = np.array([np.asarray(pr["liquid"], dtype=float)[::-1] for pr in profiles])
+        denliq = cloud_density_g_m3(q, p, t)
+    out = [np.full((nprof, nlev, len(frqs)), np.nan) for _ in range(3 if liquid else 2)]
+    for ang in np.unique(elev):                             # profiles sharing an elevation go in one launch
+        idx = np.nonzero(elev == ang)[0]
+        _, valid, jac = _native_k_matrix_vars(tables, z[idx], p[idx], t[idx], rh[idx], frqs, np.array([ang]),
+                                              None if denliq is None else denliq[idx], None, variables)
+        if (valid == 2).any():
+            raise ValueError(f"profile {int(idx[np.nonzero(valid == 2)[0][0]])} was rejected (negative absorption)")
+        for o, key in zip(out, ("dtb_dt", "dtb_dh", "dtb_dliq")):
+            o[idx] = jac[key][:, 0].transpose(0, 2, 1)[:, ::-1]     # [n][nf][nlev] ground -> top  ->  [n][nlev][nf] top -> ground
+    return tuple(out)
 
 
 def jacobians(profile: dict, model: str = "R24", frqs=HATPRO_FRQS, dT: float = 0.05, rel_q: float = 0.01,
