@@ -105,14 +105,23 @@ __device__ __forceinline__ double fdiv(double x, double d) {
 // here each constant rides in an SGPR pair (materialised by s_mov, off the VALU port), so a step
 // is ONE v_fma_f64.  ~19 VALU instead of ~35; max relative error measured < 4e-16.
 #define MWRT_FMA_SC(p, r, c) asm("v_fma_f64 %0, %1, %2, %3" : "=v"(p) : "v"(p), "v"(r), "s"(c))
-__device__ __forceinline__ double fexp(double x) {
+// The LEADING coefficient of such a Horner chain is the one operand that has to sit in a vector register (the first
+// step reads it as `p`), and the compiler re-materialises it with a v_mov_b64 at every evaluation.  A loop that
+// evaluates the polynomial per trip takes the coefficient as an argument instead and holds it in a register across the
+// loop (loop_invariant_vgpr): same constant, same chain, one VALU instruction fewer per evaluation.
+__device__ __forceinline__ double loop_invariant_vgpr(double c) {
+  asm volatile("" : "+v"(c));                        // opaque: cannot be re-materialised inside the loop
+  return c;
+}
+constexpr double FEXP_C0 = 2.5100569275813683e-08;
+__device__ __forceinline__ double fexp(double x, double c0 = FEXP_C0) {
 #if MWRT_EXACT_DIV
   return exp(x);
 #else
   const double k = __builtin_rint(x * 1.4426950408889634074);
   double r = __builtin_fma(k, -6.93147180369123816490e-01, x);
   r = __builtin_fma(k, -1.90821492927058770002e-10, r);
-  double p = 2.5100569275813683e-08;
+  double p = c0;
   MWRT_FMA_SC(p, r, 2.762032742826824e-07);
   MWRT_FMA_SC(p, r, 2.75572680728901e-06);
   MWRT_FMA_SC(p, r, 2.4801520792572694e-05);
@@ -171,8 +180,9 @@ __device__ __forceinline__ double flog(double x) {
 // (2.2e-18 relative).  9 VALU.
 // Thin layers (tau * airmass <= 1/8) are the rule for the K-band channels at every level and angle.
 constexpr double EXP_SMALL_X = 0.125;
-__device__ __forceinline__ double fexp_small(double x) {
-  double p = 2.756514908613403e-06;
+constexpr double FEXP_SMALL_C0 = 2.756514908613403e-06;
+__device__ __forceinline__ double fexp_small(double x, double c0 = FEXP_SMALL_C0) {
+  double p = c0;
   MWRT_FMA_SC(p, x, 2.4810200365624755e-05);
   MWRT_FMA_SC(p, x, 0.00019841269076602318);
   MWRT_FMA_SC(p, x, 0.001388888804772704);
@@ -187,9 +197,10 @@ __device__ __forceinline__ double fexp_small(double x) {
 // tanh(x/2) = (1 - e^-x) / (1 + e^-x) for 0 <= x <= 1/8: x (1/2 + u g(u)), u = x^2, g of degree 3 fitted at the Chebyshev
 // nodes of [0, 1/64] (6e-17 relative).  6 VALU; in the thin-layer RTE step it replaces 1 - E, 1 + E and their quotient (9 issue slots), and has none
 // of the cancellation of 1 - E.
-__device__ __forceinline__ double ftanh_half_small(double x) {
+constexpr double FTANH_HALF_SMALL_C0 = 4.257889640378761e-05;
+__device__ __forceinline__ double ftanh_half_small(double x, double c0 = FTANH_HALF_SMALL_C0) {
   const double u = x * x;
-  double p = 4.257889640378761e-05;
+  double p = c0;
   MWRT_FMA_SC(p, u, -0.0004216256671577941);
   MWRT_FMA_SC(p, u, 0.004166666662552237);
   MWRT_FMA_SC(p, u, -0.04166666666666466);
@@ -236,7 +247,7 @@ __device__ __forceinline__ float row16_max(float m) {
   m = fmaxf(m, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(m), 0x121, 0xf, 0xf, false)));
   return m;
 }
-constexpr int K2_SORT_MIN_SEGLEN = 16;     // shorter segments: dealing the items out costs more than the thin step saves
+// (K2_SORT_MIN_SEGLEN, the shortest segment whose items are dealt out sorted: mwrt_plan.h -- the row stride depends on it)
 
 // Planck function in pyrtlib's units, B = 1 / (exp(x) - 1), x = h f / (k T).  In the microwave x is a few
 // 1e-3: when the whole wave has x <= 1/32, B = (1/x) * x/(e^x - 1) with the Bernoulli series
@@ -1451,6 +1462,39 @@ __device__ __forceinline__ void blank_outputs(const FusedArgs& A, int64_t prof, 
     A.taulay[(prof * A.nf + jbase + it / nlev) * nlev + it % nlev] = qnan;
 }
 
+// The layers of one sorted K2 work item: `seglen` steps over tp[0 ..] / bp[0 ..] (zenith layer tau and B of the
+// segment's levels).  The count is the same for every lane of the workgroup, so the loop runs on a scalar counter; a
+// segment that ends past the top level reads the rows' zero padding there, and a layer of tau = 0 is an exact no-op
+// (E = 1: T *= 1, B += x * 0).
+// Four layers per trip, every value used in the registers it was loaded into: a pair of registers is reloaded only
+// after its last use -- for a B value that is the step AFTER its own, which reads it as the level below -- so no
+// copy carries anything round the loop; tau is in flight two steps ahead, B one and a half.  Each row is addressed
+// from one LDS pointer that moves once per trip (opaque to the optimiser, which otherwise rebuilds base + offset
+// every trip); the layers of a trip sit in the loads' immediate offsets.  The two layers loaded past the last one are
+// dropped (they may lie beyond the zeroed part of the row: still inside the workgroup's LDS, see the row stride).
+typedef const __attribute__((address_space(3))) double* ldoubles;
+template <class Step>
+__device__ __forceinline__ void rte_segment(const double* tau_seg, const double* bof_seg, int seglen, Step step) {
+  ldoubles tp = (ldoubles)tau_seg, bp = (ldoubles)bof_seg;
+  asm volatile("" : "+v"(tp), "+v"(bp));
+  double t0 = tp[0], t1 = tp[1], b0 = bp[0], b1 = bp[1];
+  for (int n = seglen >> 2; n > 0; --n) {
+    const double t2 = tp[2], t3 = tp[3];
+    step(t0, b0);
+    const double b2 = bp[2], b3 = bp[3];
+    step(t1, b1);
+    t0 = tp[4]; t1 = tp[5];
+    step(t2, b2);
+    b0 = bp[4]; b1 = bp[5];
+    step(t3, b3);
+    tp += 4; bp += 4;
+  }
+  const int rest = seglen & 3;
+  if (rest > 0) step(t0, b0);
+  if (rest > 1) step(t1, b1);
+  if (rest > 2) step(tp[2], bp[2]);
+}
+
 // NFC = frequencies per workgroup (accumulators in registers during K1);
 // NFK = frequencies per K2 pass (rows of tau / B kept in LDS at a time): NFC = NPASS * NFK.
 // Keeping only NFK rows resident holds the workgroup under 40 KB of LDS, so FOUR 192-thread
@@ -1679,6 +1723,14 @@ k_tb_fused(const FusedArgs A) {
     want_tau = (A.tauwet != nullptr) || (A.taudry != nullptr) || (A.tauliq != nullptr) || (A.tauice != nullptr);
   }
 
+  // The rows' padding, [nlev, ld), is zero in every row: a sorted pass runs each segment for its full length, and the
+  // last one of a row ends there (rte_segment).  No pass writes these entries, so once is enough; the barrier that
+  // every pass has between filling the rows and reading them orders these stores as well.
+  for (int k = nlev + tid; k < ld; k += nthreads) {
+#pragma unroll
+    for (int jj = 0; jj < NFK; ++jj) { tau[jj * ld + k] = 0.0; bof[jj * ld + k] = 0.0; }
+  }
+
   // ---- phase K2: slant-path RTE (RTEquation.planck, from_sat = False [EXT]), NFK rows at a time ----
 #pragma unroll
   for (int h = 0; h < NPASS; ++h) {
@@ -1812,9 +1864,22 @@ k_tb_fused(const FusedArgs A) {
       if constexpr (OPT) fr = A.amf ? A.amf + (pin * nang + a) * nlev : nullptr;
       double T = 1.0, B = 0.0;
       double bprev = (lo < nlev) ? bj[lo - 1] : 0.0;
-      if (!sorted) {
-        // short segments, several rounds, or ray-traced path factors (they vary with the level): thin or not is
-        // voted per step
+      if (!sorted && !(OPT && fr) && nseg * seglen < ld) {
+        // several rounds or short segments: thin or not is voted per step, by the lanes that hold an item -- a lane in
+        // the zero padding past its last layer votes thin and changes no vote.  (This is the loop of the headline
+        // shape: 56 pairs x 10 segments of 18 layers in three rounds, then 42 x 9 of 20 in two.)
+        const double cs = loop_invariant_vgpr(FEXP_SMALL_C0), ce = loop_invariant_vgpr(FEXP_C0);
+        rte_segment(tj + lo, bj + lo, seglen, [&](double tz, double bi) {
+          const double tl = tz * am;
+          const double E = wave_all(fabs(tl) <= EXP_SMALL_X) ? fexp_small(-tl, cs) : fexp(-tl, ce);
+          const double lay = fdiv1(__builtin_fma(bi, E, bprev), 1.0 + E);
+          B = __builtin_fma(lay * T, 1.0 - E, B);
+          T *= E;
+          bprev = bi;
+        });
+      } else if (!sorted) {
+        // ray-traced path factors (they vary with the level), or a row stride that stops short of nseg * seglen (segments
+        // under K2_SORT_MIN_SEGLEN layers): each lane runs its own layers, thin or not is voted per step
         for (int i = lo; i < hi; ++i) {
           const double tl = tj[i] * ((OPT && fr) ? fr[i] : am);
           const double E = wave_all(fabs(tl) <= EXP_SMALL_X) ? fexp_small(-tl) : fexp(-tl);
@@ -1826,42 +1891,25 @@ k_tb_fused(const FusedArgs A) {
         }
       } else if (wave_all(it0 < nthin_all)) {
         // boflay (1 - E) = (B_{i-1} + B_i E) (1 - E)/(1 + E) = (B_{i-1} + B_i E) tanh(tau/2)
-        auto step = [&](double tz, double bi) {
+        const double ce = loop_invariant_vgpr(FEXP_SMALL_C0), ct = loop_invariant_vgpr(FTANH_HALF_SMALL_C0);
+        rte_segment(tj + lo, bj + lo, seglen, [&](double tz, double bi) {
           const double tl = tz * am;
-          const double E = fexp_small(-tl);
-          const double th = ftanh_half_small(tl);
+          const double E = fexp_small(-tl, ce);
+          const double th = ftanh_half_small(tl, ct);
           B = __builtin_fma(__builtin_fma(bi, E, bprev) * T, th, B);
           T *= E;
           bprev = bi;
-        };
-        // two layers per trip, the next trip's rows already in flight (index hi <= nlev is inside the padded row)
-        int i = lo;
-        double t0 = (i < hi) ? tj[i] : 0.0, b0 = (i < hi) ? bj[i] : 0.0;
-        for (; i + 1 < hi; i += 2) {
-          const double t1 = tj[i + 1], b1 = bj[i + 1];
-          const double t2 = tj[i + 2], b2 = bj[i + 2];
-          step(t0, b0); step(t1, b1);
-          t0 = t2; b0 = b2;
-        }
-        if (i < hi) step(t0, b0);
+        });
       } else {
-        auto step = [&](double tz, double bi) {
+        const double ce = loop_invariant_vgpr(FEXP_C0);
+        rte_segment(tj + lo, bj + lo, seglen, [&](double tz, double bi) {
           const double tl = tz * am;
-          const double E = fexp(-tl);
+          const double E = fexp(-tl, ce);
           const double lay = fdiv1(__builtin_fma(bi, E, bprev), 1.0 + E);
           B = __builtin_fma(lay * T, 1.0 - E, B);
           T *= E;
           bprev = bi;
-        };
-        int i = lo;
-        double t0 = (i < hi) ? tj[i] : 0.0, b0 = (i < hi) ? bj[i] : 0.0;
-        for (; i + 1 < hi; i += 2) {
-          const double t1 = tj[i + 1], b1 = bj[i + 1];
-          const double t2 = tj[i + 2], b2 = bj[i + 2];
-          step(t0, b0); step(t1, b1);
-          t0 = t2; b0 = b2;
-        }
-        if (i < hi) step(t0, b0);
+        });
       }
       part[2 * it + 0] = B; part[2 * it + 1] = T;
     }

@@ -42,6 +42,15 @@ void set_split(LaunchGeom* g, int nlev, int nfc, int nf, int nang, int ns0, int 
   g->magic_nseg[0] = magic_of(g->nseg[0]);
   g->magic_nseg[1] = magic_of(g->nseg[1]);
   g->magic_nang = magic_of(nang);
+  // Row stride in doubles.  A pass that deals its items out sorted (seglen >= K2_SORT_MIN_SEGLEN) runs every segment for
+  // the full seglen layers, so the last segment of a row reads up to index nseg * seglen: the row reaches that far, and
+  // the kernel zero-fills it from nlev on (a layer of tau = 0 leaves B and T as they are).  An odd multiple of 2 dwords
+  // keeps ds_read_b64 rows on distinct banks.
+  int ld = nlev + 1;
+  for (int h = 0; h < 2; ++h)
+    if (g->seglen[h] >= K2_SORT_MIN_SEGLEN) ld = std::max(ld, g->nseg[h] * g->seglen[h] + 1);
+  if ((ld & 1) == 0) ld += 1;
+  g->ldrow = ld;
 }
 
 LaunchGeom plan_k2(int nlev, int nfc, int nf, int nang, int threads) {
@@ -49,10 +58,6 @@ LaunchGeom plan_k2(int nlev, int nfc, int nf, int nang, int threads) {
   const int rows1 = rows1_of(nfc, nf);
   set_split(&g, nlev, nfc, nf, nang, plan_k2_pass(nlev, rows0_of(nfc, nf) * nang, threads),
             rows1 > 0 ? plan_k2_pass(nlev, rows1 * nang, threads) : 1);
-  // row stride in doubles: odd multiple of 2 dwords keeps ds_read_b64 rows on distinct banks
-  int ld = nlev + 1;
-  if ((ld & 1) == 0) ld += 1;
-  g.ldrow = ld;
   return g;
 }
 

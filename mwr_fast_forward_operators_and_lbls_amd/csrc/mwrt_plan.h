@@ -17,7 +17,7 @@ struct LaunchGeom {          // host-computed K2 work split (see plan_k2 in mwrt
   int nseg[2];               // level segments per (freq, angle) pair
   int seglen[2];             // layers per segment
   int npart;                 // doubles of segment partials (B, T) the largest pass needs
-  int ldrow;                 // padded LDS row length (doubles) of tau/boft: conflict-free for b64
+  int ldrow;                 // padded LDS row length (doubles) of tau/boft: conflict-free for b64, > nseg * seglen of a sorted pass
   unsigned magic_nseg[2];    // ceil(2^32 / nseg), ceil(2^32 / nang): n / d = umulhi(n, magic) for n < 65536, 1 < d <= 1024
   unsigned magic_nang;       // (the work-item index splits cost two integer divisions per item otherwise)
 };
@@ -58,6 +58,9 @@ constexpr int MAX_MULTI = 8;   // absorption models evaluated by one launch (the
 
 // rows kept in LDS per K2 pass; a 14-wide chunk runs as passes of 8 and 6 rows, each with its own split
 constexpr int NFK = 8;
+// a pass whose segments are at least this long deals its work items to the lanes thin ones first (k_tb_fused); shorter
+// segments: dealing the items out costs more than the thin step saves
+constexpr int K2_SORT_MIN_SEGLEN = 16;
 
 constexpr int TAU_NFC = 16;                   // tau rows are written in 16-frequency (128-byte) pieces
 constexpr int tau_threads(int nlev) { return ((nlev - 1 + (WAVE - 2)) / (WAVE - 1)) * WAVE; }
