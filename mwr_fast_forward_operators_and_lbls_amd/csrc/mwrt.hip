@@ -2,9 +2,12 @@
 //
 // HIP only: there is no CPU fallback in this library.  Without a GPU mwrt_device_count()
 // returns 0 and mwrt_create() fails with MWRT_ERR_NO_DEVICE.
-#define MWRT_HOST_TU 1      // this translation unit owns the non-template kernels
-#include "mwrt_inst.hip.h"
+//
+// Host code only: streams, caches, argument checks and the choice of launch.  Every kernel lives in another unit
+// (mwrt_inst.hip, mwrt_tl.hip, mwrt_aux.hip) and is reached through the launchers the two headers below declare.
+#include "mwrt_args.hip.h"
 #include "mwrt_tl.hip.h"
+#include "mwrt_plan.h"
 
 #include <cmath>
 #include <cstdio>
@@ -664,9 +667,8 @@ static int tb_launch(mwrt_context* c, int nmodels, const mwrt_model* const* ms, 
     rc = workspace_acquire(c, st); if (rc) return rc;
     ws_held = true;
     HIP_TRY(hipMemsetAsync(c->d_duct.p, 0, (size_t)nprof, st));
-    hipLaunchKernelGGL(k_ray_paths, dim3((unsigned)nprof), dim3(lanes_for(nlev)), 0, st, d_z, d_p, d_t, d_rh, (int)nlev, dev_elev,
-                       (int)nang, c->d_amf.as<double>(), c->d_duct.as<uint8_t>());
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_ray_paths(d_z, d_p, d_t, d_rh, nprof, (int)nlev, dev_elev, (int)nang, c->d_amf.as<double>(),
+                             c->d_duct.as<uint8_t>(), st));
     a.amf = c->d_amf.as<double>();
     a.duct = c->d_duct.as<uint8_t>();
   }
@@ -926,7 +928,8 @@ int mwrt_tb_jacobian_batch(mwrt_context* c, const mwrt_model* m, int64_t nprof, 
   // profile batches: the five absorption sets + three Jacobian arrays of one batch stay under ~1 GiB
   const size_t per_prof = sizeof(double) * ((size_t)10 * nf * nlev + (size_t)3 * nang * nf * nlev + (size_t)nang * nf + 12 * (size_t)nlev) + 1;
   const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(nprof, (int64_t)(((size_t)1 << 30) / per_prof)));
-  DevBuf ws;                                                      // own workspace: freed on return
+  DevBuf ws;                                                      // own workspace: freed on every return path
+  auto free_ws = on_scope_exit([&] { ws.release(); });
   HIP_TRY(ws.reserve((size_t)batch * per_prof + 4096));
   for (int64_t b0 = 0; b0 < nprof; b0 += batch) {
     const int64_t nb = std::min(batch, nprof - b0);
@@ -966,11 +969,7 @@ int mwrt_tb_jacobian_batch(mwrt_context* c, const mwrt_model* m, int64_t nprof, 
     a.tb = d_tb; a.dtb_dt = d_jac; a.dtb_de = d_jac + njac; a.dtb_ddz = d_jac + 2 * njac; a.valid = d_valid;
     a.nprof = nb; a.nlev = nlev; a.nf = nf; a.nang = nang;
     HIP_TRY(hipMemsetAsync(d_valid, 1, (size_t)nb, st));
-    const int64_t nthreads = nb * nf * nang;
-    rc = timed(c, st, [&] {
-      hipLaunchKernelGGL(k_tb_jacobian, dim3((unsigned)((nthreads + 63) / 64)), dim3(64), 0, st, a);
-      return hipGetLastError();
-    });
+    rc = timed(c, st, [&] { return launch_tb_jacobian(a, st); });
     if (rc) return rc;
     const size_t o = (size_t)b0 * nang * nf;
     HIP_TRY(hipMemcpyAsync(tb + o, d_tb, sizeof(double) * ntb, hipMemcpyDeviceToHost, st));
@@ -980,7 +979,6 @@ int mwrt_tb_jacobian_batch(mwrt_context* c, const mwrt_model* m, int64_t nprof, 
     HIP_TRY(hipMemcpyAsync(valid + b0, d_valid, (size_t)nb, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
   }
-  ws.release();
   // a profile flagged 0 / 2 is blanked as a whole, whichever thread met it
   const size_t ntb = (size_t)nang * nf;
   const RowArray out[4] = {{tb, ntb}, {dtb_dt, ntb * nlev}, {dtb_de, ntb * nlev}, {dtb_ddz, ntb * nlev}};
@@ -1113,9 +1111,7 @@ int mwrt_selftest_math(mwrt_context* c, int32_t n, const double* x, const double
   HIP_TRY(c->d_out.reserve(4 * b));
   double* din = c->d_in.as<double>();
   double* dout = c->d_out.as<double>();
-  hipLaunchKernelGGL(k_selftest_math, dim3((n + 255) / 256), dim3(256), 0, c->stream, din, din + n, dout, dout + n,
-                     dout + 2 * (size_t)n, dout + 3 * (size_t)n, n);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_selftest_math(din, din + n, dout, dout + n, dout + 2 * (size_t)n, dout + 3 * (size_t)n, n, c->stream));
   double* dst[4] = {exp_x, log_y, x_div_y, x_div1_y};
   for (int k = 0; k < 4; ++k) HIP_TRY(hipMemcpyAsync(dst[k], dout + (size_t)k * n, b, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));

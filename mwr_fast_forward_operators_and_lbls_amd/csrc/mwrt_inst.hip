@@ -1,6 +1,7 @@
 // mwrt_inst.hip -- one translation unit per frequency-chunk width (compile with -DMWRT_INST_NFC=8|14|16):
-// the fused-kernel and absorption-kernel instantiations of that width and their launchers.
-#include "mwrt_inst.hip.h"
+// the fused-kernel and absorption-kernel instantiations of that width and their launchers (declared in mwrt_args.hip.h).
+#include "mwrt_fused.hip.h"
+#include "mwrt_tau.hip.h"
 
 #include <type_traits>
 

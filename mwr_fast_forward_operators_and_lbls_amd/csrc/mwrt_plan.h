@@ -2,7 +2,7 @@
 // which kernel instantiation serves a call, how its work is split, and the tables it reads (csrc/mwrt_plan.cpp).
 //
 // Plain C++17 with no HIP in it: any host compiler builds the planning unit, so it can be run and sanitised without a
-// GPU library (tests/plan_dump.cpp).  mwrt_kernels.hip.h includes this header and keeps everything that is device code.
+// GPU library (tests/plan_dump.cpp).  mwrt_args.hip.h includes this header; the device code is in the mwrt_*.hip.h headers behind it.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -45,12 +45,12 @@ struct LineMasks {
   double vf_u0, vf_h, vf_invh; // middle and half range of the chunk's f^2 values [GHz^2] (vf_h >= 1), 1 / vf_h
 };
 
-// very far lines (mwrt_kernels.hip.h vfar_add): the host picks them (chunk_masks) with the shift / width allowances
+// very far lines (mwrt_absorption.hip.h vfar_add): the host picks them (chunk_masks) with the shift / width allowances
 constexpr double VF_RATIO_MAX = 0.016;
 constexpr int VF_MIN_FREQS = 7;              // ... and chunks with fewer frequencies than this are served directly
 constexpr int VF_MIN_LINES = 4;              // fewer lines than this do not pay for the Horner pass (8 per frequency)
 
-// half-sampled speed-dependent shape (mwrt_kernels.hip.h): evaluated at 9 of a chunk's 16 frequencies, interpolated to 7
+// half-sampled speed-dependent shape (mwrt_absorption.hip.h): evaluated at 9 of a chunk's 16 frequencies, interpolated to 7
 constexpr int SD_NODES = 9, SD_TARGETS = 7;
 constexpr int sd_node_slot(int n) { return n < 8 ? 2 * n : 15; }
 

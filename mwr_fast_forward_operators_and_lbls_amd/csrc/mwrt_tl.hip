@@ -3,6 +3,8 @@
 // mwrt_tb_jacobian_batch_device, mwrt_tb_jacobian_batch_opt_device (cloud liquid / ice) and
 // mwrt_tb_jacobian_batch_vars_device (retrieval variables) in mwrt.hip; the mathematics: DESIGN.md sections 4.5 - 4.5.3.
 #include "mwrt_tl.hip.h"
+#include "mwrt_absorption.hip.h"      // level_state, goff_gratch_e, clog_, CLOUD_KICE (and the arithmetic of mwrt_math.hip.h)
+#include "mwrt_layer.hip.h"           // LOGMEAN_SMALL_S
 
 namespace mwrt {
 

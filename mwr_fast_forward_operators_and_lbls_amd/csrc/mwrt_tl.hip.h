@@ -1,4 +1,5 @@
-// mwrt_tl.hip.h -- the device K-matrix path (csrc/mwrt_tl.hip): tangent-linear absorption + adjoint RTE.
+// mwrt_tl.hip.h -- the device K-matrix path (csrc/mwrt_tl.hip): tangent-linear absorption + adjoint RTE.  Argument
+// records and launchers only, as the host unit reads them; the device helpers the kernels use are included by mwrt_tl.hip.
 //
 // Two kernels, each in this one translation unit (built by build.py next to the chunk-width units):
 //   k_absorb_tl  clearsky_absorption and its exact partial derivatives with respect to T (at fixed e) and e (at
@@ -7,7 +8,7 @@
 //                with cloud liquid / ice it forms their absorption and its tangents itself; with retrieval
 //                variables it changes the rows' variables before it stores them
 #pragma once
-#include "mwrt_kernels.hip.h"
+#include "mwrt_args.hip.h"
 
 namespace mwrt {
 

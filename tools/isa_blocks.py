@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """Per-basic-block and per-source-line instruction table of one kernel, from hipcc --save-temps ISA.
 
-    hipcc --offload-arch=gfx950 -O3 -gline-tables-only --save-temps ... csrc/mwrt.hip
-    python tools/isa_blocks.py mwrt-hip-amdgcn-amd-amdhsa-gfx950.s k_tb_fusedILi14ELi7ELi256E [--lines]
+    hipcc --offload-arch=gfx950 -O3 -gline-tables-only --save-temps ... -DMWRT_INST_NFC=14 -c csrc/mwrt_inst.hip
+    python tools/isa_blocks.py mwrt_inst-hip-amdgcn-amd-amdhsa-gfx950.s k_tb_fusedILi14ELi7ELi256E [--lines]
+
+(the unit that holds the kernel: csrc/mwrt_inst.hip for k_tb_fused, k_absorb* and k_rte_tau, csrc/mwrt_tl.hip for the
+K-matrix kernels, csrc/mwrt_aux.hip for the rest; csrc/mwrt.hip is host code only)
 
 Static counts only: multiply a loop block by its trip count (O2 line loop = n_o2, H2O = n_h2o ...)
 to estimate the dynamic VALU instructions per wave that SQ_INSTS_VALU reports.
