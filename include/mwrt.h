@@ -434,6 +434,56 @@ int mwrt_tb_jacobian_batch_vars(mwrt_context* ctx, const mwrt_model* model, int6
                                 double* dtb_dice, uint8_t* valid, const mwrt_tb_options* options,
                                 const mwrt_jac_variables* vars);
 
+/* One optimal-estimation (Gauss-Newton / 1D-Var) step per profile on the device (Rodgers 2000, eq. 5.10):
+ *     x+ = xa + Sa K^T (K Sa K^T + Se)^-1 [ y - F(x) + K (x - xa) ]
+ * for nprof profiles in one launch -- what a retrieval does next with the K-matrix of mwrt_tb_jacobian_batch_vars_device.
+ * Dimensions per profile: nblk state blocks (1 .. 4; e.g. T, humidity, liquid, ice) of nlev levels each, n = nblk * nlev;
+ * m observations (m = nang * nf when K comes from the Jacobian entries).  All DEVICE pointers, float64 unless stated:
+ *   d_k[b], b < nblk   [nprof][m][nlev]: a Jacobian output [nprof][nang][nf][nlev] as that entry wrote it; K = [K_0 | K_1 | ...]
+ *   d_x                [nprof][nblk][nlev] the current state
+ *   d_xa               the prior state: [nblk][nlev] shared by all profiles, or [nprof][nblk][nlev] with xa_per_profile != 0
+ *   d_sa               [n][n] prior covariance, shared, SYMMETRIC (only symmetric input is defined; cross-block terms allowed)
+ *   d_se               observation-error covariance, shared: [m] variances, or [m][m] symmetric with se_full != 0
+ *   d_y, d_fx          [nprof][m] the observations and the forward model at x (the tb of the Jacobian call)
+ * With d = y - F(x) + K (x - xa) and G = K Sa K^T + Se = L L^T, per profile:
+ *   d_x_new    [nprof][nblk][nlev]  xa + Sa K^T G^-1 d                                   required
+ *   d_status   [nprof] uint8        see below                                            required
+ *   d_chi2     [nprof]              d^T G^-1 d                                            optional (NULL: not wanted)
+ *   d_dfs      [nprof]              tr(A) = m_used - tr(G^-1 Se), degrees of freedom for signal          optional
+ *   d_post_var [nprof][nblk][nlev]  diag(Sa - Sa K^T G^-1 K Sa); NULL skips its second pass over the panels   optional
+ *   d_nobs     [nprof] int32        m_used                                                optional
+ * Missing observations: row i of a profile is DROPPED when y_i, fx_i, any K[i, :] or its Se entry (the variance, or any
+ *   element of row i of a full Se) is not finite.  A dropped row is algebraically deleted (K row 0, d_i 0, G_ii 1, other
+ *   G_i. 0); it is not counted in m_used and enters neither dfs nor chi2.  This is how a NaN elevation or a blanked
+ *   channel of the K-matrix call passes through.
+ * status: 1 ok;  0 x or xa of the profile not finite: every output of the profile NaN (nobs 0);  2 a Cholesky pivot fails
+ *   pivot > 0 (G not positive definite, or NaN): outputs NaN (nobs = m_used);  3 no usable observation (e.g. a profile the
+ *   Jacobian call flagged invalid): x_new = xa exactly, chi2 0, dfs 0, post_var = diag Sa, nobs 0.
+ * Determinism: a profile's outputs depend on neither its batch-mates nor nprof (one workgroup per profile, fixed
+ *   summation orders, no atomics), and x_new does not depend on which optional outputs are asked for.
+ * The record starts with its own size: fields at or beyond struct_size are not read (taken as NULL), so it can grow.  The
+ *   required pointers come first; a caller compiled against a shorter record that ends after d_status is served.
+ * Limits: m <= MWRT_OE_MAX_M (the packed triangle of G lives in LDS), nlev <= MWRT_MAX_LEVELS, hence n <= 4096; beyond
+ *   them MWRT_ERR_UNSUPPORTED with the limit in the error text.  MWRT_ERR_INVALID_ARGUMENT: a NULL required pointer,
+ *   nblk outside 1 .. 4, reserved != 0, nlev < 1, m < 1, nprof < 0, struct_size too small for the required fields.
+ * Streams as every *_device entry.  No workspace: the call never allocates and never synchronises.  The first launch of a
+ *   size above 64 KiB of LDS (m >= 65) raises that kernel's dynamic-LDS limit once per device; a repeat call of the same
+ *   size is the launch alone, so it is hipGraph-capturable after one warm-up call like the other entries (not yet
+ *   exercised under capture by a test).  A struct_size that ends inside a field leaves that field unread, too.
+ *   (MWRT_VERSION stays 301: additions.) */
+#define MWRT_OE_MAX_M 140
+typedef struct mwrt_oe_step {
+  uint32_t struct_size;        /* sizeof(mwrt_oe_step) of the caller; fields beyond it are not read */
+  int32_t  nblk, xa_per_profile, se_full, reserved;
+  const double* d_k[4];
+  const double *d_x, *d_xa, *d_sa, *d_se, *d_y, *d_fx;
+  double* d_x_new;  uint8_t* d_status;                 /* required outputs */
+  double *d_chi2, *d_dfs, *d_post_var;  int32_t* d_nobs;   /* optional outputs */
+} mwrt_oe_step;
+int mwrt_oe_step_device(mwrt_context* ctx, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_step* s, void* stream);
+/* sizeof(mwrt_oe_step) as compiled into the library (binding self-check). */
+size_t mwrt_oe_step_size(void);
+
 /* Diagnostic: evaluates the kernels' own exp / log / division helpers (fexp, flog, fdiv, fdiv1) on
  * host arrays x[n], y_pos[n] (y > 0), so their accuracy can be checked against libm. */
 int mwrt_selftest_math(mwrt_context* ctx, int32_t n, const double* x, const double* y_pos,

@@ -58,6 +58,19 @@ class JacVariables(ctypes.Structure):
         return cls(pick(cls.HUMIDITY, humidity), pick(cls.CLOUD, cloud), pick(cls.HEIGHTS, heights), int(reserved))
 
 
+class MwrtOeStep(ctypes.Structure):
+    """include/mwrt.h mwrt_oe_step: the record of one optimal-estimation step (device pointers)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("nblk", ctypes.c_int32), ("xa_per_profile", ctypes.c_int32),
+                ("se_full", ctypes.c_int32), ("reserved", ctypes.c_int32), ("d_k", ctypes.c_void_p * 4),
+                ("d_x", ctypes.c_void_p), ("d_xa", ctypes.c_void_p), ("d_sa", ctypes.c_void_p), ("d_se", ctypes.c_void_p),
+                ("d_y", ctypes.c_void_p), ("d_fx", ctypes.c_void_p), ("d_x_new", ctypes.c_void_p),
+                ("d_status", ctypes.c_void_p), ("d_chi2", ctypes.c_void_p), ("d_dfs", ctypes.c_void_p),
+                ("d_post_var", ctypes.c_void_p), ("d_nobs", ctypes.c_void_p)]
+
+
+#: include/mwrt.h MWRT_OE_MAX_M: observations per profile of one optimal-estimation step
+OE_MAX_M = 140
+
 MWRT_VERSION = 301
 
 
@@ -108,6 +121,8 @@ SIGNATURES = {
     "mwrt_tb_jacobian_batch_vars": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp,
                                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(MwrtTbOptions),
                                                    ctypes.POINTER(JacVariables)]),
+    "mwrt_oe_step_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeStep), _vp]),
+    "mwrt_oe_step_size": (ctypes.c_size_t, []),
     "mwrt_set_absorption_mode": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_set_chunk_width": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_selftest_math": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -165,6 +180,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
             fn.restype, fn.argtypes = res, args
         if lib.mwrt_model_desc_size() != ctypes.sizeof(MwrtModelDesc):
             raise NativeLibraryMissing("mwrt_model_desc layout mismatch between libmwrt.so and spectroscopy.py")
+        if lib.mwrt_oe_step_size() != ctypes.sizeof(MwrtOeStep):
+            raise NativeLibraryMissing("mwrt_oe_step layout mismatch between libmwrt.so and _native.py")
         if lib.mwrt_version() != MWRT_VERSION:
             raise NativeLibraryMissing(f"libmwrt.so is version {lib.mwrt_version()}, this binding needs {MWRT_VERSION}: "
                                        "rebuild (python -c 'import __graft_entry__ as g; g.build()')")
@@ -506,6 +523,27 @@ class Context:
             _ptr(tb), *out, _ptr(valid), ctypes.byref(opts) if opts is not None else None,
             ctypes.byref(variables) if variables is not None else None), "mwrt_tb_jacobian_batch_vars")
         return tb, valid, jac
+
+    @_serialised
+    def oe_step_device(self, nprof, nlev, m, d_k, d_x, d_xa, d_sa, d_se, d_y, d_fx, d_x_new, d_status, d_chi2=None,
+                       d_dfs=None, d_post_var=None, d_nobs=None, xa_per_profile=False, se_full=False, stream=None,
+                       reserved=0, struct_size=None):
+        """One optimal-estimation step per profile (include/mwrt.h mwrt_oe_step_device): ``d_k`` is the sequence of the
+        1 .. 4 K-matrix blocks ``[nprof][m][nlev]`` (Jacobian outputs as they were written), the state, prior and
+        covariances as the header lays them out; ``d_x_new [nprof][nblk][nlev]`` and ``d_status [nprof]`` (uint8) are
+        required, the diagnostics optional.  ``struct_size`` (default: the whole record) is what the record claims."""
+        d_k = list(d_k)
+        rec = MwrtOeStep()
+        rec.struct_size = ctypes.sizeof(MwrtOeStep) if struct_size is None else int(struct_size)
+        rec.nblk, rec.xa_per_profile, rec.se_full, rec.reserved = len(d_k), int(bool(xa_per_profile)), int(bool(se_full)), int(reserved)
+        for b, k in enumerate(d_k[:4]):
+            rec.d_k[b] = int(k) if k is not None else None
+        opt = lambda v: int(v) if v is not None else None   # noqa: E731
+        rec.d_x, rec.d_xa, rec.d_sa, rec.d_se, rec.d_y, rec.d_fx = map(opt, (d_x, d_xa, d_sa, d_se, d_y, d_fx))
+        rec.d_x_new, rec.d_status = opt(d_x_new), opt(d_status)
+        rec.d_chi2, rec.d_dfs, rec.d_post_var, rec.d_nobs = map(opt, (d_chi2, d_dfs, d_post_var, d_nobs))
+        self._check(self._lib.mwrt_oe_step_device(self._handle, int(nprof), int(nlev), int(m), ctypes.byref(rec),
+                                                  _stream(stream)), "mwrt_oe_step_device")
 
     def layer_tau_pitch(self, nf: int) -> int:
         """Doubles between consecutive levels of a layer-optical-depth array for nf frequencies (multiple of 16)."""

@@ -4,12 +4,14 @@
 // returns 0 and mwrt_create() fails with MWRT_ERR_NO_DEVICE.
 //
 // Host code only: streams, caches, argument checks and the choice of launch.  Every kernel lives in another unit
-// (mwrt_inst.hip, mwrt_tl.hip, mwrt_aux.hip) and is reached through the launchers the two headers below declare.
+// (mwrt_inst.hip, mwrt_tl.hip, mwrt_oe.hip, mwrt_aux.hip) and is reached through the launchers the headers below declare.
 #include "mwrt_args.hip.h"
 #include "mwrt_tl.hip.h"
+#include "mwrt_oe.hip.h"
 #include "mwrt_plan.h"
 
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1097,6 +1099,46 @@ int mwrt_set_absorption_mode(mwrt_context* c, int mode) {
   if (!c || mode < 0 || mode > 2) return fail(MWRT_ERR_INVALID_ARGUMENT, "mode must be 0, 1 or 2");
   c->absorption_mode = mode;
   return MWRT_OK;
+}
+
+/* The optimal-estimation step (csrc/mwrt_oe.hip).  It takes no model, so its preamble is its own: the same order as
+ * begin_call -- arguments, then limits, then the device and the stream -- without the frequency and elevation uploads. */
+size_t mwrt_oe_step_size(void) { return sizeof(mwrt_oe_step); }
+
+int mwrt_oe_step_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_step* s, void* stream) {
+  if (!c || !s) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context or mwrt_oe_step");
+  constexpr size_t required = offsetof(mwrt_oe_step, d_status) + sizeof(uint8_t*);
+  if (s->struct_size < required)
+    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_step.struct_size too small for the required fields (through d_status)");
+  mwrt_oe_step r{};                                    // fields at or beyond the caller's struct_size stay NULL
+  // ... and so does a field the size ends inside: beyond the required part every field is one pointer
+  size_t len = s->struct_size < sizeof r ? s->struct_size : sizeof r;
+  len -= (len - required) % sizeof(void*);
+  std::memcpy(&r, s, len);
+  if (nprof < 0 || nlev < 1 || m < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "nprof < 0, nlev < 1 or m < 1");
+  if (r.nblk < 1 || r.nblk > 4) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_step.nblk must be 1 .. 4");
+  if (r.reserved != 0) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_step.reserved must be 0");
+  bool buffers = r.d_x && r.d_xa && r.d_sa && r.d_se && r.d_y && r.d_fx && r.d_x_new && r.d_status;
+  for (int b = 0; b < r.nblk; ++b) buffers = buffers && r.d_k[b];
+  if (!buffers) return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
+  if (nlev > MWRT_MAX_LEVELS)
+    return fail(MWRT_ERR_UNSUPPORTED, "nlev > MWRT_MAX_LEVELS (" + std::to_string(MWRT_MAX_LEVELS) + ")");
+  if (m > MWRT_OE_MAX_M)
+    return fail(MWRT_ERR_UNSUPPORTED, "m > MWRT_OE_MAX_M (" + std::to_string(MWRT_OE_MAX_M) + " observations per profile: G lives in LDS)");
+  if (nprof > 2147483647LL) return fail(MWRT_ERR_UNSUPPORTED, "nprof exceeds grid limit");
+  oe::OeArgs a{};
+  a.k0 = r.d_k[0]; a.k1 = r.nblk > 1 ? r.d_k[1] : nullptr; a.k2 = r.nblk > 2 ? r.d_k[2] : nullptr;
+  a.k3 = r.nblk > 3 ? r.d_k[3] : nullptr;
+  a.x = r.d_x; a.xa = r.d_xa; a.sa = r.d_sa; a.se = r.d_se; a.y = r.d_y; a.fx = r.d_fx;
+  a.x_new = r.d_x_new; a.chi2 = r.d_chi2; a.dfs = r.d_dfs; a.post_var = r.d_post_var; a.nobs = r.d_nobs; a.status = r.d_status;
+  a.nblk = r.nblk; a.nlev = nlev; a.m = m; a.n = r.nblk * nlev;
+  a.xa_per_profile = r.xa_per_profile != 0; a.se_full = r.se_full != 0;
+  if (oe::lds_plan(m, a.n).total_bytes > (size_t)c->lds_max)
+    return fail(MWRT_ERR_UNSUPPORTED, "the optimal-estimation step needs more LDS than this device has per workgroup");
+  if (nprof == 0) return MWRT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = resolve_stream(c, stream);
+  return timed(c, st, [&] { return oe::launch_oe_step(a, nprof, st); });
 }
 
 int mwrt_selftest_math(mwrt_context* c, int32_t n, const double* x, const double* y_pos,

@@ -1,0 +1,193 @@
+"""Optimal-estimation (1D-Var) retrieval on the device: the K-matrix call and the Gauss-Newton update
+(include/mwrt.h ``mwrt_oe_step_device``) back to back on one stream.
+
+    ov = OneDVar("R24", frq, elev, sa, se, variables=JacVariables.of(humidity="rh"), blocks=("t", "h"), xa=xa)
+    x_new, diag = ov.step(z, p, x, y)            # one K-matrix call + one update, nothing leaves the device
+    res = ov.retrieve(z, p, y)                   # iterate from xa until every profile has converged
+
+The state ``x`` is ``[nprof][nblk][nlev]`` (float64, CUDA, levels ground -> top) with the blocks in the order given:
+``"t"`` temperature [K], ``"h"`` humidity in the variable ``variables.humidity`` names (e [hPa], rh [fraction] or ppmv),
+then optionally ``"liq"`` and ``"ice"`` in ``variables.cloud`` (g m-3 or kg/kg).  ``y`` is ``[nprof][nang][nf]`` (or
+``[nprof][m]``); a NaN in it drops that observation.  ``sa`` is ``[n][n]`` with n = nblk * nlev, ``se`` ``[m]`` variances or
+``[m][m]``, ``xa`` ``[nblk][nlev]`` shared or ``[nprof][nblk][nlev]``.  With ``variables.heights = "hydrostatic"`` the heights
+are rebuilt from the state before every forward run (the rule of mwrt_jac_variables, anchored at ``z[:, 0]``); otherwise
+``z`` is used as passed.
+
+The update is linear around x: Levenberg-Marquardt damping, the n-form and log-humidity states are not offered."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _native
+from ._native import JacVariables
+from .autodiff import goff_gratch_es
+
+
+def _native_k_matrix(model, z, p, t, rh, denliq, denice, frq, elev, variables, want, stream):
+    """One ``mwrt_tb_jacobian_batch_vars_device`` call -> (tb [nprof][nang][nf], valid, {block: K rows [nprof][nang][nf][nlev]}).
+
+    The single place the K-matrix of this module reaches the native library: CPU tests substitute a stand-in here."""
+    nprof, nlev = z.shape
+    opts = dict(dtype=torch.float64, device=z.device)
+    tb = torch.empty((nprof, elev.size, frq.size), **opts)
+    rows = {b: torch.empty((nprof, elev.size, frq.size, nlev), **opts) for b in want}
+    valid = torch.empty(nprof, dtype=torch.uint8, device=z.device)
+    ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
+    _native.default_context(z.device.index or 0).tb_jacobian_batch_vars_device(
+        model, nprof, nlev, z.data_ptr(), p.data_ptr(), t.data_ptr(), rh.data_ptr(), frq, elev, tb.data_ptr(),
+        rows["t"].data_ptr(), rows["h"].data_ptr(), valid.data_ptr(), d_denliq=ptr(denliq), d_denice=ptr(denice),
+        d_dtb_dliq=ptr(rows.get("liq")), d_dtb_dice=ptr(rows.get("ice")), variables=variables, stream=stream)
+    return tb, valid, rows
+
+
+def _native_oe_step(k_blocks, x, xa, sa, se, y, fx, want_post_var, stream):
+    """One ``mwrt_oe_step_device`` call -> dict(x_new, status, chi2, dfs, nobs, post_var or None).
+
+    The single place the update reaches the native library: CPU tests substitute the NumPy reference here."""
+    nprof, nblk, nlev = x.shape
+    m = y.shape[1]
+    opts = dict(dtype=torch.float64, device=x.device)
+    out = dict(x_new=torch.empty_like(x), status=torch.empty(nprof, dtype=torch.uint8, device=x.device),
+               chi2=torch.empty(nprof, **opts), dfs=torch.empty(nprof, **opts),
+               nobs=torch.empty(nprof, dtype=torch.int32, device=x.device),
+               post_var=torch.empty_like(x) if want_post_var else None)
+    _native.default_context(x.device.index or 0).oe_step_device(
+        nprof, nlev, m, [k.data_ptr() for k in k_blocks], x.data_ptr(), xa.data_ptr(), sa.data_ptr(), se.data_ptr(),
+        y.data_ptr(), fx.data_ptr(), out["x_new"].data_ptr(), out["status"].data_ptr(), d_chi2=out["chi2"].data_ptr(),
+        d_dfs=out["dfs"].data_ptr(), d_post_var=None if out["post_var"] is None else out["post_var"].data_ptr(),
+        d_nobs=out["nobs"].data_ptr(), xa_per_profile=xa.dim() == 3, se_full=se.dim() == 2, stream=stream)
+    return out
+
+
+@dataclass
+class Retrieval:
+    """What ``OneDVar.retrieve`` returns; every field is a tensor on the state's device."""
+    x: torch.Tensor            # [nprof][nblk][nlev] the retrieved state
+    chi2: torch.Tensor         # [nprof] d^T G^-1 d of each profile's last step
+    dfs: torch.Tensor          # [nprof] degrees of freedom for signal
+    post_var: torch.Tensor     # [nprof][nblk][nlev] diagonal of the posterior covariance
+    status: torch.Tensor       # [nprof] uint8, mwrt_oe_step_device's status of the last step
+    nobs: torch.Tensor         # [nprof] int32 observations used
+    iterations: torch.Tensor   # [nprof] int32 steps taken before the profile was frozen
+    converged: torch.Tensor    # [nprof] bool
+
+
+class OneDVar:
+    def __init__(self, model, frq, elev, sa, se, variables: Optional[JacVariables] = None, blocks=("t", "h"), xa=None):
+        blocks = tuple(blocks)
+        if blocks[:2] != ("t", "h") or blocks[2:] not in ((), ("liq",), ("ice",), ("liq", "ice")):
+            raise ValueError(f"blocks must be ('t', 'h') followed by 'liq' and / or 'ice' in that order, got {blocks}")
+        self.model, self.blocks = model, blocks
+        self.frq = np.ascontiguousarray(frq, dtype=np.float64).ravel()
+        self.elev = np.ascontiguousarray(elev, dtype=np.float64).ravel()
+        self.variables = variables if variables is not None else JacVariables.of()
+        if xa is None:
+            raise ValueError("xa (the prior state) is required")
+        self.sa, self.se, self.xa = sa.contiguous(), se.contiguous(), xa.contiguous()
+        self.m = self.frq.size * self.elev.size
+        nblk = len(blocks)
+        if self.xa.dim() not in (2, 3) or self.xa.shape[-2] != nblk:
+            raise ValueError(f"xa: expected [{nblk}][nlev] or [nprof][{nblk}][nlev], got {tuple(self.xa.shape)}")
+        n = nblk * self.xa.shape[-1]
+        if tuple(self.sa.shape) != (n, n):
+            raise ValueError(f"sa: expected [{n}][{n}], got {tuple(self.sa.shape)}")
+        if tuple(self.se.shape) not in ((self.m,), (self.m, self.m)):
+            raise ValueError(f"se: expected [{self.m}] or [{self.m}][{self.m}], got {tuple(self.se.shape)}")
+        self._sigma = torch.sqrt(torch.diagonal(self.sa)).reshape(nblk, -1)
+
+    # -- the state in the operator's inputs -----------------------------------------------------------------------------
+    def physical(self, z, p, x):
+        """(z, t, rh, denliq, denice) the forward operator takes for the state ``x`` (cloud arrays None when not a block)."""
+        v = self.variables
+        t = x[:, 0].contiguous()
+        h = x[:, 1]
+        es = goff_gratch_es(t)[0]
+        e = h if v.humidity == 0 else h * es if v.humidity == 1 else h * p / 1e6
+        rh = (e / es).contiguous()
+        cloud = {}
+        for b in ("liq", "ice"):
+            if b in self.blocks:
+                q = x[:, self.blocks.index(b)]
+                cloud[b] = (q * 1000.0 * (100.0 * p / (287.06 * t)) if v.cloud == 1 else q).contiguous()
+        if v.heights == 1:
+            tv = t * (1.0 + 0.608 * (0.622 * e / (p - 0.378 * e)))
+            dz = (287.04 / 9.80665) * 0.5 * (tv[:, 1:] + tv[:, :-1]) * torch.log(p[:, :-1] / p[:, 1:]) / 1000.0
+            z = torch.cat([z[:, :1], z[:, :1] + torch.cumsum(dz, dim=1)], dim=1).contiguous()
+        return z, t, rh, cloud.get("liq"), cloud.get("ice")
+
+    def clamp(self, x):
+        """Humidity and cloud are kept >= 0 (the linear update knows no such bound)."""
+        x = x.clone()
+        for i, b in enumerate(self.blocks):
+            if b != "t":
+                x[:, i].clamp_(min=0.0)
+        return x
+
+    # -- one Gauss-Newton step ---------------------------------------------------------------------------------------
+    def forward(self, z, p, x):
+        """The forward model at the state ``x``: ``(tb [nprof][nang][nf], valid [nprof])`` on torch's current stream (the
+        K-matrix call's TBs; its rows are discarded)."""
+        zz, t, rh, dl, di = self.physical(z, p, x)
+        tb, valid, _ = _native_k_matrix(self.model, zz.contiguous(), p.contiguous(), t, rh, dl, di, self.frq, self.elev,
+                                        self.variables, self.blocks, self._stream(x))
+        return tb, valid
+
+    @staticmethod
+    def _stream(x):
+        return torch.cuda.current_stream(x.device).cuda_stream if x.is_cuda else None
+
+    def step(self, z, p, x, y, post_var=True):
+        """One K-matrix call at ``x`` plus one update, both queued on torch's current stream -- the stream the change of
+        variables and the allocations of this method run on too (use ``torch.cuda.stream(...)`` around the call for another).
+        Returns ``(x_new, diagnostics)``: diagnostics holds ``status``, ``chi2``, ``dfs``, ``nobs``, ``post_var`` (None with
+        ``post_var=False``), ``fx`` (the forward model at x, [nprof][m]) and ``valid`` (the K-matrix call's flags).
+        ``x_new`` is the raw update: ``retrieve`` clamps it."""
+        stream = self._stream(x)
+        nprof = x.shape[0]
+        zz, t, rh, dl, di = self.physical(z, p, x)
+        tb, valid, rows = _native_k_matrix(self.model, zz.contiguous(), p.contiguous(), t, rh, dl, di, self.frq, self.elev,
+                                           self.variables, self.blocks, stream)
+        fx = tb.reshape(nprof, self.m)
+        out = _native_oe_step([rows[b] for b in self.blocks], x.contiguous(), self.xa, self.sa, self.se,
+                              y.reshape(nprof, self.m).contiguous(), fx, post_var, stream)
+        x_new = out.pop("x_new")
+        out["fx"], out["valid"] = fx, valid
+        return x_new, out
+
+    def retrieve(self, z, p, y, x0=None, max_iter=10, tol=0.05) -> Retrieval:
+        """Iterates ``step`` from ``x0`` (default: the prior).  After every step humidity and cloud are clamped to >= 0.  A
+        profile is frozen -- its state and diagnostics no longer change -- once max |x_new - x| / sqrt(diag Sa) < ``tol``
+        over its whole state, or when its step fails (status 0 or 2: the state before that step is kept).  Only the scalar
+        "is any profile still moving" leaves the device, once per iteration.  Every step asks for ``post_var`` (a profile may
+        freeze at any step), which about doubles the update's device time."""
+        nprof = y.shape[0]
+        x = (self.xa.expand(nprof, -1, -1) if self.xa.dim() == 2 else self.xa).clone() if x0 is None else x0.clone()
+        dev = x.device
+        active = torch.ones(nprof, dtype=torch.bool, device=dev)
+        converged = torch.zeros(nprof, dtype=torch.bool, device=dev)
+        iters = torch.zeros(nprof, dtype=torch.int32, device=dev)
+        keep = None
+        for _ in range(int(max_iter)):
+            x_new, d = self.step(z, p, x, y, post_var=True)
+            ok = (d["status"] == 1) | (d["status"] == 3)
+            x_new = self.clamp(torch.where(ok[:, None, None], x_new, x))
+            move = ((x_new - x).abs() / self._sigma).amax(dim=(1, 2))
+            upd = active
+            iters = iters + upd.to(torch.int32)
+            x = torch.where(upd[:, None, None], x_new, x)
+            diag = {k: d[k] for k in ("chi2", "dfs", "post_var", "status", "nobs")}
+            if keep is None:
+                keep = diag
+            else:
+                keep = {k: torch.where(upd.reshape((-1,) + (1,) * (v.dim() - 1)), v, keep[k]) for k, v in diag.items()}
+            done = upd & ((move < tol) | ~ok)
+            converged = converged | (upd & ok & (move < tol))
+            active = active & ~done
+            if not bool(active.any()):
+                break
+        return Retrieval(x=x, chi2=keep["chi2"], dfs=keep["dfs"], post_var=keep["post_var"], status=keep["status"],
+                         nobs=keep["nobs"], iterations=iters, converged=converged)

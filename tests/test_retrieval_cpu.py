@@ -1,0 +1,187 @@
+"""Host logic of retrieval.OneDVar without a GPU: the two places the module reaches the native library are replaced in
+this file -- the K-matrix call by a small (optionally mildly non-linear) forward model on CPU tensors, the update by the
+NumPy reference of tests/oe_reference.py.  What is checked is the module's own work: block ordering, the change from
+state to operator inputs, clamping, per-profile freezing, and that a linear problem lands on the analytic posterior
+mean in one step."""
+import numpy as np
+import pytest
+
+import oe_reference as oer
+
+torch = pytest.importorskip("torch")
+
+from mwr_fast_forward_operators_and_lbls_amd import retrieval  # noqa: E402
+from mwr_fast_forward_operators_and_lbls_amd._native import JacVariables  # noqa: E402
+
+NPROF, NLEV, NANG, NF = 3, 6, 2, 3
+M = NANG * NF
+FRQ, ELEV = np.array([22.24, 31.4, 53.86]), np.array([90.0, 30.0])
+
+
+class Standins:
+    """F = F0 + sum_b A_b . v_b + curve * (sum_b A_b . v_b)^2 with v = (t - 270, rh, denliq, denice); K = dF/dv."""
+
+    def __init__(self, monkeypatch, curve=0.0, seed=3):
+        rng = np.random.default_rng(seed)
+        self.A = {b: torch.as_tensor(rng.uniform(0.2, 1.0, (M, NLEV)) * s)
+                  for b, s in (("t", 0.3), ("h", 8.0), ("liq", 20.0), ("ice", 5.0))}
+        self.curve = curve
+        self.calls, self.k_seen = [], []
+        monkeypatch.setattr(retrieval, "_native_k_matrix", self.k_matrix)
+        monkeypatch.setattr(retrieval, "_native_oe_step", self.oe_step)
+
+    def forward(self, t, rh, dl=None, di=None):
+        lin = (t - 270.0) @ self.A["t"].T + rh @ self.A["h"].T
+        if dl is not None:
+            lin = lin + dl @ self.A["liq"].T
+        if di is not None:
+            lin = lin + di @ self.A["ice"].T
+        return 250.0 + lin + self.curve * lin ** 2, lin
+
+    def k_matrix(self, model, z, p, t, rh, denliq, denice, frq, elev, variables, want, stream):
+        self.calls.append(dict(want=tuple(want), z=z.clone(), t=t.clone(), rh=rh.clone(), denliq=denliq, denice=denice))
+        tb, lin = self.forward(t, rh, denliq, denice)
+        slope = 1.0 + 2.0 * self.curve * lin                              # [nprof][m]
+        rows = {b: (slope[:, :, None] * self.A[b][None]).reshape(-1, NANG, NF, NLEV).contiguous() for b in want}
+        return tb.reshape(-1, NANG, NF), torch.ones(t.shape[0], dtype=torch.uint8), rows
+
+    def oe_step(self, k_blocks, x, xa, sa, se, y, fx, want_post_var, stream):
+        self.k_seen.append([k.clone() for k in k_blocks])
+        nprof, nblk, nlev = x.shape
+        ref = oer.oe_step_reference([k.numpy().reshape(nprof, M, nlev) for k in k_blocks], x.numpy(), xa.numpy(), sa.numpy(),
+                                    se.numpy(), y.numpy(), fx.numpy())
+        out = {k: torch.as_tensor(ref[k]) for k in ("x_new", "status", "chi2", "dfs", "nobs", "post_var")}
+        if not want_post_var:
+            out["post_var"] = None
+        return out
+
+
+def setup(blocks, nprof=NPROF, seed=1):
+    rng = np.random.default_rng(seed)
+    nblk = len(blocks)
+    sig = np.array([2.0, 0.1, 0.05, 0.02])[:nblk]
+    lev = np.arange(NLEV)
+    corr = np.exp(-np.abs(lev[:, None] - lev[None, :]) / 2.0)
+    sa = np.zeros((nblk * NLEV, nblk * NLEV))
+    for b in range(nblk):
+        sa[b * NLEV:(b + 1) * NLEV, b * NLEV:(b + 1) * NLEV] = sig[b] ** 2 * corr
+    se = np.full(M, 0.25)
+    xa = np.stack([np.linspace(285, 250, NLEV), np.linspace(0.7, 0.2, NLEV), np.full(NLEV, 0.1), np.full(NLEV, 0.05)])[:nblk]
+    z = torch.as_tensor(np.tile(np.linspace(0.1, 8.0, NLEV), (nprof, 1)))
+    p = torch.as_tensor(np.tile(1000.0 * np.exp(-np.linspace(0.1, 8.0, NLEV) / 8.0), (nprof, 1)))
+    x_true = xa[None] + rng.standard_normal((nprof, nblk, NLEV)) * sig[None, :, None] * 0.5
+    return dict(sa=sa, se=se, xa=xa, z=z, p=p, x_true=torch.as_tensor(x_true), sig=sig)
+
+
+def make(blocks, s, **kw):
+    return retrieval.OneDVar("R24", FRQ, ELEV, torch.as_tensor(s["sa"]), torch.as_tensor(s["se"]),
+                             variables=kw.pop("variables", JacVariables.of(humidity="rh")), blocks=blocks,
+                             xa=torch.as_tensor(s["xa"]), **kw)
+
+
+def test_blocks_reach_the_update_in_state_order(monkeypatch):
+    st = Standins(monkeypatch)
+    blocks = ("t", "h", "liq", "ice")
+    s = setup(blocks)
+    ov = make(blocks, s)
+    y = torch.full((NPROF, NANG, NF), 255.0)
+    x_new, d = ov.step(s["z"], s["p"], s["x_true"], y)
+    assert st.calls[0]["want"] == blocks
+    for got, b in zip(st.k_seen[0], blocks):                             # K = [K_t | K_h | K_liq | K_ice]
+        assert torch.equal(got.reshape(NPROF, M, NLEV), st.A[b][None].expand(NPROF, -1, -1))
+    # the operator received the state's own blocks: T, rh (= h for humidity "rh", to rounding), densities as they are
+    c = st.calls[0]
+    assert torch.equal(c["t"], s["x_true"][:, 0]) and torch.allclose(c["rh"], s["x_true"][:, 1], rtol=1e-14, atol=0)
+    assert torch.equal(c["denliq"], s["x_true"][:, 2]) and torch.equal(c["denice"], s["x_true"][:, 3])
+    assert torch.equal(c["z"], s["z"])                                   # heights fixed: z as passed
+    assert x_new.shape == (NPROF, 4, NLEV) and d["fx"].shape == (NPROF, M) and d["status"].tolist() == [1] * NPROF
+    for bad in (("h", "t"), ("t",), ("t", "h", "ice", "liq"), ("t", "h", "x")):
+        with pytest.raises(ValueError):
+            make(bad, setup(("t", "h")))
+
+
+def test_state_variables_are_changed_to_operator_inputs(monkeypatch):
+    st = Standins(monkeypatch)
+    blocks = ("t", "h", "liq")
+    s = setup(blocks)
+    x = s["x_true"].clone()
+    x[:, 1] = x[:, 1] * 8000.0                                           # ppmv
+    x[:, 2] = 1e-4                                                       # kg/kg
+    ov = make(blocks, s, variables=JacVariables.of(humidity="ppmv", cloud="kg/kg", heights="hydrostatic"))
+    ov.step(s["z"], s["p"], x, torch.full((NPROF, M), 255.0))
+    c = st.calls[0]
+    from mwr_fast_forward_operators_and_lbls_amd.autodiff import goff_gratch_es
+    t, p = x[:, 0], s["p"]
+    e = x[:, 1] * p / 1e6
+    assert torch.allclose(c["rh"], e / goff_gratch_es(t)[0], rtol=1e-14, atol=0)
+    assert torch.allclose(c["denliq"], 1e-4 * 1000.0 * 100.0 * p / (287.06 * t), rtol=1e-14, atol=0)
+    tv = t * (1 + 0.608 * 0.622 * e / (p - 0.378 * e))
+    dz = 287.04 / 9.80665 * 0.5 * (tv[:, 1:] + tv[:, :-1]) * torch.log(p[:, :-1] / p[:, 1:]) / 1000.0
+    assert torch.equal(c["z"][:, 0], s["z"][:, 0]) and torch.allclose(c["z"][:, 1:] - c["z"][:, :-1], dz, rtol=1e-12, atol=0)
+
+
+def test_linear_problem_reaches_the_posterior_mean_in_one_step(monkeypatch):
+    st = Standins(monkeypatch)
+    blocks = ("t", "h")
+    s = setup(blocks)
+    ov = make(blocks, s)
+    y = st.forward(s["x_true"][:, 0], s["x_true"][:, 1])[0] + 0.3 * torch.as_tensor(np.random.default_rng(9).standard_normal((NPROF, M)))
+    K = torch.cat([st.A["t"], st.A["h"]], dim=1).numpy()
+    xa = s["xa"].reshape(-1)
+    fxa = st.forward(torch.as_tensor(s["xa"][None, 0]), torch.as_tensor(s["xa"][None, 1]))[0].numpy()[0]
+    post = np.linalg.inv(K.T @ K / 0.25 + np.linalg.inv(s["sa"]))
+    want = xa[None] + (y.numpy() - fxa[None]) @ (post @ K.T / 0.25).T
+    x0 = s["x_true"] + 0.3                                               # wherever the step starts from
+    x_new, d = ov.step(s["z"], s["p"], x0, y.reshape(NPROF, NANG, NF))
+    assert np.abs(x_new.numpy().reshape(NPROF, -1) - want).max() <= 1e-10 * np.abs(want - xa[None]).max()
+    assert np.abs(d["post_var"].numpy().reshape(NPROF, -1) - np.diag(post)[None]).max() <= 1e-10 * np.diag(s["sa"]).max()
+    res = ov.retrieve(s["z"], s["p"], y, max_iter=5, tol=1e-6)
+    assert res.iterations.tolist() == [2] * NPROF and res.converged.all()      # the second step confirms the first
+    assert np.abs(res.x.numpy().reshape(NPROF, -1) - want).max() <= 1e-9 * np.abs(want - xa[None]).max()
+    assert len(st.calls) == 1 + 2
+
+
+def test_humidity_and_cloud_are_clamped_after_every_step(monkeypatch):
+    st = Standins(monkeypatch)
+    blocks = ("t", "h", "liq")
+    s = setup(blocks)
+    s["xa"][1] = 0.01                                                    # a dry prior with a wide variance ...
+    s["xa"][2] = 0.0
+    ov = make(blocks, s)
+    y = torch.full((NPROF, M), 200.0)                                    # ... and observations far colder than it explains
+    raw, _ = ov.step(s["z"], s["p"], torch.as_tensor(np.broadcast_to(s["xa"], (NPROF, 3, NLEV)).copy()), y)
+    assert (raw[:, 1] < 0).any() and (raw[:, 2] < 0).any()               # step returns the raw update
+    res = ov.retrieve(s["z"], s["p"], y, max_iter=3, tol=1e-9)
+    assert (res.x[:, 1] >= 0).all() and (res.x[:, 2] >= 0).all() and (res.x[:, 1:] == 0).any()
+    assert (res.x[:, 0] != torch.as_tensor(s["xa"][0])).any()            # temperature is not clamped
+    for c in st.calls[2:]:                                               # every forward run after the first saw the clamped state
+        assert (c["rh"] >= 0).all() and (c["denliq"] >= 0).all()
+
+
+def test_profiles_freeze_one_by_one(monkeypatch):
+    st = Standins(monkeypatch, curve=2e-3)
+    blocks = ("t", "h")
+    s = setup(blocks, nprof=4)
+    ov = make(blocks, s)
+    x_true = s["x_true"].clone()
+    x_true[0] = torch.as_tensor(s["xa"])                                 # profile 0 starts at its answer
+    x_true[3] = torch.as_tensor(s["xa"]) + torch.as_tensor(s["sig"][:, None]) * 2.5     # profile 3 far from the prior
+    y = st.forward(x_true[:, 0], x_true[:, 1])[0]
+    y[2, 4] = float("nan")                                               # a missing observation on the way
+    res = ov.retrieve(s["z"], s["p"], y, max_iter=12, tol=1e-3)
+    it = res.iterations.tolist()
+    print("iterations per profile:", it)
+    assert res.converged.all() and it[0] == 1 and it[3] > it[0] and max(it) < 12
+    assert res.nobs.tolist() == [M, M, M - 1, M]
+    assert torch.equal(res.x[0], torch.as_tensor(s["xa"]))
+    # a frozen profile keeps the state and the diagnostics of the step that froze it, whatever the others still do
+    for i, n in enumerate(it):
+        short = ov.retrieve(s["z"], s["p"], y, max_iter=n, tol=1e-3)
+        assert torch.equal(short.x[i], res.x[i]) and short.chi2[i] == res.chi2[i] and short.dfs[i] == res.dfs[i]
+        assert torch.equal(short.post_var[i], res.post_var[i]) and bool(short.converged[i])
+    # a failed step (state not finite) freezes the profile where it stood
+    x0 = torch.as_tensor(np.broadcast_to(s["xa"], (4, 2, NLEV)).copy())
+    x0[1, 0, 2] = float("nan")
+    res = ov.retrieve(s["z"], s["p"], y, x0=x0, max_iter=4, tol=1e-3)
+    assert res.status.tolist()[1] == 0 and res.iterations.tolist()[1] == 1 and not bool(res.converged[1])
+    assert torch.equal(res.x[1].isnan(), x0[1].isnan()) and bool(res.converged[0])
