@@ -304,11 +304,26 @@ int mwrt_tb_from_layer_tau_device(mwrt_context* ctx, const mwrt_model* model,
  *   dtb_dt   K/K      d TB / d T_i       at fixed vapour pressure e_i, pressure and heights
  *   dtb_de   K/hPa    d TB / d e_i       (e = rh * es(T), Goff-Gratch) at fixed T_i
  *   dtb_ddz  K/km     d TB / d (z_i - z_{i-1})   thickness of the layer below level i (entry 0 = 0)
- * The absorption of a level is a local function of (p, T, e): its derivatives are central differences of five
- * evaluations per level (T +- 0.01 K, e (1 +- 1e-4)); the layer rule (exponential_integration), the Planck-space recursion
- * and bright() are differentiated analytically (adjoint), so the cost is ~6 forward runs whatever nlev -- not the
- * 3 nlev + 1 forward runs of a brute-force K-matrix.  Clear sky, plane-parallel.  HOST buffers, synchronous; tb_out as
- * mwrt_tb_batch; valid_out as there (0 / 2: that profile's outputs are NaN). */
+ * Clear sky, plane-parallel.  HOST buffers, synchronous; tb_out as mwrt_tb_batch; valid_out as there (0 / 2: that
+ * profile's outputs are NaN).
+ * This is the tangent-linear path of the device K-matrix (below) on host buffers: exactly
+ * mwrt_tb_jacobian_batch_vars with options = NULL, vars = NULL, no cloud rows and dtb_ddz required -- one implementation,
+ * the same bits.  The absorption derivatives are exact (mwrt_absorption_tl_batch_device), the layer rule
+ * (exponential_integration), the Planck-space recursion and bright() are differentiated analytically (adjoint), so the
+ * cost is a few forward runs whatever nlev -- not the 3 nlev + 1 forward runs of a brute-force K-matrix.
+ * Until the device path replaced it, this entry differenced the absorption (T +- 0.01 K, e (1 +- 1e-4)) in a kernel of
+ * its own.  What moved when that kernel was retired (MWRT_VERSION stays 301: symbol, signature, units, layouts and status
+ * codes are unchanged):
+ *   values     dtb_dt and dtb_de are the exact derivative instead of a central difference of it: they moved by the old
+ *              step error, <= 2e-5 of a row (<= 1e-3 of a row where the e-step sat at its 1e-7 hPa floor, and arbitrary
+ *              where +- 0.01 K straddled a branch of the absorption); dtb_ddz and tb_out moved by rounding only;
+ *   mode       independent of mwrt_set_absorption_mode, like every K-matrix entry (under forced mode 2 a short frequency
+ *              list used to be MWRT_ERR_UNSUPPORTED here; now it computes);
+ *   memory     no profile batching: everything is staged at once (inputs, tb and three rows in a buffer of the call's
+ *              own, freed on return) next to the context's workspace of 48 B per (profile, frequency, level), which stays
+ *              allocated; nprof * nf > 2^31 - 1 is MWRT_ERR_UNSUPPORTED, as for mwrt_tb_jacobian_batch_vars;
+ *   nprof = 0  returns MWRT_OK once sizes and pointers are checked, as mwrt_tb_jacobian_batch_vars does (a NaN frequency
+ *              used to be looked for first). */
 int mwrt_tb_jacobian_batch(mwrt_context* ctx, const mwrt_model* model,
                            int64_t nprof, int32_t nlev,
                            const double* z_km, const double* p_hpa, const double* t_k, const double* rh_frac,
@@ -331,8 +346,9 @@ int mwrt_absorption_tl_batch_device(mwrt_context* ctx, const mwrt_model* model, 
                                     double* d_awet, double* d_adry, double* d_dawet_dt, double* d_dawet_de,
                                     double* d_dadry_dt, double* d_dadry_de, void* stream);
 
-/* mwrt_tb_jacobian_batch on caller-owned HBM: the same outputs, layouts, units and valid flags, computed from the
- * tangent-linear absorption above and the adjoint of the layer rule + RTE (no finite differences).  DEVICE buffers
+/* The K-matrix on caller-owned HBM -- what mwrt_tb_jacobian_batch stages its host buffers into: the same outputs,
+ * layouts, units and valid flags, computed from the tangent-linear absorption above and the adjoint of the layer rule +
+ * RTE (no finite differences).  DEVICE buffers
  * (d_tb [nprof][nang][nf], d_dtb_* [nprof][nang][nf][nlev], d_valid [nprof]), asynchronous on `stream`; frq_ghz and
  * elev_deg are host arrays as for the other *_device entries.  Everything is decided on the device: a profile with a NaN
  * in z / p / T / rh (valid 0) or a negative absorption coefficient (valid 2) has NaN TBs and NaN Jacobian rows; a NaN

@@ -207,6 +207,23 @@ def _ptr(x):
     return x.ctypes.data_as(ctypes.c_void_p) if isinstance(x, np.ndarray) else ctypes.c_void_p(int(x))
 
 
+def _profile_args(z, p, t, rh, frq, elev):
+    """What the host-buffer entries share: contiguous [nprof][nlev] profiles and flat frequency / elevation lists."""
+    z = _f64(z)
+    if z.ndim != 2:
+        raise ValueError("profiles must be [nprof][nlev]")
+    return z, _f64(p, z.shape, "p"), _f64(t, z.shape, "t"), _f64(rh, z.shape, "rh"), _f64(frq).ravel(), _f64(elev).ravel()
+
+
+def _options(denliq=None, denice=None, ray_tracing=False, o3n=None):
+    """The ``MwrtTbOptions`` of the opt-in physics (NumPy arrays, which the caller keeps alive, or device addresses), or
+    None when nothing is opted into."""
+    if denliq is None and denice is None and not ray_tracing and o3n is None:
+        return None
+    addr = lambda x: None if x is None else x.ctypes.data if isinstance(x, np.ndarray) else int(x)   # noqa: E731
+    return MwrtTbOptions(addr(denliq), addr(denice), int(bool(ray_tracing)), 0, addr(o3n))
+
+
 #: include/mwrt.h MWRT_STREAM_LEGACY: the caller's legacy default stream (hipStream_t 0)
 STREAM_LEGACY = ctypes.c_void_p(-1).value
 
@@ -299,12 +316,8 @@ class Context:
         ``denliq`` / ``denice`` ([nprof][nlev], g m-3), ``ray_tracing`` and ``o3n`` ([nprof][nlev], molecules m-3; the
         model must carry an extra-species line table) are the opt-in physics of ``mwrt_tb_options``; left at their
         defaults the call is the reference's clear-sky plane-parallel path."""
-        z = _f64(z)
-        if z.ndim != 2:
-            raise ValueError("profiles must be [nprof][nlev]")
+        z, p, t, rh, frq, elev = _profile_args(z, p, t, rh, frq, elev)
         nprof, nlev = z.shape
-        p, t, rh = _f64(p, z.shape, "p"), _f64(t, z.shape, "t"), _f64(rh, z.shape, "rh")
-        frq, elev = _f64(frq).ravel(), _f64(elev).ravel()
         nf, nang = frq.size, elev.size
         tb = np.empty((nprof, nang, nf))
         valid = np.empty(nprof, dtype=np.uint8)
@@ -314,13 +327,10 @@ class Context:
             ex["taulay"] = np.empty((nprof, nf, nlev))
             exs = MwrtTbExtras(*[ex[k].ctypes.data for k in ("tbatm", "tmr", "tauwet", "taudry", "taulay", "tauliq",
                                                               "tauice")])
-        opts = None
-        if denliq is not None or denice is not None or ray_tracing or o3n is not None:
-            dl = None if denliq is None else _f64(denliq, z.shape, "denliq")
-            di = None if denice is None else _f64(denice, z.shape, "denice")
-            do3 = None if o3n is None else _f64(o3n, z.shape, "o3n")
-            opts = MwrtTbOptions(dl.ctypes.data if dl is not None else None, di.ctypes.data if di is not None else None,
-                                 int(bool(ray_tracing)), 0, do3.ctypes.data if do3 is not None else None)
+        dl = None if denliq is None else _f64(denliq, z.shape, "denliq")
+        di = None if denice is None else _f64(denice, z.shape, "denice")
+        do3 = None if o3n is None else _f64(o3n, z.shape, "o3n")
+        opts = _options(dl, di, ray_tracing, do3)
         self._check(self._lib.mwrt_tb_batch_opt(
             self._handle, self.model(model), nprof, nlev, _ptr(z), _ptr(p), _ptr(t), _ptr(rh),
             nf, _ptr(frq), nang, _ptr(elev), _ptr(tb), _ptr(valid),
@@ -331,12 +341,8 @@ class Context:
     @_serialised
     def tb_batch_multi(self, models, z, p, t, rh, frq, elev):
         """Several models over the same profiles in ONE launch: tb [nmodels][nprof][nang][nf], valid [nmodels][nprof]."""
-        z = _f64(z)
-        if z.ndim != 2:
-            raise ValueError("profiles must be [nprof][nlev]")
+        z, p, t, rh, frq, elev = _profile_args(z, p, t, rh, frq, elev)
         nprof, nlev = z.shape
-        p, t, rh = _f64(p, z.shape, "p"), _f64(t, z.shape, "t"), _f64(rh, z.shape, "rh")
-        frq, elev = _f64(frq).ravel(), _f64(elev).ravel()
         handles = (ctypes.c_void_p * len(models))(*[self.model(m) for m in models])
         tb = np.empty((len(models), nprof, elev.size, frq.size))
         valid = np.empty((len(models), nprof), dtype=np.uint8)
@@ -370,22 +376,11 @@ class Context:
 
     @_serialised
     def tb_jacobian_batch(self, model, z, p, t, rh, frq, elev):
-        """K-matrix in one call (include/mwrt.h mwrt_tb_jacobian_batch): returns ``tb [nprof][nang][nf]``, ``valid`` and a
-        dict of ``dtb_dt`` [K/K at fixed e], ``dtb_de`` [K/hPa], ``dtb_ddz`` [K/km of layer thickness], each
-        ``[nprof][nang][nf][nlev]`` (levels ground -> top)."""
-        z = _f64(z)
-        if z.ndim != 2:
-            raise ValueError("profiles must be [nprof][nlev]")
-        nprof, nlev = z.shape
-        p, t, rh = _f64(p, z.shape, "p"), _f64(t, z.shape, "t"), _f64(rh, z.shape, "rh")
-        frq, elev = _f64(frq).ravel(), _f64(elev).ravel()
-        nf, nang = frq.size, elev.size
-        tb = np.empty((nprof, nang, nf))
-        jac = {k: np.empty((nprof, nang, nf, nlev)) for k in ("dtb_dt", "dtb_de", "dtb_ddz")}
-        valid = np.empty(nprof, dtype=np.uint8)
-        self._check(self._lib.mwrt_tb_jacobian_batch(
-            self._handle, self.model(model), nprof, nlev, _ptr(z), _ptr(p), _ptr(t), _ptr(rh), nf, _ptr(frq), nang, _ptr(elev),
-            _ptr(tb), _ptr(jac["dtb_dt"]), _ptr(jac["dtb_de"]), _ptr(jac["dtb_ddz"]), _ptr(valid)), "mwrt_tb_jacobian_batch")
+        """K-matrix in one call, what include/mwrt.h's mwrt_tb_jacobian_batch computes: ``tb_jacobian_batch_vars`` in the
+        operator's own variables.  Returns ``tb [nprof][nang][nf]``, ``valid`` and a dict of ``dtb_dt`` [K/K at fixed e],
+        ``dtb_de`` [K/hPa], ``dtb_ddz`` [K/km of layer thickness], each ``[nprof][nang][nf][nlev]`` (levels ground -> top)."""
+        tb, valid, jac = self.tb_jacobian_batch_vars(model, z, p, t, rh, frq, elev)
+        jac["dtb_de"] = jac.pop("dtb_dh")
         return tb, valid, jac
 
     # -- device-buffer entry points (raw device addresses, e.g. torch.Tensor.data_ptr()) -------
@@ -394,16 +389,14 @@ class Context:
                         extras: Optional[MwrtTbExtras] = None, stream=None, d_denliq=None, d_denice=None,
                         ray_tracing=False, d_o3n=None):
         frq, elev = _f64(frq).ravel(), _f64(elev).ravel()
-        if d_denliq is None and d_denice is None and not ray_tracing and d_o3n is None:
+        opts = _options(d_denliq, d_denice, ray_tracing, d_o3n)
+        if opts is None:
             self._check(self._lib.mwrt_tb_batch_device(
                 self._handle, self.model(model), int(nprof), int(nlev), _ptr(d_z), _ptr(d_p), _ptr(d_t), _ptr(d_rh),
                 frq.size, _ptr(frq), elev.size, _ptr(elev), _ptr(d_tb), _ptr(d_valid),
                 ctypes.byref(extras) if extras is not None else None,
                 _stream(stream)), "mwrt_tb_batch_device")
             return
-        opts = MwrtTbOptions(int(d_denliq) if d_denliq is not None else None,
-                             int(d_denice) if d_denice is not None else None, int(bool(ray_tracing)), 0,
-                             int(d_o3n) if d_o3n is not None else None)
         self._check(self._lib.mwrt_tb_batch_opt_device(
             self._handle, self.model(model), int(nprof), int(nlev), _ptr(d_z), _ptr(d_p), _ptr(d_t), _ptr(d_rh),
             frq.size, _ptr(frq), elev.size, _ptr(elev), _ptr(d_tb), _ptr(d_valid),
@@ -459,11 +452,7 @@ class Context:
         ``d_dtb_dice`` [nprof][nang][nf][nlev] (K per g m-3) as further outputs; each may be None.  ``ray_tracing`` and
         ``d_o3n`` exist to be refused (MWRT_ERR_UNSUPPORTED)."""
         frq, elev = _f64(frq).ravel(), _f64(elev).ravel()
-        opts = None
-        if d_denliq is not None or d_denice is not None or ray_tracing or d_o3n is not None:
-            opts = MwrtTbOptions(int(d_denliq) if d_denliq is not None else None,
-                                 int(d_denice) if d_denice is not None else None, int(bool(ray_tracing)), 0,
-                                 int(d_o3n) if d_o3n is not None else None)
+        opts = _options(d_denliq, d_denice, ray_tracing, d_o3n)
         self._check(self._lib.mwrt_tb_jacobian_batch_opt_device(
             self._handle, self.model(model), int(nprof), int(nlev), _ptr(d_z), _ptr(d_p), _ptr(d_t), _ptr(d_rh),
             frq.size, _ptr(frq), elev.size, _ptr(elev), _ptr(d_tb), _ptr(d_dtb_dt), _ptr(d_dtb_de), _ptr(d_dtb_ddz),
@@ -479,11 +468,7 @@ class Context:
         ``tb_jacobian_batch_opt_device`` with ``variables`` a ``JacVariables`` (None: the raw rows) and ``d_dtb_ddz``
         optional in every mode.  ``d_dtb_dh`` receives the humidity row in the variable asked for."""
         frq, elev = _f64(frq).ravel(), _f64(elev).ravel()
-        opts = None
-        if d_denliq is not None or d_denice is not None or ray_tracing or d_o3n is not None:
-            opts = MwrtTbOptions(int(d_denliq) if d_denliq is not None else None,
-                                 int(d_denice) if d_denice is not None else None, int(bool(ray_tracing)), 0,
-                                 int(d_o3n) if d_o3n is not None else None)
+        opts = _options(d_denliq, d_denice, ray_tracing, d_o3n)
         opt_ptr = lambda x: _ptr(x) if x is not None else None   # noqa: E731
         self._check(self._lib.mwrt_tb_jacobian_batch_vars_device(
             self._handle, self.model(model), int(nprof), int(nlev), _ptr(d_z), _ptr(d_p), _ptr(d_t), _ptr(d_rh),
@@ -499,19 +484,12 @@ class Context:
         [nprof][nang][nf]``, ``valid [nprof]`` and a dict of ``dtb_dt``, ``dtb_dh`` (the humidity row in the variable
         asked for), ``dtb_ddz`` (the raw thickness row; absent with ``thickness=False``) and, for each cloud array given,
         ``dtb_dliq`` / ``dtb_dice``, each ``[nprof][nang][nf][nlev]`` (levels ground -> top)."""
-        z = _f64(z)
-        if z.ndim != 2:
-            raise ValueError("profiles must be [nprof][nlev]")
+        z, p, t, rh, frq, elev = _profile_args(z, p, t, rh, frq, elev)
         nprof, nlev = z.shape
-        p, t, rh = _f64(p, z.shape, "p"), _f64(t, z.shape, "t"), _f64(rh, z.shape, "rh")
-        frq, elev = _f64(frq).ravel(), _f64(elev).ravel()
         nf, nang = frq.size, elev.size
         dl = None if denliq is None else _f64(denliq, z.shape, "denliq")
         di = None if denice is None else _f64(denice, z.shape, "denice")
-        opts = None
-        if dl is not None or di is not None:
-            opts = MwrtTbOptions(dl.ctypes.data if dl is not None else None, di.ctypes.data if di is not None else None,
-                                 0, 0, None)
+        opts = _options(dl, di)
         keys = ["dtb_dt", "dtb_dh"] + (["dtb_ddz"] if thickness else []) + (["dtb_dliq"] if dl is not None else []) + \
                (["dtb_dice"] if di is not None else [])
         tb = np.empty((nprof, nang, nf))

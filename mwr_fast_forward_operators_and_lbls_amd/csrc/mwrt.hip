@@ -503,6 +503,53 @@ int jacobian_vars_device(mwrt_context* c, const mwrt_model* m, int64_t nprof, in
   return timed(c, st, [&] { return launch_jac_rte(ja, nprof, st); });
 }
 
+// ... and behind its two HOST-buffer entries, synchronous: staged through device buffers of this call's own (freed on
+// every return path), one jacobian_vars_device call on the context's stream -- which makes every check and every
+// decision (valid, NaN rows) -- and the results copied back as they are.
+int jacobian_vars_host(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
+                       const double* z, const double* p, const double* t, const double* rh,
+                       int32_t nf, const double* frq, int32_t nang, const double* elev,
+                       double* tb, double* dtb_dt, double* dtb_dh, double* dtb_ddz, double* dtb_dliq, double* dtb_dice,
+                       uint8_t* valid, const mwrt_tb_options* opt, const mwrt_jac_variables* vars, bool ddz_required) {
+  CallSpec s{CALL_ANGLES | CALL_HOST | CALL_STAGES, nprof, nlev, nf, frq, nang, elev, nullptr};
+  s.buffers_ok = z && p && t && rh && frq && elev && tb && dtb_dt && dtb_dh && (dtb_ddz || !ddz_required) && valid;
+  Call call;
+  int rc = begin_call(c, &m, 1, s, &call);
+  if (rc || call.empty) return rc;
+  hipStream_t st = call.st;
+  const size_t nin = (size_t)nprof * nlev, ntb = (size_t)nprof * nang * nf, njac = ntb * nlev;
+  const double* in[6] = {z, p, t, rh, opt ? opt->denliq : nullptr, opt ? opt->denice : nullptr};
+  double* out[5] = {dtb_dt, dtb_dh, dtb_ddz, dtb_dliq, dtb_dice};
+  size_t nsrc = 0, nrows = 0;
+  for (const double* x : in) nsrc += x != nullptr;
+  for (const double* x : out) nrows += x != nullptr;
+  DevBuf buf;                                                     // this call's own: inputs | tb | rows | valid
+  auto free_buf = on_scope_exit([&] { buf.release(); });
+  HIP_TRY(buf.reserve(sizeof(double) * (nsrc * nin + ntb + nrows * njac) + (size_t)nprof));
+  double* q = buf.as<double>();
+  const double* din[6] = {};
+  for (int k = 0; k < 6; ++k)
+    if (in[k]) {
+      HIP_TRY(hipMemcpyAsync(q, in[k], sizeof(double) * nin, hipMemcpyHostToDevice, st));
+      din[k] = q; q += nin;
+    }
+  double* d_tb = q; q += ntb;
+  double* dout[5] = {};
+  for (int k = 0; k < 5; ++k) if (out[k]) { dout[k] = q; q += njac; }
+  uint8_t* d_valid = reinterpret_cast<uint8_t*>(q);
+  mwrt_tb_options dopt{};
+  if (opt) { dopt = *opt; dopt.denliq = din[4]; dopt.denice = din[5]; }
+  rc = jacobian_vars_device(c, m, nprof, nlev, din[0], din[1], din[2], din[3], nf, frq, nang, elev, d_tb, dout[0], dout[1],
+                            dout[2], dout[3], dout[4], d_valid, opt ? &dopt : nullptr, vars, ddz_required, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(tb, d_tb, sizeof(double) * ntb, hipMemcpyDeviceToHost, st));
+  for (int k = 0; k < 5; ++k)
+    if (out[k]) HIP_TRY(hipMemcpyAsync(out[k], dout[k], sizeof(double) * njac, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(valid, d_valid, (size_t)nprof, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return MWRT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -798,7 +845,7 @@ static int tb_host(mwrt_context* c, hipStream_t st, int nmodels, const mwrt_mode
     out[nout_arrays++] = RowArray{ex->*x.col, per};
   }
   HIP_TRY(hipStreamSynchronize(st));
-  blank_rows(valid, (int64_t)rows, false, out, nout_arrays);
+  blank_rows(valid, (int64_t)rows, out, nout_arrays);
   return MWRT_OK;
 }
 
@@ -907,87 +954,6 @@ int mwrt_tb_from_layer_tau_device(mwrt_context* c, const mwrt_model* m, int64_t 
   return rte_tau_launch(c, m, nprof, nlev, d_tau, tau_pitch, d_t, nf, call.dev_frq, nang, call.dev_am, d_tb, d_valid, call.st);
 }
 
-// K-matrix (dTB/dT, dTB/de, dTB/d thickness per level) -- see k_tb_jacobian.  HOST buffers, synchronous.
-int mwrt_tb_jacobian_batch(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
-                           const double* z, const double* p, const double* t, const double* rh,
-                           int32_t nf, const double* frq, int32_t nang, const double* elev,
-                           double* tb, double* dtb_dt, double* dtb_de, double* dtb_ddz, uint8_t* valid) {
-  CallSpec s{CALL_ANGLES | CALL_HOST, nprof, nlev, nf, frq, nang, elev, nullptr};
-  s.buffers_ok = z && p && t && rh && frq && elev && tb && dtb_dt && dtb_de && dtb_ddz && valid;
-  Call call;
-  int rc = begin_call(c, &m, 1, s, &call);
-  if (rc || call.empty) return rc;
-  hipStream_t st = call.st;
-  const double *dev_frq = call.dev_frq, *dev_am = call.dev_am;
-  constexpr double DT = 0.01, REL_E = 1e-4, MIN_DE = 1e-7;       // local steps of the absorption derivatives
-  // Goff-Gratch over water, as RTEquation.vapor [EXT] (host copy: only used to keep e fixed while T moves)
-  auto es_of = [](double tk) {
-    const double y = 373.16 / tk;
-    const double es = -7.90298 * (y - 1.0) + 5.02808 * std::log10(y) - 1.3816e-07 * (std::pow(10.0, 11.344 * (1.0 - (1.0 / y))) - 1.0) +
-                      0.0081328 * (std::pow(10.0, -3.49149 * (y - 1.0)) - 1.0) + std::log10(1013.246);
-    return std::pow(10.0, es);
-  };
-  // profile batches: the five absorption sets + three Jacobian arrays of one batch stay under ~1 GiB
-  const size_t per_prof = sizeof(double) * ((size_t)10 * nf * nlev + (size_t)3 * nang * nf * nlev + (size_t)nang * nf + 12 * (size_t)nlev) + 1;
-  const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(nprof, (int64_t)(((size_t)1 << 30) / per_prof)));
-  DevBuf ws;                                                      // own workspace: freed on every return path
-  auto free_ws = on_scope_exit([&] { ws.release(); });
-  HIP_TRY(ws.reserve((size_t)batch * per_prof + 4096));
-  for (int64_t b0 = 0; b0 < nprof; b0 += batch) {
-    const int64_t nb = std::min(batch, nprof - b0);
-    const size_t nin = (size_t)nb * nlev, nabs = (size_t)nb * nf * nlev, njac = (size_t)nb * nang * nf * nlev, ntb = (size_t)nb * nang * nf;
-    // host side: the 12 level arrays  z p t rh | t+ rh(T+) | t- rh(T-) | rh(e+) rh(e-) | de | (pad)
-    std::vector<double> h(12 * nin);
-    double *hz = h.data(), *hp = hz + nin, *ht = hp + nin, *hrh = ht + nin, *htp = hrh + nin, *hrp = htp + nin, *htm = hrp + nin,
-           *hrm = htm + nin, *hep = hrm + nin, *hem = hep + nin, *hde = hem + nin;
-    for (size_t i = 0; i < nin; ++i) {
-      const size_t g = (size_t)b0 * nlev + i;
-      hz[i] = z[g]; hp[i] = p[g]; ht[i] = t[g]; hrh[i] = rh[g];
-      const double es = es_of(t[g]), e = rh[g] * es;
-      htp[i] = t[g] + DT; hrp[i] = e / es_of(t[g] + DT);
-      htm[i] = t[g] - DT; hrm[i] = e / es_of(t[g] - DT);
-      const double de = std::max(std::fabs(e) * REL_E, MIN_DE);
-      const double lo = std::max(e - de, 0.0);                     // a dry level: the step stays on the non-negative side
-      hep[i] = (lo + 2.0 * de) / es; hem[i] = lo / es; hde[i] = de;
-    }
-    double* base = ws.as<double>();
-    double* d_lev = base;                                          // 12 x nin
-    double* d_abs = d_lev + 12 * nin;                              // 10 x nabs
-    double* d_jac = d_abs + 10 * nabs;                             // 3 x njac
-    double* d_tb = d_jac + 3 * njac;
-    uint8_t* d_valid = (uint8_t*)(d_tb + ntb);
-    HIP_TRY(hipMemcpyAsync(d_lev, h.data(), sizeof(double) * 12 * nin, hipMemcpyHostToDevice, st));
-    const double *dz_ = d_lev, *dp_ = d_lev + nin, *dt_ = d_lev + 2 * nin, *drh_ = d_lev + 3 * nin;
-    const double* T_of[5] = {dt_, d_lev + 4 * nin, d_lev + 6 * nin, dt_, dt_};
-    const double* RH_of[5] = {drh_, d_lev + 5 * nin, d_lev + 7 * nin, d_lev + 8 * nin, d_lev + 9 * nin};
-    JacArgs a{};
-    for (int v = 0; v < 5; ++v) {
-      double* aw = d_abs + (size_t)(2 * v) * nabs; double* ad = aw + nabs;
-      rc = mwrt_absorption_batch_device(c, m, nb, nlev, dp_, T_of[v], RH_of[v], nf, frq, aw, ad, st);
-      if (rc) return rc;
-      a.a[v][0] = aw; a.a[v][1] = ad;
-    }
-    a.M = m->d_desc; a.z = dz_; a.t = dt_; a.de = d_lev + 10 * nin; a.dT = DT; a.frq = dev_frq; a.airmass = dev_am;
-    a.tb = d_tb; a.dtb_dt = d_jac; a.dtb_de = d_jac + njac; a.dtb_ddz = d_jac + 2 * njac; a.valid = d_valid;
-    a.nprof = nb; a.nlev = nlev; a.nf = nf; a.nang = nang;
-    HIP_TRY(hipMemsetAsync(d_valid, 1, (size_t)nb, st));
-    rc = timed(c, st, [&] { return launch_tb_jacobian(a, st); });
-    if (rc) return rc;
-    const size_t o = (size_t)b0 * nang * nf;
-    HIP_TRY(hipMemcpyAsync(tb + o, d_tb, sizeof(double) * ntb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(dtb_dt + o * nlev, a.dtb_dt, sizeof(double) * njac, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(dtb_de + o * nlev, a.dtb_de, sizeof(double) * njac, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(dtb_ddz + o * nlev, a.dtb_ddz, sizeof(double) * njac, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(valid + b0, d_valid, (size_t)nb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-  }
-  // a profile flagged 0 / 2 is blanked as a whole, whichever thread met it
-  const size_t ntb = (size_t)nang * nf;
-  const RowArray out[4] = {{tb, ntb}, {dtb_dt, ntb * nlev}, {dtb_de, ntb * nlev}, {dtb_ddz, ntb * nlev}};
-  blank_rows(valid, nprof, true, out, 4);
-  return MWRT_OK;
-}
-
 // Tangent-linear absorption (k_absorb_tl): alpha and d alpha / dT|e, d alpha / de|T.  DEVICE buffers, asynchronous.
 int mwrt_absorption_tl_batch_device(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
                                     const double* d_p, const double* d_t, const double* d_rh, int32_t nf, const double* frq,
@@ -1041,51 +1007,24 @@ int mwrt_tb_jacobian_batch_vars_device(mwrt_context* c, const mwrt_model* m, int
                               d_dtb_dliq, d_dtb_dice, d_valid, opt, vars, /*ddz_required=*/false, stream);
 }
 
-// ... and on HOST buffers, synchronous: staged through device buffers of this call's own (freed on every return path),
-// one mwrt_tb_jacobian_batch_vars_device call on the context's stream -- which makes every check and every decision
-// (valid, NaN rows) -- and the results copied back as they are.
+// ... and on HOST buffers, synchronous (jacobian_vars_host).
 int mwrt_tb_jacobian_batch_vars(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
                                 const double* z, const double* p, const double* t, const double* rh,
                                 int32_t nf, const double* frq, int32_t nang, const double* elev,
                                 double* tb, double* dtb_dt, double* dtb_dh, double* dtb_ddz, double* dtb_dliq, double* dtb_dice,
                                 uint8_t* valid, const mwrt_tb_options* opt, const mwrt_jac_variables* vars) {
-  CallSpec s{CALL_ANGLES | CALL_HOST | CALL_STAGES, nprof, nlev, nf, frq, nang, elev, nullptr};
-  s.buffers_ok = z && p && t && rh && frq && elev && tb && dtb_dt && dtb_dh && valid;
-  Call call;
-  int rc = begin_call(c, &m, 1, s, &call);
-  if (rc || call.empty) return rc;
-  hipStream_t st = call.st;
-  const size_t nin = (size_t)nprof * nlev, ntb = (size_t)nprof * nang * nf, njac = ntb * nlev;
-  const double* in[6] = {z, p, t, rh, opt ? opt->denliq : nullptr, opt ? opt->denice : nullptr};
-  double* out[5] = {dtb_dt, dtb_dh, dtb_ddz, dtb_dliq, dtb_dice};
-  size_t nsrc = 0, nrows = 0;
-  for (const double* x : in) nsrc += x != nullptr;
-  for (const double* x : out) nrows += x != nullptr;
-  DevBuf buf;                                                     // this call's own: inputs | tb | rows | valid
-  auto free_buf = on_scope_exit([&] { buf.release(); });
-  HIP_TRY(buf.reserve(sizeof(double) * (nsrc * nin + ntb + nrows * njac) + (size_t)nprof));
-  double* q = buf.as<double>();
-  const double* din[6] = {};
-  for (int k = 0; k < 6; ++k)
-    if (in[k]) {
-      HIP_TRY(hipMemcpyAsync(q, in[k], sizeof(double) * nin, hipMemcpyHostToDevice, st));
-      din[k] = q; q += nin;
-    }
-  double* d_tb = q; q += ntb;
-  double* dout[5] = {};
-  for (int k = 0; k < 5; ++k) if (out[k]) { dout[k] = q; q += njac; }
-  uint8_t* d_valid = reinterpret_cast<uint8_t*>(q);
-  mwrt_tb_options dopt{};
-  if (opt) { dopt = *opt; dopt.denliq = din[4]; dopt.denice = din[5]; }
-  rc = mwrt_tb_jacobian_batch_vars_device(c, m, nprof, nlev, din[0], din[1], din[2], din[3], nf, frq, nang, elev, d_tb, dout[0],
-                                          dout[1], dout[2], dout[3], dout[4], d_valid, opt ? &dopt : nullptr, vars, nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(tb, d_tb, sizeof(double) * ntb, hipMemcpyDeviceToHost, st));
-  for (int k = 0; k < 5; ++k)
-    if (out[k]) HIP_TRY(hipMemcpyAsync(out[k], dout[k], sizeof(double) * njac, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(valid, d_valid, (size_t)nprof, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return MWRT_OK;
+  return jacobian_vars_host(c, m, nprof, nlev, z, p, t, rh, nf, frq, nang, elev, tb, dtb_dt, dtb_dh, dtb_ddz, dtb_dliq, dtb_dice,
+                            valid, opt, vars, /*ddz_required=*/false);
+}
+
+// The clear-sky K-matrix in the operator's own variables (T at fixed e, e, layer thickness) on HOST buffers: the call
+// above without cloud, options or variables, and with all three rows required.
+int mwrt_tb_jacobian_batch(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
+                           const double* z, const double* p, const double* t, const double* rh,
+                           int32_t nf, const double* frq, int32_t nang, const double* elev,
+                           double* tb, double* dtb_dt, double* dtb_de, double* dtb_ddz, uint8_t* valid) {
+  return jacobian_vars_host(c, m, nprof, nlev, z, p, t, rh, nf, frq, nang, elev, tb, dtb_dt, dtb_de, dtb_ddz, nullptr, nullptr,
+                            valid, nullptr, nullptr, /*ddz_required=*/true);
 }
 
 int mwrt_set_chunk_width(mwrt_context* c, int width) {

@@ -113,20 +113,6 @@ struct RteTauArgs {
   int nlev, nf, nang, fpitch, a0;
 };
 
-// k_tb_jacobian (csrc/mwrt_aux.hip)
-struct JacArgs {
-  const ModelFlat* M;
-  const double* z; const double* t;          // [nprof][nlev]
-  const double* a[5][2];                     // {base, T+, T-, e+, e-} x {wet, dry}: [nprof][nf][nlev]
-  const double* de;                          // [nprof][nlev] the absolute vapour-pressure step used for e+-  (hPa)
-  double dT;
-  const double* frq; const double* airmass;
-  double* tb;                                // [nprof][nang][nf]
-  double* dtb_dt; double* dtb_de; double* dtb_ddz;   // [nprof][nang][nf][nlev]
-  uint8_t* valid;                            // [nprof] preset to 1; 0 NaN input, 2 negative absorption
-  int64_t nprof; int nlev, nf, nang;
-};
-
 // ---------------------------------------------------------------------------------------------
 // launchers: each returns hipGetLastError() of its launch
 // ---------------------------------------------------------------------------------------------
@@ -155,11 +141,9 @@ hipError_t launch_absorb_win(const AbsorbWinArgs& a, dim3 grid, dim3 block, hipS
 hipError_t launch_absorb_tau(const AbsorbArgs& a, dim3 grid, dim3 block, hipStream_t st);
 hipError_t launch_rte_tau(const RteTauArgs& a, dim3 grid, size_t lds, hipStream_t st, int na);
 
-// the non-template kernels (csrc/mwrt_aux.hip): one workgroup per profile and one lane per level; one thread per
-// (profile, frequency, elevation); one thread per element
+// the non-template kernels (csrc/mwrt_aux.hip): one workgroup per profile and one lane per level; one thread per element
 hipError_t launch_ray_paths(const double* z, const double* p, const double* t, const double* rh, int64_t nprof, int nlev,
                             const double* elev_deg, int nang, double* amf, uint8_t* duct, hipStream_t st);
-hipError_t launch_tb_jacobian(const JacArgs& a, hipStream_t st);
 hipError_t launch_selftest_math(const double* x, const double* y, double* out_exp, double* out_log, double* out_div,
                                 double* out_div1, int n, hipStream_t st);
 

@@ -1,8 +1,7 @@
 // mwrt_aux.hip -- the kernels that are no templates, in a translation unit of their own, and their launchers: the
-// ray-path pre-kernel of ray_tracing=True (k_ray_paths), the finite-difference K-matrix (k_tb_jacobian) and the
-// self-test of the arithmetic helpers (k_selftest_math).  Argument records and declarations: mwrt_args.hip.h.
+// ray-path pre-kernel of ray_tracing=True (k_ray_paths) and the self-test of the arithmetic helpers (k_selftest_math).
+// Declarations: mwrt_args.hip.h.  (The K-matrix kernels are csrc/mwrt_tl.hip.)
 #include "mwrt_absorption.hip.h"
-#include "mwrt_layer.hip.h"
 
 namespace mwrt {
 
@@ -106,145 +105,6 @@ k_ray_paths(const double* __restrict__ z, const double* __restrict__ p, const do
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// K-matrix: dTB/dT, dTB/de, dTB/d(layer thickness) per level from ONE pass -- the adjoint of the layer rule and of
-// the Planck-space recursion (RTEquation.exponential_integration / planck / bright [EXT]) applied to absorption
-// derivatives.  The reference parses exactly this block out of RTTOV-gb's K run (RTTOV_gb_processing.py:286-300,
-// :418-432); round 2 produced it with 3 nlev + 1 forward runs.
-//
-// Inputs: absorption at the profile's levels and at four locally perturbed states (T +- dT at fixed e, e (1 +- re) at
-// fixed T), each [nprof][nf][nlev] as k_absorb writes them -- absorption is a LOCAL function of (p, T, e), so its
-// partial derivatives are central differences of five evaluations per level, whatever the number of levels.
-// Everything downstream is differentiated analytically:
-//   tau_l = (LM(aw_l, aw_{l-1}) + LM(ad_l, ad_{l-1})) dz_l am,
-//   B_tot = sum_l c_l T_{l-1} + B_cosmic T_n,   c_l = (b_{l-1} + b_l E_l)(1 - E_l)/(1 + E_l),  E_l = exp(-tau_l),
-//   dB_tot/dtau_l = T_{l-1} dc_l/dtau_l - (B_tot - sum_{m<=l} c_m T_{m-1})     (everything above layer l is dimmed),
-//   dTB/dB_tot = hvk / (ln^2(1 + 1/B) B (B + 1)),   db/dT = b (b + 1) hvk / T^2.
-// One thread per (profile, frequency, elevation): two serial walks over the levels (the first for B_tot).  An analysis
-// product, not a throughput path.
-// ---------------------------------------------------------------------------------------------
-// log-mean layer value and its two partial derivatives, branch for branch as layer_value<true>
-__device__ __forceinline__ double layer_value_grad(double x1, double x0, double& d1, double& d0, bool& neg) {
-  if (x0 < 0.0 || x1 < 0.0) { neg = true; d1 = d0 = 0.0; return 0.0; }
-  const double d = x1 - x0;
-  if (fabs(d) < 1e-09) { d1 = 1.0; d0 = 0.0; return x1; }
-  if (x0 == 0.0 || x1 == 0.0) { d1 = d0 = 0.5; return 0.5 * (x1 + x0); }
-  const double sm = x1 + x0, s = d / sm;
-  if (fabs(s) <= LOGMEAN_SMALL_S) {
-    // L = sm/2 q(z), q = s/atanh(s), z = s^2:  dL/dx1 = q/2 + 2 s q'(z) x0/sm,  dL/dx0 = q/2 - 2 s q'(z) x1/sm
-    const double z = s * s;
-    const double c[10] = {-3.3333333333333333333e-01, -8.8888888888888888889e-02, -4.6560846560846560847e-02,
-                          -3.0194003527336860670e-02, -2.1796804019026241248e-02, -1.6787551856334925118e-02,
-                          -1.3502765051265933100e-02, -1.1203745637718733130e-02, -9.5160731945278989134e-03,
-                          -8.2312065673505011548e-03};
-    double q = 0.0, qp = 0.0;
-    for (int k = 9; k >= 0; --k) { qp = qp * z + (k + 1) * c[k]; q = (q + c[k]) * z; }
-    q += 1.0;
-    d1 = 0.5 * q + 2.0 * s * qp * x0 / sm;
-    d0 = 0.5 * q - 2.0 * s * qp * x1 / sm;
-    return 0.5 * sm * q;
-  }
-  const double ln = log(x1 / x0), L = d / ln;
-  d1 = (1.0 - L / x1) / ln;
-  d0 = (L / x0 - 1.0) / ln;
-  return L;
-}
-
-__global__ void __launch_bounds__(64)
-k_tb_jacobian(const JacArgs A) {
-  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int nlev = A.nlev, nf = A.nf, nang = A.nang;
-  if (gid >= A.nprof * nf * nang) return;
-  const int a = (int)(gid % nang);
-  const int j = (int)((gid / nang) % nf);
-  const int64_t prof = gid / ((int64_t)nang * nf);
-  const cmodel M = (cmodel)A.M;
-  const double qnan = __builtin_nan("");
-  const int64_t orow = ((prof * nang + a) * nf + j);
-  double* o_t = A.dtb_dt + orow * nlev; double* o_e = A.dtb_de + orow * nlev; double* o_z = A.dtb_ddz + orow * nlev;
-  const int64_t arow = (prof * nf + j) * nlev;
-  const double* z = A.z + prof * nlev; const double* t = A.t + prof * nlev;
-  const double am = A.airmass[a];
-  const double f = A.frq[j];
-  const double hvk = f * (1e9 * M->planck_h / M->boltzmann_k);
-  bool bad = false;
-  for (int l = 0; l < nlev; ++l)
-    bad = bad || isnan(z[l]) || isnan(t[l]) || isnan(A.a[0][0][arow + l]) || isnan(A.a[0][1][arow + l]);
-  auto blank = [&](uint8_t flag) {
-    A.tb[orow] = qnan;
-    for (int l = 0; l < nlev; ++l) { o_t[l] = qnan; o_e[l] = qnan; o_z[l] = qnan; }
-    if (flag != 1) A.valid[prof] = flag;
-  };
-  if (bad) { blank(0); return; }
-  const double* aw = A.a[0][0] + arow; const double* ad = A.a[0][1] + arow;
-  // ---- walk 1: B_tot ----
-  bool neg = false;
-  double Btot = 0.0, T = 1.0;
-  {
-    double bprev = 1.0 / (exp(hvk / t[0]) - 1.0);
-    for (int l = 1; l < nlev; ++l) {
-      double g1, g0;
-      const double dz = (z[l] - z[0]) - (z[l - 1] - z[0]);
-      const double tau = (layer_value_grad(aw[l], aw[l - 1], g1, g0, neg) * dz + layer_value_grad(ad[l], ad[l - 1], g1, g0, neg) * dz) * am;
-      const double E = exp(-tau);
-      const double bl = 1.0 / (exp(hvk / t[l]) - 1.0);
-      const double c = (bprev + bl * E) / (1.0 + E) * T * (1.0 - E);
-      Btot += c;
-      o_z[l] = c;                                                 // (scratch until walk 2: c_l T_{l-1})
-      T *= E;
-      bprev = bl;
-    }
-  }
-  if (neg) { blank(2); return; }
-  const double bbg = 1.0 / (exp(hvk / M->t_cosmic) - 1.0);
-  const bool with_bg = T > TRANS_MIN;
-  if (with_bg) Btot += bbg * T;
-  const double Lg = log(1.0 + 1.0 / Btot);
-  A.tb[orow] = hvk / Lg;
-  const double dTB_dB = hvk / (Lg * Lg * Btot * (Btot + 1.0));
-  if (isnan(am)) { blank(1); return; }                          // a NaN elevation: its rows are NaN, the profile stays valid
-  // the radiance reaching the antenna from above each layer, sum_{m > l} c_m T_{m-1} + the cosmic term, summed from the
-  // top down into o_z[l] (B_tot - S_l would cancel to ~eps B_tot where it is tiny, at levels an opaque path hides)
-  {
-    double above = with_bg ? bbg * T : 0.0;
-    for (int l = nlev - 1; l >= 1; --l) { const double c = o_z[l]; o_z[l] = above; above += c; }
-  }
-  // ---- walk 2: derivatives ----
-  const double inv2dT = 0.5 / A.dT;
-  auto dA = [&](int species, int lvl, bool wrt_e) {             // d(absorption)/dT or /de at a level, central difference
-    const double hi = A.a[wrt_e ? 3 : 1][species][arow + lvl], lo = A.a[wrt_e ? 4 : 2][species][arow + lvl];
-    return wrt_e ? (hi - lo) / (2.0 * A.de[prof * nlev + lvl]) : (hi - lo) * inv2dT;
-  };
-  double Tm = 1.0;
-  double b0 = 1.0 / (exp(hvk / t[0]) - 1.0);
-  double acc_t = 0.0, acc_e = 0.0;                              // contributions to level l-1 collected so far
-  o_z[0] = 0.0;
-  for (int l = 1; l < nlev; ++l) {
-    double w1, w0, d1, d0;
-    const double dz = (z[l] - z[0]) - (z[l - 1] - z[0]);
-    const double Lw = layer_value_grad(aw[l], aw[l - 1], w1, w0, neg), Ld = layer_value_grad(ad[l], ad[l - 1], d1, d0, neg);
-    const double tau = (Lw * dz + Ld * dz) * am;
-    const double E = exp(-tau);
-    const double b1 = 1.0 / (exp(hvk / t[l]) - 1.0);
-    const double opE = 1.0 + E, omE = 1.0 - E;
-    const double dc_dtau = E * (2.0 * b0 + 2.0 * b1 * E - b1 + b1 * E * E) / (opE * opE);
-    // everything above layer l (later layers and the cosmic term, o_z[l] from the top-down sum) is dimmed by E_l
-    const double g = dTB_dB * (Tm * dc_dtau - o_z[l]);                          // dTB/dtau_l
-    const double gk = g * am * dz;
-    // level l-1 (lower end of the layer) and level l (upper end)
-    acc_t += gk * (w0 * dA(0, l - 1, false) + d0 * dA(1, l - 1, false)) + dTB_dB * Tm * (omE / opE) * (b0 * (b0 + 1.0) * hvk / (t[l - 1] * t[l - 1]));
-    acc_e += gk * (w0 * dA(0, l - 1, true) + d0 * dA(1, l - 1, true));
-    o_t[l - 1] = acc_t; o_e[l - 1] = acc_e;
-    acc_t = gk * (w1 * dA(0, l, false) + d1 * dA(1, l, false)) + dTB_dB * Tm * (E * omE / opE) * (b1 * (b1 + 1.0) * hvk / (t[l] * t[l]));
-    acc_e = gk * (w1 * dA(0, l, true) + d1 * dA(1, l, true));
-    // dTB / d(thickness of layer l) [K/km]: tau_l = m (Lw + Ld) dz_l is linear in dz_l, so this holds at dz_l = 0 too
-    o_z[l] = g * am * (Lw + Ld);
-    Tm *= E;
-    b0 = b1;
-  }
-  o_t[nlev - 1] = acc_t; o_e[nlev - 1] = acc_e;
-}
-
 // diagnostic: the local exp / log / division helpers on caller-supplied arguments (mwrt_selftest_math)
 __global__ void k_selftest_math(const double* x, const double* y, double* out_exp, double* out_log, double* out_div,
                                 double* out_div1, int n) {
@@ -260,12 +120,6 @@ hipError_t launch_ray_paths(const double* z, const double* p, const double* t, c
                             const double* elev_deg, int nang, double* amf, uint8_t* duct, hipStream_t st) {
   hipLaunchKernelGGL(k_ray_paths, dim3((unsigned)nprof), dim3(lanes_for(nlev)), 0, st, z, p, t, rh, nlev, elev_deg, nang, amf,
                      duct);
-  return hipGetLastError();
-}
-
-hipError_t launch_tb_jacobian(const JacArgs& a, hipStream_t st) {
-  const int64_t nthreads = a.nprof * a.nf * a.nang;
-  hipLaunchKernelGGL(k_tb_jacobian, dim3((unsigned)((nthreads + 63) / 64)), dim3(64), 0, st, a);
   return hipGetLastError();
 }
 

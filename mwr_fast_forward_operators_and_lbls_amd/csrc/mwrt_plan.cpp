@@ -369,10 +369,10 @@ void pack_windows(const WindowSet& ws, int nf, std::vector<char>* blob) {
   std::memcpy(blob->data() + l.off_lagsd, ws.lag_sd.data(), sizeof(double) * ws.lag_sd.size());
 }
 
-void blank_rows(const uint8_t* valid, int64_t nrows, bool unless_one, const RowArray* arrays, int narrays) {
+void blank_rows(const uint8_t* valid, int64_t nrows, const RowArray* arrays, int narrays) {
   const double qnan = std::nan("");
   for (int64_t i = 0; i < nrows; ++i) {
-    if (unless_one ? valid[i] == 1 : valid[i] != 2) continue;
+    if (valid[i] != 2) continue;
     for (int k = 0; k < narrays; ++k) {
       if (!arrays[k].p) continue;
       double* row = arrays[k].p + (size_t)i * arrays[k].per;

@@ -133,9 +133,8 @@ struct WindowLayout { size_t off_lag, off_lagh, off_lagsd, total; };
 WindowLayout window_layout(int nwin, int nf);
 void pack_windows(const WindowSet& ws, int nf, std::vector<char>* blob);
 
-// NaN into rows of host output arrays: row i of every array (`per` doubles each) where valid[i] == 2, and with
-// `unless_one` wherever valid[i] != 1
+// NaN into rows of host output arrays: row i of every array (`per` doubles each) where valid[i] == 2
 struct RowArray { double* p; size_t per; };
-void blank_rows(const uint8_t* valid, int64_t nrows, bool unless_one, const RowArray* arrays, int narrays);
+void blank_rows(const uint8_t* valid, int64_t nrows, const RowArray* arrays, int narrays);
 
 }  // namespace mwrt

@@ -18,7 +18,7 @@ the station height, and humidity converts as e = ppmv * p / 1e6 (the reference's
 The K-matrix block the reference also parses (:286-300: per channel a header of three lines, then one row
 ``level p dTB/dT dTB/dppmv dTB/dliq`` per level) is produced for any number of profiles by ``jacobians_batch`` (the device
 K-matrix in these variables, liquid column included, ``mwrt_tb_jacobian_batch_vars``) and for one profile by ``jacobians``
-(one call of the host adjoint, ``mwrt_tb_jacobian_batch``; central / forward differences through the batched operator for
+(one call of the same K-matrix on host buffers, ``mwrt_tb_jacobian_batch``; central / forward differences through the batched operator for
 the liquid column), and written / read by ``format_jacobians`` / ``parse_jacobians``.  Liquid water
 enters through the cloud-liquid opt-in of the LBL operator (``clear_sky=False``; the reference itself runs RTTOV-gb
 with ``clear_sky_bool=True``, :82-86, so the default here is clear sky too).
@@ -148,9 +148,9 @@ def simulate(profiles: List[dict], model: str = "R24", frqs=HATPRO_FRQS, clear_s
 
 
 def jacobians_adjoint(profile: dict, model: str = "R24", frqs=HATPRO_FRQS):
-    """K-matrix of one profile from ONE call of the operator's adjoint (``mwrt_tb_jacobian_batch``): the partial
-    derivatives with respect to the LBL inputs of each level (T at fixed vapour pressure, vapour pressure, layer
-    thickness) chained to RTTOV-gb's variables -- T at fixed ppmv, ppmv -- through e = ppmv p / 1e6 and the hydrostatic
+    """K-matrix of one profile from ONE call of the operator's adjoint (``mwrt_tb_jacobian_batch``: tangent-linear
+    absorption, then the adjoint of the layer rule and the RTE -- exact, no finite differences): the partial derivatives
+    with respect to the LBL inputs of each level (T at fixed vapour pressure, vapour pressure, layer thickness) chained to RTTOV-gb's variables -- T at fixed ppmv, ppmv -- through e = ppmv p / 1e6 and the hydrostatic
     heights this module rebuilds (``to_lbl_inputs``): a level's virtual temperature sets the thickness of the two layers
     that touch it.  Returns ``(dTB_dT [nlev][nchan] K/K, dTB_dq [nlev][nchan] K/ppmv)``, levels TOP -> GROUND, like
     ``jacobians`` -- which it matches to the accuracy of that function's finite differences."""

@@ -181,13 +181,11 @@ def route(c, lds_max=LDS_MAX):
     nf = len(frq)
     if c.entry == "selftest":
         return {"k_selftest_math"}, 0
-    if c.entry == "jacobian_device":
+    if c.entry in ("jacobian", "jacobian_device"):
         return {"k_absorb_tl", "k_jac_rte"}, 0
-    if c.entry in ("absorption", "jacobian"):
+    if c.entry == "absorption":
         ks = _absorb(c.nlev, frq, c.absorption_mode, lds_max)
-        if ks is None:
-            return set(), ERR_UNSUPPORTED
-        return (ks | {"k_tb_jacobian"} if c.entry == "jacobian" else ks), 0
+        return (set(), ERR_UNSUPPORTED) if ks is None else (ks, 0)
     if c.entry == "layer_tau":                                     # layer_tau_launch
         threads = tau_threads(c.nlev)
         eligible = threads <= 1024 and windowed_ok(frq, threads, lds_max)
@@ -910,7 +908,7 @@ def test_chunk_widths_agree_on_the_tall_class(gpu_ctx, variant):
 
 @pytest.mark.gpu
 def test_remaining_kernels_at_1024_levels(gpu_ctx):
-    """k_selftest_math, k_tb_jacobian (+ k_absorb), k_absorb_tl + k_jac_rte and k_ray_paths: TBs equal tb_batch's to
+    """k_selftest_math, k_absorb_tl + k_jac_rte (behind the host and the device entry) and k_ray_paths: TBs equal tb_batch's to
     1e-9 K (their exact parity is held in test_gpu_parity / test_jacobian_device_edges)"""
     import torch
     from oracle import c_oracle as co
@@ -930,7 +928,7 @@ def test_remaining_kernels_at_1024_levels(gpu_ctx):
     ref, rv = gpu_ctx.tb_batch(c.model, P["z"], P["p"], P["t"], P["rh"], frq, ang)
     tb, valid, _ = gpu_ctx.tb_jacobian_batch(c.model, P["z"], P["p"], P["t"], P["rh"], frq, ang)
     assert (valid == 1).all() and (rv == 1).all()
-    record("k_tb_jacobian TB vs tb_batch", np.abs(tb - ref).max())
+    record("k_jac_rte (host entry) TB vs tb_batch", np.abs(tb - ref).max())
     assert np.abs(tb - ref).max() <= 1e-9
 
     c = misc["jacobian_device"]                      # same model, profile, frequencies and elevations as the host call

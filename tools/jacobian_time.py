@@ -1,6 +1,7 @@
-"""Wall time of the batched K-matrix entry (mwrt_tb_jacobian_batch, host buffers) next to the forward call.  Device work for
-1000 profiles x 14 channels x 1 elevation is ~1.5 ms (k_tb_jacobian 1.0, five k_absorb launches 0.4); the rest of the 26 ms is
-the 60 MB of partial derivatives crossing PCIe into pageable memory."""
+"""Wall time of the batched K-matrix entry on host buffers (mwrt_tb_jacobian_batch: the device K-matrix, k_absorb_tl +
+k_jac_rte, behind a staging copy) next to the forward call.  The device work is well under a millisecond (0.58 ms at 1000
+profiles x 14 channels x 7 elevations); the rest is the partial derivatives (60 MB per elevation at 1000
+profiles) crossing PCIe into pageable memory.  Record: profiles/jacobian_host_entry_time.json."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
