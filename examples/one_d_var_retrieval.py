@@ -2,7 +2,9 @@
 """A closed 1D-Var loop on the device (needs a GPU): synthetic soundings are the truth, y = F(x_true) + noise at the 14
 HATPRO channels x 7 elevations, and retrieval.OneDVar iterates the device K-matrix call and the optimal-estimation step
 (mwrt_oe_step_device) from a first guess that is off by a draw from the prior covariance.  Nothing but the convergence
-flag leaves the device between iterations.
+flag leaves the device between iterations.  The same observations are then retrieved with Levenberg-Marquardt damping
+(OneDVar.retrieve_lm on the split entries), and the example prints how many of its 200 profiles each loop
+leaves unconverged.
 
     python examples/one_d_var_retrieval.py
 """
@@ -65,3 +67,19 @@ print(f"RMS of x - x_true below 4 km, median over profiles   T: {float(err(xa, 0
 print(f"degrees of freedom for signal: median {float(res.dfs[ok].median()):.2f} (of {m} observations)")
 print(f"chi2 / m: median {float((res.chi2[ok] / m).median()):.2f}")
 print(f"posterior sigma of T at the ground: {float(res.post_var[ok][:, 0, 0].sqrt().median()):.2f} K (prior {sig_t:.1f} K)")
+
+# the same with Levenberg-Marquardt damping: no accepted step may raise the cost J
+ov.retrieve_lm(z, p, y, max_iter=1)                                            # warm-up
+torch.cuda.synchronize()
+t0 = time.perf_counter()
+lm = ov.retrieve_lm(z, p, y, max_iter=20, tol=0.05)
+torch.cuda.synchronize()
+t1 = time.perf_counter()
+okl = lm.converged
+print(f"\nwith Levenberg-Marquardt damping, {int(lm.iterations.max())} trials at most: {1e3 * (t1 - t0):.1f} ms")
+print(f"left unconverged: undamped {NPROF - int(ok.sum())} of {NPROF}, damped {NPROF - int(okl.sum())} of {NPROF}"
+      f" (of the {NPROF - int(ok.sum())} the undamped loop left, the damped loop settles {int((okl & ~ok).sum())})")
+print(f"RMS of x - x_true below 4 km, median over its converged profiles   T: {float(err(lm.x, 0)[okl].median()):.3f} K"
+      f"    rh: {float(err(lm.x, 1)[okl].median()):.4f}")
+print(f"cost J: median {float(lm.cost[okl].median()):.1f}; final gamma: median {float(lm.gamma[okl].median()):.1e},"
+      f" largest {float(lm.gamma.max()):.1e}")

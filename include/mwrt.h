@@ -500,6 +500,61 @@ int mwrt_oe_step_device(mwrt_context* ctx, int64_t nprof, int32_t nlev, int32_t 
 /* sizeof(mwrt_oe_step) as compiled into the library (binding self-check). */
 size_t mwrt_oe_step_size(void);
 
+/* The same step split for Levenberg-Marquardt damping (Rodgers 2000, eq. 5.36 in the m-form).  With
+ * dx = x - xa, r = y - F(x) and a damping factor gamma >= 0 per profile,
+ *     x+ = xa + gamma / (1 + gamma) dx + Sa K^T u,     (K Sa K^T + (1 + gamma) Se) u = r + K dx / (1 + gamma)
+ * and gamma = 0 is mwrt_oe_step_device.  G0 = K Sa K^T, r and K dx depend on x alone and are all but 1 % of the step's
+ * arithmetic: linearise once per accepted state, solve once per trial gamma.
+ *   mwrt_oe_lm_prepare_device   the linearisation at x: the row rule, r, K dx and G0, written to caller-owned buffers
+ *   mwrt_oe_lm_solve_device     one damped trial x+ on a linearisation, with gamma per profile
+ *   mwrt_oe_cost_device         J = r^T (Se,kept)^-1 r + dx^T Sa^-1 dx at a state, on the rows of a linearisation
+ * One record, mwrt_oe_lm, serves the three.  Inputs are those of mwrt_oe_step (d_k, d_x, d_xa, d_sa, d_se, d_y, d_fx,
+ * nblk, xa_per_profile, se_full; the same shapes, all DEVICE pointers, float64 unless stated) plus
+ *   d_gamma      [nprof]                 the damping factor, finite and >= 0                       (solve)
+ *   d_sa_inv     [n][n]                  Sa^-1, SYMMETRIC, formed by the caller                    (cost)
+ *   d_active     [nprof] uint8, optional a profile whose flag is 0 is skipped: NONE of its outputs is touched (all three)
+ * The linearisation, written by prepare and read by solve (all five) and cost (d_keep alone):
+ *   d_g0         [nprof][m (m + 1) / 2]  packed lower triangle of K Sa K^T, entry (i, j <= i) at i (i + 1) / 2 + j; the rows
+ *                                        and columns of a dropped observation are 0
+ *   d_r, d_kdx   [nprof][m]              y - F(x) and K (x - xa); 0 in a dropped row
+ *   d_keep       [nprof][m] uint8        1: the row is used.  The row rule is that of mwrt_oe_step_device
+ *   d_lin_status [nprof] uint8           1 ok;  0 x or xa not finite (r, K dx and G0 NaN, keep 0);  3 no usable observation
+ *                                        (r, K dx, G0 and keep 0)
+ * Outputs of solve: d_x_new [nprof][nblk][nlev] and d_status [nprof] uint8 required; d_chi2 [nprof] = d^T G^-1 d with
+ *   d = r + K dx / (1 + gamma), G = G0 + (1 + gamma) Se, and d_nobs [nprof] int32 optional.
+ *   status: 1 ok;  0 the state not finite, now or when it was linearised (d_lin_status 0): outputs NaN, nobs 0;  2 gamma
+ *   negative or not finite, or a Cholesky pivot fails pivot > 0: outputs NaN, nobs = m_used;  3 no usable observation:
+ *   x_new = xa + gamma / (1 + gamma) dx (xa exactly at gamma = 0), chi2 0, nobs 0.
+ * Outputs of cost: d_cost [nprof] required; d_cost_obs and d_cost_prior [nprof] (the two terms) and d_status optional.  The
+ *   observation term runs over the rows d_keep names, so a trial and the state it is compared with use the same rows; with
+ *   a full Se it is a Cholesky of the kept sub-matrix.  A non-finite x, xa, or y or fx in a kept row gives +inf in all
+ *   three (a trial to reject, not an error: status 1).  Se (kept) not positive definite: NaN in all three and status 2.
+ * Determinism, limits (m <= MWRT_OE_MAX_M, nlev <= MWRT_MAX_LEVELS: MWRT_ERR_UNSUPPORTED with the limit in the text) and
+ *   streams as mwrt_oe_step_device.  MWRT_ERR_INVALID_ARGUMENT: a NULL pointer among those the call reads or must write
+ *   (prepare: the inputs but d_gamma and d_sa_inv, and the linearisation; solve: d_k, d_x, d_xa, d_sa, d_se, d_gamma, the
+ *   linearisation, d_x_new, d_status; cost: d_x, d_xa, d_se, d_y, d_fx, d_keep, d_sa_inv, d_cost), nblk outside 1 .. 4,
+ *   reserved != 0, nlev < 1, m < 1, nprof < 0, struct_size smaller than the fixed part (24 bytes).
+ * The record starts with its own size: fields at or beyond struct_size (and a field it ends inside) are taken as NULL.
+ * The calls never allocate and never synchronise; each kernel's dynamic-LDS limit is raised once per device and size
+ *   above 64 KiB, so a repeat call of the same size is the launch alone.  (MWRT_VERSION stays 301: additions.) */
+typedef struct mwrt_oe_lm {
+  uint32_t struct_size;        /* sizeof(mwrt_oe_lm) of the caller; fields beyond it are not read */
+  int32_t  nblk, xa_per_profile, se_full, reserved;
+  const double* d_k[4];
+  const double *d_x, *d_xa, *d_sa, *d_se, *d_y, *d_fx;
+  const double* d_gamma;
+  double *d_g0, *d_r, *d_kdx;  uint8_t *d_keep, *d_lin_status;   /* the linearisation */
+  const uint8_t* d_active;
+  const double* d_sa_inv;
+  double *d_cost, *d_cost_obs, *d_cost_prior;          /* outputs of cost */
+  double* d_x_new;  uint8_t* d_status;  double* d_chi2;  int32_t* d_nobs;   /* outputs of solve */
+} mwrt_oe_lm;
+int mwrt_oe_lm_prepare_device(mwrt_context* ctx, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_lm* s, void* stream);
+int mwrt_oe_lm_solve_device(mwrt_context* ctx, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_lm* s, void* stream);
+int mwrt_oe_cost_device(mwrt_context* ctx, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_lm* s, void* stream);
+/* sizeof(mwrt_oe_lm) as compiled into the library (binding self-check). */
+size_t mwrt_oe_lm_size(void);
+
 /* Diagnostic: evaluates the kernels' own exp / log / division helpers (fexp, flog, fdiv, fdiv1) on
  * host arrays x[n], y_pos[n] (y > 0), so their accuracy can be checked against libm. */
 int mwrt_selftest_math(mwrt_context* ctx, int32_t n, const double* x, const double* y_pos,

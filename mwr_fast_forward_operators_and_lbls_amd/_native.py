@@ -68,6 +68,15 @@ class MwrtOeStep(ctypes.Structure):
                 ("d_post_var", ctypes.c_void_p), ("d_nobs", ctypes.c_void_p)]
 
 
+class MwrtOeLm(ctypes.Structure):
+    """include/mwrt.h mwrt_oe_lm: the record of the Levenberg-Marquardt split of the step (device pointers)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("nblk", ctypes.c_int32), ("xa_per_profile", ctypes.c_int32),
+                ("se_full", ctypes.c_int32), ("reserved", ctypes.c_int32), ("d_k", ctypes.c_void_p * 4)] + [
+        (name, ctypes.c_void_p) for name in (
+            "d_x", "d_xa", "d_sa", "d_se", "d_y", "d_fx", "d_gamma", "d_g0", "d_r", "d_kdx", "d_keep", "d_lin_status",
+            "d_active", "d_sa_inv", "d_cost", "d_cost_obs", "d_cost_prior", "d_x_new", "d_status", "d_chi2", "d_nobs")]
+
+
 #: include/mwrt.h MWRT_OE_MAX_M: observations per profile of one optimal-estimation step
 OE_MAX_M = 140
 
@@ -123,6 +132,10 @@ SIGNATURES = {
                                                    ctypes.POINTER(JacVariables)]),
     "mwrt_oe_step_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeStep), _vp]),
     "mwrt_oe_step_size": (ctypes.c_size_t, []),
+    "mwrt_oe_lm_prepare_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeLm), _vp]),
+    "mwrt_oe_lm_solve_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeLm), _vp]),
+    "mwrt_oe_cost_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeLm), _vp]),
+    "mwrt_oe_lm_size": (ctypes.c_size_t, []),
     "mwrt_set_absorption_mode": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_set_chunk_width": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_selftest_math": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -182,6 +195,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
             raise NativeLibraryMissing("mwrt_model_desc layout mismatch between libmwrt.so and spectroscopy.py")
         if lib.mwrt_oe_step_size() != ctypes.sizeof(MwrtOeStep):
             raise NativeLibraryMissing("mwrt_oe_step layout mismatch between libmwrt.so and _native.py")
+        if lib.mwrt_oe_lm_size() != ctypes.sizeof(MwrtOeLm):
+            raise NativeLibraryMissing("mwrt_oe_lm layout mismatch between libmwrt.so and _native.py")
         if lib.mwrt_version() != MWRT_VERSION:
             raise NativeLibraryMissing(f"libmwrt.so is version {lib.mwrt_version()}, this binding needs {MWRT_VERSION}: "
                                        "rebuild (python -c 'import __graft_entry__ as g; g.build()')")
@@ -522,6 +537,51 @@ class Context:
         rec.d_chi2, rec.d_dfs, rec.d_post_var, rec.d_nobs = map(opt, (d_chi2, d_dfs, d_post_var, d_nobs))
         self._check(self._lib.mwrt_oe_step_device(self._handle, int(nprof), int(nlev), int(m), ctypes.byref(rec),
                                                   _stream(stream)), "mwrt_oe_step_device")
+
+    def _oe_lm(self, entry, nprof, nlev, m, d_k, xa_per_profile, se_full, stream, reserved, struct_size, fields):
+        d_k = list(d_k)
+        rec = MwrtOeLm()
+        rec.struct_size = ctypes.sizeof(MwrtOeLm) if struct_size is None else int(struct_size)
+        rec.nblk, rec.xa_per_profile, rec.se_full, rec.reserved = len(d_k), int(bool(xa_per_profile)), int(bool(se_full)), int(reserved)
+        for b, k in enumerate(d_k[:4]):
+            rec.d_k[b] = int(k) if k is not None else None
+        for name, v in fields.items():
+            setattr(rec, name, int(v) if v is not None else None)
+        self._check(getattr(self._lib, entry)(self._handle, int(nprof), int(nlev), int(m), ctypes.byref(rec), _stream(stream)),
+                    entry)
+
+    @_serialised
+    def oe_lm_prepare_device(self, nprof, nlev, m, d_k, d_x, d_xa, d_sa, d_se, d_y, d_fx, d_g0, d_r, d_kdx, d_keep,
+                             d_lin_status, d_active=None, xa_per_profile=False, se_full=False, stream=None, reserved=0,
+                             struct_size=None):
+        """The linearisation at x (include/mwrt.h mwrt_oe_lm_prepare_device): the inputs of ``oe_step_device``; writes
+        ``d_g0 [nprof][m (m + 1) / 2]``, ``d_r`` and ``d_kdx [nprof][m]``, ``d_keep [nprof][m]`` and ``d_lin_status [nprof]``
+        (uint8).  A profile whose ``d_active`` flag (uint8, optional) is 0 is skipped."""
+        self._oe_lm("mwrt_oe_lm_prepare_device", nprof, nlev, m, d_k, xa_per_profile, se_full, stream, reserved, struct_size,
+                    dict(d_x=d_x, d_xa=d_xa, d_sa=d_sa, d_se=d_se, d_y=d_y, d_fx=d_fx, d_g0=d_g0, d_r=d_r, d_kdx=d_kdx,
+                         d_keep=d_keep, d_lin_status=d_lin_status, d_active=d_active))
+
+    @_serialised
+    def oe_lm_solve_device(self, nprof, nlev, m, d_k, d_x, d_xa, d_sa, d_se, d_gamma, d_g0, d_r, d_kdx, d_keep,
+                           d_lin_status, d_x_new, d_status, d_chi2=None, d_nobs=None, d_active=None, xa_per_profile=False,
+                           se_full=False, stream=None, reserved=0, struct_size=None):
+        """One damped trial on a linearisation (include/mwrt.h mwrt_oe_lm_solve_device) with ``d_gamma [nprof]``:
+        ``d_x_new [nprof][nblk][nlev]`` and ``d_status [nprof]`` (uint8) required, ``d_chi2`` and ``d_nobs`` optional."""
+        self._oe_lm("mwrt_oe_lm_solve_device", nprof, nlev, m, d_k, xa_per_profile, se_full, stream, reserved, struct_size,
+                    dict(d_x=d_x, d_xa=d_xa, d_sa=d_sa, d_se=d_se, d_gamma=d_gamma, d_g0=d_g0, d_r=d_r, d_kdx=d_kdx,
+                         d_keep=d_keep, d_lin_status=d_lin_status, d_x_new=d_x_new, d_status=d_status, d_chi2=d_chi2,
+                         d_nobs=d_nobs, d_active=d_active))
+
+    @_serialised
+    def oe_cost_device(self, nprof, nlev, m, nblk, d_x, d_xa, d_se, d_y, d_fx, d_keep, d_sa_inv, d_cost, d_cost_obs=None,
+                       d_cost_prior=None, d_status=None, d_active=None, xa_per_profile=False, se_full=False, stream=None,
+                       reserved=0, struct_size=None):
+        """J = r^T Se^-1 r over the rows ``d_keep`` names + (x - xa)^T Sa^-1 (x - xa) (include/mwrt.h mwrt_oe_cost_device);
+        ``nblk`` is the number of state blocks (the call reads no K)."""
+        self._oe_lm("mwrt_oe_cost_device", nprof, nlev, m, [None] * int(nblk), xa_per_profile, se_full, stream, reserved,
+                    struct_size, dict(d_x=d_x, d_xa=d_xa, d_se=d_se, d_y=d_y, d_fx=d_fx, d_keep=d_keep, d_sa_inv=d_sa_inv,
+                                      d_cost=d_cost, d_cost_obs=d_cost_obs, d_cost_prior=d_cost_prior, d_status=d_status,
+                                      d_active=d_active))
 
     def layer_tau_pitch(self, nf: int) -> int:
         """Doubles between consecutive levels of a layer-optical-depth array for nf frequencies (multiple of 16)."""

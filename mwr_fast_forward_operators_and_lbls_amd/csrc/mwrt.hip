@@ -4,10 +4,11 @@
 // returns 0 and mwrt_create() fails with MWRT_ERR_NO_DEVICE.
 //
 // Host code only: streams, caches, argument checks and the choice of launch.  Every kernel lives in another unit
-// (mwrt_inst.hip, mwrt_tl.hip, mwrt_oe.hip, mwrt_aux.hip) and is reached through the launchers the headers below declare.
+// (mwrt_inst.hip, mwrt_tl.hip, mwrt_oe.hip, mwrt_oe_lm.hip, mwrt_aux.hip) and is reached through the launchers the headers below declare.
 #include "mwrt_args.hip.h"
 #include "mwrt_tl.hip.h"
 #include "mwrt_oe.hip.h"
+#include "mwrt_oe_lm.hip.h"
 #include "mwrt_plan.h"
 
 #include <cmath>
@@ -552,6 +553,67 @@ int jacobian_vars_host(mwrt_context* c, const mwrt_model* m, int64_t nprof, int3
 
 }  // namespace
 
+// The three entries of the Levenberg-Marquardt split (csrc/mwrt_oe_lm.hip) share one record and one preamble -- the order
+// of mwrt_oe_step_device: arguments, then limits, then the device and the stream -- and differ in the pointers they
+// require and the kernel they launch.
+namespace {
+
+enum class LmCall { Prepare, Solve, Cost };
+
+int oe_lm_call(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_lm* s, void* stream, LmCall call) {
+  if (!c || !s) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context or mwrt_oe_lm");
+  constexpr size_t fixed = offsetof(mwrt_oe_lm, d_k);
+  if (s->struct_size < fixed)
+    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_lm.struct_size too small for the fixed part (through reserved)");
+  mwrt_oe_lm r{};                                      // fields at or beyond the caller's struct_size stay NULL
+  // ... and so does a field the size ends inside: beyond the fixed part every field is one pointer
+  size_t len = s->struct_size < sizeof r ? s->struct_size : sizeof r;
+  len -= (len - fixed) % sizeof(void*);
+  std::memcpy(&r, s, len);
+  if (nprof < 0 || nlev < 1 || m < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "nprof < 0, nlev < 1 or m < 1");
+  if (r.nblk < 1 || r.nblk > 4) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_lm.nblk must be 1 .. 4");
+  if (r.reserved != 0) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_lm.reserved must be 0");
+  bool buffers = r.d_x && r.d_xa && r.d_se;
+  const bool lin = r.d_g0 && r.d_r && r.d_kdx && r.d_keep && r.d_lin_status;
+  if (call != LmCall::Cost) {
+    buffers = buffers && r.d_sa && lin;
+    for (int b = 0; b < r.nblk; ++b) buffers = buffers && r.d_k[b];
+  }
+  if (call == LmCall::Prepare) buffers = buffers && r.d_y && r.d_fx;
+  if (call == LmCall::Solve) buffers = buffers && r.d_gamma && r.d_x_new && r.d_status;
+  if (call == LmCall::Cost) buffers = buffers && r.d_y && r.d_fx && r.d_keep && r.d_sa_inv && r.d_cost;
+  if (!buffers) return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
+  if (nlev > MWRT_MAX_LEVELS)
+    return fail(MWRT_ERR_UNSUPPORTED, "nlev > MWRT_MAX_LEVELS (" + std::to_string(MWRT_MAX_LEVELS) + ")");
+  if (m > MWRT_OE_MAX_M)
+    return fail(MWRT_ERR_UNSUPPORTED, "m > MWRT_OE_MAX_M (" + std::to_string(MWRT_OE_MAX_M) + " observations per profile: G lives in LDS)");
+  if (nprof > 2147483647LL) return fail(MWRT_ERR_UNSUPPORTED, "nprof exceeds grid limit");
+  lm::LmArgs a{};
+  a.o.k0 = r.d_k[0]; a.o.k1 = r.nblk > 1 ? r.d_k[1] : nullptr; a.o.k2 = r.nblk > 2 ? r.d_k[2] : nullptr;
+  a.o.k3 = r.nblk > 3 ? r.d_k[3] : nullptr;
+  a.o.x = r.d_x; a.o.xa = r.d_xa; a.o.sa = r.d_sa; a.o.se = r.d_se; a.o.y = r.d_y; a.o.fx = r.d_fx;
+  a.o.x_new = r.d_x_new; a.o.chi2 = r.d_chi2; a.o.nobs = r.d_nobs; a.o.status = r.d_status;
+  a.o.nblk = r.nblk; a.o.nlev = nlev; a.o.m = m; a.o.n = r.nblk * nlev;
+  a.o.xa_per_profile = r.xa_per_profile != 0; a.o.se_full = r.se_full != 0;
+  a.gamma = r.d_gamma; a.g0 = r.d_g0; a.r = r.d_r; a.kdx = r.d_kdx; a.keep = r.d_keep; a.lin_status = r.d_lin_status;
+  a.active = r.d_active; a.sa_inv = r.d_sa_inv; a.cost = r.d_cost; a.cost_obs = r.d_cost_obs; a.cost_prior = r.d_cost_prior;
+  const size_t lds = call == LmCall::Prepare ? oe::lds_plan(m, a.o.n).total_bytes
+                   : call == LmCall::Solve ? lm::solve_plan(m, a.o.n).total_bytes
+                                           : lm::cost_plan(m, a.o.n, a.o.se_full).total_bytes;
+  if (lds > (size_t)c->lds_max)
+    return fail(MWRT_ERR_UNSUPPORTED, "the optimal-estimation step needs more LDS than this device has per workgroup");
+  if (nprof == 0) return MWRT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = resolve_stream(c, stream);
+  return timed(c, st, [&] {
+    return call == LmCall::Prepare ? lm::launch_lm_prepare(a, nprof, st)
+         : call == LmCall::Solve ? lm::launch_lm_solve(a, nprof, st)
+                                 : lm::launch_lm_cost(a, nprof, st);
+  });
+}
+
+}  // namespace
+
 extern "C" {
 
 int mwrt_version(void) { return MWRT_VERSION; }
@@ -1078,6 +1140,20 @@ int mwrt_oe_step_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m,
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = resolve_stream(c, stream);
   return timed(c, st, [&] { return oe::launch_oe_step(a, nprof, st); });
+}
+
+/* The Levenberg-Marquardt split of the step (csrc/mwrt_oe_lm.hip): oe_lm_call above is the one preamble of its three
+ * entries. */
+size_t mwrt_oe_lm_size(void) { return sizeof(mwrt_oe_lm); }
+
+int mwrt_oe_lm_prepare_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_lm* s, void* stream) {
+  return oe_lm_call(c, nprof, nlev, m, s, stream, LmCall::Prepare);
+}
+int mwrt_oe_lm_solve_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_lm* s, void* stream) {
+  return oe_lm_call(c, nprof, nlev, m, s, stream, LmCall::Solve);
+}
+int mwrt_oe_cost_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_lm* s, void* stream) {
+  return oe_lm_call(c, nprof, nlev, m, s, stream, LmCall::Cost);
 }
 
 int mwrt_selftest_math(mwrt_context* c, int32_t n, const double* x, const double* y_pos,

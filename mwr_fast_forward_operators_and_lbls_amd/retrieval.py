@@ -4,6 +4,7 @@
     ov = OneDVar("R24", frq, elev, sa, se, variables=JacVariables.of(humidity="rh"), blocks=("t", "h"), xa=xa)
     x_new, diag = ov.step(z, p, x, y)            # one K-matrix call + one update, nothing leaves the device
     res = ov.retrieve(z, p, y)                   # iterate from xa until every profile has converged
+    res = ov.retrieve_lm(z, p, y)                # the same with Levenberg-Marquardt damping: no step may raise the cost
 
 The state ``x`` is ``[nprof][nblk][nlev]`` (float64, CUDA, levels ground -> top) with the blocks in the order given:
 ``"t"`` temperature [K], ``"h"`` humidity in the variable ``variables.humidity`` names (e [hPa], rh [fraction] or ppmv),
@@ -13,7 +14,10 @@ then optionally ``"liq"`` and ``"ice"`` in ``variables.cloud`` (g m-3 or kg/kg).
 are rebuilt from the state before every forward run (the rule of mwrt_jac_variables, anchored at ``z[:, 0]``); otherwise
 ``z`` is used as passed.
 
-The update is linear around x: Levenberg-Marquardt damping, the n-form and log-humidity states are not offered."""
+``step`` and ``retrieve`` take the undamped Gauss-Newton update, which is linear around x and may overshoot where the forward
+model is not; ``retrieve_lm`` damps it (Levenberg-Marquardt, Rodgers 2000 eq. 5.36) on the split entries
+``mwrt_oe_lm_prepare_device`` / ``mwrt_oe_lm_solve_device`` / ``mwrt_oe_cost_device``: one linearisation per accepted state,
+one m x m solve per trial.  The n-form and log-humidity states are not offered."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -63,9 +67,41 @@ def _native_oe_step(k_blocks, x, xa, sa, se, y, fx, want_post_var, stream):
     return out
 
 
+def _native_oe_lm_prepare(k_blocks, x, xa, sa, se, y, fx, lin, active, stream):
+    """One ``mwrt_oe_lm_prepare_device`` call: fills ``lin`` (dict of g0, r, kdx, keep, lin_status) in place for the profiles
+    whose ``active`` flag (uint8) is set.  CPU tests substitute the NumPy reference here."""
+    nprof, nblk, nlev = x.shape
+    _native.default_context(x.device.index or 0).oe_lm_prepare_device(
+        nprof, nlev, y.shape[1], [k.data_ptr() for k in k_blocks], x.data_ptr(), xa.data_ptr(), sa.data_ptr(), se.data_ptr(),
+        y.data_ptr(), fx.data_ptr(), lin["g0"].data_ptr(), lin["r"].data_ptr(), lin["kdx"].data_ptr(), lin["keep"].data_ptr(),
+        lin["lin_status"].data_ptr(), d_active=active.data_ptr(), xa_per_profile=xa.dim() == 3, se_full=se.dim() == 2,
+        stream=stream)
+
+
+def _native_oe_lm_solve(k_blocks, x, xa, sa, se, gamma, lin, out, active, stream):
+    """One ``mwrt_oe_lm_solve_device`` call: the damped trial of every active profile into ``out`` (dict of x_new, status) in
+    place.  CPU tests substitute the NumPy reference here."""
+    nprof, nblk, nlev = x.shape
+    _native.default_context(x.device.index or 0).oe_lm_solve_device(
+        nprof, nlev, lin["r"].shape[1], [k.data_ptr() for k in k_blocks], x.data_ptr(), xa.data_ptr(), sa.data_ptr(),
+        se.data_ptr(), gamma.data_ptr(), lin["g0"].data_ptr(), lin["r"].data_ptr(), lin["kdx"].data_ptr(),
+        lin["keep"].data_ptr(), lin["lin_status"].data_ptr(), out["x_new"].data_ptr(), out["status"].data_ptr(),
+        d_active=active.data_ptr(), xa_per_profile=xa.dim() == 3, se_full=se.dim() == 2, stream=stream)
+
+
+def _native_oe_cost(x, xa, se, y, fx, keep, sa_inv, cost, active, stream):
+    """One ``mwrt_oe_cost_device`` call: J at ``x`` on the rows ``keep`` names into ``cost`` in place, active profiles only.
+    CPU tests substitute the NumPy reference here."""
+    nprof, nblk, nlev = x.shape
+    _native.default_context(x.device.index or 0).oe_cost_device(
+        nprof, nlev, y.shape[1], nblk, x.data_ptr(), xa.data_ptr(), se.data_ptr(), y.data_ptr(), fx.data_ptr(),
+        keep.data_ptr(), sa_inv.data_ptr(), cost.data_ptr(), d_active=active.data_ptr(), xa_per_profile=xa.dim() == 3,
+        se_full=se.dim() == 2, stream=stream)
+
+
 @dataclass
 class Retrieval:
-    """What ``OneDVar.retrieve`` returns; every field is a tensor on the state's device."""
+    """What ``OneDVar.retrieve`` and ``retrieve_lm`` return; every field is a tensor on the state's device."""
     x: torch.Tensor            # [nprof][nblk][nlev] the retrieved state
     chi2: torch.Tensor         # [nprof] d^T G^-1 d of each profile's last step
     dfs: torch.Tensor          # [nprof] degrees of freedom for signal
@@ -74,6 +110,8 @@ class Retrieval:
     nobs: torch.Tensor         # [nprof] int32 observations used
     iterations: torch.Tensor   # [nprof] int32 steps taken before the profile was frozen
     converged: torch.Tensor    # [nprof] bool
+    cost: Optional[torch.Tensor] = None    # [nprof] J at x (``retrieve_lm`` only)
+    gamma: Optional[torch.Tensor] = None   # [nprof] the damping factor the profile ended with (``retrieve_lm`` only)
 
 
 class OneDVar:
@@ -98,6 +136,15 @@ class OneDVar:
         if tuple(self.se.shape) not in ((self.m,), (self.m, self.m)):
             raise ValueError(f"se: expected [{self.m}] or [{self.m}][{self.m}], got {tuple(self.se.shape)}")
         self._sigma = torch.sqrt(torch.diagonal(self.sa)).reshape(nblk, -1)
+        self._sa_inv = None
+
+    @property
+    def sa_inv(self):
+        """Sa^-1 for the cost's prior term: float64, symmetrised, formed on first use (``retrieve_lm`` alone needs it)."""
+        if self._sa_inv is None:
+            inv = torch.linalg.inv(self.sa.to(torch.float64))
+            self._sa_inv = (0.5 * (inv + inv.T)).contiguous()
+        return self._sa_inv
 
     # -- the state in the operator's inputs -----------------------------------------------------------------------------
     def physical(self, z, p, x):
@@ -191,3 +238,76 @@ class OneDVar:
                 break
         return Retrieval(x=x, chi2=keep["chi2"], dfs=keep["dfs"], post_var=keep["post_var"], status=keep["status"],
                          nobs=keep["nobs"], iterations=iters, converged=converged)
+
+    # -- the damped iteration ------------------------------------------------------------------------------------------
+    def _linearise(self, z, p, x):
+        """One K-matrix call at ``x`` -> (K blocks in the state's order, F(x) [nprof][m]); fresh tensors every call."""
+        zz, t, rh, dl, di = self.physical(z, p, x)
+        tb, _, rows = _native_k_matrix(self.model, zz.contiguous(), p.contiguous(), t, rh, dl, di, self.frq, self.elev,
+                                       self.variables, self.blocks, self._stream(x))
+        return [rows[b] for b in self.blocks], tb.reshape(x.shape[0], self.m)
+
+    def retrieve_lm(self, z, p, y, x0=None, max_iter=20, tol=0.05, gamma0=1.0, up=10.0, down=10.0, gamma_max=1e8) -> Retrieval:
+        """Levenberg-Marquardt iteration from ``x0`` (default: the prior), per profile and wholly on the device and torch's
+        current stream.  With J = r^T Se^-1 r + (x - xa)^T Sa^-1 (x - xa), every iteration
+          1  linearises the profiles whose state changed: one K-matrix call, ``prepare`` and the cost J at x;
+          2  takes the damped trial of every active profile with its own gamma (``solve``), clamps humidity and cloud to >= 0,
+             runs the forward model at the trial (into tensors of its own: K(x) stays) and takes J there on the
+             linearisation's rows;
+          3  accepts where J_trial <= J (x <- trial, gamma <- gamma / ``down``), otherwise keeps x and its linearisation and
+             sets gamma <- gamma * ``up``.
+        A profile is frozen as converged when an accepted move is below ``tol`` sqrt(diag Sa) everywhere, and as failed when
+        gamma exceeds ``gamma_max`` or its linearisation's status is not 1.  One scalar leaves the device per iteration (is
+        any profile active; does any state want a new K).  Afterwards one undamped ``mwrt_oe_step_device`` call at the
+        final states fills chi2, dfs, post_var, nobs and status -- Rodgers' diagnostics are those of gamma = 0 -- and its
+        x_new is discarded.  ``iterations`` counts the trials a profile took."""
+        nprof, m = y.shape[0], self.m
+        x = ((self.xa.expand(nprof, -1, -1) if self.xa.dim() == 2 else self.xa).clone() if x0 is None else x0.clone()).contiguous()
+        dev, stream = x.device, self._stream(x)
+        yv = y.reshape(nprof, m).contiguous()
+        f64, u8 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.uint8, device=dev)
+        lin = dict(g0=torch.zeros((nprof, m * (m + 1) // 2), **f64), r=torch.zeros((nprof, m), **f64),
+                   kdx=torch.zeros((nprof, m), **f64), keep=torch.zeros((nprof, m), **u8), lin_status=torch.zeros(nprof, **u8))
+        trial = dict(x_new=torch.zeros_like(x), status=torch.zeros(nprof, **u8))
+        cost = torch.full((nprof,), float("inf"), **f64)
+        cost_try = torch.full((nprof,), float("inf"), **f64)
+        gamma = torch.full((nprof,), float(gamma0), **f64)
+        active = torch.ones(nprof, dtype=torch.bool, device=dev)
+        stale = torch.ones(nprof, dtype=torch.bool, device=dev)          # the state changed since its linearisation
+        converged = torch.zeros(nprof, dtype=torch.bool, device=dev)
+        iters = torch.zeros(nprof, dtype=torch.int32, device=dev)
+        k_blocks = fx = None
+        relin = True
+        for _ in range(int(max_iter)):
+            if relin:
+                k_blocks, fx = self._linearise(z, p, x)
+                mask = (active & stale).to(torch.uint8)
+                _native_oe_lm_prepare(k_blocks, x, self.xa, self.sa, self.se, yv, fx, lin, mask, stream)
+                _native_oe_cost(x, self.xa, self.se, yv, fx, lin["keep"], self.sa_inv, cost, mask, stream)
+                stale = torch.zeros_like(stale)
+                active = active & (lin["lin_status"] == 1)
+            mask = active.to(torch.uint8)
+            _native_oe_lm_solve(k_blocks, x, self.xa, self.sa, self.se, gamma, lin, trial, mask, stream)
+            ok = active & (trial["status"] == 1)
+            x_try = self.clamp(torch.where(ok[:, None, None], trial["x_new"], x)).contiguous()
+            fx_try = self.forward(z, p, x_try)[0].reshape(nprof, m)
+            _native_oe_cost(x_try, self.xa, self.se, yv, fx_try, lin["keep"], self.sa_inv, cost_try, mask, stream)
+            accept = ok & (cost_try <= cost)
+            move = ((x_try - x).abs() / self._sigma).amax(dim=(1, 2))
+            iters = iters + active.to(torch.int32)
+            x = torch.where(accept[:, None, None], x_try, x).contiguous()
+            cost = torch.where(accept, cost_try, cost)
+            gamma = torch.where(accept, gamma / down, torch.where(active, gamma * up, gamma))
+            done = accept & (move < tol)
+            converged = converged | done
+            stale = stale | accept
+            active = active & ~done & ~(gamma > gamma_max)
+            flag = int((active.any().to(torch.int32) + 2 * stale.any().to(torch.int32)).item())
+            relin = bool(flag & 2)
+            if not flag & 1:
+                break
+        if relin:
+            k_blocks, fx = self._linearise(z, p, x)
+        d = _native_oe_step(k_blocks, x, self.xa, self.sa, self.se, yv, fx, True, stream)
+        return Retrieval(x=x, chi2=d["chi2"], dfs=d["dfs"], post_var=d["post_var"], status=d["status"], nobs=d["nobs"],
+                         iterations=iters, converged=converged, cost=cost, gamma=gamma)
