@@ -555,6 +555,69 @@ int mwrt_oe_cost_device(mwrt_context* ctx, int64_t nprof, int32_t nlev, int32_t 
 /* sizeof(mwrt_oe_lm) as compiled into the library (binding self-check). */
 size_t mwrt_oe_lm_size(void);
 
+/* What the step says about itself (Rodgers 2000, ch. 3): the gain matrix, the averaging kernel, the full
+ * posterior covariance and the error budget, per profile, at gamma = 0 -- Rodgers' diagnostics are those of the undamped
+ * step.  With W = K Sa [m][n] and G = K Sa K^T + Se = L L^T on the rows kept (the row rule and the statuses are those of
+ * mwrt_oe_step_device: a dropped row is algebraically deleted),
+ *     gain^T = G^-1 W                    [m][n]   row i is the contribution function d x^ / d y_i of observation i
+ *     A      = gain K                    [n][n]   A[j][k] = sum_i gain[i][j] K[i][k], the averaging kernel d x^ / d x
+ *     S^     = Sa - gain W               [n][n]   S^[j][k] = Sa[j][k] - sum_i gain[i][j] W[i][k], the posterior covariance
+ *     noise_var  = diag(gain Se gain^T)  [n]      the measurement-noise part of diag S^
+ *     smooth_var = diag((A - I) Sa (A - I)^T) = diag S^ - noise_var   [n]   the smoothing part
+ *     avk_diag   = diag A                [n]
+ *     dfs_block[b] = sum of avk_diag over block b;  their sum over b is tr(A), the step's dfs
+ *   mwrt_oe_gain_device      the gain and everything that is a vector: one launch, one workgroup per profile
+ *   mwrt_oe_product_device   A or S^ (or a window of their rows) from the gain entry's d_gain, d_keep and d_ksa
+ * One record, mwrt_oe_char, serves both.  All DEVICE pointers, float64 unless stated.
+ * mwrt_oe_gain_device reads the inputs of mwrt_oe_step (d_k, d_x, d_xa, d_sa, d_se, d_y, d_fx, nblk, xa_per_profile,
+ * se_full; the same shapes) and writes
+ *   d_status     [nprof] uint8           as mwrt_oe_step_device                                    required
+ *   d_gain       [nprof][m][n]           gain^T; 0 in a dropped row                                optional
+ *   d_ksa        [nprof][m][n]           W = K Sa; 0 in a dropped row                              optional
+ *   d_keep       [nprof][m] uint8        1: the row is used                                        optional
+ *   d_avk_diag, d_noise_var, d_smooth_var   [nprof][nblk][nlev]                                    optional
+ *   d_dfs_block  [nprof][nblk]                                                                     optional
+ *   d_nobs       [nprof] int32           m_used                                                    optional
+ *   Every output but d_status is optional (NULL: not wanted), but at least one of them must be given.
+ *   status 3 (nothing observed): gain 0, W 0, keep 0, avk_diag 0, dfs_block 0, noise_var 0, smooth_var = diag Sa, nobs 0.
+ *   status 0 and 2: every floating-point output of the profile NaN, keep 0; nobs as in the step (0, m_used).
+ * mwrt_oe_product_device reads what `product` names and writes rows row_begin .. row_begin + row_count - 1 of the n x n
+ * result to d_out [nprof][row_count][n]; row_count == 0 with row_begin == 0 means all n rows.
+ *   MWRT_OE_PRODUCT_AVK        d_out = gain K        reads d_gain, d_keep, d_k
+ *   MWRT_OE_PRODUCT_POST_COV   d_out = Sa - gain W   reads d_gain, d_keep, d_ksa, d_sa
+ *   A row of K or W whose d_keep is 0 is never read (a dropped row of K may hold NaN); it contributes nothing.  An element
+ *   of the result is the same bit for bit whatever window it is computed in.  A profile whose gain is NaN (status 0, 2)
+ *   has keep 0 throughout, so its A is 0 and its S^ is Sa: read d_status before using either.
+ * Determinism: a profile's outputs depend on neither its batch-mates nor nprof (fixed summation orders, no atomics), and
+ *   the gain does not depend on which optional outputs are asked for.
+ * The record starts with its own size: fields at or beyond struct_size (and a field it ends inside) are taken as NULL / 0.
+ * Limits: m <= MWRT_OE_MAX_M, nlev <= MWRT_MAX_LEVELS: MWRT_ERR_UNSUPPORTED with the limit in the error text (and for a
+ *   product of more than 2^31 - 1 tiles of 64 x 64 in one call).  MWRT_ERR_INVALID_ARGUMENT: a NULL pointer among those the
+ *   call reads or must write (gain: the inputs and d_status, and all of the optional outputs at once; product: d_gain,
+ *   d_keep, d_out and what its product reads), nblk outside 1 .. 4, reserved or reserved2 != 0, nlev < 1, m < 1,
+ *   nprof < 0, struct_size smaller than the fixed part (24 bytes); product alone: an unknown `product`, row_begin < 0,
+ *   row_count < 0, a window that runs over n, row_count == 0 with row_begin != 0.
+ * Streams as every *_device entry.  The calls never allocate and never synchronise; the gain kernel's dynamic-LDS limit is
+ *   raised once per device and size above 64 KiB (m >= 65), so a repeat call of the same size is the launch alone.
+ *   (MWRT_VERSION stays 301: additions.) */
+#define MWRT_OE_PRODUCT_AVK       0   /* d_out = gain^T K            (reads d_gain, d_keep, d_k)        */
+#define MWRT_OE_PRODUCT_POST_COV  1   /* d_out = Sa - gain^T (K Sa)  (reads d_gain, d_keep, d_ksa, d_sa) */
+typedef struct mwrt_oe_char {
+  uint32_t struct_size;        /* sizeof(mwrt_oe_char) of the caller; fields beyond it are not read */
+  int32_t  nblk, xa_per_profile, se_full, reserved;
+  const double* d_k[4];
+  const double *d_x, *d_xa, *d_sa, *d_se, *d_y, *d_fx;
+  uint8_t* d_status;                                   /* gain entry: required                        */
+  double *d_gain, *d_ksa;  uint8_t* d_keep;            /* [nprof][m][n], [nprof][m][n], [nprof][m]     */
+  double *d_avk_diag, *d_dfs_block, *d_noise_var, *d_smooth_var;  int32_t* d_nobs;
+  int32_t product, row_begin, row_count, reserved2;    /* product entry                               */
+  double* d_out;                                       /* [nprof][rows][n]                            */
+} mwrt_oe_char;
+int mwrt_oe_gain_device(mwrt_context* ctx, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_char* s, void* stream);
+int mwrt_oe_product_device(mwrt_context* ctx, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_char* s, void* stream);
+/* sizeof(mwrt_oe_char) as compiled into the library (binding self-check). */
+size_t mwrt_oe_char_size(void);
+
 /* Diagnostic: evaluates the kernels' own exp / log / division helpers (fexp, flog, fdiv, fdiv1) on
  * host arrays x[n], y_pos[n] (y > 0), so their accuracy can be checked against libm. */
 int mwrt_selftest_math(mwrt_context* ctx, int32_t n, const double* x, const double* y_pos,

@@ -77,6 +77,20 @@ class MwrtOeLm(ctypes.Structure):
             "d_active", "d_sa_inv", "d_cost", "d_cost_obs", "d_cost_prior", "d_x_new", "d_status", "d_chi2", "d_nobs")]
 
 
+class MwrtOeChar(ctypes.Structure):
+    """include/mwrt.h mwrt_oe_char: the record of the gain and product entries (device pointers)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("nblk", ctypes.c_int32), ("xa_per_profile", ctypes.c_int32),
+                ("se_full", ctypes.c_int32), ("reserved", ctypes.c_int32), ("d_k", ctypes.c_void_p * 4)] + [
+        (name, ctypes.c_void_p) for name in (
+            "d_x", "d_xa", "d_sa", "d_se", "d_y", "d_fx", "d_status", "d_gain", "d_ksa", "d_keep", "d_avk_diag",
+            "d_dfs_block", "d_noise_var", "d_smooth_var", "d_nobs")] + [
+        (name, ctypes.c_int32) for name in ("product", "row_begin", "row_count", "reserved2")] + [
+        ("d_out", ctypes.c_void_p)]
+
+
+#: include/mwrt.h MWRT_OE_PRODUCT_*: what mwrt_oe_product_device forms
+OE_PRODUCT_AVK, OE_PRODUCT_POST_COV = 0, 1
+
 #: include/mwrt.h MWRT_OE_MAX_M: observations per profile of one optimal-estimation step
 OE_MAX_M = 140
 
@@ -136,6 +150,9 @@ SIGNATURES = {
     "mwrt_oe_lm_solve_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeLm), _vp]),
     "mwrt_oe_cost_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeLm), _vp]),
     "mwrt_oe_lm_size": (ctypes.c_size_t, []),
+    "mwrt_oe_gain_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeChar), _vp]),
+    "mwrt_oe_product_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeChar), _vp]),
+    "mwrt_oe_char_size": (ctypes.c_size_t, []),
     "mwrt_set_absorption_mode": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_set_chunk_width": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_selftest_math": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -197,6 +214,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
             raise NativeLibraryMissing("mwrt_oe_step layout mismatch between libmwrt.so and _native.py")
         if lib.mwrt_oe_lm_size() != ctypes.sizeof(MwrtOeLm):
             raise NativeLibraryMissing("mwrt_oe_lm layout mismatch between libmwrt.so and _native.py")
+        if lib.mwrt_oe_char_size() != ctypes.sizeof(MwrtOeChar):
+            raise NativeLibraryMissing("mwrt_oe_char layout mismatch between libmwrt.so and _native.py")
         if lib.mwrt_version() != MWRT_VERSION:
             raise NativeLibraryMissing(f"libmwrt.so is version {lib.mwrt_version()}, this binding needs {MWRT_VERSION}: "
                                        "rebuild (python -c 'import __graft_entry__ as g; g.build()')")
@@ -582,6 +601,42 @@ class Context:
                     struct_size, dict(d_x=d_x, d_xa=d_xa, d_se=d_se, d_y=d_y, d_fx=d_fx, d_keep=d_keep, d_sa_inv=d_sa_inv,
                                       d_cost=d_cost, d_cost_obs=d_cost_obs, d_cost_prior=d_cost_prior, d_status=d_status,
                                       d_active=d_active))
+
+    def _oe_char(self, entry, nprof, nlev, m, d_k, xa_per_profile, se_full, stream, reserved, struct_size, fields):
+        d_k = list(d_k)
+        rec = MwrtOeChar()
+        rec.struct_size = ctypes.sizeof(MwrtOeChar) if struct_size is None else int(struct_size)
+        rec.nblk, rec.xa_per_profile, rec.se_full, rec.reserved = len(d_k), int(bool(xa_per_profile)), int(bool(se_full)), int(reserved)
+        for b, k in enumerate(d_k[:4]):
+            rec.d_k[b] = int(k) if k is not None else None
+        for name, v in fields.items():
+            setattr(rec, name, int(v) if v is not None else (0 if name in ("product", "row_begin", "row_count", "reserved2") else None))
+        self._check(getattr(self._lib, entry)(self._handle, int(nprof), int(nlev), int(m), ctypes.byref(rec), _stream(stream)),
+                    entry)
+
+    @_serialised
+    def oe_gain_device(self, nprof, nlev, m, d_k, d_x, d_xa, d_sa, d_se, d_y, d_fx, d_status, d_gain=None, d_ksa=None,
+                       d_keep=None, d_avk_diag=None, d_dfs_block=None, d_noise_var=None, d_smooth_var=None, d_nobs=None,
+                       xa_per_profile=False, se_full=False, stream=None, reserved=0, reserved2=0, struct_size=None):
+        """The gain matrix and the error budget of one step (include/mwrt.h mwrt_oe_gain_device): the inputs of
+        ``oe_step_device``; ``d_status [nprof]`` (uint8) required, and at least one of ``d_gain`` and ``d_ksa``
+        ``[nprof][m][n]``, ``d_keep [nprof][m]`` (uint8), ``d_avk_diag`` / ``d_noise_var`` / ``d_smooth_var``
+        ``[nprof][nblk][nlev]``, ``d_dfs_block [nprof][nblk]`` and ``d_nobs [nprof]`` (int32)."""
+        self._oe_char("mwrt_oe_gain_device", nprof, nlev, m, d_k, xa_per_profile, se_full, stream, reserved, struct_size,
+                      dict(d_x=d_x, d_xa=d_xa, d_sa=d_sa, d_se=d_se, d_y=d_y, d_fx=d_fx, d_status=d_status, d_gain=d_gain,
+                           d_ksa=d_ksa, d_keep=d_keep, d_avk_diag=d_avk_diag, d_dfs_block=d_dfs_block,
+                           d_noise_var=d_noise_var, d_smooth_var=d_smooth_var, d_nobs=d_nobs, reserved2=reserved2))
+
+    @_serialised
+    def oe_product_device(self, nprof, nlev, m, product, d_gain, d_keep, d_out, d_k, d_ksa=None, d_sa=None, row_begin=0,
+                          row_count=0, stream=None, reserved=0, reserved2=0, struct_size=None):
+        """The averaging kernel (``OE_PRODUCT_AVK``: reads ``d_k``) or the posterior covariance (``OE_PRODUCT_POST_COV``:
+        reads ``d_ksa`` and ``d_sa``; ``d_k`` then only tells the number of blocks and may hold None) from a gain entry's
+        ``d_gain`` and ``d_keep`` (include/mwrt.h mwrt_oe_product_device), rows ``row_begin .. row_begin + row_count - 1``
+        into ``d_out [nprof][row_count][n]``; ``row_count=0`` with ``row_begin=0`` is all n rows."""
+        self._oe_char("mwrt_oe_product_device", nprof, nlev, m, d_k, False, False, stream, reserved, struct_size,
+                      dict(d_gain=d_gain, d_keep=d_keep, d_out=d_out, d_ksa=d_ksa, d_sa=d_sa, product=product,
+                           row_begin=row_begin, row_count=row_count, reserved2=reserved2))
 
     def layer_tau_pitch(self, nf: int) -> int:
         """Doubles between consecutive levels of a layer-optical-depth array for nf frequencies (multiple of 16)."""

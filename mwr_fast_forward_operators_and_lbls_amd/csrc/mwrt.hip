@@ -4,11 +4,12 @@
 // returns 0 and mwrt_create() fails with MWRT_ERR_NO_DEVICE.
 //
 // Host code only: streams, caches, argument checks and the choice of launch.  Every kernel lives in another unit
-// (mwrt_inst.hip, mwrt_tl.hip, mwrt_oe.hip, mwrt_oe_lm.hip, mwrt_aux.hip) and is reached through the launchers the headers below declare.
+// (mwrt_inst.hip, mwrt_tl.hip, mwrt_oe.hip, mwrt_oe_lm.hip, mwrt_oe_char.hip, mwrt_aux.hip) and is reached through the launchers the headers below declare.
 #include "mwrt_args.hip.h"
 #include "mwrt_tl.hip.h"
 #include "mwrt_oe.hip.h"
 #include "mwrt_oe_lm.hip.h"
+#include "mwrt_oe_char.hip.h"
 #include "mwrt_plan.h"
 
 #include <cmath>
@@ -614,6 +615,93 @@ int oe_lm_call(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mw
 
 }  // namespace
 
+// The two entries of the characterisation (csrc/mwrt_oe_char.hip) share one record and one preamble, in the order of
+// mwrt_oe_step_device: arguments, then limits, then the device and the stream.
+namespace {
+
+enum class CharCall { Gain, Product };
+
+int oe_char_call(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_char* s, void* stream, CharCall call) {
+  if (!c || !s) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context or mwrt_oe_char");
+  constexpr size_t fixed = offsetof(mwrt_oe_char, d_k);
+  if (s->struct_size < fixed)
+    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_char.struct_size too small for the fixed part (through reserved)");
+  mwrt_oe_char r{};                                    // fields at or beyond the caller's struct_size stay NULL / 0
+  // ... and so does a field the size ends inside: pointers beyond the fixed part, but for the four int32 of the product
+  size_t len = s->struct_size < sizeof r ? s->struct_size : sizeof r;
+  constexpr size_t ints = offsetof(mwrt_oe_char, product), ints_end = offsetof(mwrt_oe_char, d_out);
+  len -= (len > ints && len < ints_end) ? (len - ints) % sizeof(int32_t) : (len - fixed) % sizeof(void*);
+  std::memcpy(&r, s, len);
+  if (nprof < 0 || nlev < 1 || m < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "nprof < 0, nlev < 1 or m < 1");
+  if (r.nblk < 1 || r.nblk > 4) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_char.nblk must be 1 .. 4");
+  if (r.reserved != 0 || r.reserved2 != 0) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_char.reserved and reserved2 must be 0");
+  const int64_t n64 = (int64_t)r.nblk * nlev;
+  int32_t rows = 0;
+  if (call == CharCall::Gain) {
+    bool buffers = r.d_x && r.d_xa && r.d_sa && r.d_se && r.d_y && r.d_fx && r.d_status;
+    for (int b = 0; b < r.nblk; ++b) buffers = buffers && r.d_k[b];
+    if (!buffers) return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
+    if (!(r.d_gain || r.d_ksa || r.d_keep || r.d_avk_diag || r.d_dfs_block || r.d_noise_var || r.d_smooth_var || r.d_nobs))
+      return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_gain_device: no output asked for beside d_status");
+  } else {
+    if (r.product != MWRT_OE_PRODUCT_AVK && r.product != MWRT_OE_PRODUCT_POST_COV)
+      return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_char.product must be MWRT_OE_PRODUCT_AVK or MWRT_OE_PRODUCT_POST_COV");
+    bool buffers = r.d_gain && r.d_keep && r.d_out;
+    if (r.product == MWRT_OE_PRODUCT_AVK)
+      for (int b = 0; b < r.nblk; ++b) buffers = buffers && r.d_k[b];
+    else
+      buffers = buffers && r.d_ksa && r.d_sa;
+    if (!buffers) return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
+    if (r.row_begin < 0 || r.row_count < 0 || (r.row_count == 0 && r.row_begin != 0) ||
+        (int64_t)r.row_begin + r.row_count > n64)
+      return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_char: rows row_begin .. row_begin + row_count - 1 must lie in 0 .. n - 1 "
+                                             "(row_count 0 with row_begin 0: all rows)");
+    rows = r.row_count == 0 ? (int32_t)(n64 > 2147483647LL ? 0 : n64) : r.row_count;
+  }
+  if (nlev > MWRT_MAX_LEVELS)
+    return fail(MWRT_ERR_UNSUPPORTED, "nlev > MWRT_MAX_LEVELS (" + std::to_string(MWRT_MAX_LEVELS) + ")");
+  if (m > MWRT_OE_MAX_M)
+    return fail(MWRT_ERR_UNSUPPORTED, "m > MWRT_OE_MAX_M (" + std::to_string(MWRT_OE_MAX_M) + " observations per profile: G lives in LDS)");
+  if (nprof > 2147483647LL) return fail(MWRT_ERR_UNSUPPORTED, "nprof exceeds grid limit");
+  const int n = (int)n64;
+  if (call == CharCall::Gain) {
+    oec::GainArgs a{};
+    a.o.k0 = r.d_k[0]; a.o.k1 = r.nblk > 1 ? r.d_k[1] : nullptr; a.o.k2 = r.nblk > 2 ? r.d_k[2] : nullptr;
+    a.o.k3 = r.nblk > 3 ? r.d_k[3] : nullptr;
+    a.o.x = r.d_x; a.o.xa = r.d_xa; a.o.sa = r.d_sa; a.o.se = r.d_se; a.o.y = r.d_y; a.o.fx = r.d_fx;
+    a.o.nobs = r.d_nobs; a.o.status = r.d_status;
+    a.o.nblk = r.nblk; a.o.nlev = nlev; a.o.m = m; a.o.n = n;
+    a.o.xa_per_profile = r.xa_per_profile != 0; a.o.se_full = r.se_full != 0;
+    a.gain = r.d_gain; a.ksa = r.d_ksa; a.keep = r.d_keep; a.avk_diag = r.d_avk_diag; a.noise_var = r.d_noise_var;
+    a.smooth_var = r.d_smooth_var; a.dfs_block = r.d_dfs_block;
+    if (oec::gain_plan(m).total_bytes > (size_t)c->lds_max)
+      return fail(MWRT_ERR_UNSUPPORTED, "the optimal-estimation gain needs more LDS than this device has per workgroup");
+    if (nprof == 0) return MWRT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = resolve_stream(c, stream);
+    return timed(c, st, [&] { return oec::launch_char_gain(a, nprof, st); });
+  }
+  oec::ProductArgs a{};
+  a.left = r.d_gain; a.keep = r.d_keep; a.out = r.d_out;
+  if (r.product == MWRT_OE_PRODUCT_AVK) {
+    a.r0 = r.d_k[0]; a.r1 = r.nblk > 1 ? r.d_k[1] : nullptr; a.r2 = r.nblk > 2 ? r.d_k[2] : nullptr;
+    a.r3 = r.nblk > 3 ? r.d_k[3] : nullptr;
+    a.rcols = nlev;
+  } else {
+    a.r0 = r.d_ksa; a.rcols = n; a.sa = r.d_sa;
+  }
+  a.m = m; a.n = n; a.row_begin = r.row_begin; a.rows = rows;
+  a.tiles_x = (n + oec::TILE - 1) / oec::TILE; a.tiles_y = (rows + oec::TILE - 1) / oec::TILE;
+  if ((int64_t)a.tiles_x * a.tiles_y * nprof > 2147483647LL)
+    return fail(MWRT_ERR_UNSUPPORTED, "mwrt_oe_product_device: more than 2147483647 tiles of 64 x 64 in one call (use row windows)");
+  if (nprof == 0) return MWRT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = resolve_stream(c, stream);
+  return timed(c, st, [&] { return oec::launch_char_product(a, nprof, st); });
+}
+
+}  // namespace
+
 extern "C" {
 
 int mwrt_version(void) { return MWRT_VERSION; }
@@ -1154,6 +1242,16 @@ int mwrt_oe_lm_solve_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_
 }
 int mwrt_oe_cost_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_lm* s, void* stream) {
   return oe_lm_call(c, nprof, nlev, m, s, stream, LmCall::Cost);
+}
+
+/* The characterisation of the step (csrc/mwrt_oe_char.hip): oe_char_call above is the one preamble of its two entries. */
+size_t mwrt_oe_char_size(void) { return sizeof(mwrt_oe_char); }
+
+int mwrt_oe_gain_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_char* s, void* stream) {
+  return oe_char_call(c, nprof, nlev, m, s, stream, CharCall::Gain);
+}
+int mwrt_oe_product_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_char* s, void* stream) {
+  return oe_char_call(c, nprof, nlev, m, s, stream, CharCall::Product);
 }
 
 int mwrt_selftest_math(mwrt_context* c, int32_t n, const double* x, const double* y_pos,

@@ -5,6 +5,7 @@
     x_new, diag = ov.step(z, p, x, y)            # one K-matrix call + one update, nothing leaves the device
     res = ov.retrieve(z, p, y)                   # iterate from xa until every profile has converged
     res = ov.retrieve_lm(z, p, y)                # the same with Levenberg-Marquardt damping: no step may raise the cost
+    ch = ov.characterise(z, p, res.x, y, avk=True, post_cov=True)   # gain, averaging kernel, posterior, error budget
 
 The state ``x`` is ``[nprof][nblk][nlev]`` (float64, CUDA, levels ground -> top) with the blocks in the order given:
 ``"t"`` temperature [K], ``"h"`` humidity in the variable ``variables.humidity`` names (e [hPa], rh [fraction] or ppmv),
@@ -17,7 +18,9 @@ are rebuilt from the state before every forward run (the rule of mwrt_jac_variab
 ``step`` and ``retrieve`` take the undamped Gauss-Newton update, which is linear around x and may overshoot where the forward
 model is not; ``retrieve_lm`` damps it (Levenberg-Marquardt, Rodgers 2000 eq. 5.36) on the split entries
 ``mwrt_oe_lm_prepare_device`` / ``mwrt_oe_lm_solve_device`` / ``mwrt_oe_cost_device``: one linearisation per accepted state,
-one m x m solve per trial.  The n-form and log-humidity states are not offered."""
+one m x m solve per trial.  ``characterise`` returns what the undamped step at a state says about itself (Rodgers 2000, ch. 3;
+DESIGN.md 4.6.2) on ``mwrt_oe_gain_device`` / ``mwrt_oe_product_device``.  The n-form and log-humidity states are not
+offered."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -97,6 +100,59 @@ def _native_oe_cost(x, xa, se, y, fx, keep, sa_inv, cost, active, stream):
         nprof, nlev, y.shape[1], nblk, x.data_ptr(), xa.data_ptr(), se.data_ptr(), y.data_ptr(), fx.data_ptr(),
         keep.data_ptr(), sa_inv.data_ptr(), cost.data_ptr(), d_active=active.data_ptr(), xa_per_profile=xa.dim() == 3,
         se_full=se.dim() == 2, stream=stream)
+
+
+def _native_oe_gain(k_blocks, x, xa, sa, se, y, fx, stream):
+    """One ``mwrt_oe_gain_device`` call with every output -> dict(gain, ksa, keep, avk_diag, dfs_block, noise_var,
+    smooth_var, status, nobs).
+
+    The single place the gain reaches the native library: CPU tests substitute the NumPy reference here."""
+    nprof, nblk, nlev = x.shape
+    m, n = y.shape[1], nblk * nlev
+    f64 = dict(dtype=torch.float64, device=x.device)
+    out = dict(gain=torch.empty((nprof, m, n), **f64), ksa=torch.empty((nprof, m, n), **f64),
+               keep=torch.empty((nprof, m), dtype=torch.uint8, device=x.device), avk_diag=torch.empty_like(x),
+               dfs_block=torch.empty((nprof, nblk), **f64), noise_var=torch.empty_like(x), smooth_var=torch.empty_like(x),
+               status=torch.empty(nprof, dtype=torch.uint8, device=x.device),
+               nobs=torch.empty(nprof, dtype=torch.int32, device=x.device))
+    _native.default_context(x.device.index or 0).oe_gain_device(
+        nprof, nlev, m, [k.data_ptr() for k in k_blocks], x.data_ptr(), xa.data_ptr(), sa.data_ptr(), se.data_ptr(),
+        y.data_ptr(), fx.data_ptr(), out["status"].data_ptr(), d_gain=out["gain"].data_ptr(), d_ksa=out["ksa"].data_ptr(),
+        d_keep=out["keep"].data_ptr(), d_avk_diag=out["avk_diag"].data_ptr(), d_dfs_block=out["dfs_block"].data_ptr(),
+        d_noise_var=out["noise_var"].data_ptr(), d_smooth_var=out["smooth_var"].data_ptr(), d_nobs=out["nobs"].data_ptr(),
+        xa_per_profile=xa.dim() == 3, se_full=se.dim() == 2, stream=stream)
+    return out
+
+
+def _native_oe_product(product, gain, keep, k_blocks, ksa, sa, rows, stream):
+    """One ``mwrt_oe_product_device`` call -> [nprof][count][n]: ``product`` "avk" (gain K) or "post_cov" (Sa - gain W),
+    rows ``rows = (begin, count)`` ((0, 0): all).
+
+    The single place the products reach the native library: CPU tests substitute the NumPy reference here."""
+    nprof, m, n = gain.shape
+    nlev = n // len(k_blocks)
+    out = torch.empty((nprof, rows[1] or n, n), dtype=torch.float64, device=gain.device)
+    _native.default_context(gain.device.index or 0).oe_product_device(
+        nprof, nlev, m, _native.OE_PRODUCT_AVK if product == "avk" else _native.OE_PRODUCT_POST_COV, gain.data_ptr(),
+        keep.data_ptr(), out.data_ptr(), [k.data_ptr() for k in k_blocks], d_ksa=ksa.data_ptr(), d_sa=sa.data_ptr(),
+        row_begin=rows[0], row_count=rows[1], stream=stream)
+    return out
+
+
+@dataclass
+class Characterisation:
+    """What ``OneDVar.characterise`` returns: the undamped step at a state, described (Rodgers 2000, ch. 3; include/mwrt.h
+    mwrt_oe_gain_device).  Every field is a tensor on the state's device; n = nblk * nlev, state index = block * nlev + level."""
+    gain: torch.Tensor         # [nprof][m][n] row i: the contribution function d x^ / d y_i; 0 in a dropped row
+    avk_diag: torch.Tensor     # [nprof][nblk][nlev] diagonal of the averaging kernel
+    dfs_block: torch.Tensor    # [nprof][nblk] degrees of freedom for signal per state block; their sum is the step's dfs
+    noise_var: torch.Tensor    # [nprof][nblk][nlev] measurement-noise part of the posterior variance
+    smooth_var: torch.Tensor   # [nprof][nblk][nlev] smoothing part; noise_var + smooth_var = diag of the posterior
+    status: torch.Tensor       # [nprof] uint8, mwrt_oe_step_device's status
+    nobs: torch.Tensor         # [nprof] int32 observations used
+    keep: torch.Tensor         # [nprof][m] uint8, 1: the observation was used
+    avk: Optional[torch.Tensor] = None        # [nprof][rows][n] averaging kernel d x^ / d x (``avk=True``)
+    post_cov: Optional[torch.Tensor] = None   # [nprof][rows][n] posterior covariance (``post_cov=True``)
 
 
 @dataclass
@@ -238,6 +294,34 @@ class OneDVar:
                 break
         return Retrieval(x=x, chi2=keep["chi2"], dfs=keep["dfs"], post_var=keep["post_var"], status=keep["status"],
                          nobs=keep["nobs"], iterations=iters, converged=converged)
+
+    # -- what the step says about itself --------------------------------------------------------------------------------
+    def characterise(self, z, p, x, y, avk=False, post_cov=False, rows=None) -> Characterisation:
+        """The gain matrix, the averaging-kernel diagonal, the degrees of freedom per block and the split of the posterior
+        variance into noise and smoothing error of the undamped step at ``x`` (e.g. ``Retrieval.x``): one K-matrix call at
+        ``x``, then ``mwrt_oe_gain_device``, then -- with ``avk`` / ``post_cov`` -- one ``mwrt_oe_product_device`` call each for
+        the full averaging kernel and posterior covariance, all on torch's current stream with nothing leaving the device.
+        ``rows=(begin, count)`` limits both products to those rows of the n x n result (a full one is nprof n^2 doubles).
+        Profiles whose status is 0 or 2 hold NaN in every floating-point field, the products included."""
+        nprof, n = x.shape[0], x.shape[1] * x.shape[2]
+        if rows is None:
+            win = (0, 0)
+        else:
+            win = (int(rows[0]), int(rows[1]))
+            if win[0] < 0 or win[1] < 1 or win[0] + win[1] > n:
+                raise ValueError(f"rows: expected (begin, count) with count >= 1 inside 0 .. {n - 1}, got {rows}")
+        stream = self._stream(x)
+        k_blocks, fx = self._linearise(z, p, x)
+        g = _native_oe_gain(k_blocks, x.contiguous(), self.xa, self.sa, self.se, y.reshape(nprof, self.m).contiguous(), fx,
+                            stream)
+        failed = ((g["status"] == 0) | (g["status"] == 2))[:, None, None]
+        prod = {}
+        for name, want in (("avk", avk), ("post_cov", post_cov)):
+            if want:
+                out = _native_oe_product(name, g["gain"], g["keep"], k_blocks, g["ksa"], self.sa, win, stream)
+                prod[name] = out.masked_fill_(failed, float("nan"))
+        return Characterisation(gain=g["gain"], avk_diag=g["avk_diag"], dfs_block=g["dfs_block"], noise_var=g["noise_var"],
+                                smooth_var=g["smooth_var"], status=g["status"], nobs=g["nobs"], keep=g["keep"], **prod)
 
     # -- the damped iteration ------------------------------------------------------------------------------------------
     def _linearise(self, z, p, x):

@@ -1,0 +1,106 @@
+"""Host logic of retrieval.OneDVar.characterise without a GPU, in the manner of test_retrieval_cpu.py: the K-matrix call is
+replaced by that file's linear forward model on CPU tensors, the gain and product entries by the NumPy reference of
+tests/oe_char_reference.py.  What is checked is the module's own work: one K-matrix call at the state given, block order,
+shapes, the optional products, the row window passed through, failed profiles blanked, and the argument refusals."""
+import numpy as np
+import pytest
+
+import oe_char_reference as ocr
+
+torch = pytest.importorskip("torch")
+
+from mwr_fast_forward_operators_and_lbls_amd import retrieval  # noqa: E402
+from test_retrieval_cpu import M, NLEV, NPROF, Standins, make, setup  # noqa: E402
+
+
+class CharStandins(Standins):
+    def __init__(self, monkeypatch, **kw):
+        super().__init__(monkeypatch, **kw)
+        self.gain_calls, self.product_calls = [], []
+        monkeypatch.setattr(retrieval, "_native_oe_gain", self.oe_gain)
+        monkeypatch.setattr(retrieval, "_native_oe_product", self.oe_product)
+
+    def oe_gain(self, k_blocks, x, xa, sa, se, y, fx, stream):
+        nprof, nblk, nlev = x.shape
+        self.gain_calls.append(dict(k=[k.clone() for k in k_blocks], x=x.clone(), y=y.clone(), fx=fx.clone()))
+        ref = ocr.oe_char_reference([k.numpy().reshape(nprof, M, nlev) for k in k_blocks], x.numpy(), xa.numpy(), sa.numpy(),
+                                    se.numpy(), y.numpy(), fx.numpy(), products=False)
+        return {k: torch.as_tensor(ref[k]) for k in ("gain", "ksa", "keep", "avk_diag", "dfs_block", "noise_var",
+                                                     "smooth_var", "status", "nobs")}
+
+    def oe_product(self, product, gain, keep, k_blocks, ksa, sa, rows, stream):
+        self.product_calls.append((product, rows))
+        nprof, m, n = gain.shape
+        right = np.concatenate([k.numpy().reshape(nprof, m, -1) for k in k_blocks], axis=2) if product == "avk" else ksa.numpy()
+        g = np.nan_to_num(gain.numpy())                                  # the device reads no row whose keep is 0
+        res, _ = ocr.product_reference(g, keep.numpy(), right, sa=None if product == "avk" else sa.numpy(),
+                                       rows=None if rows == (0, 0) else rows)
+        return torch.as_tensor(res)
+
+
+def test_characterise_shapes_and_consistency(monkeypatch):
+    st = CharStandins(monkeypatch)
+    blocks = ("t", "h", "liq")
+    s = setup(blocks)
+    ov = make(blocks, s)
+    n = 3 * NLEV
+    y = st.forward(s["x_true"][:, 0], s["x_true"][:, 1], s["x_true"][:, 2])[0]
+    ch = ov.characterise(s["z"], s["p"], s["x_true"], y.reshape(NPROF, 2, 3))
+    assert isinstance(ch, retrieval.Characterisation)
+    assert len(st.calls) == 1 and st.calls[0]["want"] == blocks and torch.equal(st.calls[0]["t"], s["x_true"][:, 0])
+    assert len(st.gain_calls) == 1 and st.product_calls == []
+    for got, b in zip(st.gain_calls[0]["k"], blocks):                    # K = [K_t | K_h | K_liq]
+        assert torch.equal(got.reshape(NPROF, M, NLEV), st.A[b][None].expand(NPROF, -1, -1))
+    assert torch.equal(st.gain_calls[0]["x"], s["x_true"]) and st.gain_calls[0]["y"].shape == (NPROF, M)
+    assert ch.gain.shape == (NPROF, M, n) and ch.keep.shape == (NPROF, M) and ch.dfs_block.shape == (NPROF, 3)
+    for f in (ch.avk_diag, ch.noise_var, ch.smooth_var):
+        assert f.shape == (NPROF, 3, NLEV)
+    assert ch.status.tolist() == [1] * NPROF and ch.nobs.tolist() == [M] * NPROF and ch.avk is None and ch.post_cov is None
+    # the step at the same state agrees: dfs and post_var
+    _, d = ov.step(s["z"], s["p"], s["x_true"], y)
+    assert torch.allclose(ch.dfs_block.sum(dim=1), d["dfs"], rtol=1e-10, atol=0)
+    assert torch.allclose(ch.noise_var + ch.smooth_var, d["post_var"], rtol=1e-9, atol=0)
+
+
+def test_optional_products_and_rows(monkeypatch):
+    st = CharStandins(monkeypatch)
+    blocks = ("t", "h")
+    s = setup(blocks)
+    ov = make(blocks, s)
+    n = 2 * NLEV
+    y = torch.full((NPROF, M), 255.0)
+    full = ov.characterise(s["z"], s["p"], s["x_true"], y, avk=True, post_cov=True)
+    assert st.product_calls == [("avk", (0, 0)), ("post_cov", (0, 0))]
+    assert full.avk.shape == (NPROF, n, n) and full.post_cov.shape == (NPROF, n, n)
+    assert torch.allclose(torch.diagonal(full.avk, dim1=1, dim2=2).reshape(NPROF, 2, NLEV), full.avk_diag, rtol=1e-10, atol=1e-14)
+    assert torch.allclose(torch.diagonal(full.post_cov, dim1=1, dim2=2).reshape(NPROF, 2, NLEV),
+                          full.noise_var + full.smooth_var, rtol=1e-9, atol=0)
+    only = ov.characterise(s["z"], s["p"], s["x_true"], y, post_cov=True)
+    assert only.avk is None and torch.equal(only.post_cov, full.post_cov)
+    win = ov.characterise(s["z"], s["p"], s["x_true"], y, avk=True, post_cov=True, rows=(NLEV - 1, 3))
+    assert st.product_calls[-2:] == [("avk", (NLEV - 1, 3)), ("post_cov", (NLEV - 1, 3))]
+    assert win.avk.shape == (NPROF, 3, n)
+    assert torch.allclose(win.avk, full.avk[:, NLEV - 1:NLEV + 2], rtol=1e-12, atol=1e-15)
+    assert torch.allclose(win.post_cov, full.post_cov[:, NLEV - 1:NLEV + 2], rtol=1e-12, atol=1e-15)
+    for bad in ((-1, 2), (0, 0), (n - 1, 2), (n, 1)):
+        with pytest.raises(ValueError):
+            ov.characterise(s["z"], s["p"], s["x_true"], y, avk=True, rows=bad)
+
+
+def test_failed_and_unobserved_profiles(monkeypatch):
+    CharStandins(monkeypatch)
+    blocks = ("t", "h")
+    s = setup(blocks)
+    ov = make(blocks, s)
+    n = 2 * NLEV
+    y = torch.full((NPROF, M), 255.0)
+    y[1] = float("nan")                                                  # nothing observed: the prior
+    y[2, 4] = float("nan")                                               # one observation missing
+    x = s["x_true"].clone()
+    x[0, 1, 2] = float("nan")                                            # a state that is not finite
+    ch = ov.characterise(s["z"], s["p"], x, y, avk=True, post_cov=True)
+    assert ch.status.tolist() == [0, 3, 1] and ch.nobs.tolist() == [0, 0, M - 1]
+    assert torch.isnan(ch.avk[0]).all() and torch.isnan(ch.post_cov[0]).all() and torch.isnan(ch.gain[0]).all()
+    assert (ch.avk[1] == 0).all() and torch.equal(ch.post_cov[1], ov.sa) and (ch.dfs_block[1] == 0).all()
+    assert ch.keep[2].tolist() == [1, 1, 1, 1, 0, 1] and (ch.gain[2, 4] == 0).all()
+    assert torch.isfinite(ch.avk[2]).all() and ch.avk.shape == (NPROF, n, n)
