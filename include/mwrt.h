@@ -618,6 +618,53 @@ int mwrt_oe_product_device(mwrt_context* ctx, int64_t nprof, int32_t nlev, int32
 /* sizeof(mwrt_oe_char) as compiled into the library (binding self-check). */
 size_t mwrt_oe_char_size(void);
 
+/* The instrument operator: channel quantities from monochromatic pencil-beam ones.  A radiometer channel
+ * integrates over its bandpass and its antenna beam; on a quadrature grid of m_in = nang_q * nf_q (elevation, frequency)
+ * nodes that is a fixed sparse linear map onto m_out = nang * nch (elevation, channel) outputs,
+ *     y_o = sum_e w[e] TB[col[e]],     K_o[l] = sum_e w[e] K[col[e]][l],     e in [row_ptr[o], row_ptr[o + 1])
+ * with the same weights for the brightness temperatures and for every row of every K-matrix block.  The operator is a
+ * handle like a model: mwrt_obs_create checks the HOST arrays row_ptr [m_out + 1], col [nnz] and w [nnz] (CSR;
+ * nnz = row_ptr[m_out]) and uploads them once, so mwrt_obs_apply_device is the launch alone.
+ *   mwrt_obs_create refuses with MWRT_ERR_INVALID_ARGUMENT: a NULL argument, m_in < 1 or m_out < 1, row_ptr[0] != 0, a
+ *   row_ptr that decreases, a col outside 0 .. m_in - 1, a weight that is not finite.  Columns need not be sorted and may
+ *   repeat within a row and between rows; a row may be empty.
+ *   mwrt_obs_destroy(NULL) is MWRT_OK.  A live operator drains the device first (a queued launch may still read it).
+ *   mwrt_obs_destroy and mwrt_destroy of the operator's context may come in either order: mwrt_destroy frees the device
+ *   copy of every operator still alive on the context and leaves the handles valid for mwrt_obs_destroy alone (apply then
+ *   refuses them).
+ * mwrt_obs_apply_device, all DEVICE pointers, float64, on `stream` as every *_device entry:
+ *   d_tb_in  [nprof][m_in]        -> d_tb_out  [nprof][m_out]           optional, as a pair
+ *   d_k_in[b][nprof][m_in][nlev]  -> d_k_out[b][nprof][m_out][nlev]     b < nblk, nblk 0 .. 4
+ *   (a Jacobian output [nprof][nang_q][nf_q][nlev] as that entry wrote it; the result is [nprof][nang][nch][nlev] when the
+ *   rows are ordered o = a * nch + c).  One launch for the K blocks and one for the TB pair (the same kernel with nlev = 1).
+ *   The sum of a row is FMA-accumulated from 0.0 in the stored order of its entries: an element of the result is the same
+ *   bit for bit whatever nprof, the blocks and pairs asked for, or the call.  An empty row gives exactly 0.0.  NaN and Inf
+ *   propagate through the entries that reference them and through no others (what a dense product with the [m_out][m_in]
+ *   matrix would not do); an explicit zero weight on a NaN input gives NaN (IEEE).
+ *   Refused with MWRT_ERR_INVALID_ARGUMENT, nothing written: a NULL context, operator or record; an operator of another
+ *   context, or one whose context was destroyed; struct_size smaller than the fixed part (12 bytes); nblk outside 0 .. 4;
+ *   reserved != 0; one pointer of a pair given without the other; a NULL pointer among the first nblk of d_k_in or
+ *   d_k_out; nothing to do (no TB pair and nblk = 0); an output pointer equal to its input; nlev < 1; nprof < 0.
+ *   MWRT_ERR_UNSUPPORTED: nlev > MWRT_MAX_LEVELS; more than 2^31 - 1 workgroups in one launch.  nprof = 0 is MWRT_OK.
+ *   The record starts with its own size: fields at or beyond struct_size (and a field it ends inside) are taken as NULL.
+ *   The call never allocates and never synchronises; it is hipGraph-capturable from the first call.
+ *   (MWRT_VERSION stays 301: additions.) */
+typedef struct mwrt_obs mwrt_obs;           /* device-resident copy of the CSR map, owned by one context */
+typedef struct mwrt_obs_apply {
+  uint32_t struct_size;        /* sizeof(mwrt_obs_apply) of the caller; fields beyond it are not read */
+  int32_t  nblk, reserved;
+  const double* d_tb_in;  double* d_tb_out;            /* [nprof][m_in] -> [nprof][m_out]              */
+  const double* d_k_in[4];                             /* [nprof][m_in][nlev]                          */
+  double* d_k_out[4];                                  /* [nprof][m_out][nlev]                         */
+} mwrt_obs_apply;
+int mwrt_obs_create(mwrt_context* ctx, int32_t m_in, int32_t m_out, const int32_t* row_ptr, const int32_t* col,
+                    const double* w, mwrt_obs** out);
+int mwrt_obs_destroy(mwrt_obs* op);
+int mwrt_obs_apply_device(mwrt_context* ctx, const mwrt_obs* op, int64_t nprof, int32_t nlev, const mwrt_obs_apply* rec,
+                          void* stream);
+/* sizeof(mwrt_obs_apply) as compiled into the library (binding self-check). */
+uint32_t mwrt_obs_apply_size(void);
+
 /* Diagnostic: evaluates the kernels' own exp / log / division helpers (fexp, flog, fdiv, fdiv1) on
  * host arrays x[n], y_pos[n] (y > 0), so their accuracy can be checked against libm. */
 int mwrt_selftest_math(mwrt_context* ctx, int32_t n, const double* x, const double* y_pos,

@@ -88,11 +88,21 @@ class MwrtOeChar(ctypes.Structure):
         ("d_out", ctypes.c_void_p)]
 
 
+class MwrtObsApply(ctypes.Structure):
+    """include/mwrt.h mwrt_obs_apply: the record of one application of an instrument operator (device pointers)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("nblk", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("d_tb_in", ctypes.c_void_p), ("d_tb_out", ctypes.c_void_p), ("d_k_in", ctypes.c_void_p * 4),
+                ("d_k_out", ctypes.c_void_p * 4)]
+
+
 #: include/mwrt.h MWRT_OE_PRODUCT_*: what mwrt_oe_product_device forms
 OE_PRODUCT_AVK, OE_PRODUCT_POST_COV = 0, 1
 
 #: include/mwrt.h MWRT_OE_MAX_M: observations per profile of one optimal-estimation step
 OE_MAX_M = 140
+
+#: include/mwrt.h MWRT_MAX_ANGLES: elevations of one forward-operator call
+MAX_ANGLES = 64
 
 MWRT_VERSION = 301
 
@@ -153,6 +163,10 @@ SIGNATURES = {
     "mwrt_oe_gain_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeChar), _vp]),
     "mwrt_oe_product_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeChar), _vp]),
     "mwrt_oe_char_size": (ctypes.c_size_t, []),
+    "mwrt_obs_create": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, ctypes.POINTER(_vp)]),
+    "mwrt_obs_destroy": (ctypes.c_int, [_vp]),
+    "mwrt_obs_apply_device": (ctypes.c_int, [_vp, _vp, _i64, _i32, ctypes.POINTER(MwrtObsApply), _vp]),
+    "mwrt_obs_apply_size": (ctypes.c_uint32, []),
     "mwrt_set_absorption_mode": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_set_chunk_width": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_selftest_math": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -216,6 +230,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
             raise NativeLibraryMissing("mwrt_oe_lm layout mismatch between libmwrt.so and _native.py")
         if lib.mwrt_oe_char_size() != ctypes.sizeof(MwrtOeChar):
             raise NativeLibraryMissing("mwrt_oe_char layout mismatch between libmwrt.so and _native.py")
+        if lib.mwrt_obs_apply_size() != ctypes.sizeof(MwrtObsApply):
+            raise NativeLibraryMissing("mwrt_obs_apply layout mismatch between libmwrt.so and _native.py")
         if lib.mwrt_version() != MWRT_VERSION:
             raise NativeLibraryMissing(f"libmwrt.so is version {lib.mwrt_version()}, this binding needs {MWRT_VERSION}: "
                                        "rebuild (python -c 'import __graft_entry__ as g; g.build()')")
@@ -637,6 +653,47 @@ class Context:
         self._oe_char("mwrt_oe_product_device", nprof, nlev, m, d_k, False, False, stream, reserved, struct_size,
                       dict(d_gain=d_gain, d_keep=d_keep, d_out=d_out, d_ksa=d_ksa, d_sa=d_sa, product=product,
                            row_begin=row_begin, row_count=row_count, reserved2=reserved2))
+
+    @_serialised
+    def obs_create(self, m_in, m_out, row_ptr, col, w) -> ctypes.c_void_p:
+        """An instrument operator on this context (include/mwrt.h mwrt_obs_create) from the host CSR arrays ``row_ptr
+        [m_out + 1]``, ``col [nnz]`` (int32) and ``w [nnz]`` (float64): checked and uploaded once.  Returns the handle
+        ``obs_apply_device`` takes; release it with ``obs_destroy`` (before or after the context is closed)."""
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32).ravel()
+        col = np.ascontiguousarray(col, dtype=np.int32).ravel()
+        w = _f64(w).ravel()
+        if row_ptr.size != int(m_out) + 1 or col.size != w.size or (row_ptr.size and row_ptr[-1] != w.size):
+            raise ValueError(f"obs_create: expected row_ptr [{int(m_out) + 1}] ending at nnz = len(col) = len(w), got "
+                             f"{row_ptr.size}, {col.size}, {w.size}")
+        h = ctypes.c_void_p()
+        self._check(self._lib.mwrt_obs_create(self._handle, int(m_in), int(m_out), _ptr(row_ptr), _ptr(col), _ptr(w),
+                                              ctypes.byref(h)), "mwrt_obs_create")
+        return h
+
+    def obs_destroy(self, handle):
+        """Releases an operator of ``obs_create`` (include/mwrt.h mwrt_obs_destroy); safe after ``close`` as well."""
+        with self._lock:
+            self._check(self._lib.mwrt_obs_destroy(handle), "mwrt_obs_destroy")
+
+    @_serialised
+    def obs_apply_device(self, handle, nprof, nlev, d_tb_in=None, d_tb_out=None, d_k_in=(), d_k_out=(), stream=None,
+                         reserved=0, struct_size=None, nblk=None):
+        """Applies an instrument operator (include/mwrt.h mwrt_obs_apply_device): ``d_tb_in [nprof][m_in]`` ->
+        ``d_tb_out [nprof][m_out]`` (optional, as a pair) and, for each of up to four blocks, ``d_k_in[b]
+        [nprof][m_in][nlev]`` -> ``d_k_out[b] [nprof][m_out][nlev]``.  ``nblk`` (default: ``len(d_k_in)``) and
+        ``struct_size`` (default: the whole record) are what the record claims."""
+        d_k_in, d_k_out = list(d_k_in), list(d_k_out)
+        rec = MwrtObsApply()
+        rec.struct_size = ctypes.sizeof(MwrtObsApply) if struct_size is None else int(struct_size)
+        rec.nblk, rec.reserved = len(d_k_in) if nblk is None else int(nblk), int(reserved)
+        opt = lambda v: int(v) if v is not None else None   # noqa: E731
+        rec.d_tb_in, rec.d_tb_out = opt(d_tb_in), opt(d_tb_out)
+        for b, k in enumerate(d_k_in[:4]):
+            rec.d_k_in[b] = opt(k)
+        for b, k in enumerate(d_k_out[:4]):
+            rec.d_k_out[b] = opt(k)
+        self._check(self._lib.mwrt_obs_apply_device(self._handle, handle, int(nprof), int(nlev), ctypes.byref(rec),
+                                                    _stream(stream)), "mwrt_obs_apply_device")
 
     def layer_tau_pitch(self, nf: int) -> int:
         """Doubles between consecutive levels of a layer-optical-depth array for nf frequencies (multiple of 16)."""

@@ -1,9 +1,10 @@
 """Build recipe for libmwrt.so (hipcc, gfx950 only, in-tree so the .so travels with the repo).
 
-Ten translation units -- the C-ABI host side (csrc/mwrt.hip, no device code in it), the kernel instantiations of
+Eleven translation units -- the C-ABI host side (csrc/mwrt.hip, no device code in it), the kernel instantiations of
 each frequency-chunk width (csrc/mwrt_inst.hip with -DMWRT_INST_NFC=8|14|16), the device K-matrix kernels
 (csrc/mwrt_tl.hip), the optimal-estimation step (csrc/mwrt_oe.hip), its
-Levenberg-Marquardt split (csrc/mwrt_oe_lm.hip), its characterisation (csrc/mwrt_oe_char.hip), the non-template
+Levenberg-Marquardt split (csrc/mwrt_oe_lm.hip), its characterisation (csrc/mwrt_oe_char.hip), the instrument
+operator (csrc/mwrt_obs.hip), the non-template
 kernels (csrc/mwrt_aux.hip) and the host-only launch planning
 (csrc/mwrt_plan.cpp, no HIP in it) -- are compiled in parallel and linked into one shared library."""
 from __future__ import annotations
@@ -23,6 +24,7 @@ TL = os.path.join(CSRC, "mwrt_tl.hip")
 OE = os.path.join(CSRC, "mwrt_oe.hip")
 OE_LM = os.path.join(CSRC, "mwrt_oe_lm.hip")
 OE_CHAR = os.path.join(CSRC, "mwrt_oe_char.hip")
+OBS = os.path.join(CSRC, "mwrt_obs.hip")
 AUX = os.path.join(CSRC, "mwrt_aux.hip")
 PLAN = os.path.join(CSRC, "mwrt_plan.cpp")
 # what the library is built from: every file of csrc/ (a new header counts without being named here) and the public header
@@ -62,6 +64,7 @@ def build_native(force: bool = False, verbose: bool = False, extra_flags=(), out
     jobs.append((OE, os.path.join(OBJ_DIR, f"mwrt_oe.{tag}.o"), []))
     jobs.append((OE_LM, os.path.join(OBJ_DIR, f"mwrt_oe_lm.{tag}.o"), []))
     jobs.append((OE_CHAR, os.path.join(OBJ_DIR, f"mwrt_oe_char.{tag}.o"), []))
+    jobs.append((OBS, os.path.join(OBJ_DIR, f"mwrt_obs.{tag}.o"), []))
     jobs.append((AUX, os.path.join(OBJ_DIR, f"mwrt_aux.{tag}.o"), []))
     jobs.append((PLAN, os.path.join(OBJ_DIR, f"mwrt_plan.{tag}.o"), []))
 

@@ -10,6 +10,7 @@
 #include "mwrt_oe.hip.h"
 #include "mwrt_oe_lm.hip.h"
 #include "mwrt_oe_char.hip.h"
+#include "mwrt_obs.hip.h"
 #include "mwrt_plan.h"
 
 #include <cmath>
@@ -152,8 +153,19 @@ struct mwrt_context {
   bool timing = false;
   std::vector<hipEvent_t> ev0, ev1;
   long ev_count = 0;
+  // instrument operators created on this context and not yet destroyed: mwrt_destroy frees their device copies
+  std::vector<mwrt_obs*> obs_live;
 };
 constexpr int TIMING_RING = 512;
+
+struct mwrt_obs {
+  mwrt_context* ctx = nullptr;  // null once the context is gone: the handle then only waits for mwrt_obs_destroy
+  int32_t m_in = 0, m_out = 0;
+  void* d_blob = nullptr;       // w [nnz] | row_ptr [m_out + 1] | col [nnz], one allocation
+  const double* d_w = nullptr;
+  const int32_t* d_row_ptr = nullptr;
+  const int32_t* d_col = nullptr;
+};
 
 struct mwrt_model {
   ModelFlat* d_desc = nullptr;
@@ -750,6 +762,10 @@ int mwrt_destroy(mwrt_context* c) {
   c->d_jac.release();
   c->d_in.release(); c->d_out.release();
   c->d_valid.release(); c->d_ex.release();
+  for (mwrt_obs* op : c->obs_live) {                    // the handles stay valid for mwrt_obs_destroy; apply refuses them
+    (void)hipFree(op->d_blob);
+    op->d_blob = nullptr; op->d_w = nullptr; op->d_row_ptr = nullptr; op->d_col = nullptr; op->ctx = nullptr;
+  }
   for (hipEvent_t e : c->ev0) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev1) (void)hipEventDestroy(e);
   if (c->ws_event) (void)hipEventDestroy(c->ws_event);
@@ -1252,6 +1268,113 @@ int mwrt_oe_gain_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m,
 }
 int mwrt_oe_product_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_char* s, void* stream) {
   return oe_char_call(c, nprof, nlev, m, s, stream, CharCall::Product);
+}
+
+/* The instrument operator (csrc/mwrt_obs.hip): a handle that owns the device copy of a CSR map, and its one launch.  The
+ * preamble of apply is in the order of mwrt_oe_step_device: arguments, then limits, then the device and the stream. */
+uint32_t mwrt_obs_apply_size(void) { return (uint32_t)sizeof(mwrt_obs_apply); }
+
+int mwrt_obs_create(mwrt_context* c, int32_t m_in, int32_t m_out, const int32_t* row_ptr, const int32_t* col, const double* w,
+                    mwrt_obs** out) {
+  if (out) *out = nullptr;
+  if (!c || !row_ptr || !col || !w || !out) return fail(MWRT_ERR_INVALID_ARGUMENT, "null argument");
+  if (m_in < 1 || m_out < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_create: m_in < 1 or m_out < 1");
+  if (row_ptr[0] != 0) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_create: row_ptr[0] must be 0");
+  for (int32_t o = 0; o < m_out; ++o)
+    if (row_ptr[o + 1] < row_ptr[o])
+      return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_create: row_ptr decreases at row " + std::to_string(o));
+  const size_t nnz = (size_t)row_ptr[m_out];
+  for (size_t e = 0; e < nnz; ++e) {
+    if (col[e] < 0 || col[e] >= m_in)
+      return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_create: col[" + std::to_string(e) + "] outside 0 .. m_in - 1");
+    if (!std::isfinite(w[e]))
+      return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_create: w[" + std::to_string(e) + "] is not finite");
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  mwrt_obs* op = new (std::nothrow) mwrt_obs();
+  if (!op) return fail(MWRT_ERR_OUT_OF_MEMORY, "host allocation failed");
+  const size_t w_bytes = sizeof(double) * nnz, rp_bytes = sizeof(int32_t) * ((size_t)m_out + 1);
+  std::vector<char> host(w_bytes + rp_bytes + sizeof(int32_t) * nnz);
+  std::memcpy(host.data(), w, w_bytes);
+  std::memcpy(host.data() + w_bytes, row_ptr, rp_bytes);
+  std::memcpy(host.data() + w_bytes + rp_bytes, col, sizeof(int32_t) * nnz);
+  hipError_t e = hipMalloc(&op->d_blob, host.size());
+  if (e == hipSuccess) e = hipMemcpy(op->d_blob, host.data(), host.size(), hipMemcpyHostToDevice);   // synchronous: in HBM on return
+  if (e != hipSuccess) {
+    if (op->d_blob) (void)hipFree(op->d_blob);
+    delete op;
+    return fail(e == hipErrorOutOfMemory ? MWRT_ERR_OUT_OF_MEMORY : MWRT_ERR_HIP, hipGetErrorString(e));
+  }
+  op->ctx = c; op->m_in = m_in; op->m_out = m_out;
+  op->d_w = static_cast<const double*>(op->d_blob);
+  op->d_row_ptr = reinterpret_cast<const int32_t*>(static_cast<const char*>(op->d_blob) + w_bytes);
+  op->d_col = reinterpret_cast<const int32_t*>(static_cast<const char*>(op->d_blob) + w_bytes + rp_bytes);
+  c->obs_live.push_back(op);
+  *out = op;
+  return MWRT_OK;
+}
+
+int mwrt_obs_destroy(mwrt_obs* op) {
+  if (!op) return MWRT_OK;
+  if (mwrt_context* c = op->ctx) {
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();                       // launches on any stream may still read the map
+    (void)hipFree(op->d_blob);
+    for (size_t i = c->obs_live.size(); i-- > 0;)
+      if (c->obs_live[i] == op) c->obs_live.erase(c->obs_live.begin() + (long)i);
+  }
+  delete op;
+  return MWRT_OK;
+}
+
+int mwrt_obs_apply_device(mwrt_context* c, const mwrt_obs* op, int64_t nprof, int32_t nlev, const mwrt_obs_apply* s,
+                          void* stream) {
+  if (!c || !op || !s) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context, mwrt_obs or mwrt_obs_apply");
+  if (op->ctx != c) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs belongs to another context, or its context was destroyed");
+  constexpr size_t fixed = offsetof(mwrt_obs_apply, reserved) + sizeof(int32_t), ptrs = offsetof(mwrt_obs_apply, d_tb_in);
+  if (s->struct_size < fixed)
+    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_apply.struct_size too small for the fixed part (through reserved)");
+  mwrt_obs_apply r{};                                  // fields at or beyond the caller's struct_size stay NULL
+  // ... and so does a field the size ends inside: beyond the fixed part every field is one pointer
+  size_t len = s->struct_size < sizeof r ? s->struct_size : sizeof r;
+  len = len < ptrs ? fixed : len - (len - ptrs) % sizeof(void*);
+  std::memcpy(&r, s, len);
+  if (nprof < 0 || nlev < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "nprof < 0 or nlev < 1");
+  if (r.nblk < 0 || r.nblk > 4) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_apply.nblk must be 0 .. 4");
+  if (r.reserved != 0) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_apply.reserved must be 0");
+  if ((r.d_tb_in == nullptr) != (r.d_tb_out == nullptr))
+    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_apply: d_tb_in and d_tb_out are given together or not at all");
+  for (int b = 0; b < r.nblk; ++b)
+    if (!r.d_k_in[b] || !r.d_k_out[b]) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_apply: null pointer among the first nblk of d_k_in / d_k_out");
+  if (!r.d_tb_in && r.nblk == 0) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_apply: nothing to do (no TB pair and nblk = 0)");
+  bool aliased = r.d_tb_in && r.d_tb_in == r.d_tb_out;
+  for (int b = 0; b < r.nblk; ++b) aliased = aliased || r.d_k_in[b] == r.d_k_out[b];
+  if (aliased) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_apply: an output pointer equals its input (the map is not applied in place)");
+  if (nlev > MWRT_MAX_LEVELS)
+    return fail(MWRT_ERR_UNSUPPORTED, "nlev > MWRT_MAX_LEVELS (" + std::to_string(MWRT_MAX_LEVELS) + ")");
+  obs::ObsArgs a{};
+  a.row_ptr = op->d_row_ptr; a.col = op->d_col; a.w = op->d_w;
+  a.m_in = op->m_in; a.m_out = op->m_out;
+  obs::ObsArgs k = a, t = a;                           // the K blocks at nlev; the TB pair as one block of one level
+  k.in0 = r.d_k_in[0]; k.in1 = r.d_k_in[1]; k.in2 = r.d_k_in[2]; k.in3 = r.d_k_in[3];
+  k.out0 = r.d_k_out[0]; k.out1 = r.d_k_out[1]; k.out2 = r.d_k_out[2]; k.out3 = r.d_k_out[3];
+  k.nlev = nlev; k.nblk = r.nblk; k.nchunks = (nlev + obs::WAVE - 1) / obs::WAVE;
+  t.in0 = r.d_tb_in; t.out0 = r.d_tb_out; t.nlev = 1; t.nblk = 1; t.nchunks = 1;
+  // one wave per (profile, block, output row, level chunk), ITEMS waves per workgroup; the per-profile count is < 2^37
+  const int64_t per_prof = (int64_t)(r.nblk > 0 ? r.nblk : 1) * op->m_out * k.nchunks;
+  if (nprof > 2147483647LL * obs::ITEMS / per_prof)
+    return fail(MWRT_ERR_UNSUPPORTED, "mwrt_obs_apply_device: more than 2147483647 workgroups in one launch (split the batch)");
+  k.items = nprof * r.nblk * op->m_out * k.nchunks;
+  t.items = nprof * op->m_out;
+  if (nprof == 0) return MWRT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = resolve_stream(c, stream);
+  if (r.nblk > 0) {
+    const int rc = timed(c, st, [&] { return obs::launch_obs_apply(k, st); });
+    if (rc != MWRT_OK) return rc;
+  }
+  if (r.d_tb_in) return timed(c, st, [&] { return obs::launch_obs_apply(t, st); });
+  return MWRT_OK;
 }
 
 int mwrt_selftest_math(mwrt_context* c, int32_t n, const double* x, const double* y_pos,

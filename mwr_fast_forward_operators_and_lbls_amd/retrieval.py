@@ -13,7 +13,9 @@ then optionally ``"liq"`` and ``"ice"`` in ``variables.cloud`` (g m-3 or kg/kg).
 ``[nprof][m]``); a NaN in it drops that observation.  ``sa`` is ``[n][n]`` with n = nblk * nlev, ``se`` ``[m]`` variances or
 ``[m][m]``, ``xa`` ``[nblk][nlev]`` shared or ``[nprof][nblk][nlev]``.  With ``variables.heights = "hydrostatic"`` the heights
 are rebuilt from the state before every forward run (the rule of mwrt_jac_variables, anchored at ``z[:, 0]``); otherwise
-``z`` is used as passed.
+``z`` is used as passed.  With ``instrument=`` (``instrument.Instrument``: antenna beam and channel bandpass)
+the forward operator runs on the instrument's quadrature grid and ``mwrt_obs_apply_device`` reduces its TBs and K rows to
+channels: ``y``, ``se`` and every diagnostic are then in channel space.
 
 ``step`` and ``retrieve`` take the undamped Gauss-Newton update, which is linear around x and may overshoot where the forward
 model is not; ``retrieve_lm`` damps it (Levenberg-Marquardt, Rodgers 2000 eq. 5.36) on the split entries
@@ -139,6 +141,35 @@ def _native_oe_product(product, gain, keep, k_blocks, ksa, sa, rows, stream):
     return out
 
 
+def _native_obs_apply(instrument, tb, k_blocks, stream):
+    """One ``mwrt_obs_apply_device`` call -> (tb_ch [nprof][nang][nch] or None, list of K blocks [nprof][nang][nch][nlev] or
+    None) from ``tb [nprof][nang_q][nf_q]`` and / or the K blocks ``[nprof][nang_q][nf_q][nlev]`` on the instrument's
+    quadrature grid.
+
+    The single place the instrument's reduction reaches the native library: CPU tests substitute the NumPy reference here."""
+    k_blocks = None if k_blocks is None else [k.contiguous() for k in k_blocks]
+    ref = tb if tb is not None else k_blocks[0]
+    nprof = ref.shape[0]
+    nang, nch = instrument.elev.size, instrument.frq.size
+    opts = dict(dtype=torch.float64, device=ref.device)
+    for name, v in [("tb", tb)] + [(f"k_blocks[{i}]", k) for i, k in enumerate(k_blocks or [])]:
+        if v is not None and (v.dtype != torch.float64 or v.shape[0] != nprof or v[0].numel() % instrument.m_in != 0):
+            raise ValueError(f"{name}: expected float64 [{nprof}][{instrument.elev_q.size}][{instrument.frq_q.size}]..., got "
+                             f"{v.dtype} {tuple(v.shape)}")
+    if tb is not None and tb[0].numel() != instrument.m_in:
+        raise ValueError(f"tb: expected [{nprof}][{instrument.m_in}], got {tuple(tb.shape)}")
+    tb_in = None if tb is None else tb.contiguous()
+    tb_out = None if tb is None else torch.empty((nprof, nang, nch), **opts)
+    nlev = k_blocks[0].shape[-1] if k_blocks else 1
+    k_out = None if k_blocks is None else [torch.empty((nprof, nang, nch, nlev), **opts) for _ in k_blocks]
+    ctx, handle = instrument.native_handle(ref.device.index or 0)
+    ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
+    ctx.obs_apply_device(handle, nprof, nlev, d_tb_in=ptr(tb_in), d_tb_out=ptr(tb_out),
+                         d_k_in=[k.data_ptr() for k in k_blocks or []], d_k_out=[k.data_ptr() for k in k_out or []],
+                         stream=stream)
+    return tb_out, k_out
+
+
 @dataclass
 class Characterisation:
     """What ``OneDVar.characterise`` returns: the undamped step at a state, described (Rodgers 2000, ch. 3; include/mwrt.h
@@ -171,7 +202,8 @@ class Retrieval:
 
 
 class OneDVar:
-    def __init__(self, model, frq, elev, sa, se, variables: Optional[JacVariables] = None, blocks=("t", "h"), xa=None):
+    def __init__(self, model, frq, elev, sa, se, variables: Optional[JacVariables] = None, blocks=("t", "h"), xa=None,
+                 instrument=None):
         blocks = tuple(blocks)
         if blocks[:2] != ("t", "h") or blocks[2:] not in ((), ("liq",), ("ice",), ("liq", "ice")):
             raise ValueError(f"blocks must be ('t', 'h') followed by 'liq' and / or 'ice' in that order, got {blocks}")
@@ -183,6 +215,14 @@ class OneDVar:
             raise ValueError("xa (the prior state) is required")
         self.sa, self.se, self.xa = sa.contiguous(), se.contiguous(), xa.contiguous()
         self.m = self.frq.size * self.elev.size
+        # with an instrument (instrument.Instrument) the forward operator runs on its quadrature grid and every TB and K row is
+        # reduced to channels before the update sees it: se, y and all diagnostics are in channel space, m = instrument.m_out
+        self.instrument = instrument
+        if instrument is not None:
+            if not (np.array_equal(self.frq, instrument.frq) and np.array_equal(self.elev, instrument.elev)):
+                raise ValueError("frq and elev must equal the instrument's channel centres and elevations "
+                                 f"(instrument.frq = {instrument.frq.tolist()}, instrument.elev = {instrument.elev.tolist()})")
+            self.m = instrument.m_out
         nblk = len(blocks)
         if self.xa.dim() not in (2, 3) or self.xa.shape[-2] != nblk:
             raise ValueError(f"xa: expected [{nblk}][nlev] or [nprof][{nblk}][nlev], got {tuple(self.xa.shape)}")
@@ -231,12 +271,26 @@ class OneDVar:
         return x
 
     # -- one Gauss-Newton step ---------------------------------------------------------------------------------------
+    def _observe(self, z, p, x, want_rows=True):
+        """One K-matrix call at ``x`` -> (tb [nprof][nang][nf], valid, K blocks in the state's order or None), in what the
+        update sees: the operator's own outputs, or with an instrument the channel quantities -- the call then runs on the
+        instrument's quadrature grid and ``_native_obs_apply`` reduces the TBs and, when wanted, every block's rows.  The one
+        place of this class that runs the forward operator."""
+        zz, t, rh, dl, di = self.physical(z, p, x)
+        inst = self.instrument
+        frq, elev = (self.frq, self.elev) if inst is None else (inst.frq_q, inst.elev_q)
+        stream = self._stream(x)
+        tb, valid, rows = _native_k_matrix(self.model, zz.contiguous(), p.contiguous(), t, rh, dl, di, frq, elev,
+                                           self.variables, self.blocks, stream)
+        k_blocks = [rows[b] for b in self.blocks] if want_rows else None
+        if inst is not None:
+            tb, k_blocks = _native_obs_apply(inst, tb, k_blocks, stream)
+        return tb, valid, k_blocks
+
     def forward(self, z, p, x):
         """The forward model at the state ``x``: ``(tb [nprof][nang][nf], valid [nprof])`` on torch's current stream (the
-        K-matrix call's TBs; its rows are discarded)."""
-        zz, t, rh, dl, di = self.physical(z, p, x)
-        tb, valid, _ = _native_k_matrix(self.model, zz.contiguous(), p.contiguous(), t, rh, dl, di, self.frq, self.elev,
-                                        self.variables, self.blocks, self._stream(x))
+        K-matrix call's TBs; its rows are discarded).  With an instrument: the channel TBs."""
+        tb, valid, _ = self._observe(z, p, x, want_rows=False)
         return tb, valid
 
     @staticmethod
@@ -251,11 +305,9 @@ class OneDVar:
         ``x_new`` is the raw update: ``retrieve`` clamps it."""
         stream = self._stream(x)
         nprof = x.shape[0]
-        zz, t, rh, dl, di = self.physical(z, p, x)
-        tb, valid, rows = _native_k_matrix(self.model, zz.contiguous(), p.contiguous(), t, rh, dl, di, self.frq, self.elev,
-                                           self.variables, self.blocks, stream)
+        tb, valid, k_blocks = self._observe(z, p, x)
         fx = tb.reshape(nprof, self.m)
-        out = _native_oe_step([rows[b] for b in self.blocks], x.contiguous(), self.xa, self.sa, self.se,
+        out = _native_oe_step(k_blocks, x.contiguous(), self.xa, self.sa, self.se,
                               y.reshape(nprof, self.m).contiguous(), fx, post_var, stream)
         x_new = out.pop("x_new")
         out["fx"], out["valid"] = fx, valid
@@ -326,10 +378,8 @@ class OneDVar:
     # -- the damped iteration ------------------------------------------------------------------------------------------
     def _linearise(self, z, p, x):
         """One K-matrix call at ``x`` -> (K blocks in the state's order, F(x) [nprof][m]); fresh tensors every call."""
-        zz, t, rh, dl, di = self.physical(z, p, x)
-        tb, _, rows = _native_k_matrix(self.model, zz.contiguous(), p.contiguous(), t, rh, dl, di, self.frq, self.elev,
-                                       self.variables, self.blocks, self._stream(x))
-        return [rows[b] for b in self.blocks], tb.reshape(x.shape[0], self.m)
+        tb, _, k_blocks = self._observe(z, p, x)
+        return k_blocks, tb.reshape(x.shape[0], self.m)
 
     def retrieve_lm(self, z, p, y, x0=None, max_iter=20, tol=0.05, gamma0=1.0, up=10.0, down=10.0, gamma_max=1e8) -> Retrieval:
         """Levenberg-Marquardt iteration from ``x0`` (default: the prior), per profile and wholly on the device and torch's
