@@ -444,13 +444,28 @@ k_tb_fused(const FusedArgs A) {
         // several rounds or short segments: thin or not is voted per step, by the lanes that hold an item -- a lane in
         // the zero padding past its last layer votes thin and changes no vote.  (This is the loop of the headline
         // shape: 56 pairs x 10 segments of 18 layers in three rounds, then 42 x 9 of 20 in two.)
+        // A step voted thin runs the body of the sorted thin loop below -- tanh(tau/2) for (1 - E)/(1 + E), no division;
+        // a padding lane (tau = 0) stays an exact no-op there as well: E = 1, th = 0.
         const double cs = loop_invariant_vgpr(FEXP_SMALL_C0), ce = loop_invariant_vgpr(FEXP_C0);
+        const double ct = loop_invariant_vgpr(FTANH_HALF_SMALL_C0);
+        // The steps work on -tau * airmass, formed with the negated air mass: both exponentials take it as it is, tanh is
+        // odd and its sign goes into the last fma's source modifier -- no negation per step, the same bits.
+        const double nam = -am;
         rte_segment(tj + lo, bj + lo, seglen, [&](double tz, double bi) {
-          const double tl = tz * am;
-          const double E = wave_all(fabs(tl) <= EXP_SMALL_X) ? fexp_small(-tl, cs) : fexp(-tl, ce);
-          const double lay = fdiv1(__builtin_fma(bi, E, bprev), 1.0 + E);
-          B = __builtin_fma(lay * T, 1.0 - E, B);
-          T *= E;
+          const double ntl = tz * nam;
+          if (wave_all(fabs(ntl) <= EXP_SMALL_X)) {
+            KEEP_BRANCH();
+            const double E = fexp_small(ntl, cs);
+            const double nth = ftanh_half_small(ntl, ct);
+            B = __builtin_fma(__builtin_fma(bi, E, bprev) * T, -nth, B);
+            T *= E;
+          } else {
+            KEEP_BRANCH();
+            const double E = fexp(ntl, ce);
+            const double lay = fdiv1(__builtin_fma(bi, E, bprev), 1.0 + E);
+            B = __builtin_fma(lay * T, 1.0 - E, B);
+            T *= E;
+          }
           bprev = bi;
         });
       } else if (!sorted) {
