@@ -665,6 +665,89 @@ int mwrt_obs_apply_device(mwrt_context* ctx, const mwrt_obs* op, int64_t nprof, 
 /* sizeof(mwrt_obs_apply) as compiled into the library (binding self-check). */
 uint32_t mwrt_obs_apply_size(void);
 
+/* The spectroscopic-parameter Jacobian: d TB / d b for entries b of the model's tables -- what the
+ * forward-model part K_b S_b K_b^T of an observation-error covariance is built from (Rodgers 2000, section 3.2.2).  The
+ * operator is mwrt_tb_jacobian_batch_device's: clear sky, plane-parallel, every line at every frequency; there is no
+ * options argument (cloud, ray tracing and ozone are not built).  A parameter is a (field, line) pair:
+ *   scalar fields (line must be 0)   MWRT_PAR_H2O_CF, _H2O_CS, _H2O_XCF, _H2O_XCS (the water-vapour continuum),
+ *                                    _O2_X (T exponent of the O2 widths), _O2_WB300 (non-resonant width), _N2_L
+ *   H2O per line (0 .. n_h2o - 1)    _H2O_S1, _H2O_B2, _H2O_W0, _H2O_X, _H2O_W0S, _H2O_XS, _H2O_SH, _H2O_SHS
+ *   O2 per line  (0 .. n_o2 - 1)     _O2_S300, _O2_BE, _O2_W300, _O2_Y0, _O2_Y1, _O2_G0, _O2_G1, _O2_DNU0, _O2_DNU1
+ * each named after the mwrt_model_desc field it differentiates.  line = MWRT_PAR_ALL_LINES on a per-line field asks for
+ * the derivative with respect to a common factor s that multiplies that field of EVERY line, at s = 1: the sum over
+ * lines k of b_k * d TB / d b_k.  The line centres, the speed-dependent-only fields (w2, d2, ...) and the remaining
+ * scalars are not offered.
+ *   params     HOST array [npar] (like frq_ghz: a content-keyed device copy is made on first use)
+ *   d_tb       [nprof][nang][nf], optional (NULL: not wanted): the TBs of mwrt_tb_jacobian_batch_device, computed by the
+ *              same statements from the same absorption arrays (equal to 1e-8 K is what is promised)
+ *   d_dtb_db   [nprof][nang][nf][npar] float64, PARAMETER fastest: [nprof][m][npar] with m = nang * nf, so it goes through
+ *              mwrt_obs_apply_device with nlev := npar, and into a batched K_b S_b K_b^T, without a copy.  ABSOLUTE
+ *              derivatives: K per unit of the table entry as mwrt_model_desc stores it
+ *   d_valid    [nprof] as the K-matrix entry
+ * Derivative conventions: those of the K-matrix rows, the derivative of the branch the forward takes --
+ *   zero slope where max(o2abs, 0) clamps; the 750-GHz cutoff and the speed-dependent switch followed as taken (the
+ *   switch's own bound 10 w0 moves with W0, X, W0S, XS: still the branch taken); the layer rule's close-level and zero-end
+ *   partials; inside a line's speed-dependent window W0, X, W0S, XS, SH, SHS act through A = w0 - 1.5 w2 + i (d1 + 1.5 delta2).
+ *   A parameter the model's modes do not read gives columns of exact 0.0 in every valid row: SH, SHS under
+ *   h2o_shift_mode == 0; G0, G1, DNU0, DNU1 under first-order mixing (o2_mix_mode == 0).
+ * NaN, valid, streams and capture as mwrt_tb_jacobian_batch_device: a NaN in z / p / T / rh -> valid 0 and NaN in every row
+ *   of the profile (d_tb too); a negative absorption coefficient -> valid 2, rows NaN; a NaN elevation blanks only its own
+ *   rows; a NaN frequency is MWRT_ERR_INVALID_ARGUMENT; nprof = 0 is MWRT_OK.
+ * Refused with MWRT_ERR_INVALID_ARGUMENT, nothing written: a NULL required pointer; npar < 1 or > MWRT_MAX_PARAMS; an
+ *   unknown field id; a line outside its table (and not MWRT_PAR_ALL_LINES); line != 0 on a scalar field.
+ * Determinism: no floating-point atomics; the sum over levels has a fixed order (lanes of a wave by a shuffle tree, waves in
+ *   index order).  A column is the same bit for bit whatever nprof, on a repeat call, and whichever other parameters are
+ *   requested beside it and in whatever order (parameters are processed in groups that bound the workspace; a column's
+ *   arithmetic does not see its group).
+ * Workspace: the K-matrix entry's own (k_absorb_tl fills it: 48 B per (profile, frequency, level); the parameter kernels
+ *   read awet, adry and the flags from it) and, for d alpha / d b, 8 B per (profile, frequency, level) and parameter of a
+ *   group -- a group being as many parameters as fit 1 GiB, at least one.  Both are owned by the context and only grown
+ *   behind a drain.  After one warm-up call with the same shapes, frequencies and parameter list the call neither allocates
+ *   nor synchronises (hipGraph-capturable).  nprof * nf * ceil(nlev / 64) > 2^31 - 1 is MWRT_ERR_UNSUPPORTED.
+ * Cost: a per-line parameter costs one line's term per (level, frequency); _O2_X and MWRT_PAR_ALL_LINES sum over every line
+ *   of their species.  Timing: DESIGN.md 4.8.  (MWRT_VERSION stays 301: additions.) */
+#define MWRT_MAX_PARAMS 256
+#define MWRT_PAR_ALL_LINES (-1)
+#define MWRT_PAR_H2O_CF    0
+#define MWRT_PAR_H2O_CS    1
+#define MWRT_PAR_H2O_XCF   2
+#define MWRT_PAR_H2O_XCS   3
+#define MWRT_PAR_O2_X      4
+#define MWRT_PAR_O2_WB300  5
+#define MWRT_PAR_N2_L      6
+#define MWRT_PAR_H2O_S1    7
+#define MWRT_PAR_H2O_B2    8
+#define MWRT_PAR_H2O_W0    9
+#define MWRT_PAR_H2O_X     10
+#define MWRT_PAR_H2O_W0S   11
+#define MWRT_PAR_H2O_XS    12
+#define MWRT_PAR_H2O_SH    13
+#define MWRT_PAR_H2O_SHS   14
+#define MWRT_PAR_O2_S300   15
+#define MWRT_PAR_O2_BE     16
+#define MWRT_PAR_O2_W300   17
+#define MWRT_PAR_O2_Y0     18
+#define MWRT_PAR_O2_Y1     19
+#define MWRT_PAR_O2_G0     20
+#define MWRT_PAR_O2_G1     21
+#define MWRT_PAR_O2_DNU0   22
+#define MWRT_PAR_O2_DNU1   23
+#define MWRT_PAR_NFIELDS   24
+typedef struct mwrt_param { int32_t field; int32_t line; } mwrt_param;
+int mwrt_tb_param_jacobian_batch_device(mwrt_context* ctx, const mwrt_model* model, int64_t nprof, int32_t nlev,
+                                        const double* d_z_km, const double* d_p_hpa, const double* d_t_k,
+                                        const double* d_rh_frac,
+                                        int32_t nf, const double* frq_ghz, int32_t nang, const double* elev_deg,
+                                        int32_t npar, const mwrt_param* params,
+                                        double* d_tb, double* d_dtb_db, uint8_t* d_valid, void* stream);
+/* The same on HOST buffers, synchronous: the arrays are staged through a device buffer of the call's own (freed on every
+ * return path) and the device entry is called on the context's stream; the results are its bits.  tb may be NULL. */
+int mwrt_tb_param_jacobian_batch(mwrt_context* ctx, const mwrt_model* model, int64_t nprof, int32_t nlev,
+                                 const double* z_km, const double* p_hpa, const double* t_k, const double* rh_frac,
+                                 int32_t nf, const double* frq_ghz, int32_t nang, const double* elev_deg,
+                                 int32_t npar, const mwrt_param* params,
+                                 double* tb, double* dtb_db, uint8_t* valid);
+
 /* Diagnostic: evaluates the kernels' own exp / log / division helpers (fexp, flog, fdiv, fdiv1) on
  * host arrays x[n], y_pos[n] (y > 0), so their accuracy can be checked against libm. */
 int mwrt_selftest_math(mwrt_context* ctx, int32_t n, const double* x, const double* y_pos,

@@ -98,6 +98,30 @@ class MwrtObsApply(ctypes.Structure):
 #: include/mwrt.h MWRT_OE_PRODUCT_*: what mwrt_oe_product_device forms
 OE_PRODUCT_AVK, OE_PRODUCT_POST_COV = 0, 1
 
+class MwrtParam(ctypes.Structure):
+    """include/mwrt.h mwrt_param: one spectroscopic parameter, a (field, line) pair."""
+    _fields_ = [("field", ctypes.c_int32), ("line", ctypes.c_int32)]
+
+
+#: include/mwrt.h MWRT_MAX_PARAMS, MWRT_PAR_ALL_LINES and the MWRT_PAR_* field ids, by the ModelTables name of the entry
+MAX_PARAMS = 256
+PAR_ALL_LINES = -1
+PARAM_FIELDS = {name: i for i, name in enumerate((
+    "h2o_cf", "h2o_cs", "h2o_xcf", "h2o_xcs", "o2_x", "o2_wb300", "n2_l",
+    "h2o_s1", "h2o_b2", "h2o_w0", "h2o_x", "h2o_w0s", "h2o_xs", "h2o_sh", "h2o_shs",
+    "o2_s300", "o2_be", "o2_w300", "o2_y0", "o2_y1", "o2_g0", "o2_g1", "o2_dnu0", "o2_dnu1"))}
+PAR_FIRST_H2O_LINE_FIELD = PARAM_FIELDS["h2o_s1"]      # below it: scalar fields (line must be 0)
+PAR_FIRST_O2_LINE_FIELD = PARAM_FIELDS["o2_s300"]
+
+
+def _params(params):
+    """A sequence of ``MwrtParam`` / (field, line) pairs -> a ctypes array the native call reads."""
+    arr = (MwrtParam * len(params))()
+    for i, q in enumerate(params):
+        arr[i].field, arr[i].line = (q.field, q.line) if isinstance(q, MwrtParam) else (int(q[0]), int(q[1]))
+    return arr
+
+
 #: include/mwrt.h MWRT_OE_MAX_M: observations per profile of one optimal-estimation step
 OE_MAX_M = 140
 
@@ -154,6 +178,10 @@ SIGNATURES = {
     "mwrt_tb_jacobian_batch_vars": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp,
                                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(MwrtTbOptions),
                                                    ctypes.POINTER(JacVariables)]),
+    "mwrt_tb_param_jacobian_batch_device": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp,
+                                                           _i32, ctypes.POINTER(MwrtParam), _vp, _vp, _vp, _vp]),
+    "mwrt_tb_param_jacobian_batch": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp,
+                                                    _i32, ctypes.POINTER(MwrtParam), _vp, _vp, _vp]),
     "mwrt_oe_step_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeStep), _vp]),
     "mwrt_oe_step_size": (ctypes.c_size_t, []),
     "mwrt_oe_lm_prepare_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeLm), _vp]),
@@ -551,6 +579,34 @@ class Context:
             _ptr(tb), *out, _ptr(valid), ctypes.byref(opts) if opts is not None else None,
             ctypes.byref(variables) if variables is not None else None), "mwrt_tb_jacobian_batch_vars")
         return tb, valid, jac
+
+    @_serialised
+    def tb_param_jacobian_device(self, model, nprof, nlev, d_z, d_p, d_t, d_rh, frq, elev, params, d_dtb_db, d_valid,
+                                 d_tb=None, stream=None):
+        """The spectroscopic-parameter Jacobian on device buffers (include/mwrt.h mwrt_tb_param_jacobian_batch_device):
+        ``params`` is a sequence of ``MwrtParam`` or (field, line) pairs, ``d_dtb_db`` [nprof][nang][nf][npar] (parameter
+        fastest, K per unit of the table entry), ``d_valid`` [nprof] and the optional ``d_tb`` [nprof][nang][nf]."""
+        frq, elev = _f64(frq).ravel(), _f64(elev).ravel()
+        arr = _params(params)
+        self._check(self._lib.mwrt_tb_param_jacobian_batch_device(
+            self._handle, self.model(model), int(nprof), int(nlev), _ptr(d_z), _ptr(d_p), _ptr(d_t), _ptr(d_rh),
+            frq.size, _ptr(frq), elev.size, _ptr(elev), len(arr), arr, _ptr(d_tb) if d_tb is not None else None,
+            _ptr(d_dtb_db), _ptr(d_valid), _stream(stream)), "mwrt_tb_param_jacobian_batch_device")
+
+    @_serialised
+    def tb_param_jacobian(self, model, z, p, t, rh, frq, elev, params):
+        """The same on NumPy arrays, synchronous (include/mwrt.h mwrt_tb_param_jacobian_batch): returns ``tb
+        [nprof][nang][nf]``, ``dtb_db [nprof][nang][nf][npar]`` and ``valid [nprof]``."""
+        z, p, t, rh, frq, elev = _profile_args(z, p, t, rh, frq, elev)
+        nprof, nlev = z.shape
+        arr = _params(params)
+        tb = np.empty((nprof, elev.size, frq.size))
+        kb = np.empty((nprof, elev.size, frq.size, len(arr)))
+        valid = np.empty(nprof, dtype=np.uint8)
+        self._check(self._lib.mwrt_tb_param_jacobian_batch(
+            self._handle, self.model(model), nprof, nlev, _ptr(z), _ptr(p), _ptr(t), _ptr(rh), frq.size, _ptr(frq),
+            elev.size, _ptr(elev), len(arr), arr, _ptr(tb), _ptr(kb), _ptr(valid)), "mwrt_tb_param_jacobian_batch")
+        return tb, kb, valid
 
     @_serialised
     def oe_step_device(self, nprof, nlev, m, d_k, d_x, d_xa, d_sa, d_se, d_y, d_fx, d_x_new, d_status, d_chi2=None,

@@ -4,9 +4,11 @@
 // returns 0 and mwrt_create() fails with MWRT_ERR_NO_DEVICE.
 //
 // Host code only: streams, caches, argument checks and the choice of launch.  Every kernel lives in another unit
-// (mwrt_inst.hip, mwrt_tl.hip, mwrt_oe.hip, mwrt_oe_lm.hip, mwrt_oe_char.hip, mwrt_aux.hip) and is reached through the launchers the headers below declare.
+// (mwrt_inst.hip, mwrt_tl.hip, mwrt_par.hip, mwrt_oe.hip, mwrt_oe_lm.hip, mwrt_oe_char.hip, mwrt_obs.hip, mwrt_aux.hip) and is reached
+// through the launchers the headers below declare.
 #include "mwrt_args.hip.h"
 #include "mwrt_tl.hip.h"
+#include "mwrt_par.hip.h"
 #include "mwrt_oe.hip.h"
 #include "mwrt_oe_lm.hip.h"
 #include "mwrt_oe_char.hip.h"
@@ -147,6 +149,10 @@ struct mwrt_context {
   // device K-matrix path: the six tangent-linear absorption arrays + per-profile flags (grown only, never shrunk;
   // handed over between streams like d_amf / d_alpha)
   DevBuf d_jac;
+  // spectroscopic-parameter Jacobian: d alpha / d b of one group of parameters (grown only, handed over like d_jac) and
+  // the content-keyed device copies of the parameter lists
+  DevBuf d_par;
+  DeviceCache par_cache{32};
   // staging for the host-buffer entry points
   DevBuf d_in, d_out, d_valid, d_ex;
   // timing: a ring of hipEvent pairs recorded around every kernel launch, on the launch stream
@@ -760,6 +766,7 @@ int mwrt_destroy(mwrt_context* c) {
   c->win_cache.release(); c->mask_cache.release();
   c->frq_cache.release(); c->am_cache.release(); c->elev_cache.release(); c->d_amf.release(); c->d_duct.release(); c->d_alpha.release();
   c->d_jac.release();
+  c->d_par.release(); c->par_cache.release();
   c->d_in.release(); c->d_out.release();
   c->d_valid.release(); c->d_ex.release();
   for (mwrt_obs* op : c->obs_live) {                    // the handles stay valid for mwrt_obs_destroy; apply refuses them
@@ -1191,6 +1198,138 @@ int mwrt_tb_jacobian_batch(mwrt_context* c, const mwrt_model* m, int64_t nprof, 
                            double* tb, double* dtb_dt, double* dtb_de, double* dtb_ddz, uint8_t* valid) {
   return jacobian_vars_host(c, m, nprof, nlev, z, p, t, rh, nf, frq, nang, elev, tb, dtb_dt, dtb_de, dtb_ddz, nullptr, nullptr,
                             valid, nullptr, nullptr, /*ddz_required=*/true);
+}
+
+// ---- the spectroscopic-parameter Jacobian (csrc/mwrt_par.hip) ----
+namespace {
+
+bool param_is_o2(int field) { return field == MWRT_PAR_O2_X || field == MWRT_PAR_O2_WB300 || field >= MWRT_PAR_O2_S300; }
+
+// what is wrong with a parameter list for this model, or null
+const char* check_params(const mwrt_model* m, int32_t npar, const mwrt_param* params) {
+  if (npar < 1 || npar > MWRT_MAX_PARAMS) return "npar outside 1 .. MWRT_MAX_PARAMS";
+  if (!params) return "null buffer";
+  for (int i = 0; i < npar; ++i) {
+    const int f = params[i].field, l = params[i].line;
+    if (f < 0 || f >= MWRT_PAR_NFIELDS) return "unknown parameter field";
+    if (f < MWRT_PAR_H2O_S1) {
+      if (l != 0) return "line != 0 on a scalar parameter field";
+      continue;
+    }
+    const int n = f < MWRT_PAR_O2_S300 ? m->h_desc.n_h2o : m->h_desc.n_o2;
+    if (l != MWRT_PAR_ALL_LINES && (l < 0 || l >= n)) return "parameter line outside the model's table";
+  }
+  return nullptr;
+}
+
+// k_absorb_tl into the K-matrix workspace, then per group of parameters k_par_tangent and k_par_contract
+int param_jacobian_device(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
+                          const double* d_z, const double* d_p, const double* d_t, const double* d_rh,
+                          int32_t nf, const double* frq, int32_t nang, const double* elev,
+                          int32_t npar, const mwrt_param* params, double* d_tb, double* d_dtb_db, uint8_t* d_valid,
+                          void* stream) {
+  if (!c || !m) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context or model");
+  CallSpec s{CALL_ANGLES, nprof, nlev, nf, frq, nang, elev, stream};
+  if (const char* bad = check_params(m, npar, params)) s.after_common = Check{MWRT_ERR_INVALID_ARGUMENT, bad};
+  s.buffers_ok = d_z && d_p && d_t && d_rh && frq && elev && d_dtb_db && d_valid;
+  const int nslab = (nlev + WAVE - 1) / WAVE;
+  if (nprof * nf * nslab > 2147483647LL) s.before_device = Check{MWRT_ERR_UNSUPPORTED, "nprof x nf x level slabs exceeds grid limit"};
+  Call call;
+  int rc = begin_call(c, &m, 1, s, &call);
+  if (rc || call.empty) return rc;
+  hipStream_t st = call.st;
+  // the parameter list, content-keyed like the frequencies (field and line as one exactly representable double each)
+  std::vector<double> key((size_t)npar);
+  for (int i = 0; i < npar; ++i) key[(size_t)i] = params[i].field * 1024.0 + (params[i].line + 1);
+  DeviceCache::Blob pb;
+  HIP_TRY(c->par_cache.get(0, 0, key.data(), npar, c->stream, [&](std::vector<char>* host) {
+    host->assign((const char*)params, (const char*)(params + npar));
+    return npar;
+  }, &pb));
+  const mwrt_param* dev_par = (const mwrt_param*)pb.dev;
+  const size_t nabs = (size_t)nprof * nf * nlev;
+  size_t gmax = par::PAR_WS_BYTES / (sizeof(double) * nabs);
+  gmax = gmax < 1 ? 1 : (gmax > (size_t)npar ? (size_t)npar : gmax);
+  HIP_TRY(grow_behind_drain(c->d_jac, sizeof(double) * 6 * nabs + sizeof(unsigned) * (size_t)nprof));
+  HIP_TRY(grow_behind_drain(c->d_par, sizeof(double) * nabs * gmax));
+  rc = workspace_acquire(c, st); if (rc) return rc;
+  auto handover = on_scope_exit([&] { (void)workspace_release(c, st); });    // on every return path from here on
+  double* w = c->d_jac.as<double>();
+  unsigned* flags = reinterpret_cast<unsigned*>(w + 6 * nabs);
+  HIP_TRY(hipMemsetAsync(flags, 0, sizeof(unsigned) * (size_t)nprof, st));
+  AbsorbTlArgs ta{};
+  ta.M = m->d_desc; ta.p = d_p; ta.t = d_t; ta.rh = d_rh; ta.frq = call.dev_frq;
+  ta.awet = w; ta.adry = w + nabs; ta.dawet_dt = w + 2 * nabs; ta.dawet_de = w + 3 * nabs;
+  ta.dadry_dt = w + 4 * nabs; ta.dadry_de = w + 5 * nabs;
+  ta.flags = flags; ta.nlev = nlev; ta.nf = nf; ta.nslab = nslab;
+  rc = timed(c, st, [&] { return launch_absorb_tl(ta, nprof, st); });
+  if (rc) return rc;
+  for (int p0 = 0; p0 < npar; p0 += (int)gmax) {
+    const int gn = npar - p0 < (int)gmax ? npar - p0 : (int)gmax;
+    par::ParTangentArgs pt{};
+    pt.M = m->d_desc; pt.p = d_p; pt.t = d_t; pt.rh = d_rh; pt.frq = call.dev_frq; pt.params = dev_par;
+    pt.dalpha = c->d_par.as<double>(); pt.nlev = nlev; pt.nf = nf; pt.nslab = nslab; pt.p0 = p0; pt.gn = gn;
+    for (int q = p0; q < p0 + gn; ++q) pt.o2_any |= param_is_o2(params[q].field) ? 1 : 0;
+    rc = timed(c, st, [&] { return par::launch_par_tangent(pt, nprof, st); });
+    if (rc) return rc;
+    par::ParContractArgs pc{};
+    pc.M = m->d_desc; pc.z = d_z; pc.t = d_t; pc.awet = ta.awet; pc.adry = ta.adry; pc.flags = flags;
+    pc.frq = call.dev_frq; pc.airmass = call.dev_am; pc.params = dev_par; pc.dalpha = pt.dalpha;
+    pc.tb = d_tb; pc.dtb_db = d_dtb_db; pc.valid = d_valid;
+    pc.nlev = nlev; pc.nf = nf; pc.nang = nang; pc.npar = npar; pc.p0 = p0; pc.gn = gn;
+    rc = timed(c, st, [&] { return par::launch_par_contract(pc, nprof, st); });
+    if (rc) return rc;
+  }
+  return MWRT_OK;
+}
+
+}  // namespace
+
+int mwrt_tb_param_jacobian_batch_device(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
+                                        const double* d_z, const double* d_p, const double* d_t, const double* d_rh,
+                                        int32_t nf, const double* frq, int32_t nang, const double* elev,
+                                        int32_t npar, const mwrt_param* params,
+                                        double* d_tb, double* d_dtb_db, uint8_t* d_valid, void* stream) {
+  return param_jacobian_device(c, m, nprof, nlev, d_z, d_p, d_t, d_rh, nf, frq, nang, elev, npar, params, d_tb, d_dtb_db,
+                               d_valid, stream);
+}
+
+// ... and on HOST buffers, synchronous: staged through a device buffer of this call's own (freed on every return path), one
+// param_jacobian_device call on the context's stream -- which makes every check and every decision -- and the results
+// copied back as they are.
+int mwrt_tb_param_jacobian_batch(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
+                                 const double* z, const double* p, const double* t, const double* rh,
+                                 int32_t nf, const double* frq, int32_t nang, const double* elev,
+                                 int32_t npar, const mwrt_param* params, double* tb, double* dtb_db, uint8_t* valid) {
+  CallSpec s{CALL_ANGLES | CALL_HOST | CALL_STAGES, nprof, nlev, nf, frq, nang, elev, nullptr};
+  if (npar < 1 || npar > MWRT_MAX_PARAMS) s.after_common = Check{MWRT_ERR_INVALID_ARGUMENT, "npar outside 1 .. MWRT_MAX_PARAMS"};
+  s.buffers_ok = z && p && t && rh && frq && elev && params && dtb_db && valid;
+  Call call;
+  int rc = begin_call(c, &m, 1, s, &call);
+  if (rc || call.empty) return rc;
+  hipStream_t st = call.st;
+  const size_t nin = (size_t)nprof * nlev, ntb = (size_t)nprof * nang * nf, nout = ntb * (size_t)npar;
+  DevBuf buf;                                                     // this call's own: inputs | tb | columns | valid
+  auto free_buf = on_scope_exit([&] { buf.release(); });
+  HIP_TRY(buf.reserve(sizeof(double) * (4 * nin + ntb + nout) + (size_t)nprof));
+  double* q = buf.as<double>();
+  const double* in[4] = {z, p, t, rh};
+  const double* din[4] = {};
+  for (int k = 0; k < 4; ++k) {
+    HIP_TRY(hipMemcpyAsync(q, in[k], sizeof(double) * nin, hipMemcpyHostToDevice, st));
+    din[k] = q; q += nin;
+  }
+  double* d_tb = q; q += ntb;
+  double* d_out = q; q += nout;
+  uint8_t* d_valid = reinterpret_cast<uint8_t*>(q);
+  rc = param_jacobian_device(c, m, nprof, nlev, din[0], din[1], din[2], din[3], nf, frq, nang, elev, npar, params,
+                             d_tb, d_out, d_valid, nullptr);
+  if (rc) return rc;
+  if (tb) HIP_TRY(hipMemcpyAsync(tb, d_tb, sizeof(double) * ntb, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(dtb_db, d_out, sizeof(double) * nout, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(valid, d_valid, (size_t)nprof, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return MWRT_OK;
 }
 
 int mwrt_set_chunk_width(mwrt_context* c, int width) {

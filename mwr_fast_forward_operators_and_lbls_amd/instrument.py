@@ -188,6 +188,15 @@ class Instrument:
         stream = torch.cuda.current_stream(ref.device).cuda_stream if ref.is_cuda else None
         return retrieval._native_obs_apply(self, tb, k_blocks, stream)
 
+    def param_jacobian(self, model, z, p, t, rh, params, relative=False):
+        """The spectroscopic-parameter Jacobian of the CHANNELS (``sensitivity.param_jacobian`` on the quadrature grid,
+        reduced by this map with the parameter axis in the place of the levels): ``(tb_ch [nprof][nang][nch],
+        kb_ch [nprof][nang][nch][npar], valid [nprof])``."""
+        from . import sensitivity
+        tb, kb, valid = sensitivity.param_jacobian(model, z, p, t, rh, self.frq_q, self.elev_q, params, relative=relative)
+        tb_ch, k_ch = self.apply(tb, [kb])
+        return tb_ch, k_ch[0], valid
+
     def close(self):
         handles, self._handles = getattr(self, "_handles", {}), {}
         for ctx, h in handles.values():
