@@ -18,7 +18,11 @@
  *   profiles   [nprof][nlev], level 0 = ground, level nlev-1 = top -- what TbCloudRTE sees
  *              after the wrapper's [::-1] (:123); z in km, p in hPa, T in K, rh as fraction
  *              (:109-114).
- *   frq_ghz    [nf]    (:87-88)
+ *   frq_ghz    [nf]    (:87-88)  Frequencies: the absorption models hold for 1 ... 1000 GHz, and that is the range
+ *              the kernels' arithmetic is bounded for (the far-line sums carry products of up to twenty line
+ *              denominators, ~f^80).  The range is a precondition, not checked: up to about 1.6 THz the
+ *              stated headroom still holds, from about 7 THz these products overflow and TBs come out inf / NaN
+ *              with valid = 1.
  *   elev_deg   [nang]  ELEVATION angles in (0, 180), 90 = zenith (:106, :37); the path is
  *              plane-parallel (air mass 1/sin elev), other values are MWRT_ERR_INVALID_ARGUMENT
  *   tb_out     [nprof][nang][nf]  == pyrtlib's DataFrame row order (angle-major) per profile

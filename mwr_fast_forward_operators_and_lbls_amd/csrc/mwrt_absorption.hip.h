@@ -112,28 +112,30 @@ struct FarLine { double P, Q, A2, Bc; };
 // Here two frequencies go side by side and the loop is software-pipelined by hand: the reciprocals of one pair are issued,
 // then the 52 independent instructions of the NEXT pair's numerators and denominators, then the first pair's Newton step and
 // accumulation; the f^2 values are read from LDS two pairs ahead.  Scheduling barriers keep the compiler from undoing it.
+// the quad at one frequency, num / den with den = d0 d1 d2 d3: 21 instructions
+__device__ __forceinline__ void far_quad_terms(double f2, const FarLine& a, const FarLine& b, const FarLine& c, const FarLine& d,
+                                               double& den, double& num) {
+  const double d0 = __builtin_fma(f2, f2 + a.A2, a.Bc);
+  const double d1 = __builtin_fma(f2, f2 + b.A2, b.Bc);
+  const double d2 = __builtin_fma(f2, f2 + c.A2, c.Bc);
+  const double d3 = __builtin_fma(f2, f2 + d.A2, d.Bc);
+  const double n0 = __builtin_fma(f2, a.P, a.Q);
+  const double n1 = __builtin_fma(f2, b.P, b.Q);
+  const double n2 = __builtin_fma(f2, c.P, c.Q);
+  const double n3 = __builtin_fma(f2, d.P, d.Q);
+  const double p01 = d0 * d1, p23 = d2 * d3;
+  const double m01 = __builtin_fma(n0, d1, n1 * d0);
+  const double m23 = __builtin_fma(n2, d3, n3 * d2);
+  den = p01 * p23;
+  num = __builtin_fma(m01, p23, m23 * p01);
+}
 template <int NFC>
 __device__ __forceinline__ void far_quad_accumulate(const double* sfq, const FarLine& a, const FarLine& b,
                                                     const FarLine& c, const FarLine& d, double (&sum)[NFC]) {
   static_assert(NFC % 2 == 0, "frequencies are taken in pairs");
   auto front = [&](const double (&f2s)[2], double (&den)[2], double (&num)[2]) {
 #pragma unroll
-    for (int g = 0; g < 2; ++g) {
-      const double f2 = f2s[g];
-      const double d0 = __builtin_fma(f2, f2 + a.A2, a.Bc);
-      const double d1 = __builtin_fma(f2, f2 + b.A2, b.Bc);
-      const double d2 = __builtin_fma(f2, f2 + c.A2, c.Bc);
-      const double d3 = __builtin_fma(f2, f2 + d.A2, d.Bc);
-      const double n0 = __builtin_fma(f2, a.P, a.Q);
-      const double n1 = __builtin_fma(f2, b.P, b.Q);
-      const double n2 = __builtin_fma(f2, c.P, c.Q);
-      const double n3 = __builtin_fma(f2, d.P, d.Q);
-      const double p01 = d0 * d1, p23 = d2 * d3;
-      const double m01 = __builtin_fma(n0, d1, n1 * d0);
-      const double m23 = __builtin_fma(n2, d3, n3 * d2);
-      den[g] = p01 * p23;
-      num[g] = __builtin_fma(m01, p23, m23 * p01);
-    }
+    for (int g = 0; g < 2; ++g) far_quad_terms(f2s[g], a, b, c, d, den[g], num[g]);
   };
   double den[2], num[2], r[2];
   double f2c[2] = {sfq[1], sfq[3]};
@@ -157,6 +159,74 @@ __device__ __forceinline__ void far_quad_accumulate(const double* sfq, const Far
     }
   }
   MWRT_STAGE();
+}
+
+// SEVERAL quads per reciprocal (the fused kernel): the far-line sum of a frequency is carried across the quads of a group
+// as a fraction N / D and divided out once per group.  With S the plain sum so far,
+//   first quad of a group   N = S den + num,           D = den              (1 instruction behind the 21 of the quad)
+//   each later quad         N = N den + num D,         D = D den            (3)
+//   end of the group        S = N (1 / D)                                   (v_rcp_f64 + Newton step + multiply, as before)
+// so nine quads in groups of 5 + 4 end in two reciprocals per frequency instead of nine.  Nothing in a quad waits for a
+// reciprocal any more: the frequencies are independent chains of FMAs and the compiler interleaves them as it likes; the
+// reciprocals of a group's end go side by side for all frequencies.  A line voted out at set-up (P = Q = 0) stays in its
+// quad: its denominator multiplies D, its numerator is zero.
+// Range of D: a far line has |f - c| >= FAR_MIN_GHZ = 0.2 GHz after its shift, so with centres and frequencies in
+// [1 GHz, 1 THz] and half widths up to 5 GHz a line's denominator ((f - c)^2 + w^2)((f + c)^2 + w^2) lies in
+// [0.04, 1.01e12] and a quad's in [2.5e-6, 1.05e48]: a group of FAR_GROUP_QUADS = 5 reaches D in [1e-28, 1e241], a factor
+// 1e67 under the overflow threshold (1.8e308) and 1e279 above the smallest normal number.  N is at most sum|term| D, and
+// the sums (S / F^2-scaled line strengths over such denominators) are far below 1e17, which leaves the 1e50 of headroom
+// this form is held to (tests/test_far_group_reference.py).  The 1 THz is the API's stated frequency limit (include/mwrt.h,
+// "Frequencies"); the headroom holds to about 1.6 THz (D grows as f^80), and from about 7 THz a group's product overflows.  Six quads (1.3e288) would still fit, without the headroom;
+// nine (1e432) overflow.
+constexpr int FAR_GROUP_QUADS = 5;
+template <int NFC, bool FIRST>
+__device__ __forceinline__ void far_quad_fraction(const double* sfq, const FarLine& a, const FarLine& b, const FarLine& c,
+                                                  const FarLine& d, const double (&sum)[NFC], double (&N)[NFC], double (&D)[NFC]) {
+#pragma unroll
+  for (int j = 0; j < NFC; ++j) {
+    double den, num;
+    far_quad_terms(sfq[2 * j + 1], a, b, c, d, den, num);
+    if constexpr (FIRST) {
+      N[j] = __builtin_fma(sum[j], den, num);
+      D[j] = den;
+    } else {
+      N[j] = __builtin_fma(N[j], den, num * D[j]);
+      D[j] *= den;
+    }
+  }
+}
+template <int NFC>
+__device__ __forceinline__ void far_group_close(const double (&N)[NFC], const double (&D)[NFC], double (&sum)[NFC]) {
+  double r[NFC];
+#pragma unroll
+  for (int j = 0; j < NFC; ++j) r[j] = __builtin_amdgcn_rcp(D[j]);
+#pragma unroll
+  for (int j = 0; j < NFC; ++j) r[j] = __builtin_fma(r[j], __builtin_fma(-D[j], r[j], 1.0), r[j]);
+#pragma unroll
+  for (int j = 0; j < NFC; ++j) sum[j] = N[j] * r[j];
+}
+// the quad loop of a species in this form: `m` holds a multiple of four lines, `setup(k, FarLine&)` is the species' far_setup
+template <int NFC, class Mask, class Setup>
+__device__ __forceinline__ void far_groups_accumulate(const double* sfq, Mask m, Setup&& setup, double (&sum)[NFC]) {
+  auto next_quad = [&](FarLine (&q)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { setup(__builtin_ctzll((unsigned long long)m), q[i]); m &= m - Mask(1); }
+    LDS_RELOAD_FENCE();
+  };
+  while (m) {
+    double N[NFC], D[NFC];
+    {
+      FarLine q[4];
+      next_quad(q);
+      far_quad_fraction<NFC, true>(sfq, q[0], q[1], q[2], q[3], sum, N, D);
+    }
+    for (int g = 1; g < FAR_GROUP_QUADS && m; ++g) {
+      FarLine q[4];
+      next_quad(q);
+      far_quad_fraction<NFC, false>(sfq, q[0], q[1], q[2], q[3], sum, N, D);
+    }
+    far_group_close<NFC>(N, D, sum);
+  }
 }
 
 // VERY far lines: a line whose poles in u = f^2 (u ~ c^2 -+ 2 i c w) lie at >= 1/VF_RATIO_MAX half ranges from the middle u0
@@ -243,7 +313,8 @@ __device__ __forceinline__ unsigned long long lowest_bits(unsigned long long m, 
 // Chebyshev nodes of the window (NODES = true: raw line sums out, no continuum, no SD lines; a line whose per-lane
 // vote fails is reported in *failed and left out) and interpolated to each chunk's frequencies; the chunk call then
 // starts from those sums (init_sum, init_bsum) and skips the lines in `excl`.  Outside window mode: excl = 0, null.
-template <int NFC, bool NODES = false>
+// GROUPED: the far quads as running fractions (far_groups_accumulate) -- the fused kernel up to 512 threads, all variants alike
+template <int NFC, bool NODES = false, bool GROUPED = false>
 __device__ __forceinline__ void h2o_absorb(cmodel M, const LevelState& L, const double* sfq /*LDS: {f, f^2} per slot*/,
                                            const LineMasks& lm, double (&awet)[NFC], unsigned excl = 0u,
                                            const double* init_sum = nullptr, double init_bsum = 0.0,
@@ -264,7 +335,7 @@ __device__ __forceinline__ void h2o_absorb(cmodel M, const LevelState& L, const 
   for (int j = 0; j < NFC; ++j) sum[j] = init_sum ? init_sum[j] : 0.0;
 
   const int nl = M->n_h2o;
-  const unsigned all = ((nl >= 32) ? 0xffffffffu : ((1u << nl) - 1u)) & ~excl;
+  const unsigned all = h2o_lines_all(nl) & ~excl;
   // The 750-GHz cutoff of each Lorentz term depends on the lane only through the (tiny) pressure
   // shift.  Three loops, each with ONE body:
   //   A  far lines (table centre >= FAR_H2O_GHZ from every frequency), both terms inside the cutoff for
@@ -275,14 +346,14 @@ __device__ __forceinline__ void h2o_absorb(cmodel M, const LevelState& L, const 
   // Lines whose two terms are beyond the cutoff for every frequency (e.g. 916 GHz from 22 GHz) are skipped.
   const double fmin = sfq[2 * NFC], fmax = sfq[2 * NFC + 1];
   double bsum = init_bsum;                                    // sum of (count * s * base), frequency independent
-  const unsigned sd_eff = lm.h2o_sd & ~lm.h2o_sdfar;          // lines that go to the speed-dependent loop straight away
+  const unsigned sd_eff = h2o_sd_near(lm);                    // lines that go to the speed-dependent loop straight away
   unsigned sd_extra = 0u;                                     // ... and the "out of reach" ones a level of this wave takes back
   unsigned deferred = (~lm.h2o_far | lm.h2o_res) & ~sd_eff & ~lm.h2o_none & all;
-  const unsigned setA = (MWRT_ABLATE & 2) ? 0u : (lm.h2o_far & ~lm.h2o_res & ~sd_eff & ~lm.h2o_none & all);
+  const unsigned setA = (MWRT_ABLATE & 2) ? 0u : h2o_far_set(lm, all);
   // ... of which the very far ones go through one Taylor polynomial (vfar_add) and the rest
   // FOUR at a time through far_quad_accumulate; the count mod 4 left over joins loop B
-  const unsigned setV = NODES ? 0u : (setA & lm.h2o_vfar);
-  const unsigned setQ = setA & ~setV;
+  const unsigned setV = h2o_vfar_set(lm, setA, NODES);
+  const unsigned setQ = h2o_quad_set(lm, setA, NODES);
   const unsigned leftA = (unsigned)lowest_bits(setQ, __builtin_popcount(setQ) & 3);
   const unsigned leftP = (__builtin_popcount(leftA) >= 2) ? (unsigned)lowest_bits(leftA, 2) : 0u;      // ... two of them as a pair
   deferred |= leftA & ~leftP;
@@ -321,7 +392,8 @@ __device__ __forceinline__ void h2o_absorb(cmodel M, const LevelState& L, const 
     LDS_RELOAD_FENCE();
     vfar_eval<NFC>(sfq, lm.vf_invh, -lm.vf_u0 * lm.vf_invh, acc, sum);
   }
-  for (unsigned m = setQ & ~leftA; m;) {
+  if constexpr (GROUPED) far_groups_accumulate<NFC>(sfq, setQ & ~leftA, far_setup, sum);
+  else for (unsigned m = setQ & ~leftA; m;) {
     FarLine q0, q1, q2, q3;
     far_setup(__builtin_ctz(m), q0); m &= m - 1u;
     far_setup(__builtin_ctz(m), q1); m &= m - 1u;
@@ -530,7 +602,7 @@ struct O2Line {            // per-(level, line) quantities, frequency independen
   double dnu;
 };
 
-template <int NFC, bool NODES = false>
+template <int NFC, bool NODES = false, bool GROUPED = false>
 __device__ __forceinline__ void dry_absorb(cmodel M, const LevelState& L, const double* sfq /*LDS: {f, f^2} per slot*/,
                                            const LineMasks& lm, double (&adry)[NFC], unsigned long long excl = 0ull,
                                            const double* init_sum = nullptr, unsigned long long* failed = nullptr) {
@@ -586,14 +658,14 @@ __device__ __forceinline__ void dry_absorb(cmodel M, const LevelState& L, const 
   };
 
   const int nl = M->n_o2;
-  const unsigned long long all = ((nl >= 64) ? ~0ull : ((1ull << nl) - 1ull)) & ~excl;
+  const unsigned long long all = o2_lines_all(nl) & ~excl;
   // loop A: far lines -- polynomial denominator; a line whose shift |dnu| exceeds the allowance at any
   // level of this wave is handed to loop B
   unsigned long long near = ~lm.o2_far & all;
-  const unsigned long long setA = (MWRT_ABLATE & 1) ? 0ull : (lm.o2_far & all);
+  const unsigned long long setA = (MWRT_ABLATE & 1) ? 0ull : o2_far_set(lm, all);
   // ... four lines at a time (far_quad_accumulate); the count mod 4 left over joins loop B
-  const unsigned long long setV = NODES ? 0ull : (setA & lm.o2_vfar);      // very far lines: one Taylor polynomial (vfar_add)
-  const unsigned long long setQ = setA & ~setV;
+  const unsigned long long setV = o2_vfar_set(lm, setA, NODES);           // very far lines: one Taylor polynomial (vfar_add)
+  const unsigned long long setQ = o2_quad_set(lm, setA, NODES);
   const unsigned long long leftA = lowest_bits(setQ, __builtin_popcountll(setQ) & 3);
   const unsigned long long leftP = (__builtin_popcountll(leftA) >= 2) ? lowest_bits(leftA, 2) : 0ull;   // ... two of them as a pair
   near |= leftA & ~leftP;
@@ -617,7 +689,8 @@ __device__ __forceinline__ void dry_absorb(cmodel M, const LevelState& L, const 
     LDS_RELOAD_FENCE();
     vfar_eval<NFC>(sfq, lm.vf_invh, -lm.vf_u0 * lm.vf_invh, acc, sum);
   }
-  for (unsigned long long m = setQ & ~leftA; m;) {
+  if constexpr (GROUPED) far_groups_accumulate<NFC>(sfq, setQ & ~leftA, far_setup, sum);
+  else for (unsigned long long m = setQ & ~leftA; m;) {
     FarLine q0, q1, q2, q3;
     far_setup(__builtin_ctzll(m), q0); m &= m - 1ull;
     far_setup(__builtin_ctzll(m), q1); m &= m - 1ull;
@@ -700,27 +773,28 @@ struct CloudLevel {
 constexpr double CLOUD_KICE = 8.18645 * 0.000959553 * (0.1 * 2.302585092994045684) / 29.9792458;
 
 __device__ __forceinline__ CloudLevel cloud_level(cmodel M, double tk) {
-  CloudLevel c{};
-  c.mode = M->liq_mode;
-  if (c.mode == 0) {
+  const int mode = M->liq_mode;
+  double eps0, a, b, c3;
+  cplx z1 = {0.0, 0.0}, icnorm = {0.0, 0.0};
+  if (mode == 0) {
     const double theta1 = 1.0 - fdiv(300.0, tk);
-    c.eps0 = 77.66 - 103.3 * theta1;
-    c.a = 0.0671 * c.eps0;
+    eps0 = 77.66 - 103.3 * theta1;
+    a = 0.0671 * eps0;
     const double fp = (316.0 * theta1 + 146.4) * theta1 + 20.2;
-    c.b = fdiv(1.0, fp);
-    c.c = fdiv(1.0, 39.8 * fp);
+    b = fdiv(1.0, fp);
+    c3 = fdiv(1.0, 39.8 * fp);
   } else {
     const double tc = tk - 273.15;
     const double lth = flog(fdiv(300.0, tk));
-    c.eps0 = -43.7527 * fexp(0.05 * lth) + 299.504 * fexp(1.47 * lth) - 399.364 * fexp(2.11 * lth) + 221.327 * fexp(2.31 * lth);
-    c.a = 80.69715 * fexp(-tc * (1.0 / 226.45));
-    c.b = 1164.023 * fexp(fdiv(-651.4728, tc + 133.07));
-    c.c = 4.008724 * fexp(-tc * (1.0 / 103.05));
+    eps0 = -43.7527 * fexp(0.05 * lth) + 299.504 * fexp(1.47 * lth) - 399.364 * fexp(2.11 * lth) + 221.327 * fexp(2.31 * lth);
+    a = 80.69715 * fexp(-tc * (1.0 / 226.45));
+    b = 1164.023 * fexp(fdiv(-651.4728, tc + 133.07));
+    c3 = 4.008724 * fexp(-tc * (1.0 / 103.05));
     const double f1 = 10.46012 + tc * (0.1454962 + tc * (0.063267156 + tc * 0.00093786645));
-    c.z1 = cplx{-0.75 * f1, f1};
-    c.icnorm = crecip(clog_(cdiv(cplx{-4500.0, 2000.0}, c.z1)));      // 1/cnorm; 1/conj(cnorm) is its conjugate
+    z1 = cplx{-0.75 * f1, f1};
+    icnorm = crecip(clog_(cdiv(cplx{-4500.0, 2000.0}, z1)));      // 1/cnorm; 1/conj(cnorm) is its conjugate
   }
-  return c;
+  return CloudLevel{mode, eps0, a, b, c3, z1, icnorm};
 }
 
 // liquid absorption for water content `denl` [g m-3] at frequency f [GHz]

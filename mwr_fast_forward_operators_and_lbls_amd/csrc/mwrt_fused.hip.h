@@ -110,6 +110,16 @@ k_tb_fused(const FusedArgs A) {
   double* part = bof + (size_t)NFK * ld;                 // [pairs*nseg][2] segment partials (B, T)
   double* scratch = part + (size_t)A.g.npart;            // [16] block_sum scratch
   double* edge = scratch + 16;                           // [nwaves][2*NFC] last lane of each wave
+  // Until K2 fills them the tau / Planck rows are scratch, [frequency][level]: the wet absorption waits there while
+  // dry_absorb runs, and the cloud block passes its liquid absorption through them.
+  auto row = [&](int j) -> double* { return (j < NFK ? tau + (size_t)j * ld : bof + (size_t)(j - NFK) * ld); };
+  // Parked wet sums and grouped far quads serve the 256- and 512-thread instantiations.  The 1024-thread ones (513 - 1024
+  // levels) run under a 128-VGPR cap, where a group's N and D (56 registers more than the plain sums) go to scratch inside the
+  // line loops: 600 levels took 260 us against 244, 1000 levels 366 against 340 (profiles/far_line_groups_ab.txt).  They keep
+  // the quad form and the shuffle path.  No call can reach two MAXT with one profile, so every pair of instantiations that can
+  // be compared bit for bit (TB-only, OPT, FULL, every chunk width) still shares one form.
+  constexpr bool GROUPED = MAXT <= 512;
+  constexpr bool PARK = !ALPHA && GROUPED;               // (ALPHA reads its coefficients just before the layer step)
   constexpr int GRP = 16;                                // levels per group of the layer-tau maxima
   const int ngrp = nthreads / GRP;
   float* gmax = (float*)(edge + (size_t)nwaves * 2 * NFC);   // [NFK][ngrp] largest zenith layer tau of 16 levels of a row
@@ -149,7 +159,7 @@ k_tb_fused(const FusedArgs A) {
   // it skips the per-level phases wave-uniformly and only meets the barriers
   const bool wave_live = wave * WAVE < nlev;
   const int64_t off = pin * nlev + (active ? tid : 0);
-  const double zi = A.z[off], ti = A.t[off];
+  double zi = A.z[off], ti = A.t[off];
   const double pi = ALPHA ? 0.0 : A.p[off], rhi = ALPHA ? 0.0 : A.rh[off];
   if (active && (isnan(zi) || isnan(pi) || isnan(ti) || isnan(rhi))) atomicOr(&s_flag, 1);
   double awet[NFC], adry[NFC];
@@ -169,7 +179,7 @@ k_tb_fused(const FusedArgs A) {
     }
     if (active && bad) atomicOr(&s_flag, 1);
   }
-  double denl = 0.0, deni = 0.0, o3n = 0.0;
+  double denl = 0.0, deni = 0.0, o3n = 0.0;               // o3n: for the NaN test only, the ozone term reads it again
   if constexpr (OPT) {
     if (A.denliq) denl = A.denliq[off];
     if (A.denice) deni = A.denice[off];
@@ -190,22 +200,41 @@ k_tb_fused(const FusedArgs A) {
     const LineMasks lm = load_masks(A.masks[mi], blockIdx.y);
     MWRT_STAMP(1);
     MWRT_SETPRIO(3);
-    h2o_absorb<NFC>(M, L, sfq, lm, awet);
+    h2o_absorb<NFC, false, GROUPED>(M, L, sfq, lm, awet);
+    // the 14 wet sums would sit in 28 registers through the whole oxygen phase: they wait in LDS instead, and the layer
+    // step reads its own and its lower neighbour's value from there (no crossbar, no wave seam for the wet half)
+    if constexpr (PARK) {
+      if (active) {
+#pragma unroll
+        for (int j = 0; j < NFC; ++j) row(j)[tid] = awet[j];
+      }
+    }
     MWRT_STAMP(2);
     MWRT_SETPRIO(2);
-    dry_absorb<NFC>(M, L, sfq, lm, adry);
+    dry_absorb<NFC, false, GROUPED>(M, L, sfq, lm, adry);
     MWRT_SETPRIO(1);
     MWRT_STAMP(3);
     if constexpr (OPT) {
-      if (A.o3n) x_absorb<NFC>(M, ti, pi, o3n, sfq, adry);       // clearsky_absorption(..., o3n): ozone joins the dry term
+      // The line loops need neither the ozone column nor z, T and p: they are read again where they are used (here and
+      // after the barrier below) instead of riding through the line loops in registers -- the OPT variant sits at the
+      // edge of its third wave.  (The fences keep the loads from being merged with the first ones.)
+      if (A.o3n) {                                                 // clearsky_absorption(..., o3n): ozone joins the dry term
+        LDS_RELOAD_FENCE();
+        x_absorb<NFC>(M, A.t[off], A.p[off], A.o3n[off], sfq, adry);
+      }
     }
   }
-  // neighbour level i-1: lane-1 through the crossbar, wave seams through a 2*NFC-double edge row
+  // neighbour level i-1 of the dry half (and of the wet half where it is not parked): lane-1 through the crossbar,
+  // wave seams through a 2*NFC-double edge row.  The barrier also orders the parking stores before the neighbour reads.
   if (lane == WAVE - 1) {
 #pragma unroll
-    for (int j = 0; j < NFC; ++j) { edge[wave * 2 * NFC + j] = awet[j]; edge[wave * 2 * NFC + NFC + j] = adry[j]; }
+    for (int j = 0; j < NFC; ++j) {
+      if constexpr (!PARK) edge[wave * 2 * NFC + j] = awet[j];
+      edge[wave * 2 * NFC + NFC + j] = adry[j];
+    }
   }
   __syncthreads();
+  if constexpr (OPT) { LDS_RELOAD_FENCE(); zi = A.z[off]; ti = A.t[off]; }
   // Wet and dry rows are kept apart only where the opacity columns are wanted (EXTRAS); otherwise td[] holds
   // the layer total (wet + dry, then + ice + liquid) and tw[] is never materialised: 28 registers fewer.
   double tw[EXTRAS ? NFC : 1], td[NFC];
@@ -215,6 +244,17 @@ k_tb_fused(const FusedArgs A) {
     const double dz = (active && tid > 0) ? ((zi - z0) - (A.z[off - 1] - z0)) : 0.0;
     const bool seam = (lane == 0) && (wave > 0);
     const bool has_prev = active && tid > 0;
+    // Parked wet sums: the rows are one block of LDS, row(j) = tau + j * ld, and a level's own value and its lower
+    // neighbour's sit side by side, so every lane reads the pair at &row(j)[tid - 1] -- unconditionally (a lane without a
+    // layer below it reads the first two entries of the row: it takes part in no vote and keeps no result), from one
+    // pointer that moves a row per frequency, one frequency ahead of its use.
+    [[maybe_unused]] ldoubles wrow = nullptr;
+    [[maybe_unused]] double pw_next = 0.0, aw_next = 0.0;
+    if constexpr (PARK) {
+      wrow = (ldoubles)(tau + (has_prev ? tid - 1 : 0));
+      asm volatile("" : "+v"(wrow));
+      if (wave_live) { pw_next = wrow[0]; aw_next = wrow[1]; }
+    }
     if (!wave_live) {
 #pragma unroll
       for (int j = 0; j < NFC; ++j) { td[j] = 0.0; if constexpr (EXTRAS) tw[j] = 0.0; }
@@ -222,10 +262,18 @@ k_tb_fused(const FusedArgs A) {
 #pragma unroll
     for (int j = 0; j < NFC; ++j) {
 #pragma clang fp contract(off)               // wet * dz + dry * dz rounds the same way in every instantiation
-      double pw = __shfl_up(awet[j], 1, WAVE);
+      double aw, pw;
+      if constexpr (PARK) {
+        aw = aw_next; pw = pw_next;
+        if (j + 1 < NFC) { wrow += ld; pw_next = wrow[0]; aw_next = wrow[1]; }
+      } else {
+        aw = awet[j];
+        pw = __shfl_up(awet[j], 1, WAVE);
+        if (seam) pw = edge[(wave - 1) * 2 * NFC + j];
+      }
       double pd = __shfl_up(adry[j], 1, WAVE);
-      if (seam) { pw = edge[(wave - 1) * 2 * NFC + j]; pd = edge[(wave - 1) * 2 * NFC + NFC + j]; }
-      const double lw = layer_value(awet[j], pw, neg, has_prev), ld_ = layer_value(adry[j], pd, neg, has_prev);
+      if (seam) pd = edge[(wave - 1) * 2 * NFC + NFC + j];
+      const double lw = layer_value(aw, pw, neg, has_prev), ld_ = layer_value(adry[j], pd, neg, has_prev);
       const double twj = has_prev ? lw * dz : 0.0;
       const double tdj = has_prev ? ld_ * dz : 0.0;
       if constexpr (EXTRAS) { tw[j] = twj; td[j] = tdj; }
@@ -240,11 +288,12 @@ k_tb_fused(const FusedArgs A) {
 #pragma unroll
     for (int j = 0; j < (CLOUD_ROWS ? NFC : 1); ++j) { tl[j] = 0.0; tci[j] = 0.0; }
     // Skipped when the profile holds no cloud at all (workgroup vote).  The liquid absorption of every level goes
-    // through the (still unused) tau / Planck rows of LDS, [frequency][level], so each lane reads its own and its
+    // through the tau / Planck rows of LDS, [frequency][level], so each lane reads its own and its
     // lower neighbour's value: no crossbar, no wave seams, and the per-level model state dies before the layer loop.
+    // The vote is the barrier between the layer loop's reads of the parked wet sums and the stores below, which reuse
+    // the same rows: no lane overwrites row(j)[tid] while lane tid + 1 still has to read it.
     const bool cloud_here = active && (denl > 0.0 || deni > 0.0);
     if ((A.denliq || A.denice) && __syncthreads_or(cloud_here)) {
-      auto row = [&](int j) -> double* { return (j < NFK ? tau + (size_t)j * ld : bof + (size_t)(j - NFK) * ld); };
       {
         const CloudLevel cl = cloud_level(M, ti);
         if (active) {

@@ -45,6 +45,23 @@ struct LineMasks {
   double vf_u0, vf_h, vf_invh; // middle and half range of the chunk's f^2 values [GHz^2] (vf_h >= 1), 1 / vf_h
 };
 
+// The sets the far-line loops of dry_absorb / h2o_absorb walk (mwrt_absorption.hip.h), shared by the kernels and by whoever
+// wants to know what they run (tests/far_set_dump.cpp).  `n` = lines in the table.  *_far_set: loop A, the rational form --
+// for water neither resonant-only, speed-dependent within reach nor beyond the cutoff.  *_vfar_set: of those (`far`), the
+// very far lines, summed as one Taylor polynomial (`nodes`: the window's node phase has none).  *_quad_set: the rest; they go
+// four at a time, the count mod 4 left over joins the general loop.
+constexpr unsigned long long o2_lines_all(int n) { return n >= 64 ? ~0ull : ((1ull << n) - 1ull); }
+constexpr unsigned h2o_lines_all(int n) { return n >= 32 ? 0xffffffffu : ((1u << n) - 1u); }
+constexpr unsigned long long o2_far_set(const LineMasks& lm, unsigned long long all) { return lm.o2_far & all; }
+constexpr unsigned long long o2_vfar_set(const LineMasks& lm, unsigned long long far, bool nodes) { return nodes ? 0ull : (far & lm.o2_vfar); }
+constexpr unsigned long long o2_quad_set(const LineMasks& lm, unsigned long long far, bool nodes) { return far & ~o2_vfar_set(lm, far, nodes); }
+constexpr unsigned h2o_sd_near(const LineMasks& lm) { return lm.h2o_sd & ~lm.h2o_sdfar; }   // straight to the speed-dependent loop
+constexpr unsigned h2o_far_set(const LineMasks& lm, unsigned all) {
+  return lm.h2o_far & ~lm.h2o_res & ~h2o_sd_near(lm) & ~lm.h2o_none & all;
+}
+constexpr unsigned h2o_vfar_set(const LineMasks& lm, unsigned far, bool nodes) { return nodes ? 0u : (far & lm.h2o_vfar); }
+constexpr unsigned h2o_quad_set(const LineMasks& lm, unsigned far, bool nodes) { return far & ~h2o_vfar_set(lm, far, nodes); }
+
 // very far lines (mwrt_absorption.hip.h vfar_add): the host picks them (chunk_masks) with the shift / width allowances
 constexpr double VF_RATIO_MAX = 0.016;
 constexpr int VF_MIN_FREQS = 7;              // ... and chunks with fewer frequencies than this are served directly
