@@ -178,6 +178,12 @@ SIGNATURES = {
     "mwrt_tb_jacobian_batch_vars": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp,
                                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(MwrtTbOptions),
                                                    ctypes.POINTER(JacVariables)]),
+    "mwrt_tb_jacobian_batch_ray_device": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp,
+                                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(MwrtTbOptions),
+                                                         ctypes.POINTER(JacVariables), _vp]),
+    "mwrt_tb_jacobian_batch_ray": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp,
+                                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(MwrtTbOptions),
+                                                  ctypes.POINTER(JacVariables)]),
     "mwrt_tb_param_jacobian_batch_device": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp,
                                                            _i32, ctypes.POINTER(MwrtParam), _vp, _vp, _vp, _vp]),
     "mwrt_tb_param_jacobian_batch": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp,
@@ -545,15 +551,39 @@ class Context:
         """The device K-matrix in retrieval variables (include/mwrt.h mwrt_tb_jacobian_batch_vars_device): as
         ``tb_jacobian_batch_opt_device`` with ``variables`` a ``JacVariables`` (None: the raw rows) and ``d_dtb_ddz``
         optional in every mode.  ``d_dtb_dh`` receives the humidity row in the variable asked for."""
+        self._jacobian_vars_device("mwrt_tb_jacobian_batch_vars_device", model, nprof, nlev, d_z, d_p, d_t, d_rh, frq, elev,
+                                   d_tb, d_dtb_dt, d_dtb_dh, d_valid, d_dtb_ddz, _options(d_denliq, d_denice, ray_tracing, d_o3n),
+                                   d_dtb_dliq, d_dtb_dice, variables, stream)
+
+    def _jacobian_vars_device(self, symbol, model, nprof, nlev, d_z, d_p, d_t, d_rh, frq, elev, d_tb, d_dtb_dt, d_dtb_dh,
+                              d_valid, d_dtb_ddz, opts, d_dtb_dliq, d_dtb_dice, variables, stream):
+        """The one parameter list mwrt_tb_jacobian_batch_vars_device and mwrt_tb_jacobian_batch_ray_device share."""
         frq, elev = _f64(frq).ravel(), _f64(elev).ravel()
-        opts = _options(d_denliq, d_denice, ray_tracing, d_o3n)
         opt_ptr = lambda x: _ptr(x) if x is not None else None   # noqa: E731
-        self._check(self._lib.mwrt_tb_jacobian_batch_vars_device(
+        self._check(getattr(self._lib, symbol)(
             self._handle, self.model(model), int(nprof), int(nlev), _ptr(d_z), _ptr(d_p), _ptr(d_t), _ptr(d_rh),
             frq.size, _ptr(frq), elev.size, _ptr(elev), _ptr(d_tb), _ptr(d_dtb_dt), _ptr(d_dtb_dh), opt_ptr(d_dtb_ddz),
             opt_ptr(d_dtb_dliq), opt_ptr(d_dtb_dice), _ptr(d_valid), ctypes.byref(opts) if opts is not None else None,
-            ctypes.byref(variables) if variables is not None else None, _stream(stream)),
-            "mwrt_tb_jacobian_batch_vars_device")
+            ctypes.byref(variables) if variables is not None else None, _stream(stream)), symbol)
+
+    @_serialised
+    def tb_jacobian_batch_ray_device(self, model, nprof, nlev, d_z, d_p, d_t, d_rh, frq, elev, d_tb, d_dtb_dt, d_dtb_dh,
+                                     d_valid, d_dtb_ddz=None, d_denliq=None, d_denice=None, d_dtb_dliq=None,
+                                     d_dtb_dice=None, variables=None, stream=None):
+        """The device K-matrix along refracted spherical ray paths (include/mwrt.h mwrt_tb_jacobian_batch_ray_device): the
+        K-matrix of ``tb_batch_device(ray_tracing=True)``, rows exact (the path's response to the state included), in the
+        layout and with the keywords of ``tb_jacobian_batch_vars_device``.  ``valid`` is 3 where a ray was trapped."""
+        self._jacobian_vars_device("mwrt_tb_jacobian_batch_ray_device", model, nprof, nlev, d_z, d_p, d_t, d_rh, frq, elev,
+                                   d_tb, d_dtb_dt, d_dtb_dh, d_valid, d_dtb_ddz, _options(d_denliq, d_denice), d_dtb_dliq,
+                                   d_dtb_dice, variables, stream)
+
+    @_serialised
+    def tb_jacobian_batch_ray(self, model, z, p, t, rh, frq, elev, denliq=None, denice=None, variables=None,
+                              thickness=True):
+        """The same on NumPy arrays, synchronous (include/mwrt.h mwrt_tb_jacobian_batch_ray): what
+        ``tb_jacobian_batch_vars`` returns, along ray-traced paths."""
+        return self._jacobian_vars_host("mwrt_tb_jacobian_batch_ray", model, z, p, t, rh, frq, elev, denliq, denice,
+                                        variables, thickness)
 
     @_serialised
     def tb_jacobian_batch_vars(self, model, z, p, t, rh, frq, elev, denliq=None, denice=None, variables=None,
@@ -562,6 +592,11 @@ class Context:
         [nprof][nang][nf]``, ``valid [nprof]`` and a dict of ``dtb_dt``, ``dtb_dh`` (the humidity row in the variable
         asked for), ``dtb_ddz`` (the raw thickness row; absent with ``thickness=False``) and, for each cloud array given,
         ``dtb_dliq`` / ``dtb_dice``, each ``[nprof][nang][nf][nlev]`` (levels ground -> top)."""
+        return self._jacobian_vars_host("mwrt_tb_jacobian_batch_vars", model, z, p, t, rh, frq, elev, denliq, denice,
+                                        variables, thickness)
+
+    def _jacobian_vars_host(self, symbol, model, z, p, t, rh, frq, elev, denliq, denice, variables, thickness):
+        """The one parameter list mwrt_tb_jacobian_batch_vars and mwrt_tb_jacobian_batch_ray share."""
         z, p, t, rh, frq, elev = _profile_args(z, p, t, rh, frq, elev)
         nprof, nlev = z.shape
         nf, nang = frq.size, elev.size
@@ -574,10 +609,10 @@ class Context:
         jac = {k: np.empty((nprof, nang, nf, nlev)) for k in keys}
         valid = np.empty(nprof, dtype=np.uint8)
         out = [_ptr(jac[k]) if k in jac else None for k in ("dtb_dt", "dtb_dh", "dtb_ddz", "dtb_dliq", "dtb_dice")]
-        self._check(self._lib.mwrt_tb_jacobian_batch_vars(
+        self._check(getattr(self._lib, symbol)(
             self._handle, self.model(model), nprof, nlev, _ptr(z), _ptr(p), _ptr(t), _ptr(rh), nf, _ptr(frq), nang, _ptr(elev),
             _ptr(tb), *out, _ptr(valid), ctypes.byref(opts) if opts is not None else None,
-            ctypes.byref(variables) if variables is not None else None), "mwrt_tb_jacobian_batch_vars")
+            ctypes.byref(variables) if variables is not None else None), symbol)
         return tb, valid, jac
 
     @_serialised

@@ -1,8 +1,8 @@
 """Build recipe for libmwrt.so (hipcc, gfx950 only, in-tree so the .so travels with the repo).
 
-Twelve translation units -- the C-ABI host side (csrc/mwrt.hip, no device code in it), the kernel instantiations of
+Thirteen translation units -- the C-ABI host side (csrc/mwrt.hip, no device code in it), the kernel instantiations of
 each frequency-chunk width (csrc/mwrt_inst.hip with -DMWRT_INST_NFC=8|14|16), the device K-matrix kernels
-(csrc/mwrt_tl.hip), the spectroscopic-parameter Jacobian (csrc/mwrt_par.hip), the optimal-estimation step (csrc/mwrt_oe.hip), its
+(csrc/mwrt_tl.hip), their ray-traced form (csrc/mwrt_ray.hip), the spectroscopic-parameter Jacobian (csrc/mwrt_par.hip), the optimal-estimation step (csrc/mwrt_oe.hip), its
 Levenberg-Marquardt split (csrc/mwrt_oe_lm.hip), its characterisation (csrc/mwrt_oe_char.hip), the instrument
 operator (csrc/mwrt_obs.hip), the non-template
 kernels (csrc/mwrt_aux.hip) and the host-only launch planning
@@ -21,6 +21,7 @@ CSRC = os.path.join(HERE, "csrc")
 SRC = os.path.join(CSRC, "mwrt.hip")
 INST = os.path.join(CSRC, "mwrt_inst.hip")
 TL = os.path.join(CSRC, "mwrt_tl.hip")
+RAY = os.path.join(CSRC, "mwrt_ray.hip")
 PAR = os.path.join(CSRC, "mwrt_par.hip")
 OE = os.path.join(CSRC, "mwrt_oe.hip")
 OE_LM = os.path.join(CSRC, "mwrt_oe_lm.hip")
@@ -62,6 +63,7 @@ def build_native(force: bool = False, verbose: bool = False, extra_flags=(), out
     jobs = [(SRC, os.path.join(OBJ_DIR, f"mwrt.{tag}.o"), [])]
     jobs += [(INST, os.path.join(OBJ_DIR, f"mwrt_inst{n}.{tag}.o"), [f"-DMWRT_INST_NFC={n}"]) for n in INST_WIDTHS]
     jobs.append((TL, os.path.join(OBJ_DIR, f"mwrt_tl.{tag}.o"), []))
+    jobs.append((RAY, os.path.join(OBJ_DIR, f"mwrt_ray.{tag}.o"), []))
     jobs.append((PAR, os.path.join(OBJ_DIR, f"mwrt_par.{tag}.o"), []))
     jobs.append((OE, os.path.join(OBJ_DIR, f"mwrt_oe.{tag}.o"), []))
     jobs.append((OE_LM, os.path.join(OBJ_DIR, f"mwrt_oe_lm.{tag}.o"), []))

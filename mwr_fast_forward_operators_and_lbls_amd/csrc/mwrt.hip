@@ -4,10 +4,11 @@
 // returns 0 and mwrt_create() fails with MWRT_ERR_NO_DEVICE.
 //
 // Host code only: streams, caches, argument checks and the choice of launch.  Every kernel lives in another unit
-// (mwrt_inst.hip, mwrt_tl.hip, mwrt_par.hip, mwrt_oe.hip, mwrt_oe_lm.hip, mwrt_oe_char.hip, mwrt_obs.hip, mwrt_aux.hip) and is reached
+// (mwrt_inst.hip, mwrt_tl.hip, mwrt_ray.hip, mwrt_par.hip, mwrt_oe.hip, mwrt_oe_lm.hip, mwrt_oe_char.hip, mwrt_obs.hip, mwrt_aux.hip) and is reached
 // through the launchers the headers below declare.
 #include "mwrt_args.hip.h"
 #include "mwrt_tl.hip.h"
+#include "mwrt_ray.hip.h"
 #include "mwrt_par.hip.h"
 #include "mwrt_oe.hip.h"
 #include "mwrt_oe_lm.hip.h"
@@ -469,18 +470,20 @@ int stage_in(mwrt_context* c, hipStream_t st, size_t n, const double* const* src
   return MWRT_OK;
 }
 
-// The device K-matrix behind its three entries (clear, cloud, retrieval variables): k_absorb_tl into the context's
+// The device K-matrix behind its entries (clear, cloud, retrieval variables, ray paths): k_absorb_tl into the context's
 // workspace, then k_jac_rte.  `ddz_required`: the entries without mwrt_jac_variables have no optional thickness row.
+// `ray`: the ray-traced entry -- options->ray_tracing is not consulted, ray::k_ray_paths_tl fills the context's path
+// workspace first and ray::k_jac_rte_ray takes the place of k_jac_rte.
 int jacobian_vars_device(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
                          const double* d_z, const double* d_p, const double* d_t, const double* d_rh,
                          int32_t nf, const double* frq, int32_t nang, const double* elev,
                          double* d_tb, double* d_dtb_dt, double* d_dtb_dh, double* d_dtb_ddz,
                          double* d_dtb_dliq, double* d_dtb_dice, uint8_t* d_valid,
-                         const mwrt_tb_options* opt, const mwrt_jac_variables* vars, bool ddz_required, void* stream) {
+                         const mwrt_tb_options* opt, const mwrt_jac_variables* vars, bool ddz_required, bool ray, void* stream) {
   const double* d_denliq = opt ? opt->denliq : nullptr;
   const double* d_denice = opt ? opt->denice : nullptr;
   CallSpec s{CALL_ANGLES, nprof, nlev, nf, frq, nang, elev, stream};
-  if (opt && opt->ray_tracing != 0) s.after_common = Check{MWRT_ERR_UNSUPPORTED, "the K-matrix is plane-parallel: ray_tracing is not supported"};
+  if (!ray && opt && opt->ray_tracing != 0) s.after_common = Check{MWRT_ERR_UNSUPPORTED, "the K-matrix is plane-parallel: ray_tracing is not supported"};
   else if (opt && opt->o3n) s.after_common = Check{MWRT_ERR_UNSUPPORTED, "the K-matrix has no ozone tangent: o3n is not supported"};
   else if (d_dtb_dliq && !d_denliq) s.after_common = Check{MWRT_ERR_INVALID_ARGUMENT, "d_dtb_dliq given without options->denliq"};
   else if (d_dtb_dice && !d_denice) s.after_common = Check{MWRT_ERR_INVALID_ARGUMENT, "d_dtb_dice given without options->denice"};
@@ -496,11 +499,26 @@ int jacobian_vars_device(mwrt_context* c, const mwrt_model* m, int64_t nprof, in
   const double *dev_frq = call.dev_frq, *dev_am = call.dev_am;
   const size_t nabs = (size_t)nprof * nf * nlev;
   HIP_TRY(grow_behind_drain(c->d_jac, sizeof(double) * 6 * nabs + sizeof(unsigned) * (size_t)nprof));
+  const double* dev_elev = nullptr;
+  if (ray) {
+    // the path workspace of the forward's ray tracing, six rows per (profile, elevation) instead of one (grown only)
+    rc = upload_small(c, c->elev_cache, elev, nang, &dev_elev); if (rc) return rc;
+    HIP_TRY(grow_behind_drain(c->d_amf, sizeof(double) * ray::PATH_ROWS * (size_t)nprof * nang * nlev));
+    HIP_TRY(grow_behind_drain(c->d_duct, (size_t)nprof));
+  }
   rc = workspace_acquire(c, st); if (rc) return rc;
   auto handover = on_scope_exit([&] { (void)workspace_release(c, st); });    // on every return path from here on
   double* w = c->d_jac.as<double>();
   unsigned* flags = reinterpret_cast<unsigned*>(w + 6 * nabs);
   HIP_TRY(hipMemsetAsync(flags, 0, sizeof(unsigned) * (size_t)nprof, st));
+  if (ray) {
+    HIP_TRY(hipMemsetAsync(c->d_duct.p, 0, (size_t)nprof, st));
+    ray::PathTlArgs pa{};
+    pa.z = d_z; pa.p = d_p; pa.t = d_t; pa.rh = d_rh; pa.elev_deg = dev_elev;
+    pa.path = c->d_amf.as<double>(); pa.duct = c->d_duct.as<uint8_t>(); pa.nlev = nlev; pa.nang = nang;
+    rc = timed(c, st, [&] { return ray::launch_ray_paths_tl(pa, nprof, st); });
+    if (rc) return rc;
+  }
   AbsorbTlArgs ta{};
   ta.M = m->d_desc; ta.p = d_p; ta.t = d_t; ta.rh = d_rh; ta.frq = dev_frq;
   ta.awet = w; ta.adry = w + nabs; ta.dawet_dt = w + 2 * nabs; ta.dawet_de = w + 3 * nabs;
@@ -520,6 +538,10 @@ int jacobian_vars_device(mwrt_context* c, const mwrt_model* m, int64_t nprof, in
   if (vars) { ja.humidity = vars->humidity; ja.cloud = vars->cloud; ja.heights = vars->heights; }
   // with cloud arrays the kernel only lowers valid (k_jac_rte): preset it
   if (d_denliq || d_denice) HIP_TRY(hipMemsetAsync(d_valid, 1, (size_t)nprof, st));
+  if (ray) {
+    const ray::RayRteArgs ra{ja, c->d_amf.as<double>(), c->d_duct.as<uint8_t>()};
+    return timed(c, st, [&] { return ray::launch_jac_rte_ray(ra, nprof, st); });
+  }
   return timed(c, st, [&] { return launch_jac_rte(ja, nprof, st); });
 }
 
@@ -530,7 +552,7 @@ int jacobian_vars_host(mwrt_context* c, const mwrt_model* m, int64_t nprof, int3
                        const double* z, const double* p, const double* t, const double* rh,
                        int32_t nf, const double* frq, int32_t nang, const double* elev,
                        double* tb, double* dtb_dt, double* dtb_dh, double* dtb_ddz, double* dtb_dliq, double* dtb_dice,
-                       uint8_t* valid, const mwrt_tb_options* opt, const mwrt_jac_variables* vars, bool ddz_required) {
+                       uint8_t* valid, const mwrt_tb_options* opt, const mwrt_jac_variables* vars, bool ddz_required, bool ray) {
   CallSpec s{CALL_ANGLES | CALL_HOST | CALL_STAGES, nprof, nlev, nf, frq, nang, elev, nullptr};
   s.buffers_ok = z && p && t && rh && frq && elev && tb && dtb_dt && dtb_dh && (dtb_ddz || !ddz_required) && valid;
   Call call;
@@ -560,7 +582,7 @@ int jacobian_vars_host(mwrt_context* c, const mwrt_model* m, int64_t nprof, int3
   mwrt_tb_options dopt{};
   if (opt) { dopt = *opt; dopt.denliq = din[4]; dopt.denice = din[5]; }
   rc = jacobian_vars_device(c, m, nprof, nlev, din[0], din[1], din[2], din[3], nf, frq, nang, elev, d_tb, dout[0], dout[1],
-                            dout[2], dout[3], dout[4], d_valid, opt ? &dopt : nullptr, vars, ddz_required, nullptr);
+                            dout[2], dout[3], dout[4], d_valid, opt ? &dopt : nullptr, vars, ddz_required, ray, nullptr);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(tb, d_tb, sizeof(double) * ntb, hipMemcpyDeviceToHost, st));
   for (int k = 0; k < 5; ++k)
@@ -1165,7 +1187,7 @@ int mwrt_tb_jacobian_batch_opt_device(mwrt_context* c, const mwrt_model* m, int6
                                       const mwrt_tb_options* opt, void* stream) {
   // (this entry has no optional thickness row: the check sits where its "null buffer" check always sat)
   return jacobian_vars_device(c, m, nprof, nlev, d_z, d_p, d_t, d_rh, nf, frq, nang, elev, d_tb, d_dtb_dt, d_dtb_de, d_dtb_ddz,
-                              d_dtb_dliq, d_dtb_dice, d_valid, opt, nullptr, /*ddz_required=*/true, stream);
+                              d_dtb_dliq, d_dtb_dice, d_valid, opt, nullptr, /*ddz_required=*/true, /*ray=*/false, stream);
 }
 
 // The same in the caller's retrieval variables (mwrt_jac_variables): k_jac_rte changes the variables of each row element
@@ -1177,7 +1199,7 @@ int mwrt_tb_jacobian_batch_vars_device(mwrt_context* c, const mwrt_model* m, int
                                        double* d_dtb_dliq, double* d_dtb_dice, uint8_t* d_valid,
                                        const mwrt_tb_options* opt, const mwrt_jac_variables* vars, void* stream) {
   return jacobian_vars_device(c, m, nprof, nlev, d_z, d_p, d_t, d_rh, nf, frq, nang, elev, d_tb, d_dtb_dt, d_dtb_dh, d_dtb_ddz,
-                              d_dtb_dliq, d_dtb_dice, d_valid, opt, vars, /*ddz_required=*/false, stream);
+                              d_dtb_dliq, d_dtb_dice, d_valid, opt, vars, /*ddz_required=*/false, /*ray=*/false, stream);
 }
 
 // ... and on HOST buffers, synchronous (jacobian_vars_host).
@@ -1187,7 +1209,31 @@ int mwrt_tb_jacobian_batch_vars(mwrt_context* c, const mwrt_model* m, int64_t np
                                 double* tb, double* dtb_dt, double* dtb_dh, double* dtb_ddz, double* dtb_dliq, double* dtb_dice,
                                 uint8_t* valid, const mwrt_tb_options* opt, const mwrt_jac_variables* vars) {
   return jacobian_vars_host(c, m, nprof, nlev, z, p, t, rh, nf, frq, nang, elev, tb, dtb_dt, dtb_dh, dtb_ddz, dtb_dliq, dtb_dice,
-                            valid, opt, vars, /*ddz_required=*/false);
+                            valid, opt, vars, /*ddz_required=*/false, /*ray=*/false);
+}
+
+// The K-matrix along refracted spherical ray paths: the operator of mwrt_tb_batch_opt_device with
+// ray_tracing = 1 and its exact rows, the response of every layer's path factor to the refractive index and the heights
+// included.  ray::k_ray_paths_tl into the context's path workspace, k_absorb_tl, then ray::k_jac_rte_ray; asynchronous, and
+// after one warm-up call with the same shapes it neither allocates nor synchronises.
+int mwrt_tb_jacobian_batch_ray_device(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
+                                      const double* d_z, const double* d_p, const double* d_t, const double* d_rh,
+                                      int32_t nf, const double* frq, int32_t nang, const double* elev,
+                                      double* d_tb, double* d_dtb_dt, double* d_dtb_dh, double* d_dtb_ddz,
+                                      double* d_dtb_dliq, double* d_dtb_dice, uint8_t* d_valid,
+                                      const mwrt_tb_options* opt, const mwrt_jac_variables* vars, void* stream) {
+  return jacobian_vars_device(c, m, nprof, nlev, d_z, d_p, d_t, d_rh, nf, frq, nang, elev, d_tb, d_dtb_dt, d_dtb_dh, d_dtb_ddz,
+                              d_dtb_dliq, d_dtb_dice, d_valid, opt, vars, /*ddz_required=*/false, /*ray=*/true, stream);
+}
+
+// ... and on HOST buffers, synchronous (jacobian_vars_host).
+int mwrt_tb_jacobian_batch_ray(mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev,
+                               const double* z, const double* p, const double* t, const double* rh,
+                               int32_t nf, const double* frq, int32_t nang, const double* elev,
+                               double* tb, double* dtb_dt, double* dtb_dh, double* dtb_ddz, double* dtb_dliq, double* dtb_dice,
+                               uint8_t* valid, const mwrt_tb_options* opt, const mwrt_jac_variables* vars) {
+  return jacobian_vars_host(c, m, nprof, nlev, z, p, t, rh, nf, frq, nang, elev, tb, dtb_dt, dtb_dh, dtb_ddz, dtb_dliq, dtb_dice,
+                            valid, opt, vars, /*ddz_required=*/false, /*ray=*/true);
 }
 
 // The clear-sky K-matrix in the operator's own variables (T at fixed e, e, layer thickness) on HOST buffers: the call
@@ -1197,7 +1243,7 @@ int mwrt_tb_jacobian_batch(mwrt_context* c, const mwrt_model* m, int64_t nprof, 
                            int32_t nf, const double* frq, int32_t nang, const double* elev,
                            double* tb, double* dtb_dt, double* dtb_de, double* dtb_ddz, uint8_t* valid) {
   return jacobian_vars_host(c, m, nprof, nlev, z, p, t, rh, nf, frq, nang, elev, tb, dtb_dt, dtb_de, dtb_ddz, nullptr, nullptr,
-                            valid, nullptr, nullptr, /*ddz_required=*/true);
+                            valid, nullptr, nullptr, /*ddz_required=*/true, /*ray=*/false);
 }
 
 // ---- the spectroscopic-parameter Jacobian (csrc/mwrt_par.hip) ----

@@ -105,7 +105,10 @@ class Instrument:
     ``tb [nang_q][nf_q]``) to outputs o = a * nch + c (angle-major, like ``tb [nang][nch]``); ``m_in = nang_q * nf_q``,
     ``m_out = nang * nch``.  Elevation nodes above 90 deg are passed on as they are (the operator takes elevations in
     (0, 180)); a node at or outside 0 or 180 deg is a ValueError.  A NaN elevation is kept as one node of the grid: the
-    operator blanks its rows and the map carries the NaN to that elevation's channels alone."""
+    operator blanks its rows and the map carries the NaN to that elevation's channels alone.  The same holds along
+    refracted ray paths (``OneDVar(..., ray_tracing=True)``): a beam node below the lowest untrapped elevation gives NaN
+    rows (and ``valid = 3``), the CSR reduction confines them to the channels that reference that node, and the step drops
+    those channels."""
 
     def __init__(self, frq, elev, beam=None, band=None, n_beam=3, n_band=3):
         self.frq = np.ascontiguousarray(frq, dtype=np.float64).ravel()

@@ -53,6 +53,22 @@ def _native_k_matrix(model, z, p, t, rh, denliq, denice, frq, elev, variables, w
     return tb, valid, rows
 
 
+def _native_k_matrix_ray(model, z, p, t, rh, denliq, denice, frq, elev, variables, want, stream):
+    """One ``mwrt_tb_jacobian_batch_ray_device`` call: ``_native_k_matrix`` along refracted spherical ray paths, what
+    ``OneDVar(..., ray_tracing=True)`` runs instead.  CPU tests substitute a stand-in here."""
+    nprof, nlev = z.shape
+    opts = dict(dtype=torch.float64, device=z.device)
+    tb = torch.empty((nprof, elev.size, frq.size), **opts)
+    rows = {b: torch.empty((nprof, elev.size, frq.size, nlev), **opts) for b in want}
+    valid = torch.empty(nprof, dtype=torch.uint8, device=z.device)
+    ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
+    _native.default_context(z.device.index or 0).tb_jacobian_batch_ray_device(
+        model, nprof, nlev, z.data_ptr(), p.data_ptr(), t.data_ptr(), rh.data_ptr(), frq, elev, tb.data_ptr(),
+        rows["t"].data_ptr(), rows["h"].data_ptr(), valid.data_ptr(), d_denliq=ptr(denliq), d_denice=ptr(denice),
+        d_dtb_dliq=ptr(rows.get("liq")), d_dtb_dice=ptr(rows.get("ice")), variables=variables, stream=stream)
+    return tb, valid, rows
+
+
 def _native_oe_step(k_blocks, x, xa, sa, se, y, fx, want_post_var, stream):
     """One ``mwrt_oe_step_device`` call -> dict(x_new, status, chi2, dfs, nobs, post_var or None).
 
@@ -203,8 +219,10 @@ class Retrieval:
 
 class OneDVar:
     def __init__(self, model, frq, elev, sa, se, variables: Optional[JacVariables] = None, blocks=("t", "h"), xa=None,
-                 instrument=None):
+                 instrument=None, ray_tracing=False):
         blocks = tuple(blocks)
+        # refracted spherical ray paths: the forward operator and its exact K rows come from mwrt_tb_jacobian_batch_ray_device
+        self.ray_tracing = bool(ray_tracing)
         if blocks[:2] != ("t", "h") or blocks[2:] not in ((), ("liq",), ("ice",), ("liq", "ice")):
             raise ValueError(f"blocks must be ('t', 'h') followed by 'liq' and / or 'ice' in that order, got {blocks}")
         self.model, self.blocks = model, blocks
@@ -280,8 +298,12 @@ class OneDVar:
         inst = self.instrument
         frq, elev = (self.frq, self.elev) if inst is None else (inst.frq_q, inst.elev_q)
         stream = self._stream(x)
-        tb, valid, rows = _native_k_matrix(self.model, zz.contiguous(), p.contiguous(), t, rh, dl, di, frq, elev,
-                                           self.variables, self.blocks, stream)
+        if self.ray_tracing:
+            tb, valid, rows = _native_k_matrix_ray(self.model, zz.contiguous(), p.contiguous(), t, rh, dl, di, frq, elev,
+                                                   self.variables, self.blocks, stream)
+        else:
+            tb, valid, rows = _native_k_matrix(self.model, zz.contiguous(), p.contiguous(), t, rh, dl, di, frq, elev,
+                                               self.variables, self.blocks, stream)
         k_blocks = [rows[b] for b in self.blocks] if want_rows else None
         if inst is not None:
             tb, k_blocks = _native_obs_apply(inst, tb, k_blocks, stream)
