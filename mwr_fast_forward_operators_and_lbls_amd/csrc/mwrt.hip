@@ -594,150 +594,164 @@ int jacobian_vars_host(mwrt_context* c, const mwrt_model* m, int64_t nprof, int3
 
 }  // namespace
 
-// The three entries of the Levenberg-Marquardt split (csrc/mwrt_oe_lm.hip) share one record and one preamble -- the order
-// of mwrt_oe_step_device: arguments, then limits, then the device and the stream -- and differ in the pointers they
-// require and the kernel they launch.
 namespace {
 
+// One preamble for the three optimal-estimation entry families (the step, its Levenberg-Marquardt split, its
+// characterisation).  They take no model, so it is not begin_call, but it keeps that order: arguments, then limits, then
+// the device and the stream.  What differs between the records is described here; what differs between the entries -- the
+// pointers they require, the LDS plan they check, the launch -- they pass in.
+struct OeRecord {
+  const char* name;                        // "mwrt_oe_step", as the refusal messages spell it
+  size_t fixed;                            // struct_size must reach this ...
+  const char* fixed_what;                  // ... "the fixed part (through reserved)"
+  const char* reserved_what = "reserved";
+  size_t ints = 0, ints_end = 0;           // a group of int32 fields beyond the fixed part; every other field there is a pointer
+};
+inline int32_t oe_reserved(const mwrt_oe_step& r) { return r.reserved; }
+inline int32_t oe_reserved(const mwrt_oe_lm& r) { return r.reserved; }
+inline int32_t oe_reserved(const mwrt_oe_char& r) { return r.reserved | r.reserved2; }
+
+// The caller's record up to its struct_size; fields at or beyond it stay NULL / 0, and so does a field the size ends inside.
+template <class R> R oe_prefix(const R* s, const OeRecord& rec) {
+  R r{};
+  size_t len = s->struct_size < sizeof r ? s->struct_size : sizeof r;
+  len -= (len > rec.ints && len < rec.ints_end) ? (len - rec.ints) % sizeof(int32_t) : (len - rec.fixed) % sizeof(void*);
+  std::memcpy(&r, s, len);
+  return r;
+}
+
+// check(r): the entry's own argument checks (MWRT_OK or its fail(...)).  plan(r, o): o holds the fields every record has
+// (K blocks, x, xa, Sa, Se, y, F, nobs, status, the dimensions); the entry adds its own, checks its LDS plan and returns
+// MWRT_OK or its fail(...).  launch(st): the hipError_t of the launch.
+template <class R, class Check, class Plan, class Launch>
+int oe_call(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const R* s, void* stream, const OeRecord& rec,
+            Check check, Plan plan, Launch launch) {
+  const std::string name = rec.name;
+  if (!c || !s) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context or " + name);
+  if (s->struct_size < rec.fixed)
+    return fail(MWRT_ERR_INVALID_ARGUMENT, name + ".struct_size too small for " + rec.fixed_what);
+  const R r = oe_prefix(s, rec);
+  if (nprof < 0 || nlev < 1 || m < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "nprof < 0, nlev < 1 or m < 1");
+  if (r.nblk < 1 || r.nblk > 4) return fail(MWRT_ERR_INVALID_ARGUMENT, name + ".nblk must be 1 .. 4");
+  if (oe_reserved(r) != 0) return fail(MWRT_ERR_INVALID_ARGUMENT, name + "." + rec.reserved_what + " must be 0");
+  if (const int rc = check(r)) return rc;
+  if (nlev > MWRT_MAX_LEVELS)
+    return fail(MWRT_ERR_UNSUPPORTED, "nlev > MWRT_MAX_LEVELS (" + std::to_string(MWRT_MAX_LEVELS) + ")");
+  if (m > MWRT_OE_MAX_M)
+    return fail(MWRT_ERR_UNSUPPORTED, "m > MWRT_OE_MAX_M (" + std::to_string(MWRT_OE_MAX_M) + " observations per profile: G lives in LDS)");
+  if (nprof > 2147483647LL) return fail(MWRT_ERR_UNSUPPORTED, "nprof exceeds grid limit");
+  oe::OeArgs o{};
+  o.k0 = r.d_k[0]; o.k1 = r.nblk > 1 ? r.d_k[1] : nullptr; o.k2 = r.nblk > 2 ? r.d_k[2] : nullptr;
+  o.k3 = r.nblk > 3 ? r.d_k[3] : nullptr;
+  o.x = r.d_x; o.xa = r.d_xa; o.sa = r.d_sa; o.se = r.d_se; o.y = r.d_y; o.fx = r.d_fx;
+  o.nobs = r.d_nobs; o.status = r.d_status;
+  o.nblk = r.nblk; o.nlev = nlev; o.m = m; o.n = r.nblk * nlev;
+  o.xa_per_profile = r.xa_per_profile != 0; o.se_full = r.se_full != 0;
+  if (const int rc = plan(r, o)) return rc;
+  if (nprof == 0) return MWRT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = resolve_stream(c, stream);
+  return timed(c, st, [&] { return launch(st); });
+}
+
+const OeRecord OE_STEP_RECORD{"mwrt_oe_step", offsetof(mwrt_oe_step, d_status) + sizeof(uint8_t*),
+                              "the required fields (through d_status)"};
+const OeRecord OE_LM_RECORD{"mwrt_oe_lm", offsetof(mwrt_oe_lm, d_k), "the fixed part (through reserved)"};
+const OeRecord OE_CHAR_RECORD{"mwrt_oe_char", offsetof(mwrt_oe_char, d_k), "the fixed part (through reserved)",
+                              "reserved and reserved2", offsetof(mwrt_oe_char, product), offsetof(mwrt_oe_char, d_out)};
+
+// The three entries of the Levenberg-Marquardt split (csrc/mwrt_oe_lm.hip) share one record and differ in the pointers
+// they require and the kernel they launch.
 enum class LmCall { Prepare, Solve, Cost };
 
 int oe_lm_call(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_lm* s, void* stream, LmCall call) {
-  if (!c || !s) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context or mwrt_oe_lm");
-  constexpr size_t fixed = offsetof(mwrt_oe_lm, d_k);
-  if (s->struct_size < fixed)
-    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_lm.struct_size too small for the fixed part (through reserved)");
-  mwrt_oe_lm r{};                                      // fields at or beyond the caller's struct_size stay NULL
-  // ... and so does a field the size ends inside: beyond the fixed part every field is one pointer
-  size_t len = s->struct_size < sizeof r ? s->struct_size : sizeof r;
-  len -= (len - fixed) % sizeof(void*);
-  std::memcpy(&r, s, len);
-  if (nprof < 0 || nlev < 1 || m < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "nprof < 0, nlev < 1 or m < 1");
-  if (r.nblk < 1 || r.nblk > 4) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_lm.nblk must be 1 .. 4");
-  if (r.reserved != 0) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_lm.reserved must be 0");
-  bool buffers = r.d_x && r.d_xa && r.d_se;
-  const bool lin = r.d_g0 && r.d_r && r.d_kdx && r.d_keep && r.d_lin_status;
-  if (call != LmCall::Cost) {
-    buffers = buffers && r.d_sa && lin;
-    for (int b = 0; b < r.nblk; ++b) buffers = buffers && r.d_k[b];
-  }
-  if (call == LmCall::Prepare) buffers = buffers && r.d_y && r.d_fx;
-  if (call == LmCall::Solve) buffers = buffers && r.d_gamma && r.d_x_new && r.d_status;
-  if (call == LmCall::Cost) buffers = buffers && r.d_y && r.d_fx && r.d_keep && r.d_sa_inv && r.d_cost;
-  if (!buffers) return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
-  if (nlev > MWRT_MAX_LEVELS)
-    return fail(MWRT_ERR_UNSUPPORTED, "nlev > MWRT_MAX_LEVELS (" + std::to_string(MWRT_MAX_LEVELS) + ")");
-  if (m > MWRT_OE_MAX_M)
-    return fail(MWRT_ERR_UNSUPPORTED, "m > MWRT_OE_MAX_M (" + std::to_string(MWRT_OE_MAX_M) + " observations per profile: G lives in LDS)");
-  if (nprof > 2147483647LL) return fail(MWRT_ERR_UNSUPPORTED, "nprof exceeds grid limit");
   lm::LmArgs a{};
-  a.o.k0 = r.d_k[0]; a.o.k1 = r.nblk > 1 ? r.d_k[1] : nullptr; a.o.k2 = r.nblk > 2 ? r.d_k[2] : nullptr;
-  a.o.k3 = r.nblk > 3 ? r.d_k[3] : nullptr;
-  a.o.x = r.d_x; a.o.xa = r.d_xa; a.o.sa = r.d_sa; a.o.se = r.d_se; a.o.y = r.d_y; a.o.fx = r.d_fx;
-  a.o.x_new = r.d_x_new; a.o.chi2 = r.d_chi2; a.o.nobs = r.d_nobs; a.o.status = r.d_status;
-  a.o.nblk = r.nblk; a.o.nlev = nlev; a.o.m = m; a.o.n = r.nblk * nlev;
-  a.o.xa_per_profile = r.xa_per_profile != 0; a.o.se_full = r.se_full != 0;
-  a.gamma = r.d_gamma; a.g0 = r.d_g0; a.r = r.d_r; a.kdx = r.d_kdx; a.keep = r.d_keep; a.lin_status = r.d_lin_status;
-  a.active = r.d_active; a.sa_inv = r.d_sa_inv; a.cost = r.d_cost; a.cost_obs = r.d_cost_obs; a.cost_prior = r.d_cost_prior;
-  const size_t lds = call == LmCall::Prepare ? oe::lds_plan(m, a.o.n).total_bytes
-                   : call == LmCall::Solve ? lm::solve_plan(m, a.o.n).total_bytes
-                                           : lm::cost_plan(m, a.o.n, a.o.se_full).total_bytes;
-  if (lds > (size_t)c->lds_max)
-    return fail(MWRT_ERR_UNSUPPORTED, "the optimal-estimation step needs more LDS than this device has per workgroup");
-  if (nprof == 0) return MWRT_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = resolve_stream(c, stream);
-  return timed(c, st, [&] {
-    return call == LmCall::Prepare ? lm::launch_lm_prepare(a, nprof, st)
-         : call == LmCall::Solve ? lm::launch_lm_solve(a, nprof, st)
-                                 : lm::launch_lm_cost(a, nprof, st);
-  });
+  return oe_call(c, nprof, nlev, m, s, stream, OE_LM_RECORD,
+    [&](const mwrt_oe_lm& r) {
+      bool buffers = r.d_x && r.d_xa && r.d_se;
+      const bool lin = r.d_g0 && r.d_r && r.d_kdx && r.d_keep && r.d_lin_status;
+      if (call != LmCall::Cost) {
+        buffers = buffers && r.d_sa && lin;
+        for (int b = 0; b < r.nblk; ++b) buffers = buffers && r.d_k[b];
+      }
+      if (call == LmCall::Prepare) buffers = buffers && r.d_y && r.d_fx;
+      if (call == LmCall::Solve) buffers = buffers && r.d_gamma && r.d_x_new && r.d_status;
+      if (call == LmCall::Cost) buffers = buffers && r.d_y && r.d_fx && r.d_keep && r.d_sa_inv && r.d_cost;
+      return buffers ? MWRT_OK : fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
+    },
+    [&](const mwrt_oe_lm& r, const oe::OeArgs& o) {
+      a.o = o;
+      a.o.x_new = r.d_x_new; a.o.chi2 = r.d_chi2;
+      a.gamma = r.d_gamma; a.g0 = r.d_g0; a.r = r.d_r; a.kdx = r.d_kdx; a.keep = r.d_keep; a.lin_status = r.d_lin_status;
+      a.active = r.d_active; a.sa_inv = r.d_sa_inv; a.cost = r.d_cost; a.cost_obs = r.d_cost_obs; a.cost_prior = r.d_cost_prior;
+      const size_t lds = call == LmCall::Prepare ? oe::lds_plan(m, o.n).total_bytes
+                       : call == LmCall::Solve ? lm::solve_plan(m, o.n).total_bytes
+                                               : lm::cost_plan(m, o.n, o.se_full).total_bytes;
+      return lds <= (size_t)c->lds_max ? MWRT_OK
+           : fail(MWRT_ERR_UNSUPPORTED, "the optimal-estimation step needs more LDS than this device has per workgroup");
+    },
+    [&](hipStream_t st) {
+      return call == LmCall::Prepare ? lm::launch_lm_prepare(a, nprof, st)
+           : call == LmCall::Solve ? lm::launch_lm_solve(a, nprof, st)
+                                   : lm::launch_lm_cost(a, nprof, st);
+    });
 }
 
-}  // namespace
-
-// The two entries of the characterisation (csrc/mwrt_oe_char.hip) share one record and one preamble, in the order of
-// mwrt_oe_step_device: arguments, then limits, then the device and the stream.
-namespace {
-
+// The two entries of the characterisation (csrc/mwrt_oe_char.hip) share one record.
 enum class CharCall { Gain, Product };
 
 int oe_char_call(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_char* s, void* stream, CharCall call) {
-  if (!c || !s) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context or mwrt_oe_char");
-  constexpr size_t fixed = offsetof(mwrt_oe_char, d_k);
-  if (s->struct_size < fixed)
-    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_char.struct_size too small for the fixed part (through reserved)");
-  mwrt_oe_char r{};                                    // fields at or beyond the caller's struct_size stay NULL / 0
-  // ... and so does a field the size ends inside: pointers beyond the fixed part, but for the four int32 of the product
-  size_t len = s->struct_size < sizeof r ? s->struct_size : sizeof r;
-  constexpr size_t ints = offsetof(mwrt_oe_char, product), ints_end = offsetof(mwrt_oe_char, d_out);
-  len -= (len > ints && len < ints_end) ? (len - ints) % sizeof(int32_t) : (len - fixed) % sizeof(void*);
-  std::memcpy(&r, s, len);
-  if (nprof < 0 || nlev < 1 || m < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "nprof < 0, nlev < 1 or m < 1");
-  if (r.nblk < 1 || r.nblk > 4) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_char.nblk must be 1 .. 4");
-  if (r.reserved != 0 || r.reserved2 != 0) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_char.reserved and reserved2 must be 0");
-  const int64_t n64 = (int64_t)r.nblk * nlev;
-  int32_t rows = 0;
-  if (call == CharCall::Gain) {
-    bool buffers = r.d_x && r.d_xa && r.d_sa && r.d_se && r.d_y && r.d_fx && r.d_status;
-    for (int b = 0; b < r.nblk; ++b) buffers = buffers && r.d_k[b];
-    if (!buffers) return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
-    if (!(r.d_gain || r.d_ksa || r.d_keep || r.d_avk_diag || r.d_dfs_block || r.d_noise_var || r.d_smooth_var || r.d_nobs))
-      return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_gain_device: no output asked for beside d_status");
-  } else {
-    if (r.product != MWRT_OE_PRODUCT_AVK && r.product != MWRT_OE_PRODUCT_POST_COV)
-      return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_char.product must be MWRT_OE_PRODUCT_AVK or MWRT_OE_PRODUCT_POST_COV");
-    bool buffers = r.d_gain && r.d_keep && r.d_out;
-    if (r.product == MWRT_OE_PRODUCT_AVK)
-      for (int b = 0; b < r.nblk; ++b) buffers = buffers && r.d_k[b];
-    else
-      buffers = buffers && r.d_ksa && r.d_sa;
-    if (!buffers) return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
-    if (r.row_begin < 0 || r.row_count < 0 || (r.row_count == 0 && r.row_begin != 0) ||
-        (int64_t)r.row_begin + r.row_count > n64)
-      return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_char: rows row_begin .. row_begin + row_count - 1 must lie in 0 .. n - 1 "
-                                             "(row_count 0 with row_begin 0: all rows)");
-    rows = r.row_count == 0 ? (int32_t)(n64 > 2147483647LL ? 0 : n64) : r.row_count;
-  }
-  if (nlev > MWRT_MAX_LEVELS)
-    return fail(MWRT_ERR_UNSUPPORTED, "nlev > MWRT_MAX_LEVELS (" + std::to_string(MWRT_MAX_LEVELS) + ")");
-  if (m > MWRT_OE_MAX_M)
-    return fail(MWRT_ERR_UNSUPPORTED, "m > MWRT_OE_MAX_M (" + std::to_string(MWRT_OE_MAX_M) + " observations per profile: G lives in LDS)");
-  if (nprof > 2147483647LL) return fail(MWRT_ERR_UNSUPPORTED, "nprof exceeds grid limit");
-  const int n = (int)n64;
-  if (call == CharCall::Gain) {
-    oec::GainArgs a{};
-    a.o.k0 = r.d_k[0]; a.o.k1 = r.nblk > 1 ? r.d_k[1] : nullptr; a.o.k2 = r.nblk > 2 ? r.d_k[2] : nullptr;
-    a.o.k3 = r.nblk > 3 ? r.d_k[3] : nullptr;
-    a.o.x = r.d_x; a.o.xa = r.d_xa; a.o.sa = r.d_sa; a.o.se = r.d_se; a.o.y = r.d_y; a.o.fx = r.d_fx;
-    a.o.nobs = r.d_nobs; a.o.status = r.d_status;
-    a.o.nblk = r.nblk; a.o.nlev = nlev; a.o.m = m; a.o.n = n;
-    a.o.xa_per_profile = r.xa_per_profile != 0; a.o.se_full = r.se_full != 0;
-    a.gain = r.d_gain; a.ksa = r.d_ksa; a.keep = r.d_keep; a.avk_diag = r.d_avk_diag; a.noise_var = r.d_noise_var;
-    a.smooth_var = r.d_smooth_var; a.dfs_block = r.d_dfs_block;
-    if (oec::gain_plan(m).total_bytes > (size_t)c->lds_max)
-      return fail(MWRT_ERR_UNSUPPORTED, "the optimal-estimation gain needs more LDS than this device has per workgroup");
-    if (nprof == 0) return MWRT_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = resolve_stream(c, stream);
-    return timed(c, st, [&] { return oec::launch_char_gain(a, nprof, st); });
-  }
+  oec::GainArgs g{};
   oec::ProductArgs a{};
-  a.left = r.d_gain; a.keep = r.d_keep; a.out = r.d_out;
-  if (r.product == MWRT_OE_PRODUCT_AVK) {
-    a.r0 = r.d_k[0]; a.r1 = r.nblk > 1 ? r.d_k[1] : nullptr; a.r2 = r.nblk > 2 ? r.d_k[2] : nullptr;
-    a.r3 = r.nblk > 3 ? r.d_k[3] : nullptr;
-    a.rcols = nlev;
-  } else {
-    a.r0 = r.d_ksa; a.rcols = n; a.sa = r.d_sa;
-  }
-  a.m = m; a.n = n; a.row_begin = r.row_begin; a.rows = rows;
-  a.tiles_x = (n + oec::TILE - 1) / oec::TILE; a.tiles_y = (rows + oec::TILE - 1) / oec::TILE;
-  if ((int64_t)a.tiles_x * a.tiles_y * nprof > 2147483647LL)
-    return fail(MWRT_ERR_UNSUPPORTED, "mwrt_oe_product_device: more than 2147483647 tiles of 64 x 64 in one call (use row windows)");
-  if (nprof == 0) return MWRT_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = resolve_stream(c, stream);
-  return timed(c, st, [&] { return oec::launch_char_product(a, nprof, st); });
+  return oe_call(c, nprof, nlev, m, s, stream, OE_CHAR_RECORD,
+    [&](const mwrt_oe_char& r) {
+      if (call == CharCall::Gain) {
+        bool buffers = r.d_x && r.d_xa && r.d_sa && r.d_se && r.d_y && r.d_fx && r.d_status;
+        for (int b = 0; b < r.nblk; ++b) buffers = buffers && r.d_k[b];
+        if (!buffers) return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
+        if (!(r.d_gain || r.d_ksa || r.d_keep || r.d_avk_diag || r.d_dfs_block || r.d_noise_var || r.d_smooth_var || r.d_nobs))
+          return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_gain_device: no output asked for beside d_status");
+        return (int)MWRT_OK;
+      }
+      if (r.product != MWRT_OE_PRODUCT_AVK && r.product != MWRT_OE_PRODUCT_POST_COV)
+        return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_char.product must be MWRT_OE_PRODUCT_AVK or MWRT_OE_PRODUCT_POST_COV");
+      bool buffers = r.d_gain && r.d_keep && r.d_out;
+      if (r.product == MWRT_OE_PRODUCT_AVK)
+        for (int b = 0; b < r.nblk; ++b) buffers = buffers && r.d_k[b];
+      else
+        buffers = buffers && r.d_ksa && r.d_sa;
+      if (!buffers) return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
+      const int64_t n64 = (int64_t)r.nblk * nlev;        // nlev is not yet held to its limit here
+      if (r.row_begin < 0 || r.row_count < 0 || (r.row_count == 0 && r.row_begin != 0) ||
+          (int64_t)r.row_begin + r.row_count > n64)
+        return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_char: rows row_begin .. row_begin + row_count - 1 must lie in 0 .. n - 1 "
+                                               "(row_count 0 with row_begin 0: all rows)");
+      return (int)MWRT_OK;
+    },
+    [&](const mwrt_oe_char& r, const oe::OeArgs& o) {
+      const int n = o.n;
+      if (call == CharCall::Gain) {
+        g.o = o;
+        g.gain = r.d_gain; g.ksa = r.d_ksa; g.keep = r.d_keep; g.avk_diag = r.d_avk_diag; g.noise_var = r.d_noise_var;
+        g.smooth_var = r.d_smooth_var; g.dfs_block = r.d_dfs_block;
+        return oec::gain_plan(m).total_bytes <= (size_t)c->lds_max ? MWRT_OK
+             : fail(MWRT_ERR_UNSUPPORTED, "the optimal-estimation gain needs more LDS than this device has per workgroup");
+      }
+      a.left = r.d_gain; a.keep = r.d_keep; a.out = r.d_out;
+      if (r.product == MWRT_OE_PRODUCT_AVK) {
+        a.r0 = o.k0; a.r1 = o.k1; a.r2 = o.k2; a.r3 = o.k3;
+        a.rcols = nlev;
+      } else {
+        a.r0 = r.d_ksa; a.rcols = n; a.sa = r.d_sa;
+      }
+      a.m = m; a.n = n; a.row_begin = r.row_begin; a.rows = r.row_count == 0 ? n : r.row_count;
+      a.tiles_x = (n + oec::TILE - 1) / oec::TILE; a.tiles_y = (a.rows + oec::TILE - 1) / oec::TILE;
+      return (int64_t)a.tiles_x * a.tiles_y * nprof <= 2147483647LL ? MWRT_OK
+           : fail(MWRT_ERR_UNSUPPORTED, "mwrt_oe_product_device: more than 2147483647 tiles of 64 x 64 in one call (use row windows)");
+    },
+    [&](hipStream_t st) {
+      return call == CharCall::Gain ? oec::launch_char_gain(g, nprof, st) : oec::launch_char_product(a, nprof, st);
+    });
 }
 
 }  // namespace
@@ -1391,44 +1405,25 @@ int mwrt_set_absorption_mode(mwrt_context* c, int mode) {
   return MWRT_OK;
 }
 
-/* The optimal-estimation step (csrc/mwrt_oe.hip).  It takes no model, so its preamble is its own: the same order as
- * begin_call -- arguments, then limits, then the device and the stream -- without the frequency and elevation uploads. */
+/* The optimal-estimation step (csrc/mwrt_oe.hip): oe_call above is the preamble; the required pointers, the LDS plan and
+ * the launch are the entry's own. */
 size_t mwrt_oe_step_size(void) { return sizeof(mwrt_oe_step); }
 
 int mwrt_oe_step_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_step* s, void* stream) {
-  if (!c || !s) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context or mwrt_oe_step");
-  constexpr size_t required = offsetof(mwrt_oe_step, d_status) + sizeof(uint8_t*);
-  if (s->struct_size < required)
-    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_step.struct_size too small for the required fields (through d_status)");
-  mwrt_oe_step r{};                                    // fields at or beyond the caller's struct_size stay NULL
-  // ... and so does a field the size ends inside: beyond the required part every field is one pointer
-  size_t len = s->struct_size < sizeof r ? s->struct_size : sizeof r;
-  len -= (len - required) % sizeof(void*);
-  std::memcpy(&r, s, len);
-  if (nprof < 0 || nlev < 1 || m < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "nprof < 0, nlev < 1 or m < 1");
-  if (r.nblk < 1 || r.nblk > 4) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_step.nblk must be 1 .. 4");
-  if (r.reserved != 0) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_step.reserved must be 0");
-  bool buffers = r.d_x && r.d_xa && r.d_sa && r.d_se && r.d_y && r.d_fx && r.d_x_new && r.d_status;
-  for (int b = 0; b < r.nblk; ++b) buffers = buffers && r.d_k[b];
-  if (!buffers) return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
-  if (nlev > MWRT_MAX_LEVELS)
-    return fail(MWRT_ERR_UNSUPPORTED, "nlev > MWRT_MAX_LEVELS (" + std::to_string(MWRT_MAX_LEVELS) + ")");
-  if (m > MWRT_OE_MAX_M)
-    return fail(MWRT_ERR_UNSUPPORTED, "m > MWRT_OE_MAX_M (" + std::to_string(MWRT_OE_MAX_M) + " observations per profile: G lives in LDS)");
-  if (nprof > 2147483647LL) return fail(MWRT_ERR_UNSUPPORTED, "nprof exceeds grid limit");
   oe::OeArgs a{};
-  a.k0 = r.d_k[0]; a.k1 = r.nblk > 1 ? r.d_k[1] : nullptr; a.k2 = r.nblk > 2 ? r.d_k[2] : nullptr;
-  a.k3 = r.nblk > 3 ? r.d_k[3] : nullptr;
-  a.x = r.d_x; a.xa = r.d_xa; a.sa = r.d_sa; a.se = r.d_se; a.y = r.d_y; a.fx = r.d_fx;
-  a.x_new = r.d_x_new; a.chi2 = r.d_chi2; a.dfs = r.d_dfs; a.post_var = r.d_post_var; a.nobs = r.d_nobs; a.status = r.d_status;
-  a.nblk = r.nblk; a.nlev = nlev; a.m = m; a.n = r.nblk * nlev;
-  a.xa_per_profile = r.xa_per_profile != 0; a.se_full = r.se_full != 0;
-  if (oe::lds_plan(m, a.n).total_bytes > (size_t)c->lds_max)
-    return fail(MWRT_ERR_UNSUPPORTED, "the optimal-estimation step needs more LDS than this device has per workgroup");
-  if (nprof == 0) return MWRT_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = resolve_stream(c, stream);
-  return timed(c, st, [&] { return oe::launch_oe_step(a, nprof, st); });
+  return oe_call(c, nprof, nlev, m, s, stream, OE_STEP_RECORD,
+    [&](const mwrt_oe_step& r) {
+      bool buffers = r.d_x && r.d_xa && r.d_sa && r.d_se && r.d_y && r.d_fx && r.d_x_new && r.d_status;
+      for (int b = 0; b < r.nblk; ++b) buffers = buffers && r.d_k[b];
+      return buffers ? MWRT_OK : fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
+    },
+    [&](const mwrt_oe_step& r, const oe::OeArgs& o) {
+      a = o;
+      a.x_new = r.d_x_new; a.chi2 = r.d_chi2; a.dfs = r.d_dfs; a.post_var = r.d_post_var;
+      return oe::lds_plan(m, a.n).total_bytes <= (size_t)c->lds_max ? MWRT_OK
+           : fail(MWRT_ERR_UNSUPPORTED, "the optimal-estimation step needs more LDS than this device has per workgroup");
+    },
+    [&](hipStream_t st) { return oe::launch_oe_step(a, nprof, st); });
 }
 
 /* The Levenberg-Marquardt split of the step (csrc/mwrt_oe_lm.hip): oe_lm_call above is the one preamble of its three

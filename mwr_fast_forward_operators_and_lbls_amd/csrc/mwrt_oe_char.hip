@@ -10,97 +10,19 @@
 //                     and S^ (R = W, one block of n columns).
 // Every sum has a fixed order and nothing is shared between workgroups, so a profile's outputs depend on neither its
 // batch-mates nor nprof, and an element of a product on neither the tile nor the row window it is computed in.  Plain fp64
-// FMAs.  The panel, chunk and sum blocks are those of k_oe_step (mwrt_oe_blocks.hip.h); the 4 x 4 triangle update, the
-// Cholesky and the inverse are written inline in that kernel, so this unit carries its own copies of them as functions.
+// FMAs.  Every step the gain kernel has in common with k_oe_step is that kernel's block (mwrt_oe_blocks.hip.h; DESIGN 4.6
+// lists them).
 #include "mwrt_oe_char.hip.h"
 #include "mwrt_oe_blocks.hip.h"
 
 #include <math.h>
-#include <atomic>
 
 namespace mwrt {
 namespace oec {
 
 namespace {
 
-using oe::OeArgs;
-using oe::finite_f64;
-using oe::tri;
-using oe::kblock;
-using oe::block_sum;
-using oe::KCHUNK;
-using oe::PANEL;
-using oe::ROW_TILE;
-
-// G += W_p[:, half h] K[:, panel half]^T in 4 x 4 tiles of the packed lower triangle (k_oe_step, step 3)
-__device__ __forceinline__ void triangle_update(double* G, const double* Wt, const double* Ks, int kpitch, int h, int m,
-                                                int ntiles, int tid) {
-  for (int tile = tid; tile < ntiles; tile += THREADS) {
-    int bi = (int)((sqrtf(8.0f * (float)tile + 1.0f) - 1.0f) * 0.5f);
-    while (bi * (bi + 1) / 2 > tile) --bi;
-    while ((bi + 1) * (bi + 2) / 2 <= tile) ++bi;
-    const int bj = tile - bi * (bi + 1) / 2;
-    double t[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) t[a][c] = 0.0;
-#pragma unroll 4
-    for (int jj = 0; jj < KCHUNK; ++jj) {
-      double w[4], q[4];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) w[a] = Wt[(KCHUNK * h + jj) * kpitch + 4 * bi + a];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) q[c] = Ks[jj * kpitch + 4 * bj + c];
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) t[a][c] = fma(w[a], q[c], t[a][c]);
-    }
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int i = 4 * bi + a, j = 4 * bj + c;
-        if (i < m && j <= i) G[tri(i, j)] += t[a][c];
-      }
-  }
-}
-
-// Cholesky of the packed lower triangle in place (k_oe_step, step 4); false when a pivot fails pivot > 0 (uniform)
-__device__ __forceinline__ bool cholesky(double* G, int m, int tid) {
-  for (int j = 0; j < m; ++j) {
-    const double piv = G[tri(j, j)];
-    if (!(piv > 0.0)) return false;                        // the same value in every thread: a uniform exit
-    const double ljj = sqrt(piv);
-    for (int i = j + 1 + tid; i < m; i += THREADS) G[tri(i, j)] /= ljj;
-    __syncthreads();
-    for (int i = j + 1 + (tid >> 4); i < m; i += THREADS / 16) {
-      const double lij = G[tri(i, j)];
-      for (int c = j + 1 + (tid & 15); c <= i; c += 16) G[tri(i, c)] = fma(-lij, G[tri(c, j)], G[tri(i, c)]);
-    }
-    if (tid == 0) G[tri(j, j)] = ljj;                      // nobody reads the pivot in this phase
-    __syncthreads();
-  }
-  return true;
-}
-
-// X = L^-1 in place, Gauss-Jordan on the rows (k_oe_step, step 7)
-__device__ __forceinline__ void invert_lower(double* G, int m, int tid) {
-  for (int k = 0; k < m; ++k) {
-    const double xkk = 1.0 / G[tri(k, k)];
-    for (int j = tid; j < k; j += THREADS) G[tri(k, j)] *= xkk;
-    __syncthreads();
-    for (int i = k + 1 + (tid >> 4); i < m; i += THREADS / 16) {
-      const double lik = G[tri(i, k)];
-      for (int j = tid & 15; j < k; j += 16) G[tri(i, j)] = fma(-lik, G[tri(k, j)], G[tri(i, j)]);
-    }
-    __syncthreads();
-    for (int i = k + 1 + tid; i < m; i += THREADS) G[tri(i, k)] *= -xkk;
-    if (tid == 0) G[tri(k, k)] = xkk;
-    __syncthreads();
-  }
-}
+using namespace oe;                        // the blocks; THREADS is the same constant in both namespaces
 
 // every output of a profile that ends early: `v` everywhere (NaN or 0), keep 0, smooth_var = diag Sa when `prior`
 __device__ __forceinline__ void fill_profile(const GainArgs& C, int64_t prof, double v, bool prior, uint8_t status, int nobs,
@@ -140,82 +62,39 @@ __device__ __forceinline__ void char_gain(const GainArgs& C) {
   double* sed = smem + P.sed;
   double* red = smem + P.red;
   int* keep = reinterpret_cast<int*>(smem + P.keep);
-  const double qnan = __longlong_as_double(0x7ff8000000000000LL);
 
   // ---- 1: the state ----
   {
     const double* xp = A.x + (size_t)prof * n;
     const double* xap = A.xa + (A.xa_per_profile ? (size_t)prof * n : 0);
-    int bad = 0;
-    for (int k = tid; k < n; k += THREADS) bad |= !finite_f64(xp[k]) || !finite_f64(xap[k]);
-    if (__syncthreads_or(bad)) {
-      fill_profile(C, prof, qnan, false, 0, 0, tid);
+    if (state_bad<false>(xp, xap, n, nullptr, tid)) {
+      fill_profile(C, prof, quiet_nan(), false, 0, 0, tid);
       return;
     }
   }
 
-  // ---- 2: rows (the row rule of k_oe_step: y, F, the K row and the row's Se finite) ----
+  // ---- 2: rows ----
   for (int i = wave; i < mp; i += THREADS / 64) {
-    bool ok = false;
-    double sii = 0.0;
-    if (i < m) {
-      ok = finite_f64(A.y[(size_t)prof * m + i]) && finite_f64(A.fx[(size_t)prof * m + i]);
-      if (A.se_full) {
-        for (int c = lane; c < m; c += 64) ok = ok && finite_f64(A.se[(size_t)i * m + c]);
-        sii = A.se[(size_t)i * m + i];
-      } else {
-        sii = A.se[i];
-        ok = ok && finite_f64(sii);
-      }
-      for (int b = 0; b < A.nblk; ++b) {
-        const double* row = kblock(A, b, prof) + (size_t)i * nlev;
-        for (int l = lane; l < nlev; l += 64) ok = ok && finite_f64(row[l]);
-      }
-      ok = __all(ok);
-    }
+    const Row r = row_rule<false>(A, prof, i, nullptr, lane);
     if (lane == 0) {
-      keep[i] = ok ? 1 : 0;
-      sed[i] = ok ? sii : 0.0;
+      keep[i] = r.keep ? 1 : 0;
+      sed[i] = r.keep ? r.sii : 0.0;
     }
   }
   __syncthreads();
-  int m_used = 0;
-  for (int i = 0; i < m; ++i) m_used += keep[i];
+  const int m_used = rows_kept(keep, m);
   if (m_used == 0) {                       // nothing observed: the prior
     fill_profile(C, prof, 0.0, true, 3, 0, tid);
     return;
   }
 
   // ---- 3: G = K Sa K^T ----
-  const int ng = m * (m + 1) / 2;
-  for (int e = tid; e < ng; e += THREADS) G[e] = 0.0;
-  __syncthreads();
-  const int nb = (m + 3) / 4, ntiles = nb * (nb + 1) / 2;
-  for (int j0 = 0; j0 < n; j0 += PANEL) {
-    oe::form_panel<MR>(A, prof, keep, j0, Wt, Ks, Ss, kpitch, tid);
-    for (int h = 0; h < PANEL / KCHUNK; ++h) {
-      oe::Chunk<MR, false> ch;
-      ch.fetch(A, prof, keep, j0 + KCHUNK * h, 0, tid);      // K[:, panel half]; columns beyond n are 0
-      ch.store(Ks, Ss, kpitch, tid);
-      __syncthreads();
-      triangle_update(G, Wt, Ks, kpitch, h, m, ntiles, tid);
-      __syncthreads();
-    }
-  }
+  form_G<MR>(A, prof, keep, G, Wt, Ks, Ss, kpitch);
 
   // ---- 4: + Se, dropped rows, Cholesky ----
-  if (A.se_full) {
-    for (int i = tid >> 4; i < m; i += THREADS / 16)
-      for (int c = tid & 15; c < i; c += 16)
-        if (keep[i] && keep[c]) G[tri(i, c)] += A.se[(size_t)i * m + c];
-  }
-  for (int i = tid; i < m; i += THREADS) {
-    if (keep[i]) G[tri(i, i)] += sed[i];
-    else G[tri(i, i)] = 1.0;
-  }
-  __syncthreads();
-  if (!cholesky(G, m, tid)) {
-    fill_profile(C, prof, qnan, false, 2, m_used, tid);
+  add_se_and_identity_rows(A, keep, sed, G, 1.0, tid);
+  if (!cholesky_packed(G, m, tid)) {
+    fill_profile(C, prof, quiet_nan(), false, 2, m_used, tid);
     return;
   }
   if (tid == 0) {
@@ -237,13 +116,15 @@ __device__ __forceinline__ void char_gain(const GainArgs& C) {
   double* colsum = Ks;                                       // [ROW_TILE][PANEL]: Ks and Ss are contiguous, >= 1040 doubles
   if (tid < 4 * PANEL) red[tid] = 0.0;                       // diag A summed per block: red[b][j] for column j of every panel
   for (int j0 = 0; j0 < n; j0 += PANEL) {
-    oe::form_panel<MR>(A, prof, keep, j0, Wt, Ks, Ss, kpitch, tid);
+    form_panel<MR>(A, prof, keep, j0, Wt, Ks, Ss, kpitch, tid);
     if (ksa_p && j0 + cj < n) {                              // rows of W, contiguous in n: 32 lanes, 32 columns of a row
       double* o = ksa_p + j0 + cj;
       const double* w = Wt + cj * kpitch;
 #pragma unroll 1
       for (int i = cq; i < m; i += PARTS) o[(size_t)i * n] = w[i];
     }
+    // The two tile products stay written out, here and in k_oe_step's step 7: as one shared function the compiler hoists
+    // their addresses differently and k_char_gain<3> goes from 128 to 162 VGPRs, over the budget its test pins.
     double z[MR][4];
 #pragma unroll
     for (int r = 0; r < MR; ++r)
@@ -340,11 +221,10 @@ __device__ __forceinline__ void char_gain(const GainArgs& C) {
     __syncthreads();
     if (tid < PANEL && j0 + tid < n) {
       const int j = j0 + tid;
-      double a = 0.0, s = 0.0, zz = 0.0;
+      double a = 0.0, s = 0.0;
 #pragma unroll 4
       for (int q = 0; q < PARTS; ++q) { a += part[q * PANEL + tid]; s += part[(PARTS + q) * PANEL + tid]; }
-#pragma unroll 4
-      for (int r = 0; r < ROW_TILE; ++r) zz += colsum[r * PANEL + tid];
+      const double zz = column_total(colsum, tid);
       const size_t o = (size_t)prof * n + j;
       if (C.avk_diag) C.avk_diag[o] = a;
       if (C.noise_var) C.noise_var[o] = s;
@@ -457,36 +337,16 @@ k_char_product(const ProductArgs P) {
   }
 }
 
-template <int MR>
-hipError_t launch_gain_mr(const GainArgs& a, int64_t nprof, size_t lds, hipStream_t st) {
-  // beyond the default dynamic LDS limit from m = 65 on.  The limit of an instantiation is raised when a launch first
-  // needs more than it had on that device, so a repeat call of the same (or a smaller) size is the launch alone
-  if (lds > 64 * 1024) {
-    constexpr int MAX_DEV = 64;
-    static std::atomic<size_t> raised[MAX_DEV];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= MAX_DEV || raised[dev].load(std::memory_order_acquire) < lds) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_char_gain<MR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      if (dev >= 0 && dev < MAX_DEV) raised[dev].store(lds, std::memory_order_release);
-    }
-  }
-  hipLaunchKernelGGL(k_char_gain<MR>, dim3((unsigned)nprof), dim3(THREADS), lds, st, a);
-  return hipGetLastError();
-}
-
 }  // namespace
 
 hipError_t launch_char_gain(const GainArgs& a, int64_t nprof, hipStream_t st) {
   const size_t lds = gain_plan(a.o.m).total_bytes;
   switch ((a.o.m + ROW_TILE - 1) / ROW_TILE) {
-    case 1: return launch_gain_mr<1>(a, nprof, lds, st);
-    case 2: return launch_gain_mr<2>(a, nprof, lds, st);
-    case 3: return launch_gain_mr<3>(a, nprof, lds, st);
-    case 4: return launch_gain_mr<4>(a, nprof, lds, st);
-    case 5: return launch_gain_mr<5>(a, nprof, lds, st);
+    case 1: return launch_raised<k_char_gain<1>>(a, nprof, lds, st);
+    case 2: return launch_raised<k_char_gain<2>>(a, nprof, lds, st);
+    case 3: return launch_raised<k_char_gain<3>>(a, nprof, lds, st);
+    case 4: return launch_raised<k_char_gain<4>>(a, nprof, lds, st);
+    case 5: return launch_raised<k_char_gain<5>>(a, nprof, lds, st);
     default: return hipErrorInvalidValue;
   }
 }
