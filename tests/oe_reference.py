@@ -3,6 +3,8 @@ case recipe the CPU and GPU tests share.
 
 ``oe_step_reference`` follows the header's definition literally: dropped observation rows are DELETED, G = K Sa K^T + Se is
 factorised with ``np.linalg.cholesky`` and every output comes from solves with that factor."""
+import functools
+
 import numpy as np
 
 SIGMA = (2.0, 0.3, 0.05, 0.05)                 # prior standard deviation per state block
@@ -11,9 +13,55 @@ TOL = 1e-8                                     # c m eps cond(G) with c = 64, m 
 COND_MAX = 1e4
 SEED = 2009                                    # a draw whose every case meets COND_MAX (test_oe_reference.py checks)
 
-# (nlev, nblk, m): wave seams of the level axis, panel remainders, m not a multiple of any tile, m = 1, the m limit
+# (nlev, nblk, m).  What the list reaches is asserted, not described, by
+# tests/test_oe_shape_coverage.py::test_the_shapes_reach_what_they_are_for, against the LDS plans and the launchers'
+# dispatch rule as the code has them: every row-tile count ceil(m / 32) = 1 .. 5 with both sides of every tile edge, m = 1
+# and the m limit, one to four state blocks, both sides of wave 0's register seams (m = 64 | 65, 128 | 129), both sides of
+# the first raise of every kernel's LDS limit, the two shapes whose state vector outgrows the panel buffers it aliases, a
+# panel remainder and the wave seam of the level axis.  A shape added here needs cond_2(G) <= COND_MAX for SEED
+# (test_oe_reference.py checks); a shape taken away has to leave that test passing.
 SHAPES = [(2, 1, 1), (2, 2, 3), (3, 3, 14), (33, 1, 17), (63, 2, 14), (64, 2, 15), (65, 2, 98), (180, 2, 98),
-          (180, 3, 140), (1024, 2, 140)]
+          (180, 3, 140), (1024, 2, 140),
+          (33, 1, 32), (33, 1, 33),                      # one tile exactly | the second by one row; n = 33
+          (20, 4, 40),                                   # four state blocks
+          (64, 2, 64), (65, 2, 65),                      # two tiles exactly | the third by one row: v0's last lane | v1's first
+          (65, 2, 64),                                   # ... and at one n, 130: the first LDS raise of k_char_gain
+          (65, 2, 69), (65, 2, 70),                      # the first LDS raise of k_oe_step and k_lm_prepare at n = 130
+          (129, 1, 96), (129, 1, 97),                    # three tiles exactly | the fourth by one row
+          (65, 2, 122), (65, 2, 123),                    # ... of k_lm_cost with a full Se
+          (65, 2, 124), (65, 2, 125),                    # ... of k_lm_solve
+          (65, 2, 128), (65, 2, 129),                    # four tiles exactly | the fifth by one row: v1's last lane | v2's first
+          (700, 3, 14), (909, 4, 33)]                    # n = 2100 and 3636: four doubles beyond the panel buffers of 1 and 2 tiles
+
+
+# Rows dropped at the seams of m = 65 (three row tiles, row 64 alone in the third and alone in wave 0's second register):
+# the last row of a tile, the first of the next, a whole tile, and every row but one.  A principal submatrix of a symmetric
+# positive-definite G is no worse conditioned than G, so COND_MAX holds for every pattern (and is asserted on each).
+SEAM_SHAPE = (65, 2, 65)
+SEAM_DROPS = {"row-31": (31,), "row-32": (32,), "row-63": (63,), "row-64": (64,), "tile-32-63": tuple(range(32, 64)),
+              "all-but-64": tuple(range(64))}
+
+
+def copy_case(case):
+    return {k: (v.copy() if isinstance(v, np.ndarray) else [b.copy() for b in v]) for k, v in case.items()}
+
+
+def drop_rows(case, what, rows, prof):
+    """A copy of ``case`` in which profile ``prof`` loses ``rows``: NaN in y ("y"), or in one element of the row in one
+    K block ("k"; block and level change with the row)."""
+    bad = copy_case(case)
+    nblk, nlev = len(bad["k"]), bad["k"][0].shape[2]
+    for row in rows:
+        if what == "k":
+            bad["k"][row % nblk][prof, row, (7 * row) % nlev] = np.nan
+        else:
+            bad[what][prof, row] = np.nan
+    return bad
+
+
+def one_profile(outputs, i):
+    """Profile i of a dict of per-profile outputs, as a batch of one: for the error of that profile alone."""
+    return {k: (None if v is None else v[i:i + 1]) for k, v in outputs.items()}
 
 
 def oe_step_reference(k, x, xa, sa, se, y, fx):
@@ -94,6 +142,24 @@ def n_form_reference(k, x, xa, sa, se, y, fx):
     return np.array(xs), np.array(posts), np.array(dfs)
 
 
+@functools.lru_cache(maxsize=None)
+def prior_covariance(nlev, nblk):
+    """Sa of the recipe: exponentially correlated blocks, the first two coupled.  It depends on (nlev, nblk) alone, so the
+    cases of a shape share one array (105 MB at n = 3636) and what is derived from it once, like its inverse; nobody
+    writes to it."""
+    lev = np.arange(nlev, dtype=np.float64)
+    n = nblk * nlev
+    corr = np.exp(-np.abs(lev[:, None] - lev[None, :]) / max(nlev / 6.0, 1.0))
+    sa = np.zeros((n, n))
+    for b in range(nblk):
+        sa[b * nlev:(b + 1) * nlev, b * nlev:(b + 1) * nlev] = SIGMA[b] ** 2 * corr
+    if nblk > 1:
+        cross = 0.3 * SIGMA[0] * SIGMA[1] * corr
+        sa[:nlev, nlev:2 * nlev] = cross
+        sa[nlev:2 * nlev, :nlev] = cross.T
+    return sa
+
+
 def make_case(nlev, nblk, m, nprof=4, se_full=False, xa_per_profile=False, seed=SEED):
     """The seeded recipe: smooth weighting-function rows, exponentially correlated prior, white or correlated noise.
     Profile i is drawn from its own stream, so it is the same profile whatever nprof is."""
@@ -116,15 +182,7 @@ def make_case(nlev, nblk, m, nprof=4, se_full=False, xa_per_profile=False, seed=
         x[i] = (xap[i] if xa_per_profile else xa_shared) + 0.1 * rng.standard_normal((nblk, nlev))
         fx[i] = 250.0 + 20.0 * rng.standard_normal(m)
         y[i] = fx[i] + rng.standard_normal(m)
-    n = nblk * nlev
-    corr = np.exp(-np.abs(lev[:, None] - lev[None, :]) / max(nlev / 6.0, 1.0))
-    sa = np.zeros((n, n))
-    for b in range(nblk):
-        sa[b * nlev:(b + 1) * nlev, b * nlev:(b + 1) * nlev] = SIGMA[b] ** 2 * corr
-    if nblk > 1:
-        cross = 0.3 * SIGMA[0] * SIGMA[1] * corr
-        sa[:nlev, nlev:2 * nlev] = cross
-        sa[nlev:2 * nlev, :nlev] = cross.T
+    sa = prior_covariance(nlev, nblk)
     if se_full:
         i = np.arange(m, dtype=np.float64)
         se = 0.7 * 0.25 * np.eye(m) + 0.3 * 0.25 * np.exp(-np.abs(i[:, None] - i[None, :]) / 3.0)

@@ -7,9 +7,13 @@ Tolerance (derived, not measured; the argument of test_oe_step.py): Cholesky, in
 floor.  The product entry alone, on exact inputs, is held element by element to the forward bound of a length-m sum:
 2 m eps (|gain|^T |K|)_jk, resp. 2 m eps (|Sa_jk| + (|gain|^T |W|)_jk).
 
-Shapes (nlev, nblk, m) are oe_reference.SHAPES: n = 2, 4, 9, 33, 126, 128, 130, 360, 540, 2048 -- the wave seams, the
-panel remainder, the product kernel's exact-tile (128) and tile + 2 (130) edges, every row-tile count and the m limit.  At
-n = 2048 the products are taken through two row windows instead of one 134-MB result per call."""
+Shapes (nlev, nblk, m) are oe_reference.SHAPES.  What they reach in the gain kernel is asserted by
+test_oe_shape_coverage.py::test_the_shapes_reach_what_they_are_for against the code's own LDS plan and dispatch rule, and
+that test is the authority: k_char_gain<1 .. 5> with both sides of every tile edge, m = 1 and the m limit, one to four K
+blocks, and both sides of the first raise of the kernel's LDS limit (m = 64 | 65).  For the product kernel the list holds
+n = 128 (its exact tile) and 130 (tile + 2), the panel remainders and a block seam inside a tile.  At n = 2048 the products
+are taken through two row windows instead of one 134-MB result per call, beyond it through three windows of 64 rows
+(_windows).  Rows are dropped at m = 98 and, on the tile seams, at m = 65 (oe_reference.SEAM_DROPS)."""
 import ctypes
 
 import numpy as np
@@ -124,8 +128,15 @@ def check_gain(got, ref, case, label):
     return err
 
 
-def _windows(n):
-    return [None] if n < 2048 else [(0, n // 2), (n // 2, n // 2)]
+def _windows(n, nlev):
+    """Row windows of the n x n products: everything below n = 2048, two halves there, and beyond it (where a half would be
+    [4][1818][3636] doubles) the first 64 rows, the last 64 and 64 rows across the first block seam -- the product kernel's
+    tile edges are reached in full at n = 128 and 130."""
+    if n < 2048:
+        return [None]
+    if n == 2048:
+        return [(0, n // 2), (n // 2, n // 2)]
+    return [(0, 64), (n - 64, 64), (nlev - 32, 64)]
 
 
 @pytest.mark.parametrize("nlev,nblk,m", oer.SHAPES, ids=SHAPE_IDS)
@@ -146,7 +157,7 @@ def test_gain_entry_and_chain_against_the_reference(gpu_ctx, nlev, nblk, m, se_f
     print(label, "against the step: dfs", e_dfs, "post_var", e_var)
     assert e_dfs <= oer.TOL and e_var <= oer.TOL
     # the chain: gain -> product on the device buffers, against the reference A and S^
-    for rows in _windows(n):
+    for rows in _windows(n, nlev):
         r = ref if rows is None else ocr.oe_char_reference(**case, rows=rows)
         chain = dict(avk=run_product(gpu_ctx, _native.OE_PRODUCT_AVK, out["gain"], out["keep"], d, rows=rows),
                      post_cov=run_product(gpu_ctx, _native.OE_PRODUCT_POST_COV, out["gain"], out["keep"], d, ksa=out["ksa"], rows=rows))
@@ -163,7 +174,7 @@ def test_product_entry_within_the_bound_of_a_length_m_sum(gpu_ctx, nlev, nblk, m
     d = upload(case)
     gain, ksa, keep = _dev(ref["gain"]), _dev(ref["ksa"]), _dev(ref["keep"])          # exact inputs: the reference's own
     K = np.concatenate(case["k"], axis=2)
-    for rows in _windows(n):
+    for rows in _windows(n, nlev):
         r0, rc = (0, n) if rows is None else rows
         a_ref, a_bound = ocr.product_reference(ref["gain"], ref["keep"], K, rows=rows)
         a = run_product(gpu_ctx, _native.OE_PRODUCT_AVK, gain, keep, d, rows=rows)
@@ -261,6 +272,34 @@ def test_dropped_rows_equal_rows_deleted(gpu_ctx, what):
             for i in (0, 2, 3):
                 for key in GAIN_KEYS:
                     assert np.array_equal(got[key][i], clean[key][i]), (what, row, i, key)
+
+
+@pytest.mark.parametrize("pattern", list(oer.SEAM_DROPS))
+@pytest.mark.parametrize("what", ["y", "k"])
+def test_dropped_rows_at_the_seams_equal_rows_deleted(gpu_ctx, what, pattern):
+    """m = 65: row 64 is the only row of the third tile of k_char_gain<3>.  Profile 1 loses the last row of a tile, the
+    first of the next, a whole tile (32 rows of zeros in the gain), or every row but 64."""
+    (nlev, nblk, m), nprof = oer.SEAM_SHAPE, 4
+    dropped = list(oer.SEAM_DROPS[pattern])
+    base, _ = case_and_reference(nlev, nblk, m, False, False)
+    clean = run_gain(gpu_ctx, base)
+    case = oer.drop_rows(base, what, dropped, 1)
+    ref = ocr.oe_char_reference(**case)
+    assert ref["nobs"].tolist() == [m, m - len(dropped), m, m]
+    got, d, out = run_gain(gpu_ctx, case, keep_device=True)
+    check_gain(got, ref, case, (what, pattern))
+    assert (got["gain"][1, dropped] == 0).all() and (got["ksa"][1, dropped] == 0).all() and (got["keep"][1, dropped] == 0).all()
+    # the chain on the device's own buffers: a NaN in K's dropped rows must not reach A
+    a = run_product(gpu_ctx, _native.OE_PRODUCT_AVK, out["gain"], out["keep"], d)
+    s = run_product(gpu_ctx, _native.OE_PRODUCT_POST_COV, out["gain"], out["keep"], d, ksa=out["ksa"])
+    err = ocr.char_errors(dict(avk=a, post_cov=s), ref, case)
+    print((what, pattern), "chain", err)
+    alone = oer.one_profile(dict(got, avk=a, post_cov=s), 1)
+    print((what, pattern), "profile 1 alone", ocr.char_errors(alone, oer.one_profile(ref, 1), case))
+    assert np.isfinite(a).all() and np.isfinite(s).all() and all(v <= oer.TOL for v in err.values()), (what, pattern, err)
+    for i in (0, 2, 3):                                        # the neighbours never see it: bit for bit
+        for key in GAIN_KEYS:
+            assert np.array_equal(got[key][i], clean[key][i]), (what, pattern, i, key)
 
 
 def test_status_values_and_untouched_neighbours(gpu_ctx):

@@ -57,19 +57,22 @@ def test_m_form_products_equal_the_n_form(nlev, nblk, m, se_full):
 
 
 @pytest.mark.parametrize("what", ["y", "fx", "k", "se"])
-@pytest.mark.parametrize("row", [0, 8, 16])
+@pytest.mark.parametrize("row", [0, 8, 16] + list(oer.SEAM_DROPS))
 def test_dropped_row_is_the_row_deleted(what, row):
-    m = 17
-    case = oer.make_case(33, 2, m, nprof=2, se_full=(what == "se"))
+    """One row of the 17-row case, or one of the multi-row patterns of oe_reference.SEAM_DROPS at m = 65."""
+    (nlev, nblk, m), dropped = ((33, 2, 17), (row,)) if isinstance(row, int) else (oer.SEAM_SHAPE, oer.SEAM_DROPS[row])
+    case = oer.make_case(nlev, nblk, m, nprof=2, se_full=(what == "se"))
     bad = _copy(case)
-    if what == "k":
-        bad["k"][1][1, row, 5] = np.nan
-    elif what == "se":
-        bad["se"][row, (row + 3) % m] = np.inf
-    else:
-        bad[what][1, row] = np.nan
+    for r in dropped:
+        if what == "k":
+            bad["k"][1][1, r, 5] = np.nan
+        elif what == "se":
+            bad["se"][r, (r + 3) % m] = np.inf
+        else:
+            bad[what][1, r] = np.nan
     ref = ocr.oe_char_reference(**bad)
-    rows = np.arange(m) != row
+    rows = ~np.isin(np.arange(m), dropped)
+    row = list(dropped)
     small = _copy(case)
     small["k"] = [b[:, rows] for b in case["k"]]
     small["y"], small["fx"] = case["y"][:, rows], case["fx"][:, rows]
@@ -77,7 +80,7 @@ def test_dropped_row_is_the_row_deleted(what, row):
     cut = ocr.oe_char_reference(**small)
     hit = [0, 1] if what == "se" else [1]
     for i in hit:
-        assert ref["nobs"][i] == m - 1 and ref["keep"][i].tolist() == rows.astype(int).tolist()
+        assert ref["nobs"][i] == m - len(dropped) and ref["keep"][i].tolist() == rows.astype(int).tolist()
         assert (ref["gain"][i, row] == 0).all() and (ref["ksa"][i, row] == 0).all()
         assert np.array_equal(ref["gain"][i, rows], cut["gain"][i]) and np.array_equal(ref["ksa"][i, rows], cut["ksa"][i])
         for key in ("avk", "post_cov", "avk_diag", "noise_var", "smooth_var", "dfs_block"):

@@ -8,7 +8,13 @@ Tolerances (derived, not measured):
   x+, chi2     Cholesky + solves are backward stable, error <~ 64 m eps cond(G_gamma) <= oe_reference.TOL with cond <= 1e4
                asserted on the reference's G_gamma per case; in the units of oe_reference.block_errors.
   J prior      2 n eps |dx|^T |Sa^-1| |dx|;  J obs  TOL max(1, J_obs) (cond(Se) <= 4 asserted).
-Shapes are oe_reference.SHAPES: every wave seam, panel and tile remainder, row-tile count and the m limit."""
+Shapes are oe_reference.SHAPES.  What they reach is asserted by
+test_oe_shape_coverage.py::test_the_shapes_reach_what_they_are_for against the code's own LDS plans and dispatch rule, and
+that test is the authority: k_lm_prepare<1 .. 5> with both sides of every tile edge, m = 1 and the m limit, one to four K
+blocks, both sides of the register seams of k_lm_solve's wave 0 (m = 64 | 65, 128 | 129), both sides of the first raise of
+each kernel's LDS limit at n = 130 (prepare m = 69 | 70, cost with a full Se 122 | 123, solve 124 | 125), and the two shapes
+whose x - xa outgrows the panel buffers of k_lm_prepare (n = 2100, 3636).  Rows are dropped at m = 98 and, on the tile and
+register seams, at m = 65 (oe_reference.SEAM_DROPS)."""
 import numpy as np
 import pytest
 
@@ -33,9 +39,19 @@ def _cur():
     return torch.cuda.current_stream().cuda_stream
 
 
+_inverses = []
+
+
 def sym_inv(sa):
+    """The symmetrised inverse of Sa, computed once per array object (a 3636 x 3636 inverse takes longer than every
+    kernel of its case); nobody writes to either."""
+    for held, inv in _inverses:
+        if held is sa:
+            return inv
     inv = np.linalg.inv(sa)
-    return 0.5 * (inv + inv.T)
+    inv = 0.5 * (inv + inv.T)
+    _inverses.append((sa, inv))
+    return inv
 
 
 class Dev:
@@ -221,6 +237,31 @@ def test_dropped_rows_equal_rows_deleted(gpu_ctx, what):
             for i in (0, 2, 3):
                 for key in LIN_KEYS + SOLVE_KEYS + COST_KEYS:
                     assert np.array_equal(got[key][i], clean[key][i]), (what, row, i, key)
+
+
+@pytest.mark.parametrize("pattern", list(oer.SEAM_DROPS))
+@pytest.mark.parametrize("what", ["y", "k"])
+def test_dropped_rows_at_the_seams_equal_rows_deleted(gpu_ctx, what, pattern):
+    """m = 65: row 64 is the only row of the third tile of k_lm_prepare<3> and the only entry of the second register of
+    k_lm_solve's wave 0.  Profile 1 (gamma = 0.25) loses the last row of a tile, the first of the next, a whole tile, or
+    every row but 64."""
+    (nlev, nblk, m), nprof = oer.SEAM_SHAPE, 4
+    dropped = oer.SEAM_DROPS[pattern]
+    base, gammas, _ = seeded(nlev, nblk, m, False, False, nprof)
+    gamma = gammas[0]
+    clean = Dev(base, gamma).run(gpu_ctx)
+    case = oer.drop_rows(base, what, dropped, 1)
+    lin, sol, cost = reference(case, gamma)
+    assert sol["nobs"].tolist() == [m, m - len(dropped), m, m]
+    got = Dev(case, gamma).run(gpu_ctx)
+    check_prepare(got, lin, (what, pattern))
+    check_solve(got, sol, case, (what, pattern))
+    check_cost(got, cost, (what, pattern))
+    alone = oer.one_profile(dict(x_new=got["x_new"], chi2=got["chi2"]), 1)
+    print((what, pattern), "profile 1 alone", oer.block_errors(alone, oer.one_profile(sol, 1), case))
+    for i in (0, 2, 3):                                       # the neighbours never see it: bit for bit
+        for key in LIN_KEYS + SOLVE_KEYS + COST_KEYS:
+            assert np.array_equal(got[key][i], clean[key][i]), (what, pattern, i, key)
 
 
 def test_status_values_and_untouched_neighbours(gpu_ctx):

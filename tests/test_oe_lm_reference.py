@@ -35,6 +35,30 @@ def test_gamma_zero_is_the_undamped_step(se_full):
     assert np.allclose(got["chi2"], ref["chi2"], rtol=1e-12, atol=0)
 
 
+@pytest.mark.parametrize("what", ["y", "k"])
+@pytest.mark.parametrize("pattern", list(oer.SEAM_DROPS))
+def test_seam_patterns_of_dropped_rows_are_the_rows_deleted(what, pattern):
+    """The multi-row patterns the GPU suite drops at m = 65 (oe_reference.SEAM_DROPS), against the rows deleted by hand:
+    the linearisation's kept rows and columns, and the damped trial of every gamma."""
+    nlev, nblk, m = oer.SEAM_SHAPE
+    dropped = oer.SEAM_DROPS[pattern]
+    case = oer.make_case(nlev, nblk, m, nprof=2)
+    bad = oer.drop_rows(case, what, dropped, 1)
+    rows = ~np.isin(np.arange(m), dropped)
+    cut = dict(case, k=[k[:, rows] for k in case["k"]], y=case["y"][:, rows], fx=case["fx"][:, rows], se=case["se"][rows])
+    lin, lin_cut, lin_full = (lmr.prepare_reference(**c) for c in (bad, cut, case))
+    assert lin["keep"].tolist() == [[1] * m, rows.astype(int).tolist()]
+    assert np.array_equal(lin["g0"][1][np.ix_(rows, rows)], lin_cut["g0"][1]) and np.array_equal(lin["g0"][0], lin_full["g0"][0])
+    assert not lin["g0"][1][~rows].any() and not lin["g0"][1][:, ~rows].any() and not lin["r"][1, ~rows].any()
+    assert np.array_equal(lin["r"][1, rows], lin_cut["r"][1]) and np.array_equal(lin["kdx"][1, rows], lin_cut["kdx"][1])
+    for gamma in lmr.GAMMAS:
+        got, want, full = (lmr.solve_reference(gamma=gamma, **c) for c in (bad, cut, case))
+        assert got["nobs"].tolist() == [m, m - len(dropped)] and got["status"].tolist() == [1, 1]
+        assert got["cond"][1] <= full["cond"][1] * (1 + 1e-9) <= oer.COND_MAX        # a principal submatrix of G_gamma
+        assert np.array_equal(got["x_new"][1], want["x_new"][1]) and got["chi2"][1] == want["chi2"][1]
+        assert np.array_equal(got["x_new"][0], full["x_new"][0]) and got["chi2"][0] == full["chi2"][0]
+
+
 def test_cost_of_the_damped_step_falls_as_gamma_falls_on_a_linear_model():
     """On F(x) = F(x0) + K (x - x0) the cost is a quadratic whose minimiser is the gamma = 0 step, and x+(gamma) moves
     monotonically along a path of non-increasing J as gamma -> 0 (the trust-region property of Levenberg-Marquardt)."""

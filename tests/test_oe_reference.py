@@ -1,12 +1,12 @@
 """The NumPy reference of the optimal-estimation step (tests/oe_reference.py) held to independent algebra, without a GPU:
-the m-form against the n-form, the diagnostics against their definitions, a dropped row against the row deleted by hand,
+the m-form against the n-form, the diagnostics against their definitions, dropped rows against the rows deleted by hand,
 and the recipe's conditioning (cond_2(G) <= 1e4 for every shape the GPU tests use -- the premise of their 1e-8 bar)."""
 import numpy as np
 import pytest
 
 import oe_reference as oer
 
-# the n-form inverts Sa: every shape of the recipe but (1024, 2, 140), whose 2048 x 2048 inverse adds seconds and no new path
+# the n-form inverts Sa: every shape of the recipe but those of n >= 2048, whose inverses add seconds and no new path
 SMALL = [s for s in oer.SHAPES if s[0] <= 180]
 
 
@@ -51,27 +51,34 @@ def test_dfs_is_the_trace_of_the_averaging_kernel():
 
 
 @pytest.mark.parametrize("what", ["y", "fx", "k", "se"])
-@pytest.mark.parametrize("row", [0, 8, 16])
+@pytest.mark.parametrize("row", [0, 8, 16] + list(oer.SEAM_DROPS))
 def test_dropped_row_is_the_row_deleted(what, row):
-    m = 17
-    case = oer.make_case(33, 2, m, nprof=2, se_full=(what == "se"))
-    bad = {k: (v.copy() if isinstance(v, np.ndarray) else [b.copy() for b in v]) for k, v in case.items()}
-    if what == "k":
-        bad["k"][1][0, row, 5] = np.nan
-    elif what == "se":
-        bad["se"][row, (row + 3) % m] = np.inf
-    else:
-        bad[what][0, row] = np.nan
+    """One row of the 17-row case, or one of the multi-row patterns the GPU suites drop at the seams of m = 65
+    (oe_reference.SEAM_DROPS: a whole tile, every row but one), against the rows deleted by hand."""
+    (nlev, nblk, m), dropped = ((33, 2, 17), (row,)) if isinstance(row, int) else (oer.SEAM_SHAPE, oer.SEAM_DROPS[row])
+    case = oer.make_case(nlev, nblk, m, nprof=2, se_full=(what == "se"))
+    bad = oer.copy_case(case)
+    for r in dropped:
+        if what == "k":
+            bad["k"][1][0, r, 5] = np.nan
+        elif what == "se":
+            bad["se"][r, (r + 3) % m] = np.inf
+        else:
+            bad[what][0, r] = np.nan
+    if what in ("y", "k") and not isinstance(row, int):          # the helper the GPU suites use says the same
+        via = oer.oe_step_reference(**oer.drop_rows(case, what, dropped, 0))
+        assert via["nobs"].tolist() == [m - len(dropped), m]
     got = oer.oe_step_reference(**bad)
-    rows = np.arange(m) != row
+    rows = ~np.isin(np.arange(m), dropped)
     cut = dict(case, k=[k[:, rows] for k in case["k"]], y=case["y"][:, rows], fx=case["fx"][:, rows],
                se=case["se"][np.ix_(rows, rows)] if what == "se" else case["se"][rows])
     want = oer.oe_step_reference(**cut)
     full = oer.oe_step_reference(**case)
+    assert np.nanmax(got["cond"]) <= np.nanmax(full["cond"]) * (1 + 1e-9) <= oer.COND_MAX   # a principal submatrix of G
     # a non-finite Se entry drops the row for every profile; the others drop it for profile 0 alone
     for i in range(2):
         src = want if (i == 0 or what == "se") else full
-        assert got["nobs"][i] == src["nobs"][i] == (m - 1 if src is want else m)
+        assert got["nobs"][i] == src["nobs"][i] == (m - len(dropped) if src is want else m)
         for key in ("x_new", "post_var", "chi2", "dfs"):
             np.testing.assert_allclose(got[key][i], src[key][i], rtol=0, atol=1e-12 * max(1.0, np.abs(src[key][i]).max()))
 

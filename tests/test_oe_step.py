@@ -4,8 +4,13 @@ Tolerance (derived, not measured): Cholesky + solves are backward stable, error 
 and cond_2(G) <= 1e4 (asserted on the reference's G for every case) that is ~1e-8.  x_new is held to 1e-8 of max |x_ref - xa|
 per block, post_var to 1e-8 of max diag Sa per block, chi2 and dfs to 1e-8 max(1, |ref|).  No mask, no floor.
 
-Shapes (nlev, nblk, m): wave seams of the level axis (63 / 64 / 65), panel remainders (n not a multiple of 32), m not a
-multiple of any tile, m = 1, every row-tile count of the kernel (m <= 32, 64, 96, 128, 160) and the m limit 140."""
+Shapes (nlev, nblk, m) are oe_reference.SHAPES.  What they reach is asserted by
+test_oe_shape_coverage.py::test_the_shapes_reach_what_they_are_for against the code's own LDS plan and dispatch rule, and
+that test is the authority: k_oe_step<1 .. 5> with m = 32 k and 32 k + 1 on both sides of every tile edge, m = 1 and the
+m limit 140, one to four K blocks, both sides of the seams of wave 0's solve registers (m = 64 | 65, 128 | 129), both
+sides of the first raise of the kernel's LDS limit (m = 69 | 70 at n = 130), the two shapes whose x - xa outgrows the panel
+buffers it aliases (n = 2100 at one tile, 3636 at two), the wave seams of the level axis (63 / 64 / 65) and a panel
+remainder.  Rows are dropped at m = 98 and, on the tile and register seams, at m = 65 (oe_reference.SEAM_DROPS)."""
 import ctypes
 
 import numpy as np
@@ -112,6 +117,26 @@ def test_dropped_rows_equal_rows_deleted(gpu_ctx, what):
             for i in (0, 2, 3):
                 for key in OUT_KEYS:
                     assert np.array_equal(got[key][i], clean[key][i]), (what, row, i, key)
+
+
+@pytest.mark.parametrize("pattern", list(oer.SEAM_DROPS))
+@pytest.mark.parametrize("what", ["y", "k"])
+def test_dropped_rows_at_the_seams_equal_rows_deleted(gpu_ctx, what, pattern):
+    """m = 65: row 64 is the only row of the third tile and the only entry of wave 0's second register.  Profile 1 loses
+    the last row of a tile, the first of the next, a whole tile (32 rows of the identity in G), or every row but 64."""
+    (nlev, nblk, m), nprof = oer.SEAM_SHAPE, 4
+    dropped = oer.SEAM_DROPS[pattern]
+    base, _ = case_and_reference(nlev, nblk, m, False, False, nprof)
+    clean = run_device(gpu_ctx, base)
+    case = oer.drop_rows(base, what, dropped, 1)
+    ref = oer.oe_step_reference(**case)
+    assert ref["nobs"].tolist() == [m, m - len(dropped), m, m]
+    got = run_device(gpu_ctx, case)
+    check_against_reference(got, ref, case, (what, pattern))
+    print((what, pattern), "profile 1 alone", oer.block_errors(oer.one_profile(got, 1), oer.one_profile(ref, 1), case))
+    for i in (0, 2, 3):                                       # the neighbours never see it: bit for bit
+        for key in OUT_KEYS:
+            assert np.array_equal(got[key][i], clean[key][i]), (what, pattern, i, key)
 
 
 def test_status_values_and_untouched_neighbours(gpu_ctx):
