@@ -179,6 +179,12 @@ __device__ __forceinline__ void far_quad_accumulate(const double* sfq, const Far
 // "Frequencies"); the headroom holds to about 1.6 THz (D grows as f^80), and from about 7 THz a group's product overflows.  Six quads (1.3e288) would still fit, without the headroom;
 // nine (1e432) overflow.
 constexpr int FAR_GROUP_QUADS = 5;
+// A later quad updates N where it lives.  The compiler forms the product num D first and lets a v_fmac accumulate into it:
+// the new N then sits beside the old one, and NFC 64-bit copies carry it back at the loop's latch.  The three-address form
+// of the same FMA, destination = first factor, is written out here instead (same operands, same operation, same bits).
+__device__ __forceinline__ void fma_in_place(double& n, double den, double t) {          // n = fma(n, den, t)
+  asm("v_fma_f64 %0, %0, %1, %2" : "+v"(n) : "v"(den), "v"(t));
+}
 template <int NFC, bool FIRST>
 __device__ __forceinline__ void far_quad_fraction(const double* sfq, const FarLine& a, const FarLine& b, const FarLine& c,
                                                   const FarLine& d, const double (&sum)[NFC], double (&N)[NFC], double (&D)[NFC]) {
@@ -190,7 +196,7 @@ __device__ __forceinline__ void far_quad_fraction(const double* sfq, const FarLi
       N[j] = __builtin_fma(sum[j], den, num);
       D[j] = den;
     } else {
-      N[j] = __builtin_fma(N[j], den, num * D[j]);
+      fma_in_place(N[j], den, num * D[j]);
       D[j] *= den;
     }
   }
@@ -595,6 +601,22 @@ __device__ __forceinline__ void h2o_absorb(cmodel M, const LevelState& L, const 
 // K1b: O2 lines + non-resonant + N2 continuum (O2AbsModel.o2_absorption / N2AbsModel [EXT])
 //   S (f/F)^2 [ (w g + d1 Y)/D1 + (w g - d2 Y)/D2 ]  with one reciprocal per line and frequency
 // ---------------------------------------------------------------------------------------------
+// fma(table value, lane value, table value): a v_fma_f64 reads one scalar operand at most, so one of the two table values
+// has to sit in a vector register pair, and the compiler takes it there with two v_mov_b32.  Table values arrive in scalar
+// registers (s_load), and gfx950 moves such a pair in ONE instruction: the addend is handed over by a v_mov_b64, and the
+// FMA accumulates into the registers it wrote.  Same operands, same operation, same bits; one VALU instruction fewer per
+// such FMA.  (FUSED: the fused kernel's set-ups only; the other kernels keep the compiler's form.)
+template <bool FUSED>
+__device__ __forceinline__ double table_addend(double s) {
+  if constexpr (FUSED) {
+    double v;
+    asm("v_mov_b64 %0, %1" : "=v"(v) : "s"(s));
+    return v;
+  } else {
+    return s;
+  }
+}
+
 struct O2Line {            // per-(level, line) quantities, frequency independent (all carry HALF the line's weight:
   double c1, df2;          //  the common factor 2 of P and Q is applied once, in the final scale)
   double P, Q;             //  n1/D1 + n2/D2 = 2 (f^2 P + Q) / (D1 D2),  P = a + c b,  Q = (c^2 + w^2)(a - c b)
@@ -633,11 +655,17 @@ __device__ __forceinline__ void dry_absorb(cmodel M, const LevelState& L, const 
   double ebe = 1.0;
   auto line_setup = [&](int k) -> O2Line {
     const auto& R = M->o2r[k];
-    const double y = ymul * __builtin_fma(R.y1, th1, R.y0);
+    // A set-up reads its record in four scalar loads, each placed in front of its first use with a wait behind it: four
+    // round trips to the scalar cache per line, and a SIMD holds only three of these waves to cover them.  Asking for BE,
+    // W300, Y0 and Y1 here makes them ONE eight-dword load at the top of the set-up (they are adjacent in O2Rec), three
+    // round trips per line.  The fused kernel only; more of the record up front costs it scratch.
+    if constexpr (GROUPED) asm volatile("" :: "s"(R.be), "s"(R.w300), "s"(R.y0), "s"(R.y1));
+    // slope and offset are both table values: the offset goes to the vector side in one move (table_addend)
+    const double y = ymul * __builtin_fma(R.y1, th1, table_addend<GROUPED>(R.y0));
     double dnu = 0.0, gfac = 1.0;
     if (second) {
-      dnu = pe2 * __builtin_fma(R.dnu1, th1, R.dnu0);
-      gfac = __builtin_fma(pe2, __builtin_fma(R.g1, th1, R.g0), 1.0);
+      dnu = pe2 * __builtin_fma(R.dnu1, th1, table_addend<GROUPED>(R.dnu0));
+      gfac = __builtin_fma(pe2, __builtin_fma(R.g1, th1, table_addend<GROUPED>(R.g0)), 1.0);
     }
     const double df = R.w300 * ((k == 0 && line1_dens) ? dens : den);
     // N- / N+ partners share BE: the exponential is redone only when the table value changes

@@ -2,7 +2,11 @@
 """Per-basic-block and per-source-line instruction table of one kernel, from hipcc --save-temps ISA.
 
     hipcc --offload-arch=gfx950 -O3 -gline-tables-only --save-temps ... -DMWRT_INST_NFC=14 -c csrc/mwrt_inst.hip
-    python tools/isa_blocks.py mwrt_inst-hip-amdgcn-amd-amdhsa-gfx950.s k_tb_fusedILi14ELi7ELi256E [--lines]
+    python tools/isa_blocks.py mwrt_inst-hip-amdgcn-amd-amdhsa-gfx950.s k_tb_fusedILi14ELi7ELi256E [--lines | --loops]
+
+--loops sums the blocks of each loop (the compiler's own "in Loop: Header=" comments; a block counts for its innermost
+loop only, "straight" is the code outside every loop) and adds an `arith` column (fma64 + mul64 + add64 + rcp64): what is
+left of VALU after it is moves, selects, compares, conversions and lane traffic.
 
 (the unit that holds the kernel: csrc/mwrt_inst.hip for k_tb_fused, k_absorb* and k_rte_tau, csrc/mwrt_tl.hip for the
 K-matrix kernels, csrc/mwrt_aux.hip for the rest; csrc/mwrt.hip is host code only)
@@ -53,6 +57,7 @@ def classify(op: str):
 def main():
     path, key = sys.argv[1], sys.argv[2]
     by_line = "--lines" in sys.argv
+    by_loop = "--loops" in sys.argv
     lines = open(path).read().split("\n")
     start = next(i for i, l in enumerate(lines) if l.startswith("_ZN") and key in l and l.rstrip().split(":")[0].endswith("E"))
     blocks, order = collections.defaultdict(collections.Counter), []
@@ -60,6 +65,7 @@ def main():
     blk_src = collections.defaultdict(collections.Counter)
     cur, loc = "entry", 0
     order.append(cur)
+    loop_of, depth_of, parent_of = {}, {}, {}          # block -> innermost loop header; header -> depth, parent header
     for l in lines[start + 1:]:
         s = l.strip()
         if s.startswith(".Lfunc_end"):
@@ -68,6 +74,23 @@ def main():
         if m:
             cur = m.group(1)
             order.append(cur)
+            h = re.search(r"in Loop: Header=(BB\d+_\d+) Depth=(\d+)", s)
+            if h:
+                loop_of[cur] = ".L" + h.group(1)
+            for par in re.finditer(r"Parent Loop (BB\d+_\d+) Depth=(\d+)", s):
+                parent_of[cur] = ".L" + par.group(1)
+            h = re.search(r"Loop Header: Depth=(\d+)", s)
+            if h:
+                loop_of[cur], depth_of[cur] = cur, int(h.group(1))
+            continue
+        h = re.search(r"Loop Header: Depth=(\d+)", s)
+        if h and s.startswith(";"):
+            loop_of[cur] = cur
+            depth_of[cur] = int(h.group(1))
+            continue
+        par = re.search(r"^;\s+Parent Loop (BB\d+_\d+) Depth=(\d+)", s)
+        if par:
+            parent_of[cur] = ".L" + par.group(1)                # the last one listed is the innermost parent
             continue
         m = re.match(r"^\.loc\s+\d+\s+(\d+)", s)
         if m:
@@ -84,7 +107,20 @@ def main():
         if op.startswith(("s_cbranch", "s_branch")):
             blocks[cur]["->" + s.split()[-1]] += 1
     hdr = f"{'block':>12} " + " ".join(f"{c:>6}" for c in CATS) + "  top source lines (VALU) / branches"
-    if by_line:
+    if by_loop:
+        cols = ("valu", "arith", "mov", "cnd", "cmp", "lane", "salu", "smem", "lds", "vmem")
+        loops, lsrc = collections.defaultdict(collections.Counter), collections.defaultdict(collections.Counter)
+        for b in order:
+            key = loop_of.get(b, "straight")
+            loops[key].update({c: blocks[b][c] for c in CATS})
+            lsrc[key].update(blk_src[b])
+        print(f"{'loop':>12} {'depth':>5} {'parent':>12} " + " ".join(f"{c:>6}" for c in cols) + "  top source lines (VALU)")
+        for key in ["straight"] + [b for b in order if b in loops]:
+            cnt = loops[key]
+            cnt["arith"] = cnt["fma64"] + cnt["mul64"] + cnt["add64"] + cnt["rcp64"]
+            top = ", ".join(f"{ln}:{n}" for ln, n in lsrc[key].most_common(4))
+            print(f"{key:>12} {depth_of.get(key, 0):>5} {parent_of.get(key, '-'):>12} " + " ".join(f"{cnt[c]:>6}" for c in cols) + f"  {top}")
+    elif by_line:
         print(f"{'line':>6} " + " ".join(f"{c:>6}" for c in CATS))
         for ln in sorted(srcs):
             if srcs[ln]["valu"]:
