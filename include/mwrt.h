@@ -721,6 +721,53 @@ int mwrt_obs_apply_device(mwrt_context* ctx, const mwrt_obs* op, int64_t nprof, 
 /* sizeof(mwrt_obs_apply) as compiled into the library (binding self-check). */
 uint32_t mwrt_obs_apply_size(void);
 
+/* The reduced-basis state: x = x_ref + B c with a basis B [n][r] shared by the batch, n = nblk * nlev (state
+ * index = block * nlev + level) and r columns (leading EOFs of the prior, coarse layers, one scale factor on a profile
+ * shape, ...).  The 1D-Var update in the coefficients c needs K B instead of K, and the optimal-estimation entries take it
+ * as they are: d_k[0] = K_c with nblk = 1, nlev = r, the state c, its prior c_a and its covariance [r][r].
+ *   mwrt_basis_create checks the HOST array b [nblk * nlev][r] (row-major, column index fastest) and uploads it once.  It
+ *   refuses with MWRT_ERR_INVALID_ARGUMENT: a NULL argument, nblk outside 1 .. 4, nlev < 1, r < 1, an entry of b that is
+ *   not finite; with MWRT_ERR_UNSUPPORTED: nlev or r > MWRT_MAX_LEVELS.
+ *   mwrt_basis_destroy(NULL) is MWRT_OK.  A live basis drains the device first (a queued launch may still read it).
+ *   mwrt_basis_destroy and mwrt_destroy of the basis' context may come in either order: mwrt_destroy frees the device copy
+ *   of every basis still alive on the context and leaves the handles valid for mwrt_basis_destroy alone (project and expand
+ *   then refuse them).
+ * mwrt_basis_project_device, all DEVICE pointers, float64, on `stream` as every *_device entry:
+ *   d_k_in[b] [nprof][m][nlev], b < nblk of the basis  ->  d_k_out [nprof][m][r],
+ *       K_c[p][i][j] = sum over b, l of K_b[p][i][l] * B[b * nlev + l][j]
+ *   (a Jacobian output [nprof][nang][nf][nlev] as that entry wrote it, or mwrt_obs_apply_device's).  Every element is one
+ *   FMA chain from 0.0 over b = 0 .. nblk - 1 (outer) and l = 0 .. nlev - 1 (ascending): the same bit for bit whatever
+ *   nprof, the rows beside it, the other columns of the basis, or the call.  A NaN or Inf in K makes its own output row
+ *   [p][i][:] non-finite and reaches no other row (the step's row rule then drops that observation); a row of zeros gives
+ *   exactly 0.0.
+ * mwrt_basis_expand_device:  d_c [nprof][r], d_x_ref [n] (or [nprof][n] with x_ref_per_profile != 0)  ->  d_x [nprof][n],
+ *       x[p][k] = x_ref[k] + sum over j of B[k][j] * c[p][j]
+ *   FMA-accumulated onto x_ref[k] for j = 0 .. r - 1 ascending.  A non-finite c[p] makes x[p][:] non-finite and no other.
+ * Both refuse with MWRT_ERR_INVALID_ARGUMENT, nothing written: a NULL context, basis or record; a basis of another context,
+ *   or one whose context was destroyed; struct_size smaller than the fixed part (8 bytes); reserved or reserved2 != 0;
+ *   nprof < 0; project: m < 1, a NULL among the first nblk of d_k_in, a NULL d_k_out, d_k_out equal to one of its inputs;
+ *   expand: a NULL d_c, d_x_ref or d_x, d_x equal to d_c or d_x_ref.  MWRT_ERR_UNSUPPORTED: more than 2^31 - 1 workgroups
+ *   in one launch.  nprof = 0 is MWRT_OK.
+ *   The record starts with its own size: fields at or beyond struct_size (and a field it ends inside) are taken as NULL / 0.
+ *   The calls never allocate and never synchronise; they are hipGraph-capturable from the first call.
+ *   (MWRT_VERSION stays 301: additions.) */
+typedef struct mwrt_basis mwrt_basis;       /* device-resident copy of B, owned by one context */
+typedef struct mwrt_basis_apply {
+  uint32_t struct_size;        /* sizeof(mwrt_basis_apply) of the caller; fields beyond it are not read */
+  int32_t  reserved;
+  const double* d_k_in[4];  double* d_k_out;                        /* project */
+  const double *d_c, *d_x_ref;  double* d_x;                        /* expand  */
+  int32_t  x_ref_per_profile, reserved2;
+} mwrt_basis_apply;
+int mwrt_basis_create(mwrt_context* ctx, int32_t nblk, int32_t nlev, int32_t r, const double* b, mwrt_basis** out);
+int mwrt_basis_destroy(mwrt_basis* basis);
+int mwrt_basis_project_device(mwrt_context* ctx, const mwrt_basis* basis, int64_t nprof, int32_t m,
+                              const mwrt_basis_apply* rec, void* stream);
+int mwrt_basis_expand_device(mwrt_context* ctx, const mwrt_basis* basis, int64_t nprof, const mwrt_basis_apply* rec,
+                             void* stream);
+/* sizeof(mwrt_basis_apply) as compiled into the library (binding self-check). */
+uint32_t mwrt_basis_apply_size(void);
+
 /* The spectroscopic-parameter Jacobian: d TB / d b for entries b of the model's tables -- what the
  * forward-model part K_b S_b K_b^T of an observation-error covariance is built from (Rodgers 2000, section 3.2.2).  The
  * operator is mwrt_tb_jacobian_batch_device's: clear sky, plane-parallel, every line at every frequency; there is no

@@ -95,6 +95,14 @@ class MwrtObsApply(ctypes.Structure):
                 ("d_k_out", ctypes.c_void_p * 4)]
 
 
+class MwrtBasisApply(ctypes.Structure):
+    """include/mwrt.h mwrt_basis_apply: the record of one projection onto, or expansion from, a reduced basis (device
+    pointers)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_int32), ("d_k_in", ctypes.c_void_p * 4),
+                ("d_k_out", ctypes.c_void_p), ("d_c", ctypes.c_void_p), ("d_x_ref", ctypes.c_void_p),
+                ("d_x", ctypes.c_void_p), ("x_ref_per_profile", ctypes.c_int32), ("reserved2", ctypes.c_int32)]
+
+
 #: include/mwrt.h MWRT_OE_PRODUCT_*: what mwrt_oe_product_device forms
 OE_PRODUCT_AVK, OE_PRODUCT_POST_COV = 0, 1
 
@@ -201,6 +209,11 @@ SIGNATURES = {
     "mwrt_obs_destroy": (ctypes.c_int, [_vp]),
     "mwrt_obs_apply_device": (ctypes.c_int, [_vp, _vp, _i64, _i32, ctypes.POINTER(MwrtObsApply), _vp]),
     "mwrt_obs_apply_size": (ctypes.c_uint32, []),
+    "mwrt_basis_create": (ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, ctypes.POINTER(_vp)]),
+    "mwrt_basis_destroy": (ctypes.c_int, [_vp]),
+    "mwrt_basis_project_device": (ctypes.c_int, [_vp, _vp, _i64, _i32, ctypes.POINTER(MwrtBasisApply), _vp]),
+    "mwrt_basis_expand_device": (ctypes.c_int, [_vp, _vp, _i64, ctypes.POINTER(MwrtBasisApply), _vp]),
+    "mwrt_basis_apply_size": (ctypes.c_uint32, []),
     "mwrt_set_absorption_mode": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_set_chunk_width": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_selftest_math": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -266,6 +279,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
             raise NativeLibraryMissing("mwrt_oe_char layout mismatch between libmwrt.so and _native.py")
         if lib.mwrt_obs_apply_size() != ctypes.sizeof(MwrtObsApply):
             raise NativeLibraryMissing("mwrt_obs_apply layout mismatch between libmwrt.so and _native.py")
+        if lib.mwrt_basis_apply_size() != ctypes.sizeof(MwrtBasisApply):
+            raise NativeLibraryMissing("mwrt_basis_apply layout mismatch between libmwrt.so and _native.py")
         if lib.mwrt_version() != MWRT_VERSION:
             raise NativeLibraryMissing(f"libmwrt.so is version {lib.mwrt_version()}, this binding needs {MWRT_VERSION}: "
                                        "rebuild (python -c 'import __graft_entry__ as g; g.build()')")
@@ -785,6 +800,51 @@ class Context:
             rec.d_k_out[b] = opt(k)
         self._check(self._lib.mwrt_obs_apply_device(self._handle, handle, int(nprof), int(nlev), ctypes.byref(rec),
                                                     _stream(stream)), "mwrt_obs_apply_device")
+
+    @_serialised
+    def basis_create(self, nblk, nlev, b) -> ctypes.c_void_p:
+        """A reduced basis on this context (include/mwrt.h mwrt_basis_create) from the host array ``b [nblk * nlev][r]``:
+        checked and uploaded once.  Returns the handle ``basis_project_device`` and ``basis_expand_device`` take; release it
+        with ``basis_destroy`` (before or after the context is closed)."""
+        b = _f64(b)
+        if b.ndim != 2 or b.shape[0] != int(nblk) * int(nlev):
+            raise ValueError(f"basis_create: expected b [{int(nblk) * int(nlev)}][r], got {b.shape}")
+        h = ctypes.c_void_p()
+        self._check(self._lib.mwrt_basis_create(self._handle, int(nblk), int(nlev), b.shape[1], _ptr(b), ctypes.byref(h)),
+                    "mwrt_basis_create")
+        return h
+
+    def basis_destroy(self, handle):
+        """Releases a basis of ``basis_create`` (include/mwrt.h mwrt_basis_destroy); safe after ``close`` as well."""
+        with self._lock:
+            self._check(self._lib.mwrt_basis_destroy(handle), "mwrt_basis_destroy")
+
+    @_serialised
+    def basis_project_device(self, handle, nprof, m, d_k_in, d_k_out, stream=None, reserved=0, struct_size=None, reserved2=0):
+        """K B (include/mwrt.h mwrt_basis_project_device): the blocks ``d_k_in[b] [nprof][m][nlev]`` of the basis' nblk ->
+        ``d_k_out [nprof][m][r]``.  ``struct_size`` (default: the whole record) is what the record claims."""
+        rec = MwrtBasisApply()
+        rec.struct_size = ctypes.sizeof(MwrtBasisApply) if struct_size is None else int(struct_size)
+        rec.reserved, rec.reserved2 = int(reserved), int(reserved2)
+        for b, k in enumerate(list(d_k_in)[:4]):
+            rec.d_k_in[b] = int(k) if k is not None else None
+        rec.d_k_out = int(d_k_out) if d_k_out is not None else None
+        self._check(self._lib.mwrt_basis_project_device(self._handle, handle, int(nprof), int(m), ctypes.byref(rec),
+                                                        _stream(stream)), "mwrt_basis_project_device")
+
+    @_serialised
+    def basis_expand_device(self, handle, nprof, d_c, d_x_ref, d_x, x_ref_per_profile=False, stream=None, reserved=0,
+                            struct_size=None, reserved2=0):
+        """x_ref + B c (include/mwrt.h mwrt_basis_expand_device): ``d_c [nprof][r]`` and ``d_x_ref [n]`` (``[nprof][n]``
+        with ``x_ref_per_profile``) -> ``d_x [nprof][n]``."""
+        rec = MwrtBasisApply()
+        rec.struct_size = ctypes.sizeof(MwrtBasisApply) if struct_size is None else int(struct_size)
+        rec.reserved, rec.reserved2 = int(reserved), int(reserved2)
+        opt = lambda v: int(v) if v is not None else None   # noqa: E731
+        rec.d_c, rec.d_x_ref, rec.d_x = opt(d_c), opt(d_x_ref), opt(d_x)
+        rec.x_ref_per_profile = int(bool(x_ref_per_profile))
+        self._check(self._lib.mwrt_basis_expand_device(self._handle, handle, int(nprof), ctypes.byref(rec),
+                                                       _stream(stream)), "mwrt_basis_expand_device")
 
     def layer_tau_pitch(self, nf: int) -> int:
         """Doubles between consecutive levels of a layer-optical-depth array for nf frequencies (multiple of 16)."""

@@ -4,7 +4,7 @@
 // returns 0 and mwrt_create() fails with MWRT_ERR_NO_DEVICE.
 //
 // Host code only: streams, caches, argument checks and the choice of launch.  Every kernel lives in another unit
-// (mwrt_inst.hip, mwrt_tl.hip, mwrt_ray.hip, mwrt_par.hip, mwrt_oe.hip, mwrt_oe_lm.hip, mwrt_oe_char.hip, mwrt_obs.hip, mwrt_aux.hip) and is reached
+// (mwrt_inst.hip, mwrt_tl.hip, mwrt_ray.hip, mwrt_par.hip, mwrt_oe.hip, mwrt_oe_lm.hip, mwrt_oe_char.hip, mwrt_obs.hip, mwrt_basis.hip, mwrt_aux.hip) and is reached
 // through the launchers the headers below declare.
 #include "mwrt_args.hip.h"
 #include "mwrt_tl.hip.h"
@@ -14,6 +14,7 @@
 #include "mwrt_oe_lm.hip.h"
 #include "mwrt_oe_char.hip.h"
 #include "mwrt_obs.hip.h"
+#include "mwrt_basis.hip.h"
 #include "mwrt_plan.h"
 
 #include <cmath>
@@ -162,6 +163,8 @@ struct mwrt_context {
   long ev_count = 0;
   // instrument operators created on this context and not yet destroyed: mwrt_destroy frees their device copies
   std::vector<mwrt_obs*> obs_live;
+  // reduced bases created on this context and not yet destroyed: the same rule
+  std::vector<mwrt_basis*> basis_live;
 };
 constexpr int TIMING_RING = 512;
 
@@ -172,6 +175,12 @@ struct mwrt_obs {
   const double* d_w = nullptr;
   const int32_t* d_row_ptr = nullptr;
   const int32_t* d_col = nullptr;
+};
+
+struct mwrt_basis {
+  mwrt_context* ctx = nullptr;  // null once the context is gone: the handle then only waits for mwrt_basis_destroy
+  int32_t nblk = 0, nlev = 0, r = 0;
+  double* d_b = nullptr;        // [nblk * nlev][r]
 };
 
 struct mwrt_model {
@@ -808,6 +817,10 @@ int mwrt_destroy(mwrt_context* c) {
   for (mwrt_obs* op : c->obs_live) {                    // the handles stay valid for mwrt_obs_destroy; apply refuses them
     (void)hipFree(op->d_blob);
     op->d_blob = nullptr; op->d_w = nullptr; op->d_row_ptr = nullptr; op->d_col = nullptr; op->ctx = nullptr;
+  }
+  for (mwrt_basis* bs : c->basis_live) {                // likewise: valid for mwrt_basis_destroy, refused by project / expand
+    (void)hipFree(bs->d_b);
+    bs->d_b = nullptr; bs->ctx = nullptr;
   }
   for (hipEvent_t e : c->ev0) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev1) (void)hipEventDestroy(e);
@@ -1555,6 +1568,117 @@ int mwrt_obs_apply_device(mwrt_context* c, const mwrt_obs* op, int64_t nprof, in
   }
   if (r.d_tb_in) return timed(c, st, [&] { return obs::launch_obs_apply(t, st); });
   return MWRT_OK;
+}
+
+/* The reduced-basis state (csrc/mwrt_basis.hip): a handle that owns the device copy of B, and its two launches.  Lifecycle
+ * and preamble as for the instrument operator above. */
+uint32_t mwrt_basis_apply_size(void) { return (uint32_t)sizeof(mwrt_basis_apply); }
+
+int mwrt_basis_create(mwrt_context* c, int32_t nblk, int32_t nlev, int32_t r, const double* b, mwrt_basis** out) {
+  if (out) *out = nullptr;
+  if (!c || !b || !out) return fail(MWRT_ERR_INVALID_ARGUMENT, "null argument");
+  if (nblk < 1 || nblk > 4) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_create: nblk must be 1 .. 4");
+  if (nlev < 1 || r < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_create: nlev < 1 or r < 1");
+  if (nlev > MWRT_MAX_LEVELS || r > MWRT_MAX_LEVELS)
+    return fail(MWRT_ERR_UNSUPPORTED, "mwrt_basis_create: nlev or r > MWRT_MAX_LEVELS (" + std::to_string(MWRT_MAX_LEVELS) + ")");
+  const size_t count = (size_t)nblk * (size_t)nlev * (size_t)r;
+  for (size_t e = 0; e < count; ++e)
+    if (!std::isfinite(b[e]))
+      return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_create: b[" + std::to_string(e / (size_t)r) + "][" +
+                                                 std::to_string(e % (size_t)r) + "] is not finite");
+  HIP_TRY(hipSetDevice(c->device));
+  mwrt_basis* bs = new (std::nothrow) mwrt_basis();
+  if (!bs) return fail(MWRT_ERR_OUT_OF_MEMORY, "host allocation failed");
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&bs->d_b), sizeof(double) * count);
+  if (e == hipSuccess) e = hipMemcpy(bs->d_b, b, sizeof(double) * count, hipMemcpyHostToDevice);   // synchronous: in HBM on return
+  if (e != hipSuccess) {
+    if (bs->d_b) (void)hipFree(bs->d_b);
+    delete bs;
+    return fail(e == hipErrorOutOfMemory ? MWRT_ERR_OUT_OF_MEMORY : MWRT_ERR_HIP, hipGetErrorString(e));
+  }
+  bs->ctx = c; bs->nblk = nblk; bs->nlev = nlev; bs->r = r;
+  c->basis_live.push_back(bs);
+  *out = bs;
+  return MWRT_OK;
+}
+
+int mwrt_basis_destroy(mwrt_basis* bs) {
+  if (!bs) return MWRT_OK;
+  if (mwrt_context* c = bs->ctx) {
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();                       // launches on any stream may still read the basis
+    (void)hipFree(bs->d_b);
+    for (size_t i = c->basis_live.size(); i-- > 0;)
+      if (c->basis_live[i] == bs) c->basis_live.erase(c->basis_live.begin() + (long)i);
+  }
+  delete bs;
+  return MWRT_OK;
+}
+
+namespace {
+
+// What project and expand share: the handle checks and the record cut at the caller's struct_size.
+int basis_record(const mwrt_context* c, const mwrt_basis* bs, int64_t nprof, const mwrt_basis_apply* s, mwrt_basis_apply* r) {
+  if (!c || !bs || !s) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context, mwrt_basis or mwrt_basis_apply");
+  if (bs->ctx != c) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis belongs to another context, or its context was destroyed");
+  constexpr size_t fixed = offsetof(mwrt_basis_apply, reserved) + sizeof(int32_t), ptrs = offsetof(mwrt_basis_apply, d_k_in);
+  constexpr size_t tail = offsetof(mwrt_basis_apply, x_ref_per_profile);
+  static_assert(fixed == ptrs, "mwrt_basis_apply: the pointers follow the fixed part");
+  if (s->struct_size < fixed)
+    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_apply.struct_size too small for the fixed part (through reserved)");
+  // fields at or beyond the caller's struct_size stay NULL / 0, and so does a field the size ends inside: pointers up to
+  // x_ref_per_profile, two int32 behind them
+  size_t len = s->struct_size < sizeof *r ? s->struct_size : sizeof *r;
+  len = len <= tail ? len - (len - ptrs) % sizeof(void*) : len - (len - tail) % sizeof(int32_t);
+  std::memcpy(r, s, len);
+  if (nprof < 0) return fail(MWRT_ERR_INVALID_ARGUMENT, "nprof < 0");
+  if (r->reserved != 0 || r->reserved2 != 0) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_apply.reserved and reserved2 must be 0");
+  return MWRT_OK;
+}
+
+}  // namespace
+
+int mwrt_basis_project_device(mwrt_context* c, const mwrt_basis* bs, int64_t nprof, int32_t m, const mwrt_basis_apply* s,
+                              void* stream) {
+  mwrt_basis_apply r{};
+  if (const int rc = basis_record(c, bs, nprof, s, &r)) return rc;
+  if (m < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "m < 1");
+  for (int b = 0; b < bs->nblk; ++b)
+    if (!r.d_k_in[b]) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_apply: null pointer among the first nblk of d_k_in");
+  if (!r.d_k_out) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_apply: d_k_out is null");
+  for (int b = 0; b < bs->nblk; ++b)
+    if (r.d_k_in[b] == r.d_k_out)
+      return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_apply: d_k_out equals one of its inputs (the product is not formed in place)");
+  // one workgroup per (ROWS rows, COLS columns): nprof * m rows may fill as many row tiles as the column tiles leave
+  const int64_t col_tiles = (bs->r + basis::COLS - 1) / basis::COLS;
+  if (nprof > 2147483647LL / col_tiles * basis::ROWS / m)
+    return fail(MWRT_ERR_UNSUPPORTED, "mwrt_basis_project_device: more than 2147483647 workgroups in one launch (split the batch)");
+  if (nprof == 0) return MWRT_OK;
+  basis::ProjectArgs a{};
+  a.in0 = r.d_k_in[0]; a.in1 = r.d_k_in[1]; a.in2 = r.d_k_in[2]; a.in3 = r.d_k_in[3];
+  a.b = bs->d_b; a.out = r.d_k_out;
+  a.nrows = nprof * m; a.nlev = bs->nlev; a.nblk = bs->nblk; a.n = bs->nblk * bs->nlev; a.r = bs->r;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = resolve_stream(c, stream);
+  return timed(c, st, [&] { return basis::launch_project(a, st); });
+}
+
+int mwrt_basis_expand_device(mwrt_context* c, const mwrt_basis* bs, int64_t nprof, const mwrt_basis_apply* s, void* stream) {
+  mwrt_basis_apply r{};
+  if (const int rc = basis_record(c, bs, nprof, s, &r)) return rc;
+  if (!r.d_c || !r.d_x_ref || !r.d_x) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_apply: d_c, d_x_ref or d_x is null");
+  if (r.d_x == r.d_c || r.d_x == r.d_x_ref)
+    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_apply: d_x equals one of its inputs (the map is not applied in place)");
+  const int64_t n = (int64_t)bs->nblk * bs->nlev;       // <= 4096
+  if (nprof > 2147483647LL * basis::THREADS / n)
+    return fail(MWRT_ERR_UNSUPPORTED, "mwrt_basis_expand_device: more than 2147483647 workgroups in one launch (split the batch)");
+  if (nprof == 0) return MWRT_OK;
+  basis::ExpandArgs a{};
+  a.b = bs->d_b; a.c = r.d_c; a.x_ref = r.d_x_ref; a.x = r.d_x;
+  a.total = nprof * n; a.n = (int32_t)n; a.r = bs->r; a.per_profile = r.x_ref_per_profile != 0;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = resolve_stream(c, stream);
+  return timed(c, st, [&] { return basis::launch_expand(a, st); });
 }
 
 int mwrt_selftest_math(mwrt_context* c, int32_t n, const double* x, const double* y_pos,

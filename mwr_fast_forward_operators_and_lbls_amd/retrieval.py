@@ -22,7 +22,15 @@ model is not; ``retrieve_lm`` damps it (Levenberg-Marquardt, Rodgers 2000 eq. 5.
 ``mwrt_oe_lm_prepare_device`` / ``mwrt_oe_lm_solve_device`` / ``mwrt_oe_cost_device``: one linearisation per accepted state,
 one m x m solve per trial.  ``characterise`` returns what the undamped step at a state says about itself (Rodgers 2000, ch. 3;
 DESIGN.md 4.6.2) on ``mwrt_oe_gain_device`` / ``mwrt_oe_product_device``.  The n-form and log-humidity states are not
-offered."""
+offered.
+
+With ``basis=StateBasis(b, sa_c)`` the retrieval runs in r coefficients of a basis shared by the batch, x = xa + B c
+(DESIGN.md 4.9): ``mwrt_basis_project_device`` contracts the K rows with B behind the K-matrix call and the update sees the
+single block K B ``[nprof][m][r]``, the state c, its prior ``c_a`` and its covariance ``sa_c``.
+
+    eof = StateBasis.from_covariance(sa, 32)     # the leading eigenvectors of Sa, sa_c = diag(lambda)
+    ov = OneDVar("R24", frq, elev, None, se, variables=..., blocks=("t", "h"), xa=xa, basis=eof)
+    res = ov.retrieve(z, p, y)                   # res.x the physical state, res.coeff [nprof][r]"""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -186,10 +194,110 @@ def _native_obs_apply(instrument, tb, k_blocks, stream):
     return tb_out, k_out
 
 
+def _native_basis_project(basis, k_blocks, stream):
+    """One ``mwrt_basis_project_device`` call -> K B ``[nprof][m][r]`` from the K blocks ``[nprof]...[nlev]`` in the state's
+    order (the K-matrix call's, or the instrument's channel rows).
+
+    The single place the projection reaches the native library: CPU tests substitute the NumPy reference here."""
+    k_blocks = [k.contiguous() for k in k_blocks]
+    nprof, nlev = k_blocks[0].shape[0], k_blocks[0].shape[-1]
+    for i, k in enumerate(k_blocks):
+        if k.dtype != torch.float64 or k.shape != k_blocks[0].shape:
+            raise ValueError(f"k_blocks[{i}]: expected float64 {tuple(k_blocks[0].shape)}, got {k.dtype} {tuple(k.shape)}")
+    if len(k_blocks) * nlev != basis.n:
+        raise ValueError(f"basis: expected b [{len(k_blocks) * nlev}][r] for {len(k_blocks)} blocks of {nlev} levels, got "
+                         f"{tuple(basis.b.shape)}")
+    m = k_blocks[0][0].numel() // nlev
+    out = torch.empty((nprof, m, basis.r), dtype=torch.float64, device=k_blocks[0].device)
+    ctx, handle = basis.native_handle(len(k_blocks), k_blocks[0].device.index or 0)
+    ctx.basis_project_device(handle, nprof, m, [k.data_ptr() for k in k_blocks], out.data_ptr(), stream=stream)
+    return out
+
+
+def _native_basis_expand(basis, c, x_ref, stream):
+    """One ``mwrt_basis_expand_device`` call -> x_ref + B c ``[nprof][nblk][nlev]`` from ``c [nprof][r]`` and ``x_ref
+    [nblk][nlev]`` (shared) or ``[nprof][nblk][nlev]``.
+
+    The single place the expansion reaches the native library: CPU tests substitute the NumPy reference here."""
+    nprof = c.shape[0]
+    nblk, nlev = x_ref.shape[-2:]
+    if c.dtype != torch.float64 or tuple(c.shape) != (nprof, basis.r) or x_ref.dtype != torch.float64 or \
+            nblk * nlev != basis.n or x_ref.dim() not in (2, 3) or (x_ref.dim() == 3 and x_ref.shape[0] != nprof):
+        raise ValueError(f"expected float64 c [{nprof}][{basis.r}] and x_ref [nblk][nlev] or [{nprof}][nblk][nlev] with nblk nlev = "
+                         f"{basis.n}, got {c.dtype} {tuple(c.shape)} and {x_ref.dtype} {tuple(x_ref.shape)}")
+    c, x_ref = c.contiguous(), x_ref.contiguous()
+    out = torch.empty((nprof, nblk, nlev), dtype=torch.float64, device=c.device)
+    ctx, handle = basis.native_handle(nblk, c.device.index or 0)
+    ctx.basis_expand_device(handle, nprof, c.data_ptr(), x_ref.data_ptr(), out.data_ptr(), x_ref_per_profile=x_ref.dim() == 3,
+                            stream=stream)
+    return out
+
+
+class StateBasis:
+    """A reduced basis for the state of ``OneDVar``: x = xa + B c with ``b [n][r]`` (n = nblk * nlev, state index = block *
+    nlev + level; float64), the prior covariance of the coefficients ``sa_c [r][r]`` and their prior mean ``c_a`` (``[r]``
+    shared or ``[nprof][r]``; default 0, so that the prior state is ``OneDVar``'s ``xa``).  The columns may be anything
+    fixed for the batch: leading EOFs of a prior ensemble (``from_covariance``), coarse layers, or a single column that
+    scales a liquid-water profile shape.  The device copy of B is made once per device and context, on first use."""
+
+    def __init__(self, b, sa_c, c_a=None):
+        b, sa_c = torch.as_tensor(b), torch.as_tensor(sa_c)
+        if b.dim() != 2 or b.dtype != torch.float64:
+            raise ValueError(f"b: expected float64 [n][r], got {b.dtype} {tuple(b.shape)}")
+        self.n, self.r = int(b.shape[0]), int(b.shape[1])
+        if tuple(sa_c.shape) != (self.r, self.r):
+            raise ValueError(f"sa_c: expected [{self.r}][{self.r}], got {tuple(sa_c.shape)}")
+        c_a = torch.zeros(self.r, dtype=torch.float64, device=b.device) if c_a is None else torch.as_tensor(c_a)
+        if c_a.dim() not in (1, 2) or c_a.shape[-1] != self.r:
+            raise ValueError(f"c_a: expected [{self.r}] or [nprof][{self.r}], got {tuple(c_a.shape)}")
+        self.b, self.sa_c, self.c_a = b.contiguous(), sa_c.to(torch.float64).contiguous(), c_a.to(torch.float64).contiguous()
+        self._handles = {}
+
+    @classmethod
+    def from_covariance(cls, sa, r, c_a=None):
+        """The leading ``r`` eigenvectors of ``sa [n][n]`` as columns (largest eigenvalue first), ``sa_c = diag(lambda)``.
+        The sign of each column is fixed so that its largest-magnitude component is positive; B^T B = I."""
+        sa = torch.as_tensor(sa)
+        n = sa.shape[0]
+        if sa.dim() != 2 or sa.shape[1] != n or not 1 <= int(r) <= n:
+            raise ValueError(f"expected sa [n][n] and 1 <= r <= n, got {tuple(sa.shape)} and r = {r}")
+        s64 = sa.detach().to("cpu", torch.float64)
+        lam, vec = torch.linalg.eigh(0.5 * (s64 + s64.T))
+        lam, vec = lam.flip(0)[:r], vec.flip(1)[:, :r]
+        top = vec.abs().argmax(dim=0)
+        vec = vec * torch.where(vec[top, torch.arange(int(r))] < 0, -1.0, 1.0).to(torch.float64)[None, :]
+        return cls(vec.contiguous().to(sa.device), torch.diag(lam).to(sa.device), c_a)
+
+    def native_handle(self, nblk, device_index=0):
+        """(context, basis handle) for ``nblk`` blocks on a device: created on first use, released with the object."""
+        key = (int(nblk), device_index)
+        hit = self._handles.get(key)
+        if hit is None or hit[0]._handle is None:             # first use, or the context was closed since
+            if hit is not None:
+                hit[0].basis_destroy(hit[1])
+            if self.n % int(nblk) != 0:
+                raise ValueError(f"basis: b [{self.n}][{self.r}] does not split into {nblk} blocks")
+            ctx = _native.default_context(device_index)
+            hit = self._handles[key] = (ctx, ctx.basis_create(nblk, self.n // int(nblk), self.b.detach().cpu().numpy()))
+        return hit
+
+    def close(self):
+        handles, self._handles = getattr(self, "_handles", {}), {}
+        for ctx, h in handles.values():
+            ctx.basis_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 @dataclass
 class Characterisation:
     """What ``OneDVar.characterise`` returns: the undamped step at a state, described (Rodgers 2000, ch. 3; include/mwrt.h
-    mwrt_oe_gain_device).  Every field is a tensor on the state's device; n = nblk * nlev, state index = block * nlev + level."""
+    mwrt_oe_gain_device).  Every field is a tensor on the state's device; n = nblk * nlev, state index = block * nlev + level.
+    With a basis the step is the one in the coefficients: n = r and nblk = 1 in every field, ``coeff`` is the state."""
     gain: torch.Tensor         # [nprof][m][n] row i: the contribution function d x^ / d y_i; 0 in a dropped row
     avk_diag: torch.Tensor     # [nprof][nblk][nlev] diagonal of the averaging kernel
     dfs_block: torch.Tensor    # [nprof][nblk] degrees of freedom for signal per state block; their sum is the step's dfs
@@ -200,6 +308,7 @@ class Characterisation:
     keep: torch.Tensor         # [nprof][m] uint8, 1: the observation was used
     avk: Optional[torch.Tensor] = None        # [nprof][rows][n] averaging kernel d x^ / d x (``avk=True``)
     post_cov: Optional[torch.Tensor] = None   # [nprof][rows][n] posterior covariance (``post_cov=True``)
+    coeff: Optional[torch.Tensor] = None      # [nprof][r] the coefficients the step was characterised at (with a basis)
 
 
 @dataclass
@@ -215,11 +324,12 @@ class Retrieval:
     converged: torch.Tensor    # [nprof] bool
     cost: Optional[torch.Tensor] = None    # [nprof] J at x (``retrieve_lm`` only)
     gamma: Optional[torch.Tensor] = None   # [nprof] the damping factor the profile ended with (``retrieve_lm`` only)
+    coeff: Optional[torch.Tensor] = None   # [nprof][r] the retrieved coefficients (with a basis; x = clamp(xa + B coeff))
 
 
 class OneDVar:
     def __init__(self, model, frq, elev, sa, se, variables: Optional[JacVariables] = None, blocks=("t", "h"), xa=None,
-                 instrument=None, ray_tracing=False):
+                 instrument=None, ray_tracing=False, basis: Optional[StateBasis] = None):
         blocks = tuple(blocks)
         # refracted spherical ray paths: the forward operator and its exact K rows come from mwrt_tb_jacobian_batch_ray_device
         self.ray_tracing = bool(ray_tracing)
@@ -231,7 +341,9 @@ class OneDVar:
         self.variables = variables if variables is not None else JacVariables.of()
         if xa is None:
             raise ValueError("xa (the prior state) is required")
-        self.sa, self.se, self.xa = sa.contiguous(), se.contiguous(), xa.contiguous()
+        if sa is None and basis is None:
+            raise ValueError("sa (the prior covariance) is required without a basis")
+        self.sa, self.se, self.xa = None if sa is None else sa.contiguous(), se.contiguous(), xa.contiguous()
         self.m = self.frq.size * self.elev.size
         # with an instrument (instrument.Instrument) the forward operator runs on its quadrature grid and every TB and K row is
         # reduced to channels before the update sees it: se, y and all diagnostics are in channel space, m = instrument.m_out
@@ -245,18 +357,34 @@ class OneDVar:
         if self.xa.dim() not in (2, 3) or self.xa.shape[-2] != nblk:
             raise ValueError(f"xa: expected [{nblk}][nlev] or [nprof][{nblk}][nlev], got {tuple(self.xa.shape)}")
         n = nblk * self.xa.shape[-1]
-        if tuple(self.sa.shape) != (n, n):
+        if self.sa is not None and tuple(self.sa.shape) != (n, n):
             raise ValueError(f"sa: expected [{n}][{n}], got {tuple(self.sa.shape)}")
         if tuple(self.se.shape) not in ((self.m,), (self.m, self.m)):
             raise ValueError(f"se: expected [{self.m}] or [{self.m}][{self.m}], got {tuple(self.se.shape)}")
-        self._sigma = torch.sqrt(torch.diagonal(self.sa)).reshape(nblk, -1)
+        # what the update works in: the state itself, or with a basis the coefficients c ([nprof][1][r] inside this class)
+        # with the prior c_a and sa_c.  The coefficients are never clamped: humidity and cloud >= 0 is applied to the
+        # physical state clamp(xa + B c) the forward model sees, not to c.
+        self.basis = basis
+        if basis is None:
+            self._prior_mean, self._prior_cov = self.xa, self.sa
+            self._sigma = torch.sqrt(torch.diagonal(self.sa)).reshape(nblk, -1)
+        else:
+            if basis.n != n:
+                raise ValueError(f"basis: expected b [{n}][r] for xa {tuple(self.xa.shape)}, got {tuple(basis.b.shape)}")
+            if basis.c_a.dim() == 2 and self.xa.dim() == 3 and basis.c_a.shape[0] != self.xa.shape[0]:
+                raise ValueError(f"basis.c_a: expected [{basis.r}] or [{self.xa.shape[0]}][{basis.r}], got {tuple(basis.c_a.shape)}")
+            dev = self.xa.device
+            self._b = basis.b.to(dev)
+            self._prior_mean = basis.c_a.to(dev).reshape((-1, 1, basis.r) if basis.c_a.dim() == 2 else (1, basis.r)).contiguous()
+            self._prior_cov = basis.sa_c.to(dev).contiguous()
+            self._sigma = torch.sqrt(torch.diagonal(self._prior_cov)).reshape(1, -1)
         self._sa_inv = None
 
     @property
     def sa_inv(self):
         """Sa^-1 for the cost's prior term: float64, symmetrised, formed on first use (``retrieve_lm`` alone needs it)."""
         if self._sa_inv is None:
-            inv = torch.linalg.inv(self.sa.to(torch.float64))
+            inv = torch.linalg.inv(self._prior_cov.to(torch.float64))
             self._sa_inv = (0.5 * (inv + inv.T)).contiguous()
         return self._sa_inv
 
@@ -288,12 +416,48 @@ class OneDVar:
                 x[:, i].clamp_(min=0.0)
         return x
 
+    # -- the reduced basis -------------------------------------------------------------------------------------------
+    def expand(self, c):
+        """xa + B c ``[nprof][nblk][nlev]`` for the coefficients ``c [nprof][r]`` (``mwrt_basis_expand_device``), unclamped."""
+        return _native_basis_expand(self.basis, c.reshape(c.shape[0], self.basis.r), self.xa, self._stream(c))
+
+    def _state(self, u):
+        """The physical state the forward model sees for the update's state ``u``: u itself, or clamp(xa + B c)."""
+        if self.basis is None:
+            return u
+        if self._prior_mean.dim() == 3 and self._prior_mean.shape[0] != u.shape[0]:
+            raise ValueError(f"basis.c_a: expected [{self.basis.r}] or [{u.shape[0]}][{self.basis.r}] for this batch, got "
+                             f"{tuple(self.basis.c_a.shape)}")
+        return self.clamp(self.expand(u))
+
+    def _bound(self, u):
+        """The update's state after a move: clamped as ``clamp`` says, except coefficients, which have no bound."""
+        return self.clamp(u) if self.basis is None else u
+
+    def _start(self, x0, nprof):
+        """The first state of an iteration ([nprof][nblk][nlev], or [nprof][1][r] with a basis): ``x0`` or the prior."""
+        prior = self._prior_mean
+        if x0 is not None:
+            return x0.clone() if self.basis is None else x0.reshape(nprof, 1, self.basis.r).clone()
+        return (prior.expand(nprof, -1, -1) if prior.dim() == 2 else prior).clone()
+
+    def _post_var_levels(self, k_blocks, u, y, fx, stream):
+        """diag(B S^_c B^T) ``[nprof][nblk][nlev]``: the posterior variance of the physical state from the posterior covariance
+        of the coefficients (``mwrt_oe_gain_device`` + ``mwrt_oe_product_device``, [r][r] per profile) and one contraction."""
+        g = _native_oe_gain(k_blocks, u, self._prior_mean, self._prior_cov, self.se, y, fx, stream)
+        s_c = _native_oe_product("post_cov", g["gain"], g["keep"], k_blocks, g["ksa"], self._prior_cov, (0, 0), stream)
+        s_c = s_c.masked_fill(((g["status"] == 0) | (g["status"] == 2))[:, None, None], float("nan"))
+        var = torch.einsum("kj,pji,ki->pk", self._b, s_c, self._b)
+        return var.reshape((u.shape[0],) + tuple(self.xa.shape[-2:]))
+
     # -- one Gauss-Newton step ---------------------------------------------------------------------------------------
     def _observe(self, z, p, x, want_rows=True):
         """One K-matrix call at ``x`` -> (tb [nprof][nang][nf], valid, K blocks in the state's order or None), in what the
         update sees: the operator's own outputs, or with an instrument the channel quantities -- the call then runs on the
-        instrument's quadrature grid and ``_native_obs_apply`` reduces the TBs and, when wanted, every block's rows.  The one
-        place of this class that runs the forward operator."""
+        instrument's quadrature grid and ``_native_obs_apply`` reduces the TBs and, when wanted, every block's rows.  With a
+        basis the rows are then contracted with it (``_native_basis_project``, behind the channel reduction, which shrinks
+        the rows first): the one block K B.  ``x`` is the physical state.  The one place of this class that runs the forward
+        operator."""
         zz, t, rh, dl, di = self.physical(z, p, x)
         inst = self.instrument
         frq, elev = (self.frq, self.elev) if inst is None else (inst.frq_q, inst.elev_q)
@@ -307,11 +471,14 @@ class OneDVar:
         k_blocks = [rows[b] for b in self.blocks] if want_rows else None
         if inst is not None:
             tb, k_blocks = _native_obs_apply(inst, tb, k_blocks, stream)
+        if self.basis is not None and k_blocks is not None:
+            k_blocks = [_native_basis_project(self.basis, k_blocks, stream)]
         return tb, valid, k_blocks
 
     def forward(self, z, p, x):
         """The forward model at the state ``x``: ``(tb [nprof][nang][nf], valid [nprof])`` on torch's current stream (the
-        K-matrix call's TBs; its rows are discarded).  With an instrument: the channel TBs."""
+        K-matrix call's TBs; its rows are discarded).  With an instrument: the channel TBs.  ``x`` is the physical state
+        also with a basis (``expand`` gives it for coefficients)."""
         tb, valid, _ = self._observe(z, p, x, want_rows=False)
         return tb, valid
 
@@ -324,9 +491,23 @@ class OneDVar:
         variables and the allocations of this method run on too (use ``torch.cuda.stream(...)`` around the call for another).
         Returns ``(x_new, diagnostics)``: diagnostics holds ``status``, ``chi2``, ``dfs``, ``nobs``, ``post_var`` (None with
         ``post_var=False``), ``fx`` (the forward model at x, [nprof][m]) and ``valid`` (the K-matrix call's flags).
-        ``x_new`` is the raw update: ``retrieve`` clamps it."""
+        ``x_new`` is the raw update: ``retrieve`` clamps it.
+
+        With a basis ``x`` holds the coefficients ``c [nprof][r]`` and so does ``x_new``: the K-matrix call runs at
+        clamp(xa + B c) -- c itself is never clamped -- and ``chi2``, ``dfs`` are those of the step in c.  ``post_var`` is
+        the level-space diag(B S^_c B^T) ``[nprof][nblk][nlev]``, which costs a gain and a product call more."""
         stream = self._stream(x)
         nprof = x.shape[0]
+        if self.basis is not None:
+            u = x.reshape(nprof, 1, self.basis.r).contiguous()
+            tb, valid, k_blocks = self._observe(z, p, self._state(u))
+            fx = tb.reshape(nprof, self.m)
+            yv = y.reshape(nprof, self.m).contiguous()
+            out = _native_oe_step(k_blocks, u, self._prior_mean, self._prior_cov, self.se, yv, fx, False, stream)
+            if post_var:
+                out["post_var"] = self._post_var_levels(k_blocks, u, yv, fx, stream)
+            out["fx"], out["valid"] = fx, valid
+            return out.pop("x_new").reshape(x.shape), out
         tb, valid, k_blocks = self._observe(z, p, x)
         fx = tb.reshape(nprof, self.m)
         out = _native_oe_step(k_blocks, x.contiguous(), self.xa, self.sa, self.se,
@@ -340,23 +521,29 @@ class OneDVar:
         profile is frozen -- its state and diagnostics no longer change -- once max |x_new - x| / sqrt(diag Sa) < ``tol``
         over its whole state, or when its step fails (status 0 or 2: the state before that step is kept).  Only the scalar
         "is any profile still moving" leaves the device, once per iteration.  Every step asks for ``post_var`` (a profile may
-        freeze at any step), which about doubles the update's device time."""
+        freeze at any step), which about doubles the update's device time.
+
+        With a basis the iteration runs in the coefficients (``x0``: ``[nprof][r]``, default ``c_a``), which are not clamped;
+        convergence is max |c_new - c| / sqrt(diag sa_c) < ``tol``.  The steps then skip ``post_var``: the level-space
+        diagonal is formed once, at the final states (one K-matrix call, a gain and a product call), so it is the posterior
+        variance at ``Retrieval.x``, not at the state before the last step as ``chi2`` and ``dfs`` are."""
         nprof = y.shape[0]
-        x = (self.xa.expand(nprof, -1, -1) if self.xa.dim() == 2 else self.xa).clone() if x0 is None else x0.clone()
+        x = self._start(x0, nprof)
         dev = x.device
+        keys = ("chi2", "dfs", "post_var", "status", "nobs") if self.basis is None else ("chi2", "dfs", "status", "nobs")
         active = torch.ones(nprof, dtype=torch.bool, device=dev)
         converged = torch.zeros(nprof, dtype=torch.bool, device=dev)
         iters = torch.zeros(nprof, dtype=torch.int32, device=dev)
         keep = None
         for _ in range(int(max_iter)):
-            x_new, d = self.step(z, p, x, y, post_var=True)
+            x_new, d = self.step(z, p, x, y, post_var=self.basis is None)
             ok = (d["status"] == 1) | (d["status"] == 3)
-            x_new = self.clamp(torch.where(ok[:, None, None], x_new, x))
+            x_new = self._bound(torch.where(ok[:, None, None], x_new, x))
             move = ((x_new - x).abs() / self._sigma).amax(dim=(1, 2))
             upd = active
             iters = iters + upd.to(torch.int32)
             x = torch.where(upd[:, None, None], x_new, x)
-            diag = {k: d[k] for k in ("chi2", "dfs", "post_var", "status", "nobs")}
+            diag = {k: d[k] for k in keys}
             if keep is None:
                 keep = diag
             else:
@@ -366,6 +553,11 @@ class OneDVar:
             active = active & ~done
             if not bool(active.any()):
                 break
+        if self.basis is not None:
+            k_blocks, fx = self._linearise(z, p, x)
+            post_var = self._post_var_levels(k_blocks, x.contiguous(), y.reshape(nprof, self.m).contiguous(), fx, self._stream(x))
+            return Retrieval(x=self._state(x), chi2=keep["chi2"], dfs=keep["dfs"], post_var=post_var, status=keep["status"],
+                             nobs=keep["nobs"], iterations=iters, converged=converged, coeff=x.reshape(nprof, -1))
         return Retrieval(x=x, chi2=keep["chi2"], dfs=keep["dfs"], post_var=keep["post_var"], status=keep["status"],
                          nobs=keep["nobs"], iterations=iters, converged=converged)
 
@@ -376,7 +568,12 @@ class OneDVar:
         ``x``, then ``mwrt_oe_gain_device``, then -- with ``avk`` / ``post_cov`` -- one ``mwrt_oe_product_device`` call each for
         the full averaging kernel and posterior covariance, all on torch's current stream with nothing leaving the device.
         ``rows=(begin, count)`` limits both products to those rows of the n x n result (a full one is nprof n^2 doubles).
-        Profiles whose status is 0 or 2 hold NaN in every floating-point field, the products included."""
+        Profiles whose status is 0 or 2 hold NaN in every floating-point field, the products included.
+
+        With a basis ``x`` holds the coefficients ``[nprof][r]`` (``Retrieval.coeff``) and everything returned is in
+        coefficient space: n = r, one block."""
+        if self.basis is not None:
+            x = x.reshape(x.shape[0], 1, self.basis.r)
         nprof, n = x.shape[0], x.shape[1] * x.shape[2]
         if rows is None:
             win = (0, 0)
@@ -386,21 +583,23 @@ class OneDVar:
                 raise ValueError(f"rows: expected (begin, count) with count >= 1 inside 0 .. {n - 1}, got {rows}")
         stream = self._stream(x)
         k_blocks, fx = self._linearise(z, p, x)
-        g = _native_oe_gain(k_blocks, x.contiguous(), self.xa, self.sa, self.se, y.reshape(nprof, self.m).contiguous(), fx,
-                            stream)
+        g = _native_oe_gain(k_blocks, x.contiguous(), self._prior_mean, self._prior_cov, self.se,
+                            y.reshape(nprof, self.m).contiguous(), fx, stream)
         failed = ((g["status"] == 0) | (g["status"] == 2))[:, None, None]
         prod = {}
         for name, want in (("avk", avk), ("post_cov", post_cov)):
             if want:
-                out = _native_oe_product(name, g["gain"], g["keep"], k_blocks, g["ksa"], self.sa, win, stream)
+                out = _native_oe_product(name, g["gain"], g["keep"], k_blocks, g["ksa"], self._prior_cov, win, stream)
                 prod[name] = out.masked_fill_(failed, float("nan"))
         return Characterisation(gain=g["gain"], avk_diag=g["avk_diag"], dfs_block=g["dfs_block"], noise_var=g["noise_var"],
-                                smooth_var=g["smooth_var"], status=g["status"], nobs=g["nobs"], keep=g["keep"], **prod)
+                                smooth_var=g["smooth_var"], status=g["status"], nobs=g["nobs"], keep=g["keep"], **prod,
+                                **({} if self.basis is None else {"coeff": x.reshape(nprof, n)}))
 
     # -- the damped iteration ------------------------------------------------------------------------------------------
     def _linearise(self, z, p, x):
-        """One K-matrix call at ``x`` -> (K blocks in the state's order, F(x) [nprof][m]); fresh tensors every call."""
-        tb, _, k_blocks = self._observe(z, p, x)
+        """One K-matrix call at ``x`` -> (K blocks in the state's order, F(x) [nprof][m]); fresh tensors every call.  With a
+        basis ``x`` holds the coefficients [nprof][1][r] and the one block is K B at clamp(xa + B c)."""
+        tb, _, k_blocks = self._observe(z, p, self._state(x))
         return k_blocks, tb.reshape(x.shape[0], self.m)
 
     def retrieve_lm(self, z, p, y, x0=None, max_iter=20, tol=0.05, gamma0=1.0, up=10.0, down=10.0, gamma_max=1e8) -> Retrieval:
@@ -416,9 +615,14 @@ class OneDVar:
         gamma exceeds ``gamma_max`` or its linearisation's status is not 1.  One scalar leaves the device per iteration (is
         any profile active; does any state want a new K).  Afterwards one undamped ``mwrt_oe_step_device`` call at the
         final states fills chi2, dfs, post_var, nobs and status -- Rodgers' diagnostics are those of gamma = 0 -- and its
-        x_new is discarded.  ``iterations`` counts the trials a profile took."""
+        x_new is discarded.  ``iterations`` counts the trials a profile took.
+
+        With a basis x is the coefficient vector c throughout (``x0``: ``[nprof][r]``, default ``c_a``), J's prior term is
+        (c - c_a)^T sa_c^-1 (c - c_a), trials are not clamped and the forward model runs at clamp(xa + B c); ``post_var`` is
+        the level-space diag(B S^_c B^T) at the final states."""
         nprof, m = y.shape[0], self.m
-        x = ((self.xa.expand(nprof, -1, -1) if self.xa.dim() == 2 else self.xa).clone() if x0 is None else x0.clone()).contiguous()
+        x = self._start(x0, nprof).contiguous()
+        xa, sa = self._prior_mean, self._prior_cov
         dev, stream = x.device, self._stream(x)
         yv = y.reshape(nprof, m).contiguous()
         f64, u8 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.uint8, device=dev)
@@ -438,16 +642,16 @@ class OneDVar:
             if relin:
                 k_blocks, fx = self._linearise(z, p, x)
                 mask = (active & stale).to(torch.uint8)
-                _native_oe_lm_prepare(k_blocks, x, self.xa, self.sa, self.se, yv, fx, lin, mask, stream)
-                _native_oe_cost(x, self.xa, self.se, yv, fx, lin["keep"], self.sa_inv, cost, mask, stream)
+                _native_oe_lm_prepare(k_blocks, x, xa, sa, self.se, yv, fx, lin, mask, stream)
+                _native_oe_cost(x, xa, self.se, yv, fx, lin["keep"], self.sa_inv, cost, mask, stream)
                 stale = torch.zeros_like(stale)
                 active = active & (lin["lin_status"] == 1)
             mask = active.to(torch.uint8)
-            _native_oe_lm_solve(k_blocks, x, self.xa, self.sa, self.se, gamma, lin, trial, mask, stream)
+            _native_oe_lm_solve(k_blocks, x, xa, sa, self.se, gamma, lin, trial, mask, stream)
             ok = active & (trial["status"] == 1)
-            x_try = self.clamp(torch.where(ok[:, None, None], trial["x_new"], x)).contiguous()
-            fx_try = self.forward(z, p, x_try)[0].reshape(nprof, m)
-            _native_oe_cost(x_try, self.xa, self.se, yv, fx_try, lin["keep"], self.sa_inv, cost_try, mask, stream)
+            x_try = self._bound(torch.where(ok[:, None, None], trial["x_new"], x)).contiguous()
+            fx_try = self.forward(z, p, self._state(x_try))[0].reshape(nprof, m)
+            _native_oe_cost(x_try, xa, self.se, yv, fx_try, lin["keep"], self.sa_inv, cost_try, mask, stream)
             accept = ok & (cost_try <= cost)
             move = ((x_try - x).abs() / self._sigma).amax(dim=(1, 2))
             iters = iters + active.to(torch.int32)
@@ -464,6 +668,10 @@ class OneDVar:
                 break
         if relin:
             k_blocks, fx = self._linearise(z, p, x)
-        d = _native_oe_step(k_blocks, x, self.xa, self.sa, self.se, yv, fx, True, stream)
+        d = _native_oe_step(k_blocks, x, xa, sa, self.se, yv, fx, self.basis is None, stream)
+        if self.basis is not None:
+            return Retrieval(x=self._state(x), chi2=d["chi2"], dfs=d["dfs"],
+                             post_var=self._post_var_levels(k_blocks, x, yv, fx, stream), status=d["status"], nobs=d["nobs"],
+                             iterations=iters, converged=converged, cost=cost, gamma=gamma, coeff=x.reshape(nprof, -1))
         return Retrieval(x=x, chi2=d["chi2"], dfs=d["dfs"], post_var=d["post_var"], status=d["status"], nobs=d["nobs"],
                          iterations=iters, converged=converged, cost=cost, gamma=gamma)

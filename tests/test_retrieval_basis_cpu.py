@@ -1,0 +1,258 @@
+"""retrieval.OneDVar with a reduced basis, without a GPU: the seams to the native library are replaced as in
+tests/test_retrieval_instrument_cpu.py, the gain and product entries by the NumPy reference of tests/oe_char_reference.py and
+the two basis seams by tests/basis_reference.py.  What is checked is the module's own work: without ``basis=`` nothing reaches
+the seams that did not before; with it the update sees the one block K B, the coefficients, ``c_a`` and ``sa_c``; the forward
+model asks for no projection; the instrument's reduction runs before the projection; a linear problem lands on the analytic
+posterior mean xa + B c^; and the level-space posterior variance is diag(B S^_c B^T)."""
+import numpy as np
+import pytest
+
+import basis_reference as bar
+import oe_char_reference as ocr
+
+torch = pytest.importorskip("torch")
+
+from mwr_fast_forward_operators_and_lbls_amd import retrieval  # noqa: E402
+from mwr_fast_forward_operators_and_lbls_amd.instrument import Instrument  # noqa: E402
+from mwr_fast_forward_operators_and_lbls_amd.retrieval import StateBasis  # noqa: E402
+from test_retrieval_instrument_cpu import ELEV, FRQ, M, NLEV, NPROF, Standins, make, setup  # noqa: E402
+
+N, R = 2 * NLEV, 4
+EXPAND, PROJECT = retrieval._native_basis_expand, retrieval._native_basis_project    # the real seams: their shape checks
+
+
+class BasisStandins(Standins):
+    def __init__(self, monkeypatch):
+        super().__init__(monkeypatch)
+        self.order, self.project_calls, self.expand_calls, self.gain_calls, self.product_calls = [], [], [], [], []
+        monkeypatch.setattr(retrieval, "_native_oe_gain", self.oe_gain)
+        monkeypatch.setattr(retrieval, "_native_oe_product", self.oe_product)
+        monkeypatch.setattr(retrieval, "_native_basis_project", self.basis_project)
+        monkeypatch.setattr(retrieval, "_native_basis_expand", self.basis_expand)
+
+    def obs_apply(self, inst, tb, k_blocks, stream):
+        self.order.append("reduce")
+        return super().obs_apply(inst, tb, k_blocks, stream)
+
+    def basis_project(self, basis, k_blocks, stream):
+        self.order.append("project")
+        self.project_calls.append(dict(basis=basis, k=list(k_blocks), stream=stream))
+        nprof, nlev = k_blocks[0].shape[0], k_blocks[0].shape[-1]
+        out, _ = bar.project_reference([k.numpy().reshape(nprof, -1, nlev) for k in k_blocks], basis.b.numpy())
+        return torch.as_tensor(out)
+
+    def basis_expand(self, basis, c, x_ref, stream):
+        self.expand_calls.append(dict(basis=basis, c=c.clone(), x_ref=x_ref))
+        nblk, nlev = x_ref.shape[-2:]
+        out, _ = bar.expand_reference(basis.b.numpy(), c.numpy(), x_ref.numpy().reshape(-1, nblk * nlev))
+        return torch.as_tensor(out).reshape(c.shape[0], nblk, nlev)
+
+    def oe_gain(self, k_blocks, x, xa, sa, se, y, fx, stream):
+        nprof, nblk, nlev = x.shape
+        self.gain_calls.append(dict(k=list(k_blocks), x=x.clone(), xa=xa, sa=sa))
+        ref = ocr.oe_char_reference([k.numpy().reshape(nprof, y.shape[1], nlev) for k in k_blocks], x.numpy(), xa.numpy(),
+                                    sa.numpy(), se.numpy(), y.numpy(), fx.numpy(), products=False)
+        return {k: torch.as_tensor(ref[k]) for k in ("gain", "ksa", "keep", "avk_diag", "dfs_block", "noise_var",
+                                                     "smooth_var", "status", "nobs")}
+
+    def oe_product(self, product, gain, keep, k_blocks, ksa, sa, rows, stream):
+        self.product_calls.append((product, rows))
+        nprof, m, n = gain.shape
+        right = np.concatenate([k.numpy().reshape(nprof, m, -1) for k in k_blocks], axis=2) if product == "avk" else ksa.numpy()
+        res, _ = ocr.product_reference(np.nan_to_num(gain.numpy()), keep.numpy(), right,
+                                       sa=None if product == "avk" else sa.numpy(), rows=None if rows == (0, 0) else rows)
+        return torch.as_tensor(res)
+
+
+def eofs(s, r=R, **kw):
+    return StateBasis.from_covariance(torch.as_tensor(s["sa"]), r, **kw)
+
+
+def test_without_a_basis_the_seams_see_what_they_saw(monkeypatch):
+    st = BasisStandins(monkeypatch)
+    s = setup()
+    ov = make(s)
+    assert ov.basis is None
+    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0)
+    x_new, d = ov.step(s["z"], s["p"], s["x_true"], y)
+    ov.forward(s["z"], s["p"], s["x_true"])
+    res = ov.retrieve(s["z"], s["p"], y, max_iter=2)
+    ch = ov.characterise(s["z"], s["p"], res.x, y)
+    assert st.project_calls == [] and st.expand_calls == [] and st.order == []
+    c = st.step_calls[0]
+    assert [tuple(k.shape) for k in c["k"]] == [(NPROF, ELEV.size, FRQ.size, NLEV)] * 2
+    assert c["args"][1] is ov.xa and c["args"][2] is ov.sa and c["args"][3] is ov.se and torch.equal(c["args"][0], s["x_true"])
+    assert st.gain_calls[0]["xa"] is ov.xa and st.gain_calls[0]["sa"] is ov.sa
+    assert x_new.shape == (NPROF, 2, NLEV) and d["post_var"].shape == (NPROF, 2, NLEV)
+    assert res.coeff is None and ch.coeff is None and res.post_var.shape == (NPROF, 2, NLEV)
+    # every step of retrieve asked for post_var, as before
+    assert all(call["args"][0].shape == (NPROF, 2, NLEV) for call in st.step_calls)
+
+
+def test_with_a_basis_the_update_sees_one_block_in_coefficients(monkeypatch):
+    st = BasisStandins(monkeypatch)
+    s = setup()
+    c_a = torch.as_tensor(np.random.default_rng(2).standard_normal((NPROF, R)) * 0.1)
+    sb = eofs(s, c_a=c_a)
+    ov = make(s, basis=sb)
+    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0)
+    c = torch.as_tensor(np.random.default_rng(3).standard_normal((NPROF, R)))
+    c_new, d = ov.step(s["z"], s["p"], c, y, post_var=False)
+    # the forward model ran at clamp(xa + B c): the expansion got c and xa, the K-matrix call its result
+    assert len(st.expand_calls) == 1 and torch.equal(st.expand_calls[0]["c"], c) and st.expand_calls[0]["x_ref"] is ov.xa
+    x_phys = ov.clamp(torch.as_tensor(s["xa"])[None] + (c @ sb.b.T).reshape(NPROF, 2, NLEV))
+    assert torch.allclose(st.k_calls[0]["args"][3], x_phys[:, 0], rtol=1e-14, atol=0)
+    # the projection got both blocks as the K-matrix call wrote them, the update its one block [nprof][m][r]
+    assert len(st.project_calls) == 1 and st.project_calls[0]["basis"] is sb
+    assert [tuple(k.shape) for k in st.project_calls[0]["k"]] == [(NPROF, ELEV.size, FRQ.size, NLEV)] * 2
+    call = st.step_calls[0]
+    assert [tuple(k.shape) for k in call["k"]] == [(NPROF, M, R)]
+    x, xa, sa, se, _ = call["args"]
+    assert tuple(x.shape) == (NPROF, 1, R) and torch.equal(x.reshape(NPROF, R), c)
+    assert tuple(xa.shape) == (NPROF, 1, R) and torch.equal(xa.reshape(NPROF, R), c_a)
+    assert torch.equal(sa, sb.sa_c) and se is ov.se
+    rows = st.rows(FRQ, ELEV)
+    want = np.concatenate([rows["t"].numpy(), rows["h"].numpy()], axis=1) @ sb.b.numpy()
+    assert np.abs(call["k"][0].numpy() - want[None]).max() <= 1e-13 * np.abs(want).max()
+    assert c_new.shape == (NPROF, R) and d["post_var"] is None and d["fx"].shape == (NPROF, M)
+    assert st.gain_calls == [] and st.product_calls == []
+    # a shared prior of the coefficients reaches the update as [1][r]
+    ov2 = make(s, basis=eofs(s))
+    ov2.step(s["z"], s["p"], c, y, post_var=False)
+    assert tuple(st.step_calls[-1]["args"][1].shape) == (1, R) and (st.step_calls[-1]["args"][1] == 0).all()
+    # sa may be left out with a basis: the update never reads it
+    ov3 = retrieval.OneDVar("R24", FRQ, ELEV, None, torch.as_tensor(s["se"]), variables=ov.variables, blocks=("t", "h"),
+                            xa=torch.as_tensor(s["xa"]), basis=eofs(s))
+    assert torch.equal(ov3.step(s["z"], s["p"], c, y, post_var=False)[0], ov2.step(s["z"], s["p"], c, y, post_var=False)[0])
+
+
+def test_forward_asks_for_no_projection(monkeypatch):
+    st = BasisStandins(monkeypatch)
+    s = setup()
+    ov = make(s, basis=eofs(s))
+    tb, valid = ov.forward(s["z"], s["p"], s["x_true"])
+    assert st.project_calls == [] and st.expand_calls == [] and tb.shape == (NPROF, ELEV.size, FRQ.size)
+    k_blocks, fx = ov._linearise(s["z"], s["p"], torch.zeros((NPROF, 1, R), dtype=torch.float64))
+    assert len(st.project_calls) == 1 and [tuple(k.shape) for k in k_blocks] == [(NPROF, M, R)] and fx.shape == (NPROF, M)
+
+
+def test_instrument_and_basis_reduce_then_project(monkeypatch):
+    st = BasisStandins(monkeypatch)
+    s = setup()
+    inst = Instrument(FRQ, ELEV, beam=3.5, band=[0.23, 0.23, 2.0], n_beam=3, n_band=2)
+    sb = eofs(s)
+    ov = make(s, instrument=inst, basis=sb)
+    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0)
+    ov.step(s["z"], s["p"], torch.zeros((NPROF, R), dtype=torch.float64), y, post_var=False)
+    assert st.order == ["reduce", "project"]
+    # the projection got channel rows (m_out of them), not the quadrature grid's
+    assert [tuple(k.shape) for k in st.project_calls[0]["k"]] == [(NPROF, ELEV.size, FRQ.size, NLEV)] * 2
+    grid = st.rows(inst.frq_q, inst.elev_q)
+    want = inst.dense() @ np.concatenate([grid["t"].numpy(), grid["h"].numpy()], axis=1) @ sb.b.numpy()
+    got = st.step_calls[0]["k"][0].numpy()
+    assert got.shape == (NPROF, M, R) and np.abs(got - want[None]).max() <= 1e-12 * np.abs(want).max()
+    ov.forward(s["z"], s["p"], s["x_true"])
+    assert st.order == ["reduce", "project", "reduce"]
+
+
+def test_linear_problem_reaches_the_posterior_mean_in_the_span(monkeypatch):
+    st = BasisStandins(monkeypatch)
+    s = setup()
+    sb = eofs(s)
+    b, sa_c = sb.b.numpy(), sb.sa_c.numpy()
+    ov = make(s, basis=sb)
+    rows = st.rows(FRQ, ELEV)
+    K = np.concatenate([rows["t"].numpy(), rows["h"].numpy()], axis=1)    # [m][n]
+    Kc = K @ b
+    rng = np.random.default_rng(9)
+    c_true = rng.standard_normal((NPROF, R)) * np.sqrt(np.diag(sa_c)) * 0.3      # small: humidity stays positive, no clamp
+    xa_t = torch.as_tensor(s["xa"][None])
+    x_true = xa_t + torch.as_tensor(c_true @ b.T).reshape(NPROF, 2, NLEV)
+    assert (x_true[:, 1] > 0).all()
+    y = st.forward(x_true[:, 0], ov.physical(s["z"], s["p"], x_true)[2], FRQ, ELEV).numpy() + 0.3 * rng.standard_normal((NPROF, M))
+    fxa = st.forward(xa_t[:, 0], ov.physical(s["z"][:1], s["p"][:1], xa_t)[2], FRQ, ELEV).numpy()[0]
+    post_c = np.linalg.inv(Kc.T @ Kc / 0.25 + np.linalg.inv(sa_c))
+    c_hat = (y - fxa[None]) @ (post_c @ Kc.T / 0.25).T
+    c0 = torch.as_tensor(rng.standard_normal((NPROF, R)) * 0.1)
+    c_new, d = ov.step(s["z"], s["p"], c0, torch.as_tensor(y))
+    assert np.abs(c_new.numpy() - c_hat).max() <= 1e-10 * np.abs(c_hat).max()
+    # post_var of the step: the level-space diagonal of B S^_c B^T, from one gain and one product call in coefficient space
+    want_var = np.diag(b @ post_c @ b.T)
+    assert d["post_var"].shape == (NPROF, 2, NLEV) and st.product_calls == [("post_cov", (0, 0))]
+    assert tuple(st.gain_calls[0]["x"].shape) == (NPROF, 1, R) and torch.equal(st.gain_calls[0]["sa"], sb.sa_c)
+    assert np.abs(d["post_var"].numpy().reshape(NPROF, N) - want_var[None]).max() <= 1e-10 * np.diag(s["sa"]).max()
+    # retrieve: two steps (the second moves nothing), the physical state is xa + B c^
+    res = ov.retrieve(s["z"], s["p"], torch.as_tensor(y), max_iter=5, tol=1e-6)
+    assert res.iterations.tolist() == [2] * NPROF and res.converged.all()
+    assert np.abs(res.coeff.numpy() - c_hat).max() <= 1e-9 * np.abs(c_hat).max()
+    want_x = s["xa"].reshape(-1)[None] + c_hat @ b.T
+    assert res.x.shape == (NPROF, 2, NLEV)
+    assert np.abs(res.x.numpy().reshape(NPROF, N) - want_x).max() <= 1e-9 * np.abs(want_x - s["xa"].reshape(-1)[None]).max()
+    assert np.abs(res.post_var.numpy().reshape(NPROF, N) - want_var[None]).max() <= 1e-10 * np.diag(s["sa"]).max()
+    # the steps of retrieve asked for no post_var: one product call for the step above, one at the end of retrieve
+    assert st.product_calls == [("post_cov", (0, 0))] * 2
+    # characterise answers in coefficient space
+    ch = ov.characterise(s["z"], s["p"], res.coeff, torch.as_tensor(y), avk=True, post_cov=True)
+    assert ch.gain.shape == (NPROF, M, R) and ch.avk.shape == (NPROF, R, R) and ch.dfs_block.shape == (NPROF, 1)
+    assert torch.equal(ch.coeff, res.coeff) and (ch.dfs_block[:, 0] <= R).all()
+    assert np.abs(ch.post_cov.numpy() - post_c[None]).max() <= 1e-10 * np.abs(sa_c).max()
+
+
+def test_coefficients_are_not_clamped_but_the_state_is(monkeypatch):
+    st = BasisStandins(monkeypatch)
+    s = setup()
+    b = np.zeros((N, 1))
+    b[NLEV:, 0] = 1.0                                                    # one column: a shift of the whole humidity profile
+    sb = StateBasis(torch.as_tensor(b), torch.as_tensor([[4.0]]))
+    ov = make(s, basis=sb)
+    c = torch.full((NPROF, 1), -5.0, dtype=torch.float64)                # far below zero humidity
+    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0)
+    c_new, d = ov.step(s["z"], s["p"], c, y, post_var=False)
+    assert (st.k_calls[0]["args"][4] == 0).all()                         # the forward model saw rh clamped to 0 ...
+    assert torch.equal(st.step_calls[0]["args"][0].reshape(NPROF, 1), c)  # ... the update the coefficient as it is
+    res = ov.retrieve(s["z"], s["p"], y, x0=c, max_iter=1)
+    assert (res.x[:, 1] >= 0).all() and res.coeff.shape == (NPROF, 1)
+
+
+def test_shape_errors_name_the_expected_shapes(monkeypatch):
+    BasisStandins(monkeypatch)
+    s = setup()
+    with pytest.raises(ValueError, match=r"sa_c: expected \[4\]\[4\]"):
+        StateBasis(torch.zeros((N, 4), dtype=torch.float64), torch.eye(3, dtype=torch.float64))
+    with pytest.raises(ValueError, match=r"b: expected float64 \[n\]\[r\]"):
+        StateBasis(torch.zeros(N, dtype=torch.float64), torch.eye(1, dtype=torch.float64))
+    with pytest.raises(ValueError, match=r"c_a: expected \[4\] or \[nprof\]\[4\]"):
+        StateBasis(torch.zeros((N, 4), dtype=torch.float64), torch.eye(4, dtype=torch.float64), c_a=torch.zeros(3, dtype=torch.float64))
+    with pytest.raises(ValueError, match=r"1 <= r <= n"):
+        StateBasis.from_covariance(torch.as_tensor(s["sa"]), N + 1)
+    short = StateBasis(torch.zeros((N - 1, 4), dtype=torch.float64), torch.eye(4, dtype=torch.float64))
+    with pytest.raises(ValueError, match=r"basis: expected b \[%d\]\[r\]" % N):
+        make(s, basis=short)
+    # a per-profile prior of another batch size, and what the seams refuse before they reach the library
+    ov = make(s, basis=eofs(s, c_a=torch.zeros((NPROF + 1, R), dtype=torch.float64)))
+    with pytest.raises(ValueError, match=r"basis.c_a: expected \[4\] or \[%d\]\[4\]" % NPROF):
+        ov.step(s["z"], s["p"], torch.zeros((NPROF, R), dtype=torch.float64), torch.full((NPROF, M), 255.0))
+    sb = eofs(s)
+    with pytest.raises(ValueError, match=r"x_ref \[nblk\]\[nlev\] or \[%d\]\[nblk\]\[nlev\]" % NPROF):
+        EXPAND(sb, torch.zeros((NPROF, R), dtype=torch.float64), torch.zeros((NPROF + 1, 2, NLEV), dtype=torch.float64), None)
+    with pytest.raises(ValueError, match=r"basis: expected b \[%d\]\[r\] for 3 blocks" % (3 * NLEV)):
+        PROJECT(sb, [torch.zeros((NPROF, M, NLEV), dtype=torch.float64)] * 3, None)
+    with pytest.raises(ValueError, match="sa .* is required without a basis"):
+        retrieval.OneDVar("R24", FRQ, ELEV, None, torch.as_tensor(s["se"]), blocks=("t", "h"), xa=torch.as_tensor(s["xa"]))
+
+
+def test_from_covariance_is_reproducible_and_orthonormal():
+    s = setup()
+    sa = torch.as_tensor(s["sa"])
+    one, two = StateBasis.from_covariance(sa, 5), StateBasis.from_covariance(sa.clone(), 5)
+    assert torch.equal(one.b, two.b) and torch.equal(one.sa_c, two.sa_c) and (one.c_a == 0).all() and one.c_a.shape == (5,)
+    b = one.b.numpy()
+    assert b.shape == (N, 5) and np.abs(b.T @ b - np.eye(5)).max() <= 1e-13
+    lam = np.diag(one.sa_c.numpy())
+    assert (np.diff(lam) <= 0).all() and np.abs(one.sa_c.numpy() - np.diag(lam)).max() == 0      # largest first, diagonal
+    assert np.abs(s["sa"] @ b - b * lam[None, :]).max() <= 1e-12 * lam[0]
+    top = np.abs(b).argmax(axis=0)
+    assert (b[top, np.arange(5)] > 0).all()                              # the sign rule
+    # all n columns rebuild Sa
+    full = StateBasis.from_covariance(sa, N)
+    assert np.abs(full.b.numpy() @ full.sa_c.numpy() @ full.b.numpy().T - s["sa"]).max() <= 1e-12 * np.abs(s["sa"]).max()
