@@ -768,6 +768,66 @@ int mwrt_basis_expand_device(mwrt_context* ctx, const mwrt_basis* basis, int64_t
 /* sizeof(mwrt_basis_apply) as compiled into the library (binding self-check). */
 uint32_t mwrt_basis_apply_size(void);
 
+/* Pre-whitening with a per-profile observation-error covariance.  The optimal-estimation entries take one
+ * Se for the batch.  With Se_p = L_p L_p^T (Cholesky) on the rows profile p keeps,
+ *     K~ = L^-1 K,    y~ = L^-1 y,    F~ = L^-1 F(x)
+ * make mwrt_oe_step_device, the Levenberg-Marquardt split, mwrt_oe_cost_device and mwrt_oe_gain_device, called with
+ * Se = 1 ([m] ones), compute exactly the x_new, chi2, dfs, post_var, A, S^, budget and cost J of the step with Se_p; only the
+ * gain has to be restored, gain = L^-T gain~.  All DEVICE pointers, float64, on `stream` as every *_device entry.
+ * mwrt_obs_whiten_device decides, factorises and applies:
+ *   in:   d_se [nprof][m] variances, or [nprof][m][m] symmetric (the lower triangle is read) with se_full != 0;
+ *         d_y, d_fx [nprof][m];  d_k_in[b] [nprof][m][nlev], b < nblk, nblk 0 .. 4 (a Jacobian output,
+ *         mwrt_obs_apply_device's rows, or mwrt_basis_project_device's K B with nlev := r)
+ *   out:  d_l [nprof][m (m + 1) / 2], the lower triangle packed by rows, L_ij at i (i + 1) / 2 + j;  d_keep [nprof][m] uint8;
+ *         d_status [nprof] uint8;  optional, each on its own: d_y_out, d_fx_out [nprof][m], d_k_out[b] [nprof][m][nlev]
+ *   Row rule, that of mwrt_oe_step_device: row i is kept when y_i, fx_i, every K_b[i][:] and its Se entry -- the variance,
+ *   or every element of row i of a full Se_p -- are finite.  A dropped row is deleted from Se_p BEFORE the factorisation (a
+ *   NaN left inside would reach every later row through L): d_l is the factor of the kept sub-matrix in full indexing, a
+ *   dropped row being a row of the identity.  In the outputs a dropped row is NaN in y_out and fx_out, so that the step's
+ *   own row rule drops the same rows, and exact 0.0 in the K blocks.
+ *   status 1: ok.  2: a pivot fails pivot > 0 (the kept Se_p is not positive definite): d_l and every other floating-point
+ *   output of the profile are NaN, keep is 0.  3: no row kept: y_out, fx_out NaN, K rows 0.0, keep 0, L the identity.
+ *   Arithmetic, fixed per element: the Cholesky is that of the step's kernels (right-looking, column by column); then per
+ *   column v:  acc = v_i;  for j < i ascending: acc = fma(-L_ij, w_j, acc);  w_i = acc / L_ii, where a dropped row takes
+ *   part as w_j = 0 with L_ij = 0 (its input is loaded first and selected afterwards: 0 * NaN never gets in).  A profile's
+ *   outputs depend on neither its batch-mates, nprof, the column's neighbours nor the outputs asked for.  No atomics.
+ *   mode must be 0.
+ * mwrt_obs_whiten_apply_device applies a stored d_l and d_keep (inputs here; d_se and d_status are not read) to the vectors
+ *   d_y -> d_y_out and d_fx -> d_fx_out (each optional, as a pair) and to the blocks d_k_in[b] -> d_k_out[b], b < nblk:
+ *   mode 0: L^-1, as above, bit for bit what mwrt_obs_whiten_device wrote from the same inputs (F(x_trial) of a damped
+ *           iteration on the rows of its linearisation; a non-finite value in a kept row stays in that row and reaches the
+ *           kept rows after it, so mwrt_oe_cost_device returns +inf and the trial is rejected);
+ *   mode 1: L^-T:  i descending, acc = v_i;  for j > i descending: acc = fma(-L_ji, w_j, acc);  w_i = acc / L_ii (the
+ *           [nprof][m][n] gain of mwrt_oe_gain_device with nlev := n, so that it is d x^ / d y again).
+ *   In both modes a dropped row is exact 0.0 in a block and NaN in a vector, and a profile whose d_l[0] is NaN (status 2)
+ *   gets NaN in every output.
+ * Both refuse with MWRT_ERR_INVALID_ARGUMENT, nothing written: a NULL context or record; struct_size smaller than the fixed
+ *   part (24 bytes); nblk outside 0 .. 4; reserved != 0; an unknown mode; m < 1, nlev < 1, nprof < 0; a NULL among the
+ *   required pointers (whiten: d_se, d_y, d_fx, d_l, d_keep, d_status, the first nblk of d_k_in; apply: d_l, d_keep, the
+ *   first nblk of d_k_in and d_k_out); apply: one of a vector pair without the other, nothing to do (no vector and
+ *   nblk = 0); an output pointer equal to an input.  MWRT_ERR_UNSUPPORTED: m > MWRT_OE_MAX_M, nlev > MWRT_MAX_LEVELS, more
+ *   than 2^31 - 1 workgroups in one launch.  nprof = 0 is MWRT_OK.
+ *   The record starts with its own size: fields at or beyond struct_size (and a field it ends inside) are taken as NULL.
+ *   The calls never allocate and never synchronise; after a first call of the same m they are the launches alone (beyond
+ *   m = 120 the kernels' dynamic LDS limit is raised once per device).  Timing: DESIGN.md 4.10.
+ *   (MWRT_VERSION stays 301: additions.) */
+typedef struct mwrt_obs_whiten {
+  uint32_t struct_size;        /* sizeof(mwrt_obs_whiten) of the caller; fields beyond it are not read */
+  int32_t  nblk, se_full, mode;
+  int64_t  reserved;
+  const double *d_se, *d_y, *d_fx;
+  const double* d_k_in[4];                             /* [nprof][m][nlev]                             */
+  double* d_l;  uint8_t* d_keep;  uint8_t* d_status;   /* out of whiten; d_l, d_keep in of apply       */
+  double *d_y_out, *d_fx_out;
+  double* d_k_out[4];                                  /* [nprof][m][nlev]                             */
+} mwrt_obs_whiten;
+int mwrt_obs_whiten_device(mwrt_context* ctx, int64_t nprof, int32_t nlev, int32_t m, const mwrt_obs_whiten* rec,
+                           void* stream);
+int mwrt_obs_whiten_apply_device(mwrt_context* ctx, int64_t nprof, int32_t nlev, int32_t m, const mwrt_obs_whiten* rec,
+                                 void* stream);
+/* sizeof(mwrt_obs_whiten) as compiled into the library (binding self-check). */
+uint32_t mwrt_obs_whiten_size(void);
+
 /* The spectroscopic-parameter Jacobian: d TB / d b for entries b of the model's tables -- what the
  * forward-model part K_b S_b K_b^T of an observation-error covariance is built from (Rodgers 2000, section 3.2.2).  The
  * operator is mwrt_tb_jacobian_batch_device's: clear sky, plane-parallel, every line at every frequency; there is no

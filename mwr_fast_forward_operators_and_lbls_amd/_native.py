@@ -103,6 +103,19 @@ class MwrtBasisApply(ctypes.Structure):
                 ("d_x", ctypes.c_void_p), ("x_ref_per_profile", ctypes.c_int32), ("reserved2", ctypes.c_int32)]
 
 
+class MwrtObsWhiten(ctypes.Structure):
+    """include/mwrt.h mwrt_obs_whiten: the record of one pre-whitening with a per-profile observation-error covariance, or
+    of one application of its stored factor (device pointers)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("nblk", ctypes.c_int32), ("se_full", ctypes.c_int32),
+                ("mode", ctypes.c_int32), ("reserved", ctypes.c_int64), ("d_se", ctypes.c_void_p), ("d_y", ctypes.c_void_p),
+                ("d_fx", ctypes.c_void_p), ("d_k_in", ctypes.c_void_p * 4), ("d_l", ctypes.c_void_p),
+                ("d_keep", ctypes.c_void_p), ("d_status", ctypes.c_void_p), ("d_y_out", ctypes.c_void_p),
+                ("d_fx_out", ctypes.c_void_p), ("d_k_out", ctypes.c_void_p * 4)]
+
+
+#: include/mwrt.h mwrt_obs_whiten.mode: L^-1 (whitening) and L^-T (the gain back to d x^ / d y)
+WHITEN_FORWARD, WHITEN_TRANSPOSED = 0, 1
+
 #: include/mwrt.h MWRT_OE_PRODUCT_*: what mwrt_oe_product_device forms
 OE_PRODUCT_AVK, OE_PRODUCT_POST_COV = 0, 1
 
@@ -214,6 +227,9 @@ SIGNATURES = {
     "mwrt_basis_project_device": (ctypes.c_int, [_vp, _vp, _i64, _i32, ctypes.POINTER(MwrtBasisApply), _vp]),
     "mwrt_basis_expand_device": (ctypes.c_int, [_vp, _vp, _i64, ctypes.POINTER(MwrtBasisApply), _vp]),
     "mwrt_basis_apply_size": (ctypes.c_uint32, []),
+    "mwrt_obs_whiten_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtObsWhiten), _vp]),
+    "mwrt_obs_whiten_apply_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtObsWhiten), _vp]),
+    "mwrt_obs_whiten_size": (ctypes.c_uint32, []),
     "mwrt_set_absorption_mode": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_set_chunk_width": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_selftest_math": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -281,6 +297,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
             raise NativeLibraryMissing("mwrt_obs_apply layout mismatch between libmwrt.so and _native.py")
         if lib.mwrt_basis_apply_size() != ctypes.sizeof(MwrtBasisApply):
             raise NativeLibraryMissing("mwrt_basis_apply layout mismatch between libmwrt.so and _native.py")
+        if lib.mwrt_obs_whiten_size() != ctypes.sizeof(MwrtObsWhiten):
+            raise NativeLibraryMissing("mwrt_obs_whiten layout mismatch between libmwrt.so and _native.py")
         if lib.mwrt_version() != MWRT_VERSION:
             raise NativeLibraryMissing(f"libmwrt.so is version {lib.mwrt_version()}, this binding needs {MWRT_VERSION}: "
                                        "rebuild (python -c 'import __graft_entry__ as g; g.build()')")
@@ -845,6 +863,48 @@ class Context:
         rec.x_ref_per_profile = int(bool(x_ref_per_profile))
         self._check(self._lib.mwrt_basis_expand_device(self._handle, handle, int(nprof), ctypes.byref(rec),
                                                        _stream(stream)), "mwrt_basis_expand_device")
+
+    @staticmethod
+    def _whiten_record(d_se, d_y, d_fx, d_k_in, d_l, d_keep, d_status, d_y_out, d_fx_out, d_k_out, se_full, mode, reserved,
+                       struct_size, nblk):
+        d_k_in, d_k_out = list(d_k_in), list(d_k_out)
+        rec = MwrtObsWhiten()
+        rec.struct_size = ctypes.sizeof(MwrtObsWhiten) if struct_size is None else int(struct_size)
+        rec.nblk = len(d_k_in) if nblk is None else int(nblk)
+        rec.se_full, rec.mode, rec.reserved = int(bool(se_full)), int(mode), int(reserved)
+        opt = lambda v: int(v) if v is not None else None   # noqa: E731
+        rec.d_se, rec.d_y, rec.d_fx = opt(d_se), opt(d_y), opt(d_fx)
+        rec.d_l, rec.d_keep, rec.d_status = opt(d_l), opt(d_keep), opt(d_status)
+        rec.d_y_out, rec.d_fx_out = opt(d_y_out), opt(d_fx_out)
+        for b, k in enumerate(d_k_in[:4]):
+            rec.d_k_in[b] = opt(k)
+        for b, k in enumerate(d_k_out[:4]):
+            rec.d_k_out[b] = opt(k)
+        return rec
+
+    @_serialised
+    def obs_whiten_device(self, nprof, nlev, m, d_se, d_y, d_fx, d_k_in, d_l, d_keep, d_status, d_y_out=None, d_fx_out=None,
+                          d_k_out=(), se_full=False, stream=None, mode=0, reserved=0, struct_size=None, nblk=None):
+        """Pre-whitening with a per-profile Se (include/mwrt.h mwrt_obs_whiten_device): decides the rows each profile
+        keeps, factorises the kept ``d_se [nprof][m]`` (``[nprof][m][m]`` with ``se_full``) into ``d_l [nprof][m (m + 1) / 2]``
+        with ``d_keep [nprof][m]`` and ``d_status [nprof]`` (uint8), and writes L^-1 y, L^-1 F and L^-1 K_b into the outputs
+        asked for (``None`` in ``d_k_out`` skips a block).  ``nblk`` (default: ``len(d_k_in)``) and ``struct_size``
+        (default: the whole record) are what the record claims."""
+        rec = self._whiten_record(d_se, d_y, d_fx, d_k_in, d_l, d_keep, d_status, d_y_out, d_fx_out, d_k_out, se_full, mode,
+                                  reserved, struct_size, nblk)
+        self._check(self._lib.mwrt_obs_whiten_device(self._handle, int(nprof), int(nlev), int(m), ctypes.byref(rec),
+                                                     _stream(stream)), "mwrt_obs_whiten_device")
+
+    @_serialised
+    def obs_whiten_apply_device(self, nprof, nlev, m, d_l, d_keep, mode=0, d_y=None, d_y_out=None, d_fx=None, d_fx_out=None,
+                                d_k_in=(), d_k_out=(), stream=None, reserved=0, struct_size=None, nblk=None):
+        """Applies a stored factor (include/mwrt.h mwrt_obs_whiten_apply_device): ``mode`` 0 is L^-1, 1 is L^-T, on the
+        vectors ``d_y -> d_y_out`` and ``d_fx -> d_fx_out`` ``[nprof][m]`` (each optional, as a pair) and on the blocks
+        ``d_k_in[b] -> d_k_out[b] [nprof][m][nlev]``."""
+        rec = self._whiten_record(None, d_y, d_fx, d_k_in, d_l, d_keep, None, d_y_out, d_fx_out, d_k_out, False, mode,
+                                  reserved, struct_size, nblk)
+        self._check(self._lib.mwrt_obs_whiten_apply_device(self._handle, int(nprof), int(nlev), int(m), ctypes.byref(rec),
+                                                           _stream(stream)), "mwrt_obs_whiten_apply_device")
 
     def layer_tau_pitch(self, nf: int) -> int:
         """Doubles between consecutive levels of a layer-optical-depth array for nf frequencies (multiple of 16)."""

@@ -7,7 +7,8 @@ Levenberg-Marquardt split (csrc/mwrt_oe_lm.hip), its characterisation (csrc/mwrt
 operator (csrc/mwrt_obs.hip), the non-template
 kernels (csrc/mwrt_aux.hip) and the host-only launch planning
 (csrc/mwrt_plan.cpp, no HIP in it) -- and a fourteenth, the reduced-basis state map (csrc/mwrt_basis.hip), are compiled in
-parallel and linked into one shared library."""
+parallel and linked into one shared library; so is a fifteenth, the pre-whitening with a per-profile observation-error
+covariance (csrc/mwrt_whiten.hip)."""
 from __future__ import annotations
 
 import concurrent.futures
@@ -29,6 +30,7 @@ OE_LM = os.path.join(CSRC, "mwrt_oe_lm.hip")
 OE_CHAR = os.path.join(CSRC, "mwrt_oe_char.hip")
 OBS = os.path.join(CSRC, "mwrt_obs.hip")
 BASIS = os.path.join(CSRC, "mwrt_basis.hip")
+WHITEN = os.path.join(CSRC, "mwrt_whiten.hip")
 AUX = os.path.join(CSRC, "mwrt_aux.hip")
 PLAN = os.path.join(CSRC, "mwrt_plan.cpp")
 # what the library is built from: every file of csrc/ (a new header counts without being named here) and the public header
@@ -72,6 +74,7 @@ def build_native(force: bool = False, verbose: bool = False, extra_flags=(), out
     jobs.append((OE_CHAR, os.path.join(OBJ_DIR, f"mwrt_oe_char.{tag}.o"), []))
     jobs.append((OBS, os.path.join(OBJ_DIR, f"mwrt_obs.{tag}.o"), []))
     jobs.append((BASIS, os.path.join(OBJ_DIR, f"mwrt_basis.{tag}.o"), []))
+    jobs.append((WHITEN, os.path.join(OBJ_DIR, f"mwrt_whiten.{tag}.o"), []))
     jobs.append((AUX, os.path.join(OBJ_DIR, f"mwrt_aux.{tag}.o"), []))
     jobs.append((PLAN, os.path.join(OBJ_DIR, f"mwrt_plan.{tag}.o"), []))
 

@@ -15,6 +15,7 @@
 #include "mwrt_oe_char.hip.h"
 #include "mwrt_obs.hip.h"
 #include "mwrt_basis.hip.h"
+#include "mwrt_whiten.hip.h"
 #include "mwrt_plan.h"
 
 #include <cmath>
@@ -1679,6 +1680,124 @@ int mwrt_basis_expand_device(mwrt_context* c, const mwrt_basis* bs, int64_t npro
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = resolve_stream(c, stream);
   return timed(c, st, [&] { return basis::launch_expand(a, st); });
+}
+
+/* Pre-whitening with a per-profile observation-error covariance (csrc/mwrt_whiten.hip): no handle, two entries that share
+ * the record, its cut at the caller's struct_size and the preamble of mwrt_obs_apply_device. */
+uint32_t mwrt_obs_whiten_size(void) { return (uint32_t)sizeof(mwrt_obs_whiten); }
+
+namespace {
+
+// What the two entries share: the record cut at the caller's struct_size, the sizes, and the limits.  *tiles is the number
+// of workgroups of k_wh_apply per profile when every block and a vector are asked for.
+int whiten_record(const mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_obs_whiten* s, mwrt_obs_whiten* r,
+                  int max_mode) {
+  if (!c || !s) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context or mwrt_obs_whiten");
+  constexpr size_t fixed = offsetof(mwrt_obs_whiten, reserved) + sizeof(int64_t), ptrs = offsetof(mwrt_obs_whiten, d_se);
+  static_assert(fixed == ptrs, "mwrt_obs_whiten: the pointers follow the fixed part");
+  if (s->struct_size < fixed)
+    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten.struct_size too small for the fixed part (through reserved)");
+  // fields at or beyond the caller's struct_size stay NULL, and so does a field the size ends inside: all are pointers
+  size_t len = s->struct_size < sizeof *r ? s->struct_size : sizeof *r;
+  len -= (len - ptrs) % sizeof(void*);
+  std::memcpy(r, s, len);
+  if (nprof < 0 || nlev < 1 || m < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "nprof < 0, nlev < 1 or m < 1");
+  if (r->nblk < 0 || r->nblk > 4) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten.nblk must be 0 .. 4");
+  if (r->reserved != 0) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten.reserved must be 0");
+  if (r->mode < 0 || r->mode > max_mode)
+    return fail(MWRT_ERR_INVALID_ARGUMENT, max_mode == 0 ? "mwrt_obs_whiten.mode must be 0 in mwrt_obs_whiten_device"
+                                                         : "mwrt_obs_whiten.mode must be 0 (L^-1) or 1 (L^-T)");
+  return MWRT_OK;
+}
+
+int whiten_limits(int64_t nprof, int32_t nlev, int32_t m, int nblk) {
+  if (m > MWRT_OE_MAX_M) return fail(MWRT_ERR_UNSUPPORTED, "m > MWRT_OE_MAX_M (" + std::to_string(MWRT_OE_MAX_M) + ")");
+  if (nlev > MWRT_MAX_LEVELS)
+    return fail(MWRT_ERR_UNSUPPORTED, "nlev > MWRT_MAX_LEVELS (" + std::to_string(MWRT_MAX_LEVELS) + ")");
+  // one workgroup per (profile, tile of wh::COLS columns), and one more per profile for the vectors: at most 65 a profile
+  const int64_t tiles = (int64_t)nblk * ((nlev + wh::COLS - 1) / wh::COLS) + 1;
+  if (nprof > 2147483647LL / tiles)
+    return fail(MWRT_ERR_UNSUPPORTED, "mwrt_obs_whiten: more than 2147483647 workgroups in one launch (split the batch)");
+  return MWRT_OK;
+}
+
+// an output that is also one of the inputs
+bool whiten_aliased(const mwrt_obs_whiten& r, bool l_is_output) {
+  const void* ins[10] = {r.d_se, r.d_y, r.d_fx, r.d_k_in[0], r.d_k_in[1], r.d_k_in[2], r.d_k_in[3],
+                         l_is_output ? nullptr : r.d_l, l_is_output ? nullptr : r.d_keep, nullptr};
+  const void* outs[9] = {r.d_y_out, r.d_fx_out, r.d_k_out[0], r.d_k_out[1], r.d_k_out[2], r.d_k_out[3],
+                         l_is_output ? r.d_l : nullptr, l_is_output ? r.d_keep : nullptr, l_is_output ? r.d_status : nullptr};
+  for (const void* o : outs)
+    for (const void* i : ins)
+      if (o && o == i) return true;
+  return false;
+}
+
+// the blocks with an output asked for, packed to the front; the vectors as they are
+wh::ApplyArgs whiten_apply_args(const mwrt_obs_whiten& r, int32_t nlev, int32_t m) {
+  wh::ApplyArgs a{};
+  const double* in[4] = {};
+  double* out[4] = {};
+  int n = 0;
+  for (int b = 0; b < r.nblk; ++b)
+    if (r.d_k_out[b]) { in[n] = r.d_k_in[b]; out[n] = r.d_k_out[b]; ++n; }
+  a.in0 = in[0]; a.in1 = in[1]; a.in2 = in[2]; a.in3 = in[3];
+  a.out0 = out[0]; a.out1 = out[1]; a.out2 = out[2]; a.out3 = out[3];
+  if (r.d_y_out) { a.v_in0 = r.d_y; a.v_out0 = r.d_y_out; }
+  if (r.d_fx_out) { a.v_in1 = r.d_fx; a.v_out1 = r.d_fx_out; }
+  a.l = r.d_l; a.keep = r.d_keep;
+  a.nblk = n; a.nlev = nlev; a.m = m; a.mode = r.mode;
+  a.ctiles = (nlev + wh::COLS - 1) / wh::COLS;
+  a.tiles = n * a.ctiles + ((a.v_in0 || a.v_in1) ? 1 : 0);
+  return a;
+}
+
+}  // namespace
+
+int mwrt_obs_whiten_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_obs_whiten* s, void* stream) {
+  mwrt_obs_whiten r{};
+  if (const int rc = whiten_record(c, nprof, nlev, m, s, &r, 0)) return rc;
+  if (!r.d_se || !r.d_y || !r.d_fx || !r.d_l || !r.d_keep || !r.d_status)
+    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten: d_se, d_y, d_fx, d_l, d_keep or d_status is null");
+  for (int b = 0; b < r.nblk; ++b)
+    if (!r.d_k_in[b]) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten: null pointer among the first nblk of d_k_in");
+  if (whiten_aliased(r, true))
+    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten: an output pointer equals an input (nothing is whitened in place)");
+  if (const int rc = whiten_limits(nprof, nlev, m, r.nblk)) return rc;
+  if (nprof == 0) return MWRT_OK;
+  wh::FactorArgs f{};
+  f.k0 = r.d_k_in[0]; f.k1 = r.d_k_in[1]; f.k2 = r.d_k_in[2]; f.k3 = r.d_k_in[3];
+  f.se = r.d_se; f.y = r.d_y; f.fx = r.d_fx;
+  f.l = r.d_l; f.keep = r.d_keep; f.status = r.d_status;
+  f.nblk = r.nblk; f.nlev = nlev; f.m = m; f.se_full = r.se_full != 0;
+  const wh::ApplyArgs a = whiten_apply_args(r, nlev, m);
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = resolve_stream(c, stream);
+  const int rc = timed(c, st, [&] { return wh::launch_factor(f, nprof, st); });
+  if (rc != MWRT_OK || a.tiles == 0) return rc;
+  return timed(c, st, [&] { return wh::launch_apply(a, nprof, st); });
+}
+
+int mwrt_obs_whiten_apply_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_obs_whiten* s,
+                                 void* stream) {
+  mwrt_obs_whiten r{};
+  if (const int rc = whiten_record(c, nprof, nlev, m, s, &r, 1)) return rc;
+  if (!r.d_l || !r.d_keep) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten: d_l or d_keep is null");
+  if ((r.d_y == nullptr) != (r.d_y_out == nullptr) || (r.d_fx == nullptr) != (r.d_fx_out == nullptr))
+    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten: d_y and d_y_out (d_fx and d_fx_out) are given together or not at all");
+  for (int b = 0; b < r.nblk; ++b)
+    if (!r.d_k_in[b] || !r.d_k_out[b])
+      return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten: null pointer among the first nblk of d_k_in / d_k_out");
+  if (!r.d_y && !r.d_fx && r.nblk == 0)
+    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten: nothing to do (no vector and nblk = 0)");
+  if (whiten_aliased(r, false))
+    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten: an output pointer equals an input (nothing is applied in place)");
+  if (const int rc = whiten_limits(nprof, nlev, m, r.nblk)) return rc;
+  if (nprof == 0) return MWRT_OK;
+  const wh::ApplyArgs a = whiten_apply_args(r, nlev, m);
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = resolve_stream(c, stream);
+  return timed(c, st, [&] { return wh::launch_apply(a, nprof, st); });
 }
 
 int mwrt_selftest_math(mwrt_context* c, int32_t n, const double* x, const double* y_pos,

@@ -30,7 +30,15 @@ single block K B ``[nprof][m][r]``, the state c, its prior ``c_a`` and its covar
 
     eof = StateBasis.from_covariance(sa, 32)     # the leading eigenvectors of Sa, sa_c = diag(lambda)
     ov = OneDVar("R24", frq, elev, None, se, variables=..., blocks=("t", "h"), xa=xa, basis=eof)
-    res = ov.retrieve(z, p, y)                   # res.x the physical state, res.coeff [nprof][r]"""
+    res = ov.retrieve(z, p, y)                   # res.x the physical state, res.coeff [nprof][r]
+
+With ``se=`` on ``step``, ``retrieve``, ``retrieve_lm`` and ``characterise`` every profile has its own observation-error
+covariance, ``[nprof][m]`` variances or ``[nprof][m][m]``: each linearisation is pre-whitened with the
+Cholesky factor of the profile's Se_p on the rows it keeps (``mwrt_obs_whiten_device``, behind the instrument's reduction
+and the basis projection) and the unchanged update entries run with Se = 1, which gives exactly the step of Se_p.
+
+    se_p = noise[None] + ov.representation_error(z, p, x)            # K S_res K^T of a truncated basis, per profile
+    res = ov.retrieve(z, p, y, se=se_p)"""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -233,6 +241,50 @@ def _native_basis_expand(basis, c, x_ref, stream):
     return out
 
 
+def _native_obs_whiten(k_blocks, se, y, fx, stream):
+    """One ``mwrt_obs_whiten_device`` call -> dict(k: list of L^-1 K blocks in the shapes given, y, fx: L^-1 y and L^-1 F
+    ``[nprof][m]``, l ``[nprof][m (m + 1) / 2]``, keep ``[nprof][m]`` and status ``[nprof]`` uint8) from the K blocks
+    ``[nprof]...[nlev]`` the update would see, ``se [nprof][m]`` or ``[nprof][m][m]`` and ``y``, ``fx [nprof][m]``.
+
+    The single place the pre-whitening reaches the native library: CPU tests substitute the NumPy reference here."""
+    k_blocks = [k.contiguous() for k in k_blocks]
+    nprof, m = y.shape
+    nlev = k_blocks[0].shape[-1] if k_blocks else 1
+    for i, k in enumerate(k_blocks):
+        if k.dtype != torch.float64 or k.shape[0] != nprof or k.shape[-1] != nlev or k[0].numel() != m * nlev:
+            raise ValueError(f"k_blocks[{i}]: expected float64 [{nprof}][{m}][{nlev}], got {k.dtype} {tuple(k.shape)}")
+    if se.dtype != torch.float64 or tuple(se.shape) not in ((nprof, m), (nprof, m, m)):
+        raise ValueError(f"se: expected float64 [{nprof}][{m}] or [{nprof}][{m}][{m}], got {se.dtype} {tuple(se.shape)}")
+    se, y, fx = se.contiguous(), y.contiguous(), fx.contiguous()
+    f64, u8 = dict(dtype=torch.float64, device=y.device), dict(dtype=torch.uint8, device=y.device)
+    out = dict(k=[torch.empty_like(k) for k in k_blocks], y=torch.empty_like(y), fx=torch.empty_like(fx),
+               l=torch.empty((nprof, m * (m + 1) // 2), **f64), keep=torch.empty((nprof, m), **u8),
+               status=torch.empty(nprof, **u8))
+    _native.default_context(y.device.index or 0).obs_whiten_device(
+        nprof, nlev, m, se.data_ptr(), y.data_ptr(), fx.data_ptr(), [k.data_ptr() for k in k_blocks], out["l"].data_ptr(),
+        out["keep"].data_ptr(), out["status"].data_ptr(), d_y_out=out["y"].data_ptr(), d_fx_out=out["fx"].data_ptr(),
+        d_k_out=[k.data_ptr() for k in out["k"]], se_full=se.dim() == 3, stream=stream)
+    return out
+
+
+def _native_obs_whiten_apply(l, keep, mode, vec, block, stream):
+    """One ``mwrt_obs_whiten_apply_device`` call with a stored factor: ``mode`` 0 is L^-1, 1 is L^-T, on ``vec [nprof][m]``
+    and / or ``block [nprof][m][ncol]`` (either may be None) -> (vec_out or None, block_out or None).
+
+    The single place the stored factor reaches the native library: CPU tests substitute the NumPy reference here."""
+    nprof, m = keep.shape
+    vec = None if vec is None else vec.contiguous()
+    block = None if block is None else block.contiguous()
+    v_out = None if vec is None else torch.empty_like(vec)
+    b_out = None if block is None else torch.empty_like(block)
+    ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
+    _native.default_context(keep.device.index or 0).obs_whiten_apply_device(
+        nprof, 1 if block is None else block.shape[-1], m, l.data_ptr(), keep.data_ptr(), mode=mode, d_y=ptr(vec),
+        d_y_out=ptr(v_out), d_k_in=[] if block is None else [block.data_ptr()],
+        d_k_out=[] if block is None else [b_out.data_ptr()], stream=stream)
+    return v_out, b_out
+
+
 class StateBasis:
     """A reduced basis for the state of ``OneDVar``: x = xa + B c with ``b [n][r]`` (n = nblk * nlev, state index = block *
     nlev + level; float64), the prior covariance of the coefficients ``sa_c [r][r]`` and their prior mean ``c_a`` (``[r]``
@@ -251,12 +303,15 @@ class StateBasis:
         if c_a.dim() not in (1, 2) or c_a.shape[-1] != self.r:
             raise ValueError(f"c_a: expected [{self.r}] or [nprof][{self.r}], got {tuple(c_a.shape)}")
         self.b, self.sa_c, self.c_a = b.contiguous(), sa_c.to(torch.float64).contiguous(), c_a.to(torch.float64).contiguous()
+        self.sa_res = None         # [n][n] what the basis leaves out of the prior covariance (``from_covariance`` sets it)
         self._handles = {}
 
     @classmethod
     def from_covariance(cls, sa, r, c_a=None):
         """The leading ``r`` eigenvectors of ``sa [n][n]`` as columns (largest eigenvalue first), ``sa_c = diag(lambda)``.
-        The sign of each column is fixed so that its largest-magnitude component is positive; B^T B = I."""
+        The sign of each column is fixed so that its largest-magnitude component is positive; B^T B = I.  The truncated
+        part ``sa - B diag(lambda) B^T``, symmetrised, is kept as ``sa_res [n][n]`` (formed in torch on the host): what
+        ``OneDVar.representation_error`` turns into the observation-error term of the truncation."""
         sa = torch.as_tensor(sa)
         n = sa.shape[0]
         if sa.dim() != 2 or sa.shape[1] != n or not 1 <= int(r) <= n:
@@ -266,7 +321,10 @@ class StateBasis:
         lam, vec = lam.flip(0)[:r], vec.flip(1)[:, :r]
         top = vec.abs().argmax(dim=0)
         vec = vec * torch.where(vec[top, torch.arange(int(r))] < 0, -1.0, 1.0).to(torch.float64)[None, :]
-        return cls(vec.contiguous().to(sa.device), torch.diag(lam).to(sa.device), c_a)
+        basis = cls(vec.contiguous().to(sa.device), torch.diag(lam).to(sa.device), c_a)
+        res = 0.5 * (s64 + s64.T) - (vec * lam[None, :]) @ vec.T
+        basis.sa_res = (0.5 * (res + res.T)).contiguous().to(sa.device)
+        return basis
 
     def native_handle(self, nblk, device_index=0):
         """(context, basis handle) for ``nblk`` blocks on a device: created on first use, released with the object."""
@@ -441,17 +499,67 @@ class OneDVar:
             return x0.clone() if self.basis is None else x0.reshape(nprof, 1, self.basis.r).clone()
         return (prior.expand(nprof, -1, -1) if prior.dim() == 2 else prior).clone()
 
-    def _post_var_levels(self, k_blocks, u, y, fx, stream):
+    # -- a per-profile Se ---------------------------------------------------------------------------------------------
+    def _per_profile_se(self, se, nprof):
+        """``se=`` of a call, checked: None (the constructor's shared se) or float64 [nprof][m] / [nprof][m][m]."""
+        if se is None:
+            return None
+        m = self.m
+        if not torch.is_tensor(se) or se.dtype != torch.float64 or tuple(se.shape) not in ((nprof, m), (nprof, m, m)):
+            got = f"{se.dtype} {tuple(se.shape)}" if torch.is_tensor(se) else type(se).__name__
+            raise ValueError(f"se: expected a float64 tensor [{nprof}][{m}] or [{nprof}][{m}][{m}], got {got}")
+        return se.contiguous()
+
+    def _whiten(self, se_p, k_blocks, y, fx, stream):
+        """What the update entries are given: ``(k_blocks, y, fx, se, None)`` as they are without a per-profile Se; with one
+        ``(L^-1 K, L^-1 y, L^-1 F, ones(m), w)`` from one ``_native_obs_whiten`` call, w holding l, keep and status."""
+        if se_p is None:
+            return k_blocks, y, fx, self.se, None
+        w = _native_obs_whiten(k_blocks, se_p, y, fx, stream)
+        return w["k"], w["y"], w["fx"], torch.ones(self.m, dtype=torch.float64, device=y.device), w
+
+    @staticmethod
+    def _fail_whitened(w, out):
+        """A profile whose Se_p is not positive definite (whiten status 2) reaches the update with every row dropped, which
+        the update calls status 3 and answers with the prior: make it status 2 with NaN in every floating-point field."""
+        if w is None:
+            return out
+        bad = w["status"] == 2
+        for key, v in out.items():
+            if v is None or key in ("fx", "valid", "keep"):
+                continue
+            mask = bad.reshape((-1,) + (1,) * (v.dim() - 1))
+            if key == "status":
+                out[key] = torch.where(bad, torch.full_like(v, 2), v)
+            elif v.is_floating_point():
+                out[key] = v.masked_fill(mask, float("nan"))
+            else:
+                out[key] = v.masked_fill(mask, 0)
+        return out
+
+    def representation_error(self, z, p, x):
+        """K S_res K^T ``[nprof][m][m]`` at the physical state ``x [nprof][nblk][nlev]``: the observation-error covariance
+        of what the basis leaves out of the prior (``basis.sa_res``, e.g. of ``StateBasis.from_covariance``), from the
+        unprojected K rows at ``x`` -- the instrument's channel rows when there is one.  One K-matrix call and two batched
+        products in torch; add it to the noise covariance and pass the sum as ``se=``."""
+        if self.basis is None or self.basis.sa_res is None:
+            raise ValueError("representation_error needs a basis with sa_res (StateBasis.from_covariance sets it)")
+        _, _, k_blocks = self._observe(z, p, x, project=False)
+        nprof = x.shape[0]
+        k = torch.cat([b.reshape(nprof, self.m, -1) for b in k_blocks], dim=2)
+        return k @ self.basis.sa_res.to(k.device) @ k.transpose(1, 2)
+
+    def _post_var_levels(self, k_blocks, u, y, fx, stream, se=None):
         """diag(B S^_c B^T) ``[nprof][nblk][nlev]``: the posterior variance of the physical state from the posterior covariance
         of the coefficients (``mwrt_oe_gain_device`` + ``mwrt_oe_product_device``, [r][r] per profile) and one contraction."""
-        g = _native_oe_gain(k_blocks, u, self._prior_mean, self._prior_cov, self.se, y, fx, stream)
+        g = _native_oe_gain(k_blocks, u, self._prior_mean, self._prior_cov, self.se if se is None else se, y, fx, stream)
         s_c = _native_oe_product("post_cov", g["gain"], g["keep"], k_blocks, g["ksa"], self._prior_cov, (0, 0), stream)
         s_c = s_c.masked_fill(((g["status"] == 0) | (g["status"] == 2))[:, None, None], float("nan"))
         var = torch.einsum("kj,pji,ki->pk", self._b, s_c, self._b)
         return var.reshape((u.shape[0],) + tuple(self.xa.shape[-2:]))
 
     # -- one Gauss-Newton step ---------------------------------------------------------------------------------------
-    def _observe(self, z, p, x, want_rows=True):
+    def _observe(self, z, p, x, want_rows=True, project=True):
         """One K-matrix call at ``x`` -> (tb [nprof][nang][nf], valid, K blocks in the state's order or None), in what the
         update sees: the operator's own outputs, or with an instrument the channel quantities -- the call then runs on the
         instrument's quadrature grid and ``_native_obs_apply`` reduces the TBs and, when wanted, every block's rows.  With a
@@ -471,7 +579,7 @@ class OneDVar:
         k_blocks = [rows[b] for b in self.blocks] if want_rows else None
         if inst is not None:
             tb, k_blocks = _native_obs_apply(inst, tb, k_blocks, stream)
-        if self.basis is not None and k_blocks is not None:
+        if self.basis is not None and k_blocks is not None and project:
             k_blocks = [_native_basis_project(self.basis, k_blocks, stream)]
         return tb, valid, k_blocks
 
@@ -486,7 +594,7 @@ class OneDVar:
     def _stream(x):
         return torch.cuda.current_stream(x.device).cuda_stream if x.is_cuda else None
 
-    def step(self, z, p, x, y, post_var=True):
+    def step(self, z, p, x, y, post_var=True, se=None):
         """One K-matrix call at ``x`` plus one update, both queued on torch's current stream -- the stream the change of
         variables and the allocations of this method run on too (use ``torch.cuda.stream(...)`` around the call for another).
         Returns ``(x_new, diagnostics)``: diagnostics holds ``status``, ``chi2``, ``dfs``, ``nobs``, ``post_var`` (None with
@@ -495,28 +603,40 @@ class OneDVar:
 
         With a basis ``x`` holds the coefficients ``c [nprof][r]`` and so does ``x_new``: the K-matrix call runs at
         clamp(xa + B c) -- c itself is never clamped -- and ``chi2``, ``dfs`` are those of the step in c.  ``post_var`` is
-        the level-space diag(B S^_c B^T) ``[nprof][nblk][nlev]``, which costs a gain and a product call more."""
+        the level-space diag(B S^_c B^T) ``[nprof][nblk][nlev]``, which costs a gain and a product call more.
+
+        ``se=`` gives every profile its own observation-error covariance, ``[nprof][m]`` or ``[nprof][m][m]`` on the state's
+        device, in place of the constructor's: K, y and F are whitened with its factor (behind the instrument and the basis)
+        and the update runs with Se = 1.  ``fx`` stays the physical F(x); ``whiten_status`` is added (uint8: 1 ok, 2 Se_p not
+        positive definite -- then ``status`` is 2 and x_new and the diagnostics are NaN --, 3 no row kept)."""
         stream = self._stream(x)
         nprof = x.shape[0]
+        se_p = self._per_profile_se(se, nprof)
         if self.basis is not None:
             u = x.reshape(nprof, 1, self.basis.r).contiguous()
             tb, valid, k_blocks = self._observe(z, p, self._state(u))
             fx = tb.reshape(nprof, self.m)
             yv = y.reshape(nprof, self.m).contiguous()
-            out = _native_oe_step(k_blocks, u, self._prior_mean, self._prior_cov, self.se, yv, fx, False, stream)
+            k_w, y_w, fx_w, se_w, w = self._whiten(se_p, k_blocks, yv, fx, stream)
+            out = _native_oe_step(k_w, u, self._prior_mean, self._prior_cov, se_w, y_w, fx_w, False, stream)
             if post_var:
-                out["post_var"] = self._post_var_levels(k_blocks, u, yv, fx, stream)
+                out["post_var"] = self._post_var_levels(k_w, u, y_w, fx_w, stream, se=se_w)
+            out = self._fail_whitened(w, out)
             out["fx"], out["valid"] = fx, valid
+            if w is not None:
+                out["whiten_status"] = w["status"]
             return out.pop("x_new").reshape(x.shape), out
         tb, valid, k_blocks = self._observe(z, p, x)
         fx = tb.reshape(nprof, self.m)
-        out = _native_oe_step(k_blocks, x.contiguous(), self.xa, self.sa, self.se,
-                              y.reshape(nprof, self.m).contiguous(), fx, post_var, stream)
+        k_w, y_w, fx_w, se_w, w = self._whiten(se_p, k_blocks, y.reshape(nprof, self.m).contiguous(), fx, stream)
+        out = self._fail_whitened(w, _native_oe_step(k_w, x.contiguous(), self.xa, self.sa, se_w, y_w, fx_w, post_var, stream))
         x_new = out.pop("x_new")
         out["fx"], out["valid"] = fx, valid
+        if w is not None:
+            out["whiten_status"] = w["status"]
         return x_new, out
 
-    def retrieve(self, z, p, y, x0=None, max_iter=10, tol=0.05) -> Retrieval:
+    def retrieve(self, z, p, y, x0=None, max_iter=10, tol=0.05, se=None) -> Retrieval:
         """Iterates ``step`` from ``x0`` (default: the prior).  After every step humidity and cloud are clamped to >= 0.  A
         profile is frozen -- its state and diagnostics no longer change -- once max |x_new - x| / sqrt(diag Sa) < ``tol``
         over its whole state, or when its step fails (status 0 or 2: the state before that step is kept).  Only the scalar
@@ -526,8 +646,12 @@ class OneDVar:
         With a basis the iteration runs in the coefficients (``x0``: ``[nprof][r]``, default ``c_a``), which are not clamped;
         convergence is max |c_new - c| / sqrt(diag sa_c) < ``tol``.  The steps then skip ``post_var``: the level-space
         diagonal is formed once, at the final states (one K-matrix call, a gain and a product call), so it is the posterior
-        variance at ``Retrieval.x``, not at the state before the last step as ``chi2`` and ``dfs`` are."""
+        variance at ``Retrieval.x``, not at the state before the last step as ``chi2`` and ``dfs`` are.
+
+        ``se=``: a per-profile observation-error covariance as in ``step``; every step whitens its own linearisation.  A
+        profile whose Se_p is not positive definite is frozen as failed at its first step: status 2, NaN diagnostics."""
         nprof = y.shape[0]
+        se_p = self._per_profile_se(se, nprof)
         x = self._start(x0, nprof)
         dev = x.device
         keys = ("chi2", "dfs", "post_var", "status", "nobs") if self.basis is None else ("chi2", "dfs", "status", "nobs")
@@ -536,7 +660,7 @@ class OneDVar:
         iters = torch.zeros(nprof, dtype=torch.int32, device=dev)
         keep = None
         for _ in range(int(max_iter)):
-            x_new, d = self.step(z, p, x, y, post_var=self.basis is None)
+            x_new, d = self.step(z, p, x, y, post_var=self.basis is None, **({} if se_p is None else {"se": se_p}))
             ok = (d["status"] == 1) | (d["status"] == 3)
             x_new = self._bound(torch.where(ok[:, None, None], x_new, x))
             move = ((x_new - x).abs() / self._sigma).amax(dim=(1, 2))
@@ -555,14 +679,16 @@ class OneDVar:
                 break
         if self.basis is not None:
             k_blocks, fx = self._linearise(z, p, x)
-            post_var = self._post_var_levels(k_blocks, x.contiguous(), y.reshape(nprof, self.m).contiguous(), fx, self._stream(x))
+            k_w, y_w, fx_w, se_w, w = self._whiten(se_p, k_blocks, y.reshape(nprof, self.m).contiguous(), fx, self._stream(x))
+            post_var = self._post_var_levels(k_w, x.contiguous(), y_w, fx_w, self._stream(x), se=None if w is None else se_w)
+            post_var = self._fail_whitened(w, dict(post_var=post_var))["post_var"]
             return Retrieval(x=self._state(x), chi2=keep["chi2"], dfs=keep["dfs"], post_var=post_var, status=keep["status"],
                              nobs=keep["nobs"], iterations=iters, converged=converged, coeff=x.reshape(nprof, -1))
         return Retrieval(x=x, chi2=keep["chi2"], dfs=keep["dfs"], post_var=keep["post_var"], status=keep["status"],
                          nobs=keep["nobs"], iterations=iters, converged=converged)
 
     # -- what the step says about itself --------------------------------------------------------------------------------
-    def characterise(self, z, p, x, y, avk=False, post_cov=False, rows=None) -> Characterisation:
+    def characterise(self, z, p, x, y, avk=False, post_cov=False, rows=None, se=None) -> Characterisation:
         """The gain matrix, the averaging-kernel diagonal, the degrees of freedom per block and the split of the posterior
         variance into noise and smoothing error of the undamped step at ``x`` (e.g. ``Retrieval.x``): one K-matrix call at
         ``x``, then ``mwrt_oe_gain_device``, then -- with ``avk`` / ``post_cov`` -- one ``mwrt_oe_product_device`` call each for
@@ -571,7 +697,11 @@ class OneDVar:
         Profiles whose status is 0 or 2 hold NaN in every floating-point field, the products included.
 
         With a basis ``x`` holds the coefficients ``[nprof][r]`` (``Retrieval.coeff``) and everything returned is in
-        coefficient space: n = r, one block."""
+        coefficient space: n = r, one block.
+
+        ``se=``: a per-profile observation-error covariance as in ``step``.  The gain entry and the products run on the
+        whitened linearisation; the gain is then un-whitened (``mwrt_obs_whiten_apply_device``, L^-T), so that ``gain`` is
+        d x^ / d y of the physical observations as without ``se=``.  Every other field is the same in both frames."""
         if self.basis is not None:
             x = x.reshape(x.shape[0], 1, self.basis.r)
         nprof, n = x.shape[0], x.shape[1] * x.shape[2]
@@ -583,14 +713,18 @@ class OneDVar:
                 raise ValueError(f"rows: expected (begin, count) with count >= 1 inside 0 .. {n - 1}, got {rows}")
         stream = self._stream(x)
         k_blocks, fx = self._linearise(z, p, x)
-        g = _native_oe_gain(k_blocks, x.contiguous(), self._prior_mean, self._prior_cov, self.se,
-                            y.reshape(nprof, self.m).contiguous(), fx, stream)
+        k_blocks, y_w, fx, se_w, w = self._whiten(self._per_profile_se(se, nprof), k_blocks,
+                                                  y.reshape(nprof, self.m).contiguous(), fx, stream)
+        g = self._fail_whitened(w, _native_oe_gain(k_blocks, x.contiguous(), self._prior_mean, self._prior_cov, se_w, y_w, fx,
+                                                   stream))
         failed = ((g["status"] == 0) | (g["status"] == 2))[:, None, None]
         prod = {}
         for name, want in (("avk", avk), ("post_cov", post_cov)):
             if want:
                 out = _native_oe_product(name, g["gain"], g["keep"], k_blocks, g["ksa"], self._prior_cov, win, stream)
                 prod[name] = out.masked_fill_(failed, float("nan"))
+        if w is not None:                                   # after the products, which pair the whitened gain with L^-1 K
+            g["gain"] = _native_obs_whiten_apply(w["l"], w["keep"], 1, None, g["gain"], stream)[1]
         return Characterisation(gain=g["gain"], avk_diag=g["avk_diag"], dfs_block=g["dfs_block"], noise_var=g["noise_var"],
                                 smooth_var=g["smooth_var"], status=g["status"], nobs=g["nobs"], keep=g["keep"], **prod,
                                 **({} if self.basis is None else {"coeff": x.reshape(nprof, n)}))
@@ -602,7 +736,8 @@ class OneDVar:
         tb, _, k_blocks = self._observe(z, p, self._state(x))
         return k_blocks, tb.reshape(x.shape[0], self.m)
 
-    def retrieve_lm(self, z, p, y, x0=None, max_iter=20, tol=0.05, gamma0=1.0, up=10.0, down=10.0, gamma_max=1e8) -> Retrieval:
+    def retrieve_lm(self, z, p, y, x0=None, max_iter=20, tol=0.05, gamma0=1.0, up=10.0, down=10.0, gamma_max=1e8,
+                    se=None) -> Retrieval:
         """Levenberg-Marquardt iteration from ``x0`` (default: the prior), per profile and wholly on the device and torch's
         current stream.  With J = r^T Se^-1 r + (x - xa)^T Sa^-1 (x - xa), every iteration
           1  linearises the profiles whose state changed: one K-matrix call, ``prepare`` and the cost J at x;
@@ -619,8 +754,15 @@ class OneDVar:
 
         With a basis x is the coefficient vector c throughout (``x0``: ``[nprof][r]``, default ``c_a``), J's prior term is
         (c - c_a)^T sa_c^-1 (c - c_a), trials are not clamped and the forward model runs at clamp(xa + B c); ``post_var`` is
-        the level-space diag(B S^_c B^T) at the final states."""
+        the level-space diag(B S^_c B^T) at the final states.
+
+        ``se=``: a per-profile observation-error covariance as in ``step``.  Every linearisation is whitened (the whole
+        batch: a profile whose state did not move gets the same factor bit for bit), F(x_trial) is whitened with the factor
+        and the rows of the linearisation it is compared on (``mwrt_obs_whiten_apply_device``, L^-1), and J is that of Se_p.
+        A profile whose Se_p is not positive definite is frozen as failed: status 2, NaN diagnostics."""
         nprof, m = y.shape[0], self.m
+        se_p = self._per_profile_se(se, nprof)
+        se_w, w, y_w = self.se, None, None
         x = self._start(x0, nprof).contiguous()
         xa, sa = self._prior_mean, self._prior_cov
         dev, stream = x.device, self._stream(x)
@@ -641,17 +783,20 @@ class OneDVar:
         for _ in range(int(max_iter)):
             if relin:
                 k_blocks, fx = self._linearise(z, p, x)
+                k_blocks, y_w, fx, se_w, w = self._whiten(se_p, k_blocks, yv, fx, stream)
                 mask = (active & stale).to(torch.uint8)
-                _native_oe_lm_prepare(k_blocks, x, xa, sa, self.se, yv, fx, lin, mask, stream)
-                _native_oe_cost(x, xa, self.se, yv, fx, lin["keep"], self.sa_inv, cost, mask, stream)
+                _native_oe_lm_prepare(k_blocks, x, xa, sa, se_w, y_w, fx, lin, mask, stream)
+                _native_oe_cost(x, xa, se_w, y_w, fx, lin["keep"], self.sa_inv, cost, mask, stream)
                 stale = torch.zeros_like(stale)
                 active = active & (lin["lin_status"] == 1)
             mask = active.to(torch.uint8)
-            _native_oe_lm_solve(k_blocks, x, xa, sa, self.se, gamma, lin, trial, mask, stream)
+            _native_oe_lm_solve(k_blocks, x, xa, sa, se_w, gamma, lin, trial, mask, stream)
             ok = active & (trial["status"] == 1)
             x_try = self._bound(torch.where(ok[:, None, None], trial["x_new"], x)).contiguous()
             fx_try = self.forward(z, p, self._state(x_try))[0].reshape(nprof, m)
-            _native_oe_cost(x_try, xa, self.se, yv, fx_try, lin["keep"], self.sa_inv, cost_try, mask, stream)
+            if w is not None:
+                fx_try = _native_obs_whiten_apply(w["l"], w["keep"], 0, fx_try, None, stream)[0]
+            _native_oe_cost(x_try, xa, se_w, y_w, fx_try, lin["keep"], self.sa_inv, cost_try, mask, stream)
             accept = ok & (cost_try <= cost)
             move = ((x_try - x).abs() / self._sigma).amax(dim=(1, 2))
             iters = iters + active.to(torch.int32)
@@ -668,10 +813,14 @@ class OneDVar:
                 break
         if relin:
             k_blocks, fx = self._linearise(z, p, x)
-        d = _native_oe_step(k_blocks, x, xa, sa, self.se, yv, fx, self.basis is None, stream)
+            k_blocks, y_w, fx, se_w, w = self._whiten(se_p, k_blocks, yv, fx, stream)
+        d = _native_oe_step(k_blocks, x, xa, sa, se_w, y_w, fx, self.basis is None, stream)
+        if self.basis is not None:
+            d["post_var"] = self._post_var_levels(k_blocks, x, y_w, fx, stream, se=None if w is None else se_w)
+        d = self._fail_whitened(w, d)
         if self.basis is not None:
             return Retrieval(x=self._state(x), chi2=d["chi2"], dfs=d["dfs"],
-                             post_var=self._post_var_levels(k_blocks, x, yv, fx, stream), status=d["status"], nobs=d["nobs"],
+                             post_var=d["post_var"], status=d["status"], nobs=d["nobs"],
                              iterations=iters, converged=converged, cost=cost, gamma=gamma, coeff=x.reshape(nprof, -1))
         return Retrieval(x=x, chi2=d["chi2"], dfs=d["dfs"], post_var=d["post_var"], status=d["status"], nobs=d["nobs"],
                          iterations=iters, converged=converged, cost=cost, gamma=gamma)
