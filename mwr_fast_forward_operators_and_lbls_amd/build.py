@@ -1,14 +1,9 @@
 """Build recipe for libmwrt.so (hipcc, gfx950 only, in-tree so the .so travels with the repo).
 
-Thirteen translation units -- the C-ABI host side (csrc/mwrt.hip, no device code in it), the kernel instantiations of
-each frequency-chunk width (csrc/mwrt_inst.hip with -DMWRT_INST_NFC=8|14|16), the device K-matrix kernels
-(csrc/mwrt_tl.hip), their ray-traced form (csrc/mwrt_ray.hip), the spectroscopic-parameter Jacobian (csrc/mwrt_par.hip), the optimal-estimation step (csrc/mwrt_oe.hip), its
-Levenberg-Marquardt split (csrc/mwrt_oe_lm.hip), its characterisation (csrc/mwrt_oe_char.hip), the instrument
-operator (csrc/mwrt_obs.hip), the non-template
-kernels (csrc/mwrt_aux.hip) and the host-only launch planning
-(csrc/mwrt_plan.cpp, no HIP in it) -- and a fourteenth, the reduced-basis state map (csrc/mwrt_basis.hip), are compiled in
-parallel and linked into one shared library; so is a fifteenth, the pre-whitening with a per-profile observation-error
-covariance (csrc/mwrt_whiten.hip)."""
+UNITS lists the translation units, each a source of csrc/ with the defines it is compiled under: the two C-ABI host units
+(mwrt.hip and mwrt_retrieval.hip, no device code in either), one kernel unit per stage (mwrt_inst.hip once per
+frequency-chunk width), and the host-only planning and argument stage (mwrt_plan.cpp and mwrt_records.cpp, no HIP in
+them).  They are compiled in parallel and linked into one shared library."""
 from __future__ import annotations
 
 import concurrent.futures
@@ -33,11 +28,19 @@ BASIS = os.path.join(CSRC, "mwrt_basis.hip")
 WHITEN = os.path.join(CSRC, "mwrt_whiten.hip")
 AUX = os.path.join(CSRC, "mwrt_aux.hip")
 PLAN = os.path.join(CSRC, "mwrt_plan.cpp")
+RETRIEVAL = os.path.join(CSRC, "mwrt_retrieval.hip")
+RECORDS = os.path.join(CSRC, "mwrt_records.cpp")
+INST_WIDTHS = (8, 14, 16)
+#: the translation units of the library: (source, extra defines)
+UNITS = [(SRC, []), (RETRIEVAL, [])] + [(INST, [f"-DMWRT_INST_NFC={n}"]) for n in INST_WIDTHS] + [
+    (unit, []) for unit in (TL, RAY, PAR, OE, OE_LM, OE_CHAR, OBS, BASIS, WHITEN, AUX, PLAN, RECORDS)]
+#: the units that hold the C entry points: host code only
+HOST_UNITS = (SRC, RETRIEVAL)
+MAX_COMPILE_WORKERS = 16
 # what the library is built from: every file of csrc/ (a new header counts without being named here) and the public header
 DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [os.path.join(ROOT, "include", "mwrt.h")]
 LIB = os.path.join(HERE, "libmwrt.so")
 OBJ_DIR = os.path.join(HERE, "build")
-INST_WIDTHS = (8, 14, 16)
 
 
 def hipcc_path() -> str:
@@ -64,19 +67,8 @@ def build_native(force: bool = False, verbose: bool = False, extra_flags=(), out
     tag = str(os.getpid())
     common = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
               *extra_flags]
-    jobs = [(SRC, os.path.join(OBJ_DIR, f"mwrt.{tag}.o"), [])]
-    jobs += [(INST, os.path.join(OBJ_DIR, f"mwrt_inst{n}.{tag}.o"), [f"-DMWRT_INST_NFC={n}"]) for n in INST_WIDTHS]
-    jobs.append((TL, os.path.join(OBJ_DIR, f"mwrt_tl.{tag}.o"), []))
-    jobs.append((RAY, os.path.join(OBJ_DIR, f"mwrt_ray.{tag}.o"), []))
-    jobs.append((PAR, os.path.join(OBJ_DIR, f"mwrt_par.{tag}.o"), []))
-    jobs.append((OE, os.path.join(OBJ_DIR, f"mwrt_oe.{tag}.o"), []))
-    jobs.append((OE_LM, os.path.join(OBJ_DIR, f"mwrt_oe_lm.{tag}.o"), []))
-    jobs.append((OE_CHAR, os.path.join(OBJ_DIR, f"mwrt_oe_char.{tag}.o"), []))
-    jobs.append((OBS, os.path.join(OBJ_DIR, f"mwrt_obs.{tag}.o"), []))
-    jobs.append((BASIS, os.path.join(OBJ_DIR, f"mwrt_basis.{tag}.o"), []))
-    jobs.append((WHITEN, os.path.join(OBJ_DIR, f"mwrt_whiten.{tag}.o"), []))
-    jobs.append((AUX, os.path.join(OBJ_DIR, f"mwrt_aux.{tag}.o"), []))
-    jobs.append((PLAN, os.path.join(OBJ_DIR, f"mwrt_plan.{tag}.o"), []))
+    jobs = [(src, os.path.join(OBJ_DIR, f"{os.path.splitext(os.path.basename(src))[0]}.{i}.{tag}.o"), defs)
+            for i, (src, defs) in enumerate(UNITS)]
 
     def compile_one(job):
         src, obj, defs = job
@@ -87,7 +79,7 @@ def build_native(force: bool = False, verbose: bool = False, extra_flags=(), out
         return obj
 
     try:
-        with concurrent.futures.ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1)) as pool:
+        with concurrent.futures.ThreadPoolExecutor(max_workers=min(len(jobs), MAX_COMPILE_WORKERS, os.cpu_count() or 1)) as pool:
             objs = list(pool.map(compile_one, jobs))
         link = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib + ".tmp", *objs]
         if verbose:

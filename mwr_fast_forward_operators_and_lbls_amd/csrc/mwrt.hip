@@ -1,21 +1,18 @@
-// mwrt.hip -- C-ABI host side of libmwrt.so (declarations + reference citations: include/mwrt.h).
+// mwrt.hip -- C-ABI host side of libmwrt.so (declarations + reference citations: include/mwrt.h): context and model
+// lifecycle, the TB, absorption, layer-optical-depth, Jacobian and parameter-Jacobian entries, and the utilities.  The
+// entries that take a versioned record, and the handles they use, are csrc/mwrt_retrieval.hip.
 //
 // HIP only: there is no CPU fallback in this library.  Without a GPU mwrt_device_count()
 // returns 0 and mwrt_create() fails with MWRT_ERR_NO_DEVICE.
 //
 // Host code only: streams, caches, argument checks and the choice of launch.  Every kernel lives in another unit
-// (mwrt_inst.hip, mwrt_tl.hip, mwrt_ray.hip, mwrt_par.hip, mwrt_oe.hip, mwrt_oe_lm.hip, mwrt_oe_char.hip, mwrt_obs.hip, mwrt_basis.hip, mwrt_aux.hip) and is reached
-// through the launchers the headers below declare.
+// (mwrt_inst.hip, mwrt_tl.hip, mwrt_ray.hip, mwrt_par.hip, mwrt_aux.hip) and is reached through the launchers the headers
+// below declare.
+#include "mwrt_host.hip.h"
 #include "mwrt_args.hip.h"
 #include "mwrt_tl.hip.h"
 #include "mwrt_ray.hip.h"
 #include "mwrt_par.hip.h"
-#include "mwrt_oe.hip.h"
-#include "mwrt_oe_lm.hip.h"
-#include "mwrt_oe_char.hip.h"
-#include "mwrt_obs.hip.h"
-#include "mwrt_basis.hip.h"
-#include "mwrt_whiten.hip.h"
 #include "mwrt_plan.h"
 
 #include <cmath>
@@ -31,158 +28,10 @@
 using namespace mwrt;
 
 namespace {
-
 thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
-
-#define HIP_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess)                                                                    \
-      return fail(e_ == hipErrorOutOfMemory ? MWRT_ERR_OUT_OF_MEMORY : MWRT_ERR_HIP,         \
-                  std::string(#expr) + ": " + hipGetErrorString(e_));                        \
-  } while (0)
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) { hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) return e; }
-    size_t want = bytes + bytes / 8 + 256;
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-  template <class T> T* as() { return static_cast<T*>(p); }
-};
-
-// Content-keyed, immutable device blobs: the small per-call parameter arrays (frq, air mass, elevations), the line
-// masks of a frequency list and its window tables.  The key is (model id or 0, a small integer tag, doubles).  A blob is
-// never overwritten or freed while the context lives (bar LRU eviction behind a device-wide drain), so launches still
-// queued on ANY stream and captured hipGraphs keep reading valid memory.
-class DeviceCache {
- public:
-  struct Blob { const char* dev = nullptr; int count = 0; };     // count: what the builder returned (records in the blob)
-  explicit DeviceCache(size_t capacity) : capacity_(capacity) {}
-  // The blob of (model, tag, key[0..n)).  A hit is one linear memcmp scan: it never evicts or synchronises.  On a miss
-  // `build(std::vector<char>* host)` fills the host bytes and returns the count; uploads go through `copy_stream`
-  // (never a capturing stream).
-  template <class Build>
-  hipError_t get(uint64_t model, int tag, const double* key, int n, hipStream_t copy_stream, Build build, Blob* out) {
-    for (Entry& e : entries_)
-      if (e.model == model && e.tag == tag && (int)e.key.size() == n &&
-          std::memcmp(e.key.data(), key, sizeof(double) * (size_t)n) == 0) {
-        // least recently USED goes first: a hit is stamped anew, so a warm-up call keeps what it touched (a later miss of the
-        // same sequence must not evict it -- the eviction drains the device, which a capturing stream refuses)
-        e.stamp = ++clock_;
-        *out = Blob{e.dev, e.count};
-        return hipSuccess;
-      }
-    std::vector<char> host;
-    const int count = build(&host);
-    return insert(model, tag, key, n, host, count, copy_stream, out);
-  }
-  void release() { for (Entry& e : entries_) (void)hipFree(e.dev); entries_.clear(); }
-  // the caller has drained the device: launches on any stream may still read the blobs
-  void drop_model(uint64_t model) {
-    for (size_t i = entries_.size(); i-- > 0;)
-      if (entries_[i].model == model) { (void)hipFree(entries_[i].dev); entries_.erase(entries_.begin() + (long)i); }
-  }
-
- private:
-  struct Entry { uint64_t model; int tag; std::vector<double> key; char* dev; int count; unsigned long stamp; };
-  hipError_t insert(uint64_t model, int tag, const double* key, int n, const std::vector<char>& host, int count,
-                    hipStream_t copy_stream, Blob* out) {
-    if (entries_.size() >= capacity_) {
-      // bounded: evict the least recently used blob -- only after everything queued on the device has drained
-      hipError_t e = hipDeviceSynchronize();
-      if (e != hipSuccess) return e;
-      size_t lru = 0;
-      for (size_t i = 1; i < entries_.size(); ++i) if (entries_[i].stamp < entries_[lru].stamp) lru = i;
-      (void)hipFree(entries_[lru].dev);
-      entries_.erase(entries_.begin() + (long)lru);
-    }
-    Entry ne{model, tag, std::vector<double>(key, key + n), nullptr, count, 0};
-    hipError_t e = hipMalloc((void**)&ne.dev, host.empty() ? 1 : host.size());
-    if (e != hipSuccess) return e;
-    // a fresh buffer nobody reads yet: copy on the context's own stream and wait for it, so the
-    // bytes are in HBM before any stream (the caller's included) can launch a reader
-    e = hipMemcpyAsync(ne.dev, host.data(), host.size(), hipMemcpyHostToDevice, copy_stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(copy_stream);
-    if (e != hipSuccess) { (void)hipFree(ne.dev); return e; }
-    ne.stamp = ++clock_;
-    entries_.push_back(std::move(ne));
-    *out = Blob{entries_.back().dev, count};
-    return hipSuccess;
-  }
-  std::vector<Entry> entries_;
-  size_t capacity_;
-  unsigned long clock_ = 0;
-};
-
 }  // namespace
 
-struct mwrt_context {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int lds_max = 65536;
-  int num_cus = 256;            // compute units of the device (MI355X: 256)
-  // small per-call parameter arrays (frq, airmass, elevations): content-keyed device copies
-  DeviceCache frq_cache{32}, am_cache{32}, elev_cache{32};
-  int absorption_mode = 0;      // 0 auto, 1 direct, 2 windowed
-  int chunk_width = 0;          // 0 auto, 8 / 14 / 16: frequencies per workgroup of the fused TB kernel (mwrt_set_chunk_width)
-  // fine-grid absorption: window descriptors + Lagrange matrices per (model, frequency list)
-  DeviceCache win_cache{16};
-  // line classification of every frequency chunk (LineMasks), per (model, frequency list, chunk width): depends on the
-  // frequencies and the table only, so the host computes it once instead of every workgroup voting on it
-  DeviceCache mask_cache{64};
-  // ray-tracing workspace: path factors [nprof][nang][nlev] and the per-profile ducting flag
-  DevBuf d_amf, d_duct;
-  // fine-grid two-kernel path: materialised absorption of one profile batch (awet | adry)
-  DevBuf d_alpha;
-  size_t alpha_batch_bytes = (size_t)4 << 30;   // 4 GiB of a 288-GB card: configs[4]'s per-GPU share is one batch
-  // the two workspaces above are shared by consecutive calls: a call that uses one on a different stream than
-  // the previous user first waits (on the device) for that user's last kernel
-  hipEvent_t ws_event = nullptr;
-  hipStream_t ws_stream = nullptr;
-  bool ws_used = false;
-  // device K-matrix path: the six tangent-linear absorption arrays + per-profile flags (grown only, never shrunk;
-  // handed over between streams like d_amf / d_alpha)
-  DevBuf d_jac;
-  // spectroscopic-parameter Jacobian: d alpha / d b of one group of parameters (grown only, handed over like d_jac) and
-  // the content-keyed device copies of the parameter lists
-  DevBuf d_par;
-  DeviceCache par_cache{32};
-  // staging for the host-buffer entry points
-  DevBuf d_in, d_out, d_valid, d_ex;
-  // timing: a ring of hipEvent pairs recorded around every kernel launch, on the launch stream
-  bool timing = false;
-  std::vector<hipEvent_t> ev0, ev1;
-  long ev_count = 0;
-  // instrument operators created on this context and not yet destroyed: mwrt_destroy frees their device copies
-  std::vector<mwrt_obs*> obs_live;
-  // reduced bases created on this context and not yet destroyed: the same rule
-  std::vector<mwrt_basis*> basis_live;
-};
-constexpr int TIMING_RING = 512;
-
-struct mwrt_obs {
-  mwrt_context* ctx = nullptr;  // null once the context is gone: the handle then only waits for mwrt_obs_destroy
-  int32_t m_in = 0, m_out = 0;
-  void* d_blob = nullptr;       // w [nnz] | row_ptr [m_out + 1] | col [nnz], one allocation
-  const double* d_w = nullptr;
-  const int32_t* d_row_ptr = nullptr;
-  const int32_t* d_col = nullptr;
-};
-
-struct mwrt_basis {
-  mwrt_context* ctx = nullptr;  // null once the context is gone: the handle then only waits for mwrt_basis_destroy
-  int32_t nblk = 0, nlev = 0, r = 0;
-  double* d_b = nullptr;        // [nblk * nlev][r]
-};
+int mwrt::fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 struct mwrt_model {
   ModelFlat* d_desc = nullptr;
@@ -236,14 +85,6 @@ template <class F> struct ScopeExit {
 };
 template <class F> ScopeExit<F> on_scope_exit(F fn) { return ScopeExit<F>{fn}; }
 
-// `stream` argument of the *_device entry points: NULL = the context's own (non-blocking) stream,
-// MWRT_STREAM_LEGACY = the caller's legacy default stream (hipStream_t 0), else the handle itself
-hipStream_t resolve_stream(const mwrt_context* c, void* stream) {
-  if (!stream) return c->stream;
-  if (stream == MWRT_STREAM_LEGACY) return (hipStream_t) nullptr;
-  return (hipStream_t)stream;
-}
-
 int check_common(const mwrt_context* c, const mwrt_model* m, int64_t nprof, int32_t nlev, int32_t nf) {
   if (!c || !m) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context or model");
   if (nprof < 0 || nf < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "nprof < 0 or nf < 1");
@@ -259,15 +100,6 @@ hipError_t grow_behind_drain(DevBuf& b, size_t bytes) {
   if (bytes <= b.cap) return hipSuccess;
   const hipError_t e = hipDeviceSynchronize();
   return e != hipSuccess ? e : b.reserve(bytes);
-}
-
-// one kernel launch (`launch()` -> hipError_t), between a pair of the ring's events when timing is on
-template <class F> int timed(mwrt_context* c, hipStream_t st, F launch) {
-  if (c->timing) (void)hipEventRecord(c->ev0[c->ev_count % TIMING_RING], st);
-  const hipError_t e = launch();
-  if (c->timing) { (void)hipEventRecord(c->ev1[c->ev_count % TIMING_RING], st); c->ev_count++; }
-  HIP_TRY(e);
-  return MWRT_OK;
 }
 
 #if MWRT_PHASE_CLOCK
@@ -604,168 +436,6 @@ int jacobian_vars_host(mwrt_context* c, const mwrt_model* m, int64_t nprof, int3
 
 }  // namespace
 
-namespace {
-
-// One preamble for the three optimal-estimation entry families (the step, its Levenberg-Marquardt split, its
-// characterisation).  They take no model, so it is not begin_call, but it keeps that order: arguments, then limits, then
-// the device and the stream.  What differs between the records is described here; what differs between the entries -- the
-// pointers they require, the LDS plan they check, the launch -- they pass in.
-struct OeRecord {
-  const char* name;                        // "mwrt_oe_step", as the refusal messages spell it
-  size_t fixed;                            // struct_size must reach this ...
-  const char* fixed_what;                  // ... "the fixed part (through reserved)"
-  const char* reserved_what = "reserved";
-  size_t ints = 0, ints_end = 0;           // a group of int32 fields beyond the fixed part; every other field there is a pointer
-};
-inline int32_t oe_reserved(const mwrt_oe_step& r) { return r.reserved; }
-inline int32_t oe_reserved(const mwrt_oe_lm& r) { return r.reserved; }
-inline int32_t oe_reserved(const mwrt_oe_char& r) { return r.reserved | r.reserved2; }
-
-// The caller's record up to its struct_size; fields at or beyond it stay NULL / 0, and so does a field the size ends inside.
-template <class R> R oe_prefix(const R* s, const OeRecord& rec) {
-  R r{};
-  size_t len = s->struct_size < sizeof r ? s->struct_size : sizeof r;
-  len -= (len > rec.ints && len < rec.ints_end) ? (len - rec.ints) % sizeof(int32_t) : (len - rec.fixed) % sizeof(void*);
-  std::memcpy(&r, s, len);
-  return r;
-}
-
-// check(r): the entry's own argument checks (MWRT_OK or its fail(...)).  plan(r, o): o holds the fields every record has
-// (K blocks, x, xa, Sa, Se, y, F, nobs, status, the dimensions); the entry adds its own, checks its LDS plan and returns
-// MWRT_OK or its fail(...).  launch(st): the hipError_t of the launch.
-template <class R, class Check, class Plan, class Launch>
-int oe_call(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const R* s, void* stream, const OeRecord& rec,
-            Check check, Plan plan, Launch launch) {
-  const std::string name = rec.name;
-  if (!c || !s) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context or " + name);
-  if (s->struct_size < rec.fixed)
-    return fail(MWRT_ERR_INVALID_ARGUMENT, name + ".struct_size too small for " + rec.fixed_what);
-  const R r = oe_prefix(s, rec);
-  if (nprof < 0 || nlev < 1 || m < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "nprof < 0, nlev < 1 or m < 1");
-  if (r.nblk < 1 || r.nblk > 4) return fail(MWRT_ERR_INVALID_ARGUMENT, name + ".nblk must be 1 .. 4");
-  if (oe_reserved(r) != 0) return fail(MWRT_ERR_INVALID_ARGUMENT, name + "." + rec.reserved_what + " must be 0");
-  if (const int rc = check(r)) return rc;
-  if (nlev > MWRT_MAX_LEVELS)
-    return fail(MWRT_ERR_UNSUPPORTED, "nlev > MWRT_MAX_LEVELS (" + std::to_string(MWRT_MAX_LEVELS) + ")");
-  if (m > MWRT_OE_MAX_M)
-    return fail(MWRT_ERR_UNSUPPORTED, "m > MWRT_OE_MAX_M (" + std::to_string(MWRT_OE_MAX_M) + " observations per profile: G lives in LDS)");
-  if (nprof > 2147483647LL) return fail(MWRT_ERR_UNSUPPORTED, "nprof exceeds grid limit");
-  oe::OeArgs o{};
-  o.k0 = r.d_k[0]; o.k1 = r.nblk > 1 ? r.d_k[1] : nullptr; o.k2 = r.nblk > 2 ? r.d_k[2] : nullptr;
-  o.k3 = r.nblk > 3 ? r.d_k[3] : nullptr;
-  o.x = r.d_x; o.xa = r.d_xa; o.sa = r.d_sa; o.se = r.d_se; o.y = r.d_y; o.fx = r.d_fx;
-  o.nobs = r.d_nobs; o.status = r.d_status;
-  o.nblk = r.nblk; o.nlev = nlev; o.m = m; o.n = r.nblk * nlev;
-  o.xa_per_profile = r.xa_per_profile != 0; o.se_full = r.se_full != 0;
-  if (const int rc = plan(r, o)) return rc;
-  if (nprof == 0) return MWRT_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = resolve_stream(c, stream);
-  return timed(c, st, [&] { return launch(st); });
-}
-
-const OeRecord OE_STEP_RECORD{"mwrt_oe_step", offsetof(mwrt_oe_step, d_status) + sizeof(uint8_t*),
-                              "the required fields (through d_status)"};
-const OeRecord OE_LM_RECORD{"mwrt_oe_lm", offsetof(mwrt_oe_lm, d_k), "the fixed part (through reserved)"};
-const OeRecord OE_CHAR_RECORD{"mwrt_oe_char", offsetof(mwrt_oe_char, d_k), "the fixed part (through reserved)",
-                              "reserved and reserved2", offsetof(mwrt_oe_char, product), offsetof(mwrt_oe_char, d_out)};
-
-// The three entries of the Levenberg-Marquardt split (csrc/mwrt_oe_lm.hip) share one record and differ in the pointers
-// they require and the kernel they launch.
-enum class LmCall { Prepare, Solve, Cost };
-
-int oe_lm_call(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_lm* s, void* stream, LmCall call) {
-  lm::LmArgs a{};
-  return oe_call(c, nprof, nlev, m, s, stream, OE_LM_RECORD,
-    [&](const mwrt_oe_lm& r) {
-      bool buffers = r.d_x && r.d_xa && r.d_se;
-      const bool lin = r.d_g0 && r.d_r && r.d_kdx && r.d_keep && r.d_lin_status;
-      if (call != LmCall::Cost) {
-        buffers = buffers && r.d_sa && lin;
-        for (int b = 0; b < r.nblk; ++b) buffers = buffers && r.d_k[b];
-      }
-      if (call == LmCall::Prepare) buffers = buffers && r.d_y && r.d_fx;
-      if (call == LmCall::Solve) buffers = buffers && r.d_gamma && r.d_x_new && r.d_status;
-      if (call == LmCall::Cost) buffers = buffers && r.d_y && r.d_fx && r.d_keep && r.d_sa_inv && r.d_cost;
-      return buffers ? MWRT_OK : fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
-    },
-    [&](const mwrt_oe_lm& r, const oe::OeArgs& o) {
-      a.o = o;
-      a.o.x_new = r.d_x_new; a.o.chi2 = r.d_chi2;
-      a.gamma = r.d_gamma; a.g0 = r.d_g0; a.r = r.d_r; a.kdx = r.d_kdx; a.keep = r.d_keep; a.lin_status = r.d_lin_status;
-      a.active = r.d_active; a.sa_inv = r.d_sa_inv; a.cost = r.d_cost; a.cost_obs = r.d_cost_obs; a.cost_prior = r.d_cost_prior;
-      const size_t lds = call == LmCall::Prepare ? oe::lds_plan(m, o.n).total_bytes
-                       : call == LmCall::Solve ? lm::solve_plan(m, o.n).total_bytes
-                                               : lm::cost_plan(m, o.n, o.se_full).total_bytes;
-      return lds <= (size_t)c->lds_max ? MWRT_OK
-           : fail(MWRT_ERR_UNSUPPORTED, "the optimal-estimation step needs more LDS than this device has per workgroup");
-    },
-    [&](hipStream_t st) {
-      return call == LmCall::Prepare ? lm::launch_lm_prepare(a, nprof, st)
-           : call == LmCall::Solve ? lm::launch_lm_solve(a, nprof, st)
-                                   : lm::launch_lm_cost(a, nprof, st);
-    });
-}
-
-// The two entries of the characterisation (csrc/mwrt_oe_char.hip) share one record.
-enum class CharCall { Gain, Product };
-
-int oe_char_call(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_char* s, void* stream, CharCall call) {
-  oec::GainArgs g{};
-  oec::ProductArgs a{};
-  return oe_call(c, nprof, nlev, m, s, stream, OE_CHAR_RECORD,
-    [&](const mwrt_oe_char& r) {
-      if (call == CharCall::Gain) {
-        bool buffers = r.d_x && r.d_xa && r.d_sa && r.d_se && r.d_y && r.d_fx && r.d_status;
-        for (int b = 0; b < r.nblk; ++b) buffers = buffers && r.d_k[b];
-        if (!buffers) return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
-        if (!(r.d_gain || r.d_ksa || r.d_keep || r.d_avk_diag || r.d_dfs_block || r.d_noise_var || r.d_smooth_var || r.d_nobs))
-          return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_gain_device: no output asked for beside d_status");
-        return (int)MWRT_OK;
-      }
-      if (r.product != MWRT_OE_PRODUCT_AVK && r.product != MWRT_OE_PRODUCT_POST_COV)
-        return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_char.product must be MWRT_OE_PRODUCT_AVK or MWRT_OE_PRODUCT_POST_COV");
-      bool buffers = r.d_gain && r.d_keep && r.d_out;
-      if (r.product == MWRT_OE_PRODUCT_AVK)
-        for (int b = 0; b < r.nblk; ++b) buffers = buffers && r.d_k[b];
-      else
-        buffers = buffers && r.d_ksa && r.d_sa;
-      if (!buffers) return fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
-      const int64_t n64 = (int64_t)r.nblk * nlev;        // nlev is not yet held to its limit here
-      if (r.row_begin < 0 || r.row_count < 0 || (r.row_count == 0 && r.row_begin != 0) ||
-          (int64_t)r.row_begin + r.row_count > n64)
-        return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_oe_char: rows row_begin .. row_begin + row_count - 1 must lie in 0 .. n - 1 "
-                                               "(row_count 0 with row_begin 0: all rows)");
-      return (int)MWRT_OK;
-    },
-    [&](const mwrt_oe_char& r, const oe::OeArgs& o) {
-      const int n = o.n;
-      if (call == CharCall::Gain) {
-        g.o = o;
-        g.gain = r.d_gain; g.ksa = r.d_ksa; g.keep = r.d_keep; g.avk_diag = r.d_avk_diag; g.noise_var = r.d_noise_var;
-        g.smooth_var = r.d_smooth_var; g.dfs_block = r.d_dfs_block;
-        return oec::gain_plan(m).total_bytes <= (size_t)c->lds_max ? MWRT_OK
-             : fail(MWRT_ERR_UNSUPPORTED, "the optimal-estimation gain needs more LDS than this device has per workgroup");
-      }
-      a.left = r.d_gain; a.keep = r.d_keep; a.out = r.d_out;
-      if (r.product == MWRT_OE_PRODUCT_AVK) {
-        a.r0 = o.k0; a.r1 = o.k1; a.r2 = o.k2; a.r3 = o.k3;
-        a.rcols = nlev;
-      } else {
-        a.r0 = r.d_ksa; a.rcols = n; a.sa = r.d_sa;
-      }
-      a.m = m; a.n = n; a.row_begin = r.row_begin; a.rows = r.row_count == 0 ? n : r.row_count;
-      a.tiles_x = (n + oec::TILE - 1) / oec::TILE; a.tiles_y = (a.rows + oec::TILE - 1) / oec::TILE;
-      return (int64_t)a.tiles_x * a.tiles_y * nprof <= 2147483647LL ? MWRT_OK
-           : fail(MWRT_ERR_UNSUPPORTED, "mwrt_oe_product_device: more than 2147483647 tiles of 64 x 64 in one call (use row windows)");
-    },
-    [&](hipStream_t st) {
-      return call == CharCall::Gain ? oec::launch_char_gain(g, nprof, st) : oec::launch_char_product(a, nprof, st);
-    });
-}
-
-}  // namespace
-
 extern "C" {
 
 int mwrt_version(void) { return MWRT_VERSION; }
@@ -815,13 +485,9 @@ int mwrt_destroy(mwrt_context* c) {
   c->d_par.release(); c->par_cache.release();
   c->d_in.release(); c->d_out.release();
   c->d_valid.release(); c->d_ex.release();
-  for (mwrt_obs* op : c->obs_live) {                    // the handles stay valid for mwrt_obs_destroy; apply refuses them
-    (void)hipFree(op->d_blob);
-    op->d_blob = nullptr; op->d_w = nullptr; op->d_row_ptr = nullptr; op->d_col = nullptr; op->ctx = nullptr;
-  }
-  for (mwrt_basis* bs : c->basis_live) {                // likewise: valid for mwrt_basis_destroy, refused by project / expand
-    (void)hipFree(bs->d_b);
-    bs->d_b = nullptr; bs->ctx = nullptr;
+  for (DeviceHandle* h : c->handles_live) {             // the handles stay valid for their *_destroy; every entry refuses them
+    (void)hipFree(h->d_blob);
+    h->d_blob = nullptr; h->ctx = nullptr;
   }
   for (hipEvent_t e : c->ev0) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev1) (void)hipEventDestroy(e);
@@ -1417,387 +1083,6 @@ int mwrt_set_absorption_mode(mwrt_context* c, int mode) {
   if (!c || mode < 0 || mode > 2) return fail(MWRT_ERR_INVALID_ARGUMENT, "mode must be 0, 1 or 2");
   c->absorption_mode = mode;
   return MWRT_OK;
-}
-
-/* The optimal-estimation step (csrc/mwrt_oe.hip): oe_call above is the preamble; the required pointers, the LDS plan and
- * the launch are the entry's own. */
-size_t mwrt_oe_step_size(void) { return sizeof(mwrt_oe_step); }
-
-int mwrt_oe_step_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_step* s, void* stream) {
-  oe::OeArgs a{};
-  return oe_call(c, nprof, nlev, m, s, stream, OE_STEP_RECORD,
-    [&](const mwrt_oe_step& r) {
-      bool buffers = r.d_x && r.d_xa && r.d_sa && r.d_se && r.d_y && r.d_fx && r.d_x_new && r.d_status;
-      for (int b = 0; b < r.nblk; ++b) buffers = buffers && r.d_k[b];
-      return buffers ? MWRT_OK : fail(MWRT_ERR_INVALID_ARGUMENT, "null buffer");
-    },
-    [&](const mwrt_oe_step& r, const oe::OeArgs& o) {
-      a = o;
-      a.x_new = r.d_x_new; a.chi2 = r.d_chi2; a.dfs = r.d_dfs; a.post_var = r.d_post_var;
-      return oe::lds_plan(m, a.n).total_bytes <= (size_t)c->lds_max ? MWRT_OK
-           : fail(MWRT_ERR_UNSUPPORTED, "the optimal-estimation step needs more LDS than this device has per workgroup");
-    },
-    [&](hipStream_t st) { return oe::launch_oe_step(a, nprof, st); });
-}
-
-/* The Levenberg-Marquardt split of the step (csrc/mwrt_oe_lm.hip): oe_lm_call above is the one preamble of its three
- * entries. */
-size_t mwrt_oe_lm_size(void) { return sizeof(mwrt_oe_lm); }
-
-int mwrt_oe_lm_prepare_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_lm* s, void* stream) {
-  return oe_lm_call(c, nprof, nlev, m, s, stream, LmCall::Prepare);
-}
-int mwrt_oe_lm_solve_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_lm* s, void* stream) {
-  return oe_lm_call(c, nprof, nlev, m, s, stream, LmCall::Solve);
-}
-int mwrt_oe_cost_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_lm* s, void* stream) {
-  return oe_lm_call(c, nprof, nlev, m, s, stream, LmCall::Cost);
-}
-
-/* The characterisation of the step (csrc/mwrt_oe_char.hip): oe_char_call above is the one preamble of its two entries. */
-size_t mwrt_oe_char_size(void) { return sizeof(mwrt_oe_char); }
-
-int mwrt_oe_gain_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_char* s, void* stream) {
-  return oe_char_call(c, nprof, nlev, m, s, stream, CharCall::Gain);
-}
-int mwrt_oe_product_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_char* s, void* stream) {
-  return oe_char_call(c, nprof, nlev, m, s, stream, CharCall::Product);
-}
-
-/* The instrument operator (csrc/mwrt_obs.hip): a handle that owns the device copy of a CSR map, and its one launch.  The
- * preamble of apply is in the order of mwrt_oe_step_device: arguments, then limits, then the device and the stream. */
-uint32_t mwrt_obs_apply_size(void) { return (uint32_t)sizeof(mwrt_obs_apply); }
-
-int mwrt_obs_create(mwrt_context* c, int32_t m_in, int32_t m_out, const int32_t* row_ptr, const int32_t* col, const double* w,
-                    mwrt_obs** out) {
-  if (out) *out = nullptr;
-  if (!c || !row_ptr || !col || !w || !out) return fail(MWRT_ERR_INVALID_ARGUMENT, "null argument");
-  if (m_in < 1 || m_out < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_create: m_in < 1 or m_out < 1");
-  if (row_ptr[0] != 0) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_create: row_ptr[0] must be 0");
-  for (int32_t o = 0; o < m_out; ++o)
-    if (row_ptr[o + 1] < row_ptr[o])
-      return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_create: row_ptr decreases at row " + std::to_string(o));
-  const size_t nnz = (size_t)row_ptr[m_out];
-  for (size_t e = 0; e < nnz; ++e) {
-    if (col[e] < 0 || col[e] >= m_in)
-      return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_create: col[" + std::to_string(e) + "] outside 0 .. m_in - 1");
-    if (!std::isfinite(w[e]))
-      return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_create: w[" + std::to_string(e) + "] is not finite");
-  }
-  HIP_TRY(hipSetDevice(c->device));
-  mwrt_obs* op = new (std::nothrow) mwrt_obs();
-  if (!op) return fail(MWRT_ERR_OUT_OF_MEMORY, "host allocation failed");
-  const size_t w_bytes = sizeof(double) * nnz, rp_bytes = sizeof(int32_t) * ((size_t)m_out + 1);
-  std::vector<char> host(w_bytes + rp_bytes + sizeof(int32_t) * nnz);
-  std::memcpy(host.data(), w, w_bytes);
-  std::memcpy(host.data() + w_bytes, row_ptr, rp_bytes);
-  std::memcpy(host.data() + w_bytes + rp_bytes, col, sizeof(int32_t) * nnz);
-  hipError_t e = hipMalloc(&op->d_blob, host.size());
-  if (e == hipSuccess) e = hipMemcpy(op->d_blob, host.data(), host.size(), hipMemcpyHostToDevice);   // synchronous: in HBM on return
-  if (e != hipSuccess) {
-    if (op->d_blob) (void)hipFree(op->d_blob);
-    delete op;
-    return fail(e == hipErrorOutOfMemory ? MWRT_ERR_OUT_OF_MEMORY : MWRT_ERR_HIP, hipGetErrorString(e));
-  }
-  op->ctx = c; op->m_in = m_in; op->m_out = m_out;
-  op->d_w = static_cast<const double*>(op->d_blob);
-  op->d_row_ptr = reinterpret_cast<const int32_t*>(static_cast<const char*>(op->d_blob) + w_bytes);
-  op->d_col = reinterpret_cast<const int32_t*>(static_cast<const char*>(op->d_blob) + w_bytes + rp_bytes);
-  c->obs_live.push_back(op);
-  *out = op;
-  return MWRT_OK;
-}
-
-int mwrt_obs_destroy(mwrt_obs* op) {
-  if (!op) return MWRT_OK;
-  if (mwrt_context* c = op->ctx) {
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();                       // launches on any stream may still read the map
-    (void)hipFree(op->d_blob);
-    for (size_t i = c->obs_live.size(); i-- > 0;)
-      if (c->obs_live[i] == op) c->obs_live.erase(c->obs_live.begin() + (long)i);
-  }
-  delete op;
-  return MWRT_OK;
-}
-
-int mwrt_obs_apply_device(mwrt_context* c, const mwrt_obs* op, int64_t nprof, int32_t nlev, const mwrt_obs_apply* s,
-                          void* stream) {
-  if (!c || !op || !s) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context, mwrt_obs or mwrt_obs_apply");
-  if (op->ctx != c) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs belongs to another context, or its context was destroyed");
-  constexpr size_t fixed = offsetof(mwrt_obs_apply, reserved) + sizeof(int32_t), ptrs = offsetof(mwrt_obs_apply, d_tb_in);
-  if (s->struct_size < fixed)
-    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_apply.struct_size too small for the fixed part (through reserved)");
-  mwrt_obs_apply r{};                                  // fields at or beyond the caller's struct_size stay NULL
-  // ... and so does a field the size ends inside: beyond the fixed part every field is one pointer
-  size_t len = s->struct_size < sizeof r ? s->struct_size : sizeof r;
-  len = len < ptrs ? fixed : len - (len - ptrs) % sizeof(void*);
-  std::memcpy(&r, s, len);
-  if (nprof < 0 || nlev < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "nprof < 0 or nlev < 1");
-  if (r.nblk < 0 || r.nblk > 4) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_apply.nblk must be 0 .. 4");
-  if (r.reserved != 0) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_apply.reserved must be 0");
-  if ((r.d_tb_in == nullptr) != (r.d_tb_out == nullptr))
-    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_apply: d_tb_in and d_tb_out are given together or not at all");
-  for (int b = 0; b < r.nblk; ++b)
-    if (!r.d_k_in[b] || !r.d_k_out[b]) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_apply: null pointer among the first nblk of d_k_in / d_k_out");
-  if (!r.d_tb_in && r.nblk == 0) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_apply: nothing to do (no TB pair and nblk = 0)");
-  bool aliased = r.d_tb_in && r.d_tb_in == r.d_tb_out;
-  for (int b = 0; b < r.nblk; ++b) aliased = aliased || r.d_k_in[b] == r.d_k_out[b];
-  if (aliased) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_apply: an output pointer equals its input (the map is not applied in place)");
-  if (nlev > MWRT_MAX_LEVELS)
-    return fail(MWRT_ERR_UNSUPPORTED, "nlev > MWRT_MAX_LEVELS (" + std::to_string(MWRT_MAX_LEVELS) + ")");
-  obs::ObsArgs a{};
-  a.row_ptr = op->d_row_ptr; a.col = op->d_col; a.w = op->d_w;
-  a.m_in = op->m_in; a.m_out = op->m_out;
-  obs::ObsArgs k = a, t = a;                           // the K blocks at nlev; the TB pair as one block of one level
-  k.in0 = r.d_k_in[0]; k.in1 = r.d_k_in[1]; k.in2 = r.d_k_in[2]; k.in3 = r.d_k_in[3];
-  k.out0 = r.d_k_out[0]; k.out1 = r.d_k_out[1]; k.out2 = r.d_k_out[2]; k.out3 = r.d_k_out[3];
-  k.nlev = nlev; k.nblk = r.nblk; k.nchunks = (nlev + obs::WAVE - 1) / obs::WAVE;
-  t.in0 = r.d_tb_in; t.out0 = r.d_tb_out; t.nlev = 1; t.nblk = 1; t.nchunks = 1;
-  // one wave per (profile, block, output row, level chunk), ITEMS waves per workgroup; the per-profile count is < 2^37
-  const int64_t per_prof = (int64_t)(r.nblk > 0 ? r.nblk : 1) * op->m_out * k.nchunks;
-  if (nprof > 2147483647LL * obs::ITEMS / per_prof)
-    return fail(MWRT_ERR_UNSUPPORTED, "mwrt_obs_apply_device: more than 2147483647 workgroups in one launch (split the batch)");
-  k.items = nprof * r.nblk * op->m_out * k.nchunks;
-  t.items = nprof * op->m_out;
-  if (nprof == 0) return MWRT_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = resolve_stream(c, stream);
-  if (r.nblk > 0) {
-    const int rc = timed(c, st, [&] { return obs::launch_obs_apply(k, st); });
-    if (rc != MWRT_OK) return rc;
-  }
-  if (r.d_tb_in) return timed(c, st, [&] { return obs::launch_obs_apply(t, st); });
-  return MWRT_OK;
-}
-
-/* The reduced-basis state (csrc/mwrt_basis.hip): a handle that owns the device copy of B, and its two launches.  Lifecycle
- * and preamble as for the instrument operator above. */
-uint32_t mwrt_basis_apply_size(void) { return (uint32_t)sizeof(mwrt_basis_apply); }
-
-int mwrt_basis_create(mwrt_context* c, int32_t nblk, int32_t nlev, int32_t r, const double* b, mwrt_basis** out) {
-  if (out) *out = nullptr;
-  if (!c || !b || !out) return fail(MWRT_ERR_INVALID_ARGUMENT, "null argument");
-  if (nblk < 1 || nblk > 4) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_create: nblk must be 1 .. 4");
-  if (nlev < 1 || r < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_create: nlev < 1 or r < 1");
-  if (nlev > MWRT_MAX_LEVELS || r > MWRT_MAX_LEVELS)
-    return fail(MWRT_ERR_UNSUPPORTED, "mwrt_basis_create: nlev or r > MWRT_MAX_LEVELS (" + std::to_string(MWRT_MAX_LEVELS) + ")");
-  const size_t count = (size_t)nblk * (size_t)nlev * (size_t)r;
-  for (size_t e = 0; e < count; ++e)
-    if (!std::isfinite(b[e]))
-      return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_create: b[" + std::to_string(e / (size_t)r) + "][" +
-                                                 std::to_string(e % (size_t)r) + "] is not finite");
-  HIP_TRY(hipSetDevice(c->device));
-  mwrt_basis* bs = new (std::nothrow) mwrt_basis();
-  if (!bs) return fail(MWRT_ERR_OUT_OF_MEMORY, "host allocation failed");
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&bs->d_b), sizeof(double) * count);
-  if (e == hipSuccess) e = hipMemcpy(bs->d_b, b, sizeof(double) * count, hipMemcpyHostToDevice);   // synchronous: in HBM on return
-  if (e != hipSuccess) {
-    if (bs->d_b) (void)hipFree(bs->d_b);
-    delete bs;
-    return fail(e == hipErrorOutOfMemory ? MWRT_ERR_OUT_OF_MEMORY : MWRT_ERR_HIP, hipGetErrorString(e));
-  }
-  bs->ctx = c; bs->nblk = nblk; bs->nlev = nlev; bs->r = r;
-  c->basis_live.push_back(bs);
-  *out = bs;
-  return MWRT_OK;
-}
-
-int mwrt_basis_destroy(mwrt_basis* bs) {
-  if (!bs) return MWRT_OK;
-  if (mwrt_context* c = bs->ctx) {
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();                       // launches on any stream may still read the basis
-    (void)hipFree(bs->d_b);
-    for (size_t i = c->basis_live.size(); i-- > 0;)
-      if (c->basis_live[i] == bs) c->basis_live.erase(c->basis_live.begin() + (long)i);
-  }
-  delete bs;
-  return MWRT_OK;
-}
-
-namespace {
-
-// What project and expand share: the handle checks and the record cut at the caller's struct_size.
-int basis_record(const mwrt_context* c, const mwrt_basis* bs, int64_t nprof, const mwrt_basis_apply* s, mwrt_basis_apply* r) {
-  if (!c || !bs || !s) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context, mwrt_basis or mwrt_basis_apply");
-  if (bs->ctx != c) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis belongs to another context, or its context was destroyed");
-  constexpr size_t fixed = offsetof(mwrt_basis_apply, reserved) + sizeof(int32_t), ptrs = offsetof(mwrt_basis_apply, d_k_in);
-  constexpr size_t tail = offsetof(mwrt_basis_apply, x_ref_per_profile);
-  static_assert(fixed == ptrs, "mwrt_basis_apply: the pointers follow the fixed part");
-  if (s->struct_size < fixed)
-    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_apply.struct_size too small for the fixed part (through reserved)");
-  // fields at or beyond the caller's struct_size stay NULL / 0, and so does a field the size ends inside: pointers up to
-  // x_ref_per_profile, two int32 behind them
-  size_t len = s->struct_size < sizeof *r ? s->struct_size : sizeof *r;
-  len = len <= tail ? len - (len - ptrs) % sizeof(void*) : len - (len - tail) % sizeof(int32_t);
-  std::memcpy(r, s, len);
-  if (nprof < 0) return fail(MWRT_ERR_INVALID_ARGUMENT, "nprof < 0");
-  if (r->reserved != 0 || r->reserved2 != 0) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_apply.reserved and reserved2 must be 0");
-  return MWRT_OK;
-}
-
-}  // namespace
-
-int mwrt_basis_project_device(mwrt_context* c, const mwrt_basis* bs, int64_t nprof, int32_t m, const mwrt_basis_apply* s,
-                              void* stream) {
-  mwrt_basis_apply r{};
-  if (const int rc = basis_record(c, bs, nprof, s, &r)) return rc;
-  if (m < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "m < 1");
-  for (int b = 0; b < bs->nblk; ++b)
-    if (!r.d_k_in[b]) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_apply: null pointer among the first nblk of d_k_in");
-  if (!r.d_k_out) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_apply: d_k_out is null");
-  for (int b = 0; b < bs->nblk; ++b)
-    if (r.d_k_in[b] == r.d_k_out)
-      return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_apply: d_k_out equals one of its inputs (the product is not formed in place)");
-  // one workgroup per (ROWS rows, COLS columns): nprof * m rows may fill as many row tiles as the column tiles leave
-  const int64_t col_tiles = (bs->r + basis::COLS - 1) / basis::COLS;
-  if (nprof > 2147483647LL / col_tiles * basis::ROWS / m)
-    return fail(MWRT_ERR_UNSUPPORTED, "mwrt_basis_project_device: more than 2147483647 workgroups in one launch (split the batch)");
-  if (nprof == 0) return MWRT_OK;
-  basis::ProjectArgs a{};
-  a.in0 = r.d_k_in[0]; a.in1 = r.d_k_in[1]; a.in2 = r.d_k_in[2]; a.in3 = r.d_k_in[3];
-  a.b = bs->d_b; a.out = r.d_k_out;
-  a.nrows = nprof * m; a.nlev = bs->nlev; a.nblk = bs->nblk; a.n = bs->nblk * bs->nlev; a.r = bs->r;
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = resolve_stream(c, stream);
-  return timed(c, st, [&] { return basis::launch_project(a, st); });
-}
-
-int mwrt_basis_expand_device(mwrt_context* c, const mwrt_basis* bs, int64_t nprof, const mwrt_basis_apply* s, void* stream) {
-  mwrt_basis_apply r{};
-  if (const int rc = basis_record(c, bs, nprof, s, &r)) return rc;
-  if (!r.d_c || !r.d_x_ref || !r.d_x) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_apply: d_c, d_x_ref or d_x is null");
-  if (r.d_x == r.d_c || r.d_x == r.d_x_ref)
-    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_basis_apply: d_x equals one of its inputs (the map is not applied in place)");
-  const int64_t n = (int64_t)bs->nblk * bs->nlev;       // <= 4096
-  if (nprof > 2147483647LL * basis::THREADS / n)
-    return fail(MWRT_ERR_UNSUPPORTED, "mwrt_basis_expand_device: more than 2147483647 workgroups in one launch (split the batch)");
-  if (nprof == 0) return MWRT_OK;
-  basis::ExpandArgs a{};
-  a.b = bs->d_b; a.c = r.d_c; a.x_ref = r.d_x_ref; a.x = r.d_x;
-  a.total = nprof * n; a.n = (int32_t)n; a.r = bs->r; a.per_profile = r.x_ref_per_profile != 0;
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = resolve_stream(c, stream);
-  return timed(c, st, [&] { return basis::launch_expand(a, st); });
-}
-
-/* Pre-whitening with a per-profile observation-error covariance (csrc/mwrt_whiten.hip): no handle, two entries that share
- * the record, its cut at the caller's struct_size and the preamble of mwrt_obs_apply_device. */
-uint32_t mwrt_obs_whiten_size(void) { return (uint32_t)sizeof(mwrt_obs_whiten); }
-
-namespace {
-
-// What the two entries share: the record cut at the caller's struct_size, the sizes, and the limits.  *tiles is the number
-// of workgroups of k_wh_apply per profile when every block and a vector are asked for.
-int whiten_record(const mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_obs_whiten* s, mwrt_obs_whiten* r,
-                  int max_mode) {
-  if (!c || !s) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context or mwrt_obs_whiten");
-  constexpr size_t fixed = offsetof(mwrt_obs_whiten, reserved) + sizeof(int64_t), ptrs = offsetof(mwrt_obs_whiten, d_se);
-  static_assert(fixed == ptrs, "mwrt_obs_whiten: the pointers follow the fixed part");
-  if (s->struct_size < fixed)
-    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten.struct_size too small for the fixed part (through reserved)");
-  // fields at or beyond the caller's struct_size stay NULL, and so does a field the size ends inside: all are pointers
-  size_t len = s->struct_size < sizeof *r ? s->struct_size : sizeof *r;
-  len -= (len - ptrs) % sizeof(void*);
-  std::memcpy(r, s, len);
-  if (nprof < 0 || nlev < 1 || m < 1) return fail(MWRT_ERR_INVALID_ARGUMENT, "nprof < 0, nlev < 1 or m < 1");
-  if (r->nblk < 0 || r->nblk > 4) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten.nblk must be 0 .. 4");
-  if (r->reserved != 0) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten.reserved must be 0");
-  if (r->mode < 0 || r->mode > max_mode)
-    return fail(MWRT_ERR_INVALID_ARGUMENT, max_mode == 0 ? "mwrt_obs_whiten.mode must be 0 in mwrt_obs_whiten_device"
-                                                         : "mwrt_obs_whiten.mode must be 0 (L^-1) or 1 (L^-T)");
-  return MWRT_OK;
-}
-
-int whiten_limits(int64_t nprof, int32_t nlev, int32_t m, int nblk) {
-  if (m > MWRT_OE_MAX_M) return fail(MWRT_ERR_UNSUPPORTED, "m > MWRT_OE_MAX_M (" + std::to_string(MWRT_OE_MAX_M) + ")");
-  if (nlev > MWRT_MAX_LEVELS)
-    return fail(MWRT_ERR_UNSUPPORTED, "nlev > MWRT_MAX_LEVELS (" + std::to_string(MWRT_MAX_LEVELS) + ")");
-  // one workgroup per (profile, tile of wh::COLS columns), and one more per profile for the vectors: at most 65 a profile
-  const int64_t tiles = (int64_t)nblk * ((nlev + wh::COLS - 1) / wh::COLS) + 1;
-  if (nprof > 2147483647LL / tiles)
-    return fail(MWRT_ERR_UNSUPPORTED, "mwrt_obs_whiten: more than 2147483647 workgroups in one launch (split the batch)");
-  return MWRT_OK;
-}
-
-// an output that is also one of the inputs
-bool whiten_aliased(const mwrt_obs_whiten& r, bool l_is_output) {
-  const void* ins[10] = {r.d_se, r.d_y, r.d_fx, r.d_k_in[0], r.d_k_in[1], r.d_k_in[2], r.d_k_in[3],
-                         l_is_output ? nullptr : r.d_l, l_is_output ? nullptr : r.d_keep, nullptr};
-  const void* outs[9] = {r.d_y_out, r.d_fx_out, r.d_k_out[0], r.d_k_out[1], r.d_k_out[2], r.d_k_out[3],
-                         l_is_output ? r.d_l : nullptr, l_is_output ? r.d_keep : nullptr, l_is_output ? r.d_status : nullptr};
-  for (const void* o : outs)
-    for (const void* i : ins)
-      if (o && o == i) return true;
-  return false;
-}
-
-// the blocks with an output asked for, packed to the front; the vectors as they are
-wh::ApplyArgs whiten_apply_args(const mwrt_obs_whiten& r, int32_t nlev, int32_t m) {
-  wh::ApplyArgs a{};
-  const double* in[4] = {};
-  double* out[4] = {};
-  int n = 0;
-  for (int b = 0; b < r.nblk; ++b)
-    if (r.d_k_out[b]) { in[n] = r.d_k_in[b]; out[n] = r.d_k_out[b]; ++n; }
-  a.in0 = in[0]; a.in1 = in[1]; a.in2 = in[2]; a.in3 = in[3];
-  a.out0 = out[0]; a.out1 = out[1]; a.out2 = out[2]; a.out3 = out[3];
-  if (r.d_y_out) { a.v_in0 = r.d_y; a.v_out0 = r.d_y_out; }
-  if (r.d_fx_out) { a.v_in1 = r.d_fx; a.v_out1 = r.d_fx_out; }
-  a.l = r.d_l; a.keep = r.d_keep;
-  a.nblk = n; a.nlev = nlev; a.m = m; a.mode = r.mode;
-  a.ctiles = (nlev + wh::COLS - 1) / wh::COLS;
-  a.tiles = n * a.ctiles + ((a.v_in0 || a.v_in1) ? 1 : 0);
-  return a;
-}
-
-}  // namespace
-
-int mwrt_obs_whiten_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_obs_whiten* s, void* stream) {
-  mwrt_obs_whiten r{};
-  if (const int rc = whiten_record(c, nprof, nlev, m, s, &r, 0)) return rc;
-  if (!r.d_se || !r.d_y || !r.d_fx || !r.d_l || !r.d_keep || !r.d_status)
-    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten: d_se, d_y, d_fx, d_l, d_keep or d_status is null");
-  for (int b = 0; b < r.nblk; ++b)
-    if (!r.d_k_in[b]) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten: null pointer among the first nblk of d_k_in");
-  if (whiten_aliased(r, true))
-    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten: an output pointer equals an input (nothing is whitened in place)");
-  if (const int rc = whiten_limits(nprof, nlev, m, r.nblk)) return rc;
-  if (nprof == 0) return MWRT_OK;
-  wh::FactorArgs f{};
-  f.k0 = r.d_k_in[0]; f.k1 = r.d_k_in[1]; f.k2 = r.d_k_in[2]; f.k3 = r.d_k_in[3];
-  f.se = r.d_se; f.y = r.d_y; f.fx = r.d_fx;
-  f.l = r.d_l; f.keep = r.d_keep; f.status = r.d_status;
-  f.nblk = r.nblk; f.nlev = nlev; f.m = m; f.se_full = r.se_full != 0;
-  const wh::ApplyArgs a = whiten_apply_args(r, nlev, m);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = resolve_stream(c, stream);
-  const int rc = timed(c, st, [&] { return wh::launch_factor(f, nprof, st); });
-  if (rc != MWRT_OK || a.tiles == 0) return rc;
-  return timed(c, st, [&] { return wh::launch_apply(a, nprof, st); });
-}
-
-int mwrt_obs_whiten_apply_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_obs_whiten* s,
-                                 void* stream) {
-  mwrt_obs_whiten r{};
-  if (const int rc = whiten_record(c, nprof, nlev, m, s, &r, 1)) return rc;
-  if (!r.d_l || !r.d_keep) return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten: d_l or d_keep is null");
-  if ((r.d_y == nullptr) != (r.d_y_out == nullptr) || (r.d_fx == nullptr) != (r.d_fx_out == nullptr))
-    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten: d_y and d_y_out (d_fx and d_fx_out) are given together or not at all");
-  for (int b = 0; b < r.nblk; ++b)
-    if (!r.d_k_in[b] || !r.d_k_out[b])
-      return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten: null pointer among the first nblk of d_k_in / d_k_out");
-  if (!r.d_y && !r.d_fx && r.nblk == 0)
-    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten: nothing to do (no vector and nblk = 0)");
-  if (whiten_aliased(r, false))
-    return fail(MWRT_ERR_INVALID_ARGUMENT, "mwrt_obs_whiten: an output pointer equals an input (nothing is applied in place)");
-  if (const int rc = whiten_limits(nprof, nlev, m, r.nblk)) return rc;
-  if (nprof == 0) return MWRT_OK;
-  const wh::ApplyArgs a = whiten_apply_args(r, nlev, m);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = resolve_stream(c, stream);
-  return timed(c, st, [&] { return wh::launch_apply(a, nprof, st); });
 }
 
 int mwrt_selftest_math(mwrt_context* c, int32_t n, const double* x, const double* y_pos,

@@ -1,6 +1,6 @@
-"""The host unit of libmwrt.so (csrc/mwrt.hip: streams, caches, argument checks, entry points) holds no kernel: its device
-side, cross-compiled for gfx950 with the library's flags (no GPU), defines none.  Kernels live in mwrt_inst.hip,
-mwrt_tl.hip and mwrt_aux.hip and are reached through the launchers that mwrt_args.hip.h and mwrt_tl.hip.h declare."""
+"""The host units of libmwrt.so (csrc/mwrt.hip and csrc/mwrt_retrieval.hip: streams, caches, handles, argument checks,
+entry points) hold no kernel: their device side, cross-compiled for gfx950 with the library's flags (no GPU), defines none.
+Kernels live in the kernel units and are reached through the launchers that their interface headers declare."""
 import os
 import subprocess
 
@@ -18,6 +18,8 @@ def device_assembly(unit, tmp_path):
 
 
 def test_host_unit_defines_no_kernel(tmp_path):
-    asm = device_assembly(build.SRC, tmp_path)
-    assert "amdgcn" in asm, asm[:200]                 # it is the gfx950 side that was read
-    assert ".amdhsa_kernel" not in asm, [l for l in asm.splitlines() if ".amdhsa_kernel" in l]
+    assert build.SRC in build.HOST_UNITS and len(build.HOST_UNITS) == 2
+    for unit in build.HOST_UNITS:
+        asm = device_assembly(unit, tmp_path)
+        assert "amdgcn" in asm, (unit, asm[:200])     # it is the gfx950 side that was read
+        assert ".amdhsa_kernel" not in asm, (unit, [l for l in asm.splitlines() if ".amdhsa_kernel" in l])

@@ -55,12 +55,12 @@ def test_library_holds_exactly_the_obs_kernel(native_lib):
 
 
 def test_host_unit_carries_no_obs_device_code():
-    text = open(build.SRC).read()
-    assert '#include "mwrt_obs.hip.h"' in text and "__global__" not in text
+    hosts = {unit: open(unit).read() for unit in build.HOST_UNITS}
+    assert '#include "mwrt_obs.hip.h"' in hosts[build.RETRIEVAL]
+    assert all("__global__" not in text and "mwrt_oe_blocks.hip.h" not in text for text in hosts.values())
     head = open(os.path.join(os.path.dirname(build.OBS), "mwrt_obs.hip.h")).read()
     assert "__global__" not in head
-    import inspect
-    assert "jobs.append((OBS," in inspect.getsource(build.build_native) and "csrc/mwrt_obs.hip" in build.__doc__
+    assert (build.OBS, []) in build.UNITS
 
 
 def test_abi_surface_of_the_instrument_operator(native_lib):

@@ -58,8 +58,9 @@ def test_library_holds_exactly_the_parameter_kernels(native_lib):
 
 
 def test_host_unit_carries_no_parameter_device_code():
-    text = open(build.SRC).read()
-    assert '#include "mwrt_par.hip.h"' in text and "__global__" not in text
+    hosts = {unit: open(unit).read() for unit in build.HOST_UNITS}
+    assert '#include "mwrt_par.hip.h"' in hosts[build.SRC]
+    assert all("__global__" not in text and "mwrt_oe_blocks.hip.h" not in text for text in hosts.values())
     csrc = os.path.dirname(build.PAR)
     assert "__global__" not in open(os.path.join(csrc, "mwrt_par.hip.h")).read()
     # the helpers both tangent-linear units use live in one device header, included by both
@@ -69,8 +70,7 @@ def test_host_unit_carries_no_parameter_device_code():
         assert not re.search(r"^(?:__device__|struct|template).*\b%s\b" % re.escape(name.split()[-1]), open(build.TL).read(), re.M), name
     for unit in (build.TL, build.PAR):
         assert '#include "mwrt_tl_dev.hip.h"' in open(unit).read(), unit
-    import inspect
-    assert "jobs.append((PAR," in inspect.getsource(build.build_native) and "csrc/mwrt_par.hip" in build.__doc__
+    assert (build.PAR, []) in build.UNITS
 
 
 def test_abi_surface_of_the_parameter_jacobian(native_lib):

@@ -62,12 +62,12 @@ def test_unit_layout_and_build_recipe():
     csrc = os.path.dirname(build.RAY)
     assert "__global__" not in open(os.path.join(csrc, "mwrt_ray.hip.h")).read()
     assert "__global__" not in open(os.path.join(csrc, "mwrt_tl_rte.hip.h")).read()
-    host = open(build.SRC).read()
-    assert '#include "mwrt_ray.hip.h"' in host and "__global__" not in host
+    hosts = {unit: open(unit).read() for unit in build.HOST_UNITS}
+    assert '#include "mwrt_ray.hip.h"' in hosts[build.SRC]
+    assert all("__global__" not in text and "mwrt_oe_blocks.hip.h" not in text for text in hosts.values())
     # one adjoint RTE, two kernels: both units instantiate the shared body
     assert "jac_rte_body<false>" in open(build.TL).read() and "jac_rte_body<true>" in open(build.RAY).read()
-    assert "jobs.append((RAY," in inspect.getsource(build.build_native) and "csrc/mwrt_ray.hip" in build.__doc__
-    assert "Thirteen translation units" in build.__doc__
+    assert (build.RAY, []) in build.UNITS
 
 
 def test_abi_surface_of_the_ray_entries(native_lib):

@@ -3,7 +3,6 @@ cross-compiled for gfx950 with the library's flags; the inventory of mwrt::wh ke
 declared, exported, bound, and the record laid out alike on both sides; and the guard of the GPU tests' shape list against
 the plan constants of the header as the code has them."""
 import ctypes
-import inspect
 import os
 import re
 import subprocess
@@ -81,10 +80,11 @@ def test_library_holds_exactly_the_whiten_kernels(native_lib):
 
 
 def test_host_unit_carries_no_whiten_device_code():
-    text = open(build.SRC).read()
-    assert '#include "mwrt_whiten.hip.h"' in text and "__global__" not in text and "mwrt_oe_blocks.hip.h" not in text
+    hosts = {unit: open(unit).read() for unit in build.HOST_UNITS}
+    assert '#include "mwrt_whiten.hip.h"' in hosts[build.RETRIEVAL]
+    assert all("__global__" not in text and "mwrt_oe_blocks.hip.h" not in text for text in hosts.values())
     assert "__global__" not in open(HEADER).read()
-    assert "jobs.append((WHITEN," in inspect.getsource(build.build_native) and "csrc/mwrt_whiten.hip" in build.__doc__
+    assert (build.WHITEN, []) in build.UNITS
 
 
 def test_abi_surface_of_the_pre_whitening(native_lib):
