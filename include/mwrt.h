@@ -828,6 +828,83 @@ int mwrt_obs_whiten_apply_device(mwrt_context* ctx, int64_t nprof, int32_t nlev,
 /* sizeof(mwrt_obs_whiten) as compiled into the library (binding self-check). */
 uint32_t mwrt_obs_whiten_size(void);
 
+/* The same step in the n-form (Rodgers 2000, eq. 5.9 and, damped, eq. 5.36 as printed): an n x n system
+ * per profile instead of an m x m one, for small states (a reduced basis, a coarse grid) and ANY number of observations:
+ *     H = K^T W K,  g = K^T W r,  r = y - F(x),  W = diag(1 / se_i) over the rows kept
+ *     C = H + (1 + gamma) Sa^-1 = L L^T,      x+ = x + C^-1 [ g - Sa^-1 (x - xa) ]
+ * gamma = 0 gives mwrt_oe_step_device's x+ and C^-1 is the posterior covariance.  Nothing of size m x m exists.
+ *   mwrt_oe_nform_prepare_device   the linearisation at x: the row rule, H, g and r^T W r in ONE pass over K
+ *   mwrt_oe_nform_solve_device     one (optionally damped) step on a linearisation, and the diagnostics at gamma = 0
+ *   mwrt_oe_nform_cost_device      J = sum_kept (y - fx)^2 / se + (x - xa)^T Sa^-1 (x - xa) at a state, on a linearisation's rows
+ * One record, mwrt_oe_nform, serves the three.  Layouts are those of mwrt_oe_step / mwrt_oe_lm (all DEVICE pointers,
+ * float64 unless stated): d_k[b], b < nblk (1 .. 4), [nprof][m][nlev] -- with a reduced basis the one block K B
+ * [nprof][m][r] and nlev = r; d_x the current state; d_xa shared or, with xa_per_profile != 0, per profile; d_y, d_fx
+ * [nprof][m]; and
+ *   d_sa_inv     [n][n]                  Sa^-1, SYMMETRIC, formed by the caller as for mwrt_oe_cost_device   (solve, cost)
+ *   d_se         [m], or [nprof][m] with se_per_profile != 0: VARIANCES ONLY.  A full Se is not taken by this family
+ *                                        (whiten first: mwrt_obs_whiten_device, then variances of 1)         (prepare, cost)
+ *   d_gamma      [nprof], optional       the damping factor; NULL: gamma = 0                                  (solve)
+ *   d_active     [nprof] uint8, optional a profile whose flag is 0 is skipped: NONE of its outputs is touched (all three)
+ * The linearisation, written by prepare to caller-owned buffers, read by solve (d_h, d_g, d_rwr, d_lin_status) and by
+ * cost (d_keep):
+ *   d_keep       [nprof][m] uint8        1: the row is used.  The row rule is that of mwrt_oe_step_device: row i is dropped
+ *                                        when y_i, fx_i, any K[i, :] or its variance is not finite
+ *   d_nobs       [nprof] int32           m_used
+ *   d_h          [nprof][n (n + 1) / 2]  packed lower triangle of H, entry (i, j <= i) at i (i + 1) / 2 + j
+ *   d_g          [nprof][n]              K^T W r
+ *   d_rwr        [nprof]                 r^T W r
+ *   d_lin_status [nprof] uint8           1 ok;  0 x or xa not finite (h, g, rwr NaN, keep 0, nobs 0);  2 a kept row's
+ *                                        variance is <= 0 (h, g, rwr NaN; keep and nobs as decided);  3 no usable row
+ *                                        (h, g, rwr, keep and nobs 0)
+ * Outputs of solve: d_x_new [nprof][nblk][nlev] and d_status [nprof] uint8 required.  Optional, defined at gamma = 0 only
+ *   (a call that gives d_gamma and asks for one of them is MWRT_ERR_INVALID_ARGUMENT):
+ *   d_chi2     [nprof]              d^T G^-1 d, the m-form step's chi2, formed without a second pass over K as the cost at
+ *                                   the linear solution: with s = x+ - x and e = x+ - xa,
+ *                                   (r^T W r - 2 s^T g + s^T H s) + e^T Sa^-1 e; its rounding error scales with d^T W d
+ *   d_dfs      [nprof]              tr(C^-1 H), summed element by element in a fixed order
+ *   d_post_var [nprof][nblk][nlev]  diag C^-1
+ *   d_post_cov [nprof][n][n]        C^-1, full and symmetric
+ *   status: 1 ok;  0 d_lin_status 0, or x / xa not finite now: outputs NaN;  2 d_lin_status 2, gamma negative or not
+ *   finite, or a Cholesky pivot fails pivot > 0: outputs NaN;  3 d_lin_status 3: x_new = xa + gamma / (1 + gamma) (x - xa)
+ *   (xa exactly at gamma = 0), chi2 and dfs 0, post_var and post_cov from the inverse of Sa^-1 as computed (NaN when that
+ *   factorisation fails).  x_new does not depend on which optional outputs are asked for.
+ * Outputs of cost: d_cost [nprof] required; d_cost_obs, d_cost_prior [nprof] and d_status optional.  A non-finite x or
+ *   xa, or y or fx in a kept row, gives +inf in all three with status 1 (a trial to reject, as in mwrt_oe_cost_device); a
+ *   kept row's variance <= 0 gives NaN in all three and status 2.
+ * Determinism: a profile's outputs depend on neither its batch-mates nor nprof (one workgroup per profile, every sum in
+ *   one fixed order, no atomics).  No workspace: the calls never allocate and never synchronise; a launch above 64 KiB of
+ *   dynamic LDS (solve from n = 122 on) raises that kernel's limit once per device and size, so the entries are
+ *   hipGraph-capturable after one warm-up call.
+ * Limits: n = nblk * nlev <= MWRT_OE_NFORM_MAX_N (the packed triangle of C lives in LDS): beyond it MWRT_ERR_UNSUPPORTED
+ *   with the limit in the text.  m >= 1 and otherwise unbounded: MWRT_OE_MAX_M does not apply.  MWRT_ERR_INVALID_ARGUMENT,
+ *   checked in this order: struct_size smaller than the fixed part (24 bytes); nprof < 0, nlev < 1 or m < 1; nblk outside
+ *   1 .. 4; reserved != 0; a NULL pointer among those the call reads or must write (prepare: d_k, d_x, d_xa, d_se, d_y,
+ *   d_fx and the linearisation; solve: d_x, d_xa, d_sa_inv, d_h, d_g, d_rwr, d_lin_status, d_x_new, d_status; cost: d_x,
+ *   d_xa, d_sa_inv, d_se, d_y, d_fx, d_keep, d_cost); d_gamma with a gamma = 0-only output.  nprof = 0 is MWRT_OK and
+ *   launches nothing.  The record starts with its own size: fields at or beyond struct_size (and a field it ends inside)
+ *   are taken as NULL.  Measured on an MI355X (profiles/nform_errors.json, profiles/nform_time.json): x_new
+ *   within 1.1e-12 of the reference in units of max |x+ - xa| per block; at 1000 profiles x 98 observations and r = 32,
+ *   prepare 0.049 ms and solve 0.045 ms against 0.83 ms of mwrt_oe_step_device on the same K B.
+ *   (MWRT_VERSION stays 301: additions.) */
+#define MWRT_OE_NFORM_MAX_N 128
+typedef struct mwrt_oe_nform {
+  uint32_t struct_size;        /* sizeof(mwrt_oe_nform) of the caller; fields beyond it are not read */
+  int32_t  nblk, xa_per_profile, se_per_profile, reserved;
+  const double* d_k[4];
+  const double *d_x, *d_xa, *d_sa_inv, *d_se, *d_y, *d_fx;
+  const double* d_gamma;
+  const uint8_t* d_active;
+  double *d_h, *d_g, *d_rwr;  uint8_t* d_keep;  int32_t* d_nobs;  uint8_t* d_lin_status;   /* the linearisation */
+  double* d_x_new;  uint8_t* d_status;                 /* required outputs of solve; d_status optional in cost */
+  double *d_chi2, *d_dfs, *d_post_var, *d_post_cov;    /* optional outputs of solve, gamma = 0 only */
+  double *d_cost, *d_cost_obs, *d_cost_prior;          /* outputs of cost */
+} mwrt_oe_nform;
+int mwrt_oe_nform_prepare_device(mwrt_context* ctx, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_nform* s, void* stream);
+int mwrt_oe_nform_solve_device(mwrt_context* ctx, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_nform* s, void* stream);
+int mwrt_oe_nform_cost_device(mwrt_context* ctx, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_nform* s, void* stream);
+/* sizeof(mwrt_oe_nform) as compiled into the library (binding self-check). */
+size_t mwrt_oe_nform_size(void);
+
 /* The spectroscopic-parameter Jacobian: d TB / d b for entries b of the model's tables -- what the
  * forward-model part K_b S_b K_b^T of an observation-error covariance is built from (Rodgers 2000, section 3.2.2).  The
  * operator is mwrt_tb_jacobian_batch_device's: clear sky, plane-parallel, every line at every frequency; there is no

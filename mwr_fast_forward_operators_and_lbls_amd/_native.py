@@ -77,6 +77,16 @@ class MwrtOeLm(ctypes.Structure):
             "d_active", "d_sa_inv", "d_cost", "d_cost_obs", "d_cost_prior", "d_x_new", "d_status", "d_chi2", "d_nobs")]
 
 
+class MwrtOeNform(ctypes.Structure):
+    """include/mwrt.h mwrt_oe_nform: the record of the n-form of the step (device pointers)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("nblk", ctypes.c_int32), ("xa_per_profile", ctypes.c_int32),
+                ("se_per_profile", ctypes.c_int32), ("reserved", ctypes.c_int32), ("d_k", ctypes.c_void_p * 4)] + [
+        (name, ctypes.c_void_p) for name in (
+            "d_x", "d_xa", "d_sa_inv", "d_se", "d_y", "d_fx", "d_gamma", "d_active", "d_h", "d_g", "d_rwr", "d_keep",
+            "d_nobs", "d_lin_status", "d_x_new", "d_status", "d_chi2", "d_dfs", "d_post_var", "d_post_cov", "d_cost",
+            "d_cost_obs", "d_cost_prior")]
+
+
 class MwrtOeChar(ctypes.Structure):
     """include/mwrt.h mwrt_oe_char: the record of the gain and product entries (device pointers)."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("nblk", ctypes.c_int32), ("xa_per_profile", ctypes.c_int32),
@@ -145,6 +155,9 @@ def _params(params):
 
 #: include/mwrt.h MWRT_OE_MAX_M: observations per profile of one optimal-estimation step
 OE_MAX_M = 140
+
+#: include/mwrt.h MWRT_OE_NFORM_MAX_N: state elements per profile of one n-form step (its m is not bounded)
+OE_NFORM_MAX_N = 128
 
 #: include/mwrt.h MWRT_MAX_ANGLES: elevations of one forward-operator call
 MAX_ANGLES = 64
@@ -215,6 +228,10 @@ SIGNATURES = {
     "mwrt_oe_lm_solve_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeLm), _vp]),
     "mwrt_oe_cost_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeLm), _vp]),
     "mwrt_oe_lm_size": (ctypes.c_size_t, []),
+    "mwrt_oe_nform_prepare_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeNform), _vp]),
+    "mwrt_oe_nform_solve_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeNform), _vp]),
+    "mwrt_oe_nform_cost_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeNform), _vp]),
+    "mwrt_oe_nform_size": (ctypes.c_size_t, []),
     "mwrt_oe_gain_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeChar), _vp]),
     "mwrt_oe_product_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeChar), _vp]),
     "mwrt_oe_char_size": (ctypes.c_size_t, []),
@@ -291,6 +308,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
             raise NativeLibraryMissing("mwrt_oe_step layout mismatch between libmwrt.so and _native.py")
         if lib.mwrt_oe_lm_size() != ctypes.sizeof(MwrtOeLm):
             raise NativeLibraryMissing("mwrt_oe_lm layout mismatch between libmwrt.so and _native.py")
+        if lib.mwrt_oe_nform_size() != ctypes.sizeof(MwrtOeNform):
+            raise NativeLibraryMissing("mwrt_oe_nform layout mismatch between libmwrt.so and _native.py")
         if lib.mwrt_oe_char_size() != ctypes.sizeof(MwrtOeChar):
             raise NativeLibraryMissing("mwrt_oe_char layout mismatch between libmwrt.so and _native.py")
         if lib.mwrt_obs_apply_size() != ctypes.sizeof(MwrtObsApply):
@@ -741,6 +760,57 @@ class Context:
                     struct_size, dict(d_x=d_x, d_xa=d_xa, d_se=d_se, d_y=d_y, d_fx=d_fx, d_keep=d_keep, d_sa_inv=d_sa_inv,
                                       d_cost=d_cost, d_cost_obs=d_cost_obs, d_cost_prior=d_cost_prior, d_status=d_status,
                                       d_active=d_active))
+
+    def _oe_nform(self, entry, nprof, nlev, m, d_k, xa_per_profile, se_per_profile, stream, reserved, struct_size, fields):
+        d_k = list(d_k)
+        rec = MwrtOeNform()
+        rec.struct_size = ctypes.sizeof(MwrtOeNform) if struct_size is None else int(struct_size)
+        rec.nblk, rec.xa_per_profile, rec.se_per_profile, rec.reserved = (
+            len(d_k), int(bool(xa_per_profile)), int(bool(se_per_profile)), int(reserved))
+        for b, k in enumerate(d_k[:4]):
+            rec.d_k[b] = int(k) if k is not None else None
+        for name, v in fields.items():
+            setattr(rec, name, int(v) if v is not None else None)
+        self._check(getattr(self._lib, entry)(self._handle, int(nprof), int(nlev), int(m), ctypes.byref(rec), _stream(stream)),
+                    entry)
+
+    @_serialised
+    def oe_nform_prepare_device(self, nprof, nlev, m, d_k, d_x, d_xa, d_se, d_y, d_fx, d_h, d_g, d_rwr, d_keep, d_nobs,
+                                d_lin_status, d_active=None, xa_per_profile=False, se_per_profile=False, stream=None,
+                                reserved=0, struct_size=None):
+        """The n-form linearisation at x (include/mwrt.h mwrt_oe_nform_prepare_device), one pass over ``d_k``: writes
+        ``d_h [nprof][n (n + 1) / 2]`` (K^T W K packed), ``d_g [nprof][n]``, ``d_rwr [nprof]``, ``d_keep [nprof][m]`` (uint8),
+        ``d_nobs [nprof]`` (int32) and ``d_lin_status [nprof]`` (uint8).  ``d_se`` holds variances, ``[m]`` or, with
+        ``se_per_profile``, ``[nprof][m]``; m is not bounded, n = nblk nlev is (``OE_NFORM_MAX_N``)."""
+        self._oe_nform("mwrt_oe_nform_prepare_device", nprof, nlev, m, d_k, xa_per_profile, se_per_profile, stream, reserved,
+                       struct_size, dict(d_x=d_x, d_xa=d_xa, d_se=d_se, d_y=d_y, d_fx=d_fx, d_h=d_h, d_g=d_g, d_rwr=d_rwr,
+                                         d_keep=d_keep, d_nobs=d_nobs, d_lin_status=d_lin_status, d_active=d_active))
+
+    @_serialised
+    def oe_nform_solve_device(self, nprof, nlev, m, nblk, d_x, d_xa, d_sa_inv, d_h, d_g, d_rwr, d_lin_status, d_x_new,
+                              d_status, d_gamma=None, d_chi2=None, d_dfs=None, d_post_var=None, d_post_cov=None,
+                              d_active=None, xa_per_profile=False, stream=None, reserved=0, struct_size=None):
+        """One step on an n-form linearisation (include/mwrt.h mwrt_oe_nform_solve_device), damped with ``d_gamma [nprof]``
+        when it is given: ``d_x_new [nprof][nblk][nlev]`` and ``d_status [nprof]`` (uint8) required; ``d_chi2``, ``d_dfs``,
+        ``d_post_var`` and ``d_post_cov [nprof][n][n]`` optional and defined without ``d_gamma`` only.  ``nblk`` is the number
+        of state blocks (the call reads no K)."""
+        self._oe_nform("mwrt_oe_nform_solve_device", nprof, nlev, m, [None] * int(nblk), xa_per_profile, False, stream,
+                       reserved, struct_size,
+                       dict(d_x=d_x, d_xa=d_xa, d_sa_inv=d_sa_inv, d_h=d_h, d_g=d_g, d_rwr=d_rwr, d_lin_status=d_lin_status,
+                            d_x_new=d_x_new, d_status=d_status, d_gamma=d_gamma, d_chi2=d_chi2, d_dfs=d_dfs,
+                            d_post_var=d_post_var, d_post_cov=d_post_cov, d_active=d_active))
+
+    @_serialised
+    def oe_nform_cost_device(self, nprof, nlev, m, nblk, d_x, d_xa, d_sa_inv, d_se, d_y, d_fx, d_keep, d_cost,
+                             d_cost_obs=None, d_cost_prior=None, d_status=None, d_active=None, xa_per_profile=False,
+                             se_per_profile=False, stream=None, reserved=0, struct_size=None):
+        """J = sum over the rows ``d_keep`` names of (y - fx)^2 / se + (x - xa)^T Sa^-1 (x - xa) (include/mwrt.h
+        mwrt_oe_nform_cost_device); ``nblk`` is the number of state blocks (the call reads no K)."""
+        self._oe_nform("mwrt_oe_nform_cost_device", nprof, nlev, m, [None] * int(nblk), xa_per_profile, se_per_profile,
+                       stream, reserved, struct_size,
+                       dict(d_x=d_x, d_xa=d_xa, d_sa_inv=d_sa_inv, d_se=d_se, d_y=d_y, d_fx=d_fx, d_keep=d_keep,
+                            d_cost=d_cost, d_cost_obs=d_cost_obs, d_cost_prior=d_cost_prior, d_status=d_status,
+                            d_active=d_active))
 
     def _oe_char(self, entry, nprof, nlev, m, d_k, xa_per_profile, se_full, stream, reserved, struct_size, fields):
         d_k = list(d_k)

@@ -34,9 +34,13 @@ constexpr Record BASIS_APPLY{"mwrt_basis_apply", sizeof(mwrt_basis_apply), offse
 // the int64 `reserved` is as wide as the pointers behind it
 constexpr Record OBS_WHITEN{"mwrt_obs_whiten", sizeof(mwrt_obs_whiten), offsetof(mwrt_obs_whiten, reserved) + sizeof(int64_t),
                             FIXED_PART, {{0, I32, 4}, {offsetof(mwrt_obs_whiten, reserved), PTR, 17}}};
+// struct_size and four int32, then pointers to the end, as mwrt_oe_lm
+constexpr Record OE_NFORM{"mwrt_oe_nform", sizeof(mwrt_oe_nform), offsetof(mwrt_oe_nform, d_k), FIXED_PART,
+                          {{0, I32, 5}, {offsetof(mwrt_oe_nform, d_k), PTR, 27}}};
 static_assert(end_of(OE_STEP) == sizeof(mwrt_oe_step) && end_of(OE_LM) == sizeof(mwrt_oe_lm) &&
               end_of(OE_CHAR) == sizeof(mwrt_oe_char) && end_of(OBS_APPLY) == sizeof(mwrt_obs_apply) &&
-              end_of(BASIS_APPLY) == sizeof(mwrt_basis_apply) && end_of(OBS_WHITEN) == sizeof(mwrt_obs_whiten),
+              end_of(BASIS_APPLY) == sizeof(mwrt_basis_apply) && end_of(OBS_WHITEN) == sizeof(mwrt_obs_whiten) &&
+              end_of(OE_NFORM) == sizeof(mwrt_oe_nform),
               "the runs of a record end where the record ends");
 static_assert(sizeof(int64_t) == PTR, "mwrt_obs_whiten: one run from reserved on");
 
@@ -220,6 +224,30 @@ Refusal whiten_args(WhitenCall call, int64_t nprof, int32_t nlev, int32_t m, con
   }
   if (m > MWRT_OE_MAX_M) return unsupported("m > MWRT_OE_MAX_M (" + std::to_string(MWRT_OE_MAX_M) + ")");
   if (nlev > MWRT_MAX_LEVELS) return nlev_limit();
+  return {};
+}
+
+// The n-form family: the start of the optimal-estimation records (se_per_profile where they have se_full), the order of
+// oe_args, and its own limit -- on n, not on m.
+Refusal oe_nform_args(NfCall call, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_nform* s, mwrt_oe_nform* r) {
+  if (!cut(OE_NFORM, s, r)) return too_small(OE_NFORM);
+  if (nprof < 0 || nlev < 1 || m < 1) return invalid("nprof < 0, nlev < 1 or m < 1");
+  if (r->nblk < 1 || r->nblk > 4) return invalid("mwrt_oe_nform.nblk must be 1 .. 4");
+  if (r->reserved != 0) return invalid("mwrt_oe_nform.reserved must be 0");
+  bool buffers = r->d_x && r->d_xa;
+  if (call == NfCall::Prepare)
+    buffers = buffers && r->d_se && r->d_y && r->d_fx && r->d_h && r->d_g && r->d_rwr && r->d_keep && r->d_nobs &&
+              r->d_lin_status && first_blocks(*r);
+  if (call == NfCall::Solve)
+    buffers = buffers && r->d_sa_inv && r->d_h && r->d_g && r->d_rwr && r->d_lin_status && r->d_x_new && r->d_status;
+  if (call == NfCall::Cost) buffers = buffers && r->d_sa_inv && r->d_se && r->d_y && r->d_fx && r->d_keep && r->d_cost;
+  if (!buffers) return invalid("null buffer");
+  if (call == NfCall::Solve && r->d_gamma && (r->d_chi2 || r->d_dfs || r->d_post_var || r->d_post_cov))
+    return invalid("mwrt_oe_nform: d_chi2, d_dfs, d_post_var and d_post_cov are defined at gamma = 0 only (d_gamma must be NULL)");
+  if ((int64_t)r->nblk * nlev > MWRT_OE_NFORM_MAX_N)
+    return unsupported("n = nblk * nlev > MWRT_OE_NFORM_MAX_N (" + std::to_string(MWRT_OE_NFORM_MAX_N) +
+                       " state elements per profile: the packed triangle of C lives in LDS)");
+  if (nprof > GRID_MAX) return unsupported("nprof exceeds grid limit");
   return {};
 }
 

@@ -30,7 +30,7 @@ struct Record {
   const char* min_what;        // ... "the fixed part (through reserved)"
   Run runs[4];                 // unused ones {0, 0, 0}
 };
-extern const Record OE_STEP, OE_LM, OE_CHAR, OBS_APPLY, BASIS_APPLY, OBS_WHITEN;
+extern const Record OE_STEP, OE_LM, OE_CHAR, OBS_APPLY, BASIS_APPLY, OBS_WHITEN, OE_NFORM;
 
 // The one cut: *out (rec.size bytes) is the caller's record with every field that is not wholly below
 // min(struct_size, rec.size) left zero.  False, *out all zero: struct_size is below rec.min_size.
@@ -45,6 +45,7 @@ struct Refusal {
 enum class LmCall { Prepare, Solve, Cost };      // the three entries of mwrt_oe_lm
 enum class CharCall { Gain, Product };           // the two of mwrt_oe_char
 enum class WhitenCall { Whiten, Apply };         // the two of mwrt_obs_whiten
+enum class NfCall { Prepare, Solve, Cost };      // the three of mwrt_oe_nform
 
 Refusal oe_step_args(int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_step* s, mwrt_oe_step* r);
 Refusal oe_lm_args(LmCall call, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_lm* s, mwrt_oe_lm* r);
@@ -54,6 +55,8 @@ Refusal obs_apply_args(int64_t nprof, int32_t nlev, const mwrt_obs_apply* s, mwr
 Refusal basis_project_args(int32_t basis_nblk, int64_t nprof, int32_t m, const mwrt_basis_apply* s, mwrt_basis_apply* r);
 Refusal basis_expand_args(int64_t nprof, const mwrt_basis_apply* s, mwrt_basis_apply* r);
 Refusal whiten_args(WhitenCall call, int64_t nprof, int32_t nlev, int32_t m, const mwrt_obs_whiten* s, mwrt_obs_whiten* r);
+// its limit is on n = nblk * nlev (MWRT_OE_NFORM_MAX_N); m is not bounded
+Refusal oe_nform_args(NfCall call, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_nform* s, mwrt_oe_nform* r);
 
 }  // namespace records
 }  // namespace mwrt

@@ -7,7 +7,7 @@
 // limits of the launch geometry and the LDS plan, then launch_tail: an empty batch, the device, the stream, the launches.
 //
 // Host code only: every kernel lives in its own unit (mwrt_oe.hip, mwrt_oe_lm.hip, mwrt_oe_char.hip, mwrt_obs.hip,
-// mwrt_basis.hip, mwrt_whiten.hip) and is reached through the launchers the headers below declare.
+// mwrt_basis.hip, mwrt_whiten.hip, mwrt_nform.hip) and is reached through the launchers the headers below declare.
 #include "mwrt_host.hip.h"
 #include "mwrt_records.h"
 #include "mwrt_oe.hip.h"
@@ -16,6 +16,7 @@
 #include "mwrt_obs.hip.h"
 #include "mwrt_basis.hip.h"
 #include "mwrt_whiten.hip.h"
+#include "mwrt_nform.hip.h"
 
 #include <cmath>
 #include <new>
@@ -23,6 +24,7 @@
 using namespace mwrt;
 using records::CharCall;
 using records::LmCall;
+using records::NfCall;
 using records::WhitenCall;
 
 struct mwrt_obs : DeviceHandle {    // the blob: w [nnz] | row_ptr [m_out + 1] | col [nnz]
@@ -132,6 +134,33 @@ int oe_lm_call(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mw
   }));
 }
 
+// The three entries of the n-form (csrc/mwrt_nform.hip) share one record, too.
+int oe_nform_call(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_nform* s, void* stream, NfCall call) {
+  if (!c || !s) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context or mwrt_oe_nform");
+  mwrt_oe_nform r;
+  if (const auto no = records::oe_nform_args(call, nprof, nlev, m, s, &r)) return refused(no);
+  nf::NfArgs a{};
+  a.k0 = r.d_k[0]; a.k1 = r.nblk > 1 ? r.d_k[1] : nullptr; a.k2 = r.nblk > 2 ? r.d_k[2] : nullptr;
+  a.k3 = r.nblk > 3 ? r.d_k[3] : nullptr;
+  a.x = r.d_x; a.xa = r.d_xa; a.sa_inv = r.d_sa_inv; a.se = r.d_se; a.y = r.d_y; a.fx = r.d_fx;
+  a.gamma = r.d_gamma; a.active = r.d_active;
+  a.h = r.d_h; a.g = r.d_g; a.rwr = r.d_rwr; a.keep = r.d_keep; a.nobs = r.d_nobs; a.lin_status = r.d_lin_status;
+  a.x_new = r.d_x_new; a.status = r.d_status;
+  a.chi2 = r.d_chi2; a.dfs = r.d_dfs; a.post_var = r.d_post_var; a.post_cov = r.d_post_cov;
+  a.cost = r.d_cost; a.cost_obs = r.d_cost_obs; a.cost_prior = r.d_cost_prior;
+  a.nblk = r.nblk; a.nlev = nlev; a.m = m; a.n = r.nblk * nlev;
+  a.xa_per_profile = r.xa_per_profile != 0; a.se_per_profile = r.se_per_profile != 0;
+  const size_t lds = call == NfCall::Prepare ? nf::normal_plan(a.n).total_bytes
+                   : call == NfCall::Solve ? nf::solve_plan(a.n).total_bytes
+                                           : nf::cost_plan(a.n).total_bytes;
+  if (const int rc = lds_fits(c, lds, STEP_LDS)) return rc;
+  return launch_tail(c, nprof, stream, launch([&](hipStream_t st) {
+    return call == NfCall::Prepare ? nf::launch_nf_normal(a, nprof, st)
+         : call == NfCall::Solve ? nf::launch_nf_solve(a, nprof, st)
+                                 : nf::launch_nf_cost(a, nprof, st);
+  }));
+}
+
 // The two entries of the characterisation (csrc/mwrt_oe_char.hip) share one record.
 int oe_char_call(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_char* s, void* stream, CharCall call) {
   if (!c || !s) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context or mwrt_oe_char");
@@ -235,6 +264,19 @@ int mwrt_oe_lm_solve_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_
 }
 int mwrt_oe_cost_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_lm* s, void* stream) {
   return oe_lm_call(c, nprof, nlev, m, s, stream, LmCall::Cost);
+}
+
+/* The same step in the n-form (csrc/mwrt_nform.hip). */
+size_t mwrt_oe_nform_size(void) { return sizeof(mwrt_oe_nform); }
+
+int mwrt_oe_nform_prepare_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_nform* s, void* stream) {
+  return oe_nform_call(c, nprof, nlev, m, s, stream, NfCall::Prepare);
+}
+int mwrt_oe_nform_solve_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_nform* s, void* stream) {
+  return oe_nform_call(c, nprof, nlev, m, s, stream, NfCall::Solve);
+}
+int mwrt_oe_nform_cost_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_nform* s, void* stream) {
+  return oe_nform_call(c, nprof, nlev, m, s, stream, NfCall::Cost);
 }
 
 /* Its characterisation (csrc/mwrt_oe_char.hip). */

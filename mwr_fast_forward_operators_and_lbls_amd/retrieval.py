@@ -21,8 +21,17 @@ channels: ``y``, ``se`` and every diagnostic are then in channel space.
 model is not; ``retrieve_lm`` damps it (Levenberg-Marquardt, Rodgers 2000 eq. 5.36) on the split entries
 ``mwrt_oe_lm_prepare_device`` / ``mwrt_oe_lm_solve_device`` / ``mwrt_oe_cost_device``: one linearisation per accepted state,
 one m x m solve per trial.  ``characterise`` returns what the undamped step at a state says about itself (Rodgers 2000, ch. 3;
-DESIGN.md 4.6.2) on ``mwrt_oe_gain_device`` / ``mwrt_oe_product_device``.  The n-form and log-humidity states are not
-offered.
+DESIGN.md 4.6.2) on ``mwrt_oe_gain_device`` / ``mwrt_oe_product_device``.  Log-humidity states are not offered.
+
+All of this is the m-form, an m x m system per profile with m <= 140.  ``OneDVar(..., form="n")`` runs ``step``, ``retrieve``
+and ``retrieve_lm`` in the n-form instead (``mwrt_oe_nform_prepare_device`` / ``mwrt_oe_nform_solve_device`` /
+``mwrt_oe_nform_cost_device``): an n x n system for a state of at most 128 elements -- the r coefficients of a basis, or a
+coarse full state -- and any number of observations.  The constructor's ``se`` is then ``[m]`` variances; ``se=`` of a call as
+``[nprof][m]`` goes straight in, as ``[nprof][m][m]`` through the pre-whitening below.  ``step(..., post_cov=True)`` returns the
+posterior covariance it has formed anyway; ``characterise`` stays with ``form="m"``.
+
+    ov = OneDVar("R24", frq, elev16, None, se, variables=..., blocks=("t", "h"), xa=xa, basis=eof, form="n")   # m = 224
+    res = ov.retrieve(z, p, y)
 
 With ``basis=StateBasis(b, sa_c)`` the retrieval runs in r coefficients of a basis shared by the batch, x = xa + B c
 (DESIGN.md 4.9): ``mwrt_basis_project_device`` contracts the K rows with B behind the K-matrix call and the update sees the
@@ -134,6 +143,42 @@ def _native_oe_cost(x, xa, se, y, fx, keep, sa_inv, cost, active, stream):
         nprof, nlev, y.shape[1], nblk, x.data_ptr(), xa.data_ptr(), se.data_ptr(), y.data_ptr(), fx.data_ptr(),
         keep.data_ptr(), sa_inv.data_ptr(), cost.data_ptr(), d_active=active.data_ptr(), xa_per_profile=xa.dim() == 3,
         se_full=se.dim() == 2, stream=stream)
+
+
+def _native_oe_nform_prepare(k_blocks, x, xa, se, y, fx, lin, active, stream):
+    """One ``mwrt_oe_nform_prepare_device`` call: fills ``lin`` (dict of h, g, rwr, keep, nobs, lin_status) in place, for the
+    profiles whose ``active`` flag (uint8) is set or, with ``active=None``, for all.  ``se`` holds variances, ``[m]`` or
+    ``[nprof][m]``.  CPU tests substitute the NumPy reference here."""
+    nprof, nblk, nlev = x.shape
+    _native.default_context(x.device.index or 0).oe_nform_prepare_device(
+        nprof, nlev, y.shape[1], [k.data_ptr() for k in k_blocks], x.data_ptr(), xa.data_ptr(), se.data_ptr(), y.data_ptr(),
+        fx.data_ptr(), lin["h"].data_ptr(), lin["g"].data_ptr(), lin["rwr"].data_ptr(), lin["keep"].data_ptr(),
+        lin["nobs"].data_ptr(), lin["lin_status"].data_ptr(), d_active=None if active is None else active.data_ptr(),
+        xa_per_profile=xa.dim() == 3, se_per_profile=se.dim() == 2, stream=stream)
+
+
+def _native_oe_nform_solve(x, xa, sa_inv, lin, gamma, out, active, stream):
+    """One ``mwrt_oe_nform_solve_device`` call on the linearisation ``lin`` into ``out`` in place: x_new and status, and --
+    with ``gamma=None`` only -- whichever of chi2, dfs, post_var and post_cov it holds a tensor for.  CPU tests substitute
+    the NumPy reference here."""
+    nprof, nblk, nlev = x.shape
+    ptr = lambda v: None if v is None else v.data_ptr()   # noqa: E731
+    _native.default_context(x.device.index or 0).oe_nform_solve_device(
+        nprof, nlev, lin["keep"].shape[1], nblk, x.data_ptr(), xa.data_ptr(), sa_inv.data_ptr(), lin["h"].data_ptr(),
+        lin["g"].data_ptr(), lin["rwr"].data_ptr(), lin["lin_status"].data_ptr(), out["x_new"].data_ptr(),
+        out["status"].data_ptr(), d_gamma=ptr(gamma), d_chi2=ptr(out.get("chi2")), d_dfs=ptr(out.get("dfs")),
+        d_post_var=ptr(out.get("post_var")), d_post_cov=ptr(out.get("post_cov")), d_active=ptr(active),
+        xa_per_profile=xa.dim() == 3, stream=stream)
+
+
+def _native_oe_nform_cost(x, xa, sa_inv, se, y, fx, keep, cost, active, stream):
+    """One ``mwrt_oe_nform_cost_device`` call: J at ``x`` on the rows ``keep`` names into ``cost`` in place, active profiles
+    only.  CPU tests substitute the NumPy reference here."""
+    nprof, nblk, nlev = x.shape
+    _native.default_context(x.device.index or 0).oe_nform_cost_device(
+        nprof, nlev, y.shape[1], nblk, x.data_ptr(), xa.data_ptr(), sa_inv.data_ptr(), se.data_ptr(), y.data_ptr(),
+        fx.data_ptr(), keep.data_ptr(), cost.data_ptr(), d_active=None if active is None else active.data_ptr(),
+        xa_per_profile=xa.dim() == 3, se_per_profile=se.dim() == 2, stream=stream)
 
 
 def _native_oe_gain(k_blocks, x, xa, sa, se, y, fx, stream):
@@ -387,8 +432,11 @@ class Retrieval:
 
 class OneDVar:
     def __init__(self, model, frq, elev, sa, se, variables: Optional[JacVariables] = None, blocks=("t", "h"), xa=None,
-                 instrument=None, ray_tracing=False, basis: Optional[StateBasis] = None):
+                 instrument=None, ray_tracing=False, basis: Optional[StateBasis] = None, form="m"):
         blocks = tuple(blocks)
+        if form not in ("m", "n"):
+            raise ValueError(f"form must be 'm' (an m x m system per profile) or 'n' (an n x n one), got {form!r}")
+        self.form = form
         # refracted spherical ray paths: the forward operator and its exact K rows come from mwrt_tb_jacobian_batch_ray_device
         self.ray_tracing = bool(ray_tracing)
         if blocks[:2] != ("t", "h") or blocks[2:] not in ((), ("liq",), ("ice",), ("liq", "ice")):
@@ -437,6 +485,17 @@ class OneDVar:
             self._prior_cov = basis.sa_c.to(dev).contiguous()
             self._sigma = torch.sqrt(torch.diagonal(self._prior_cov)).reshape(1, -1)
         self._sa_inv = None
+        if form == "n":
+            # the n-form entries (include/mwrt.h mwrt_oe_nform_*_device): an n x n system per profile, any m, variances only
+            size = n if basis is None else basis.r
+            if size > _native.OE_NFORM_MAX_N:
+                what = f"{nblk} blocks of {self.xa.shape[-1]} levels" if basis is None else f"a basis of r = {basis.r}"
+                raise ValueError(f"form='n' takes a state of at most {_native.OE_NFORM_MAX_N} elements, got {size} ({what}): "
+                                 "use a reduced basis (basis=StateBasis(...)), a coarser grid, or form='m'")
+            if self.se.dim() != 1:
+                raise ValueError(f"form='n' takes se [{self.m}] variances in the constructor, got {tuple(self.se.shape)}: pass "
+                                 f"the variances here and a per-profile full covariance [nprof][{self.m}][{self.m}] as se= of "
+                                 "the call (it is pre-whitened), or use form='m'")
 
     @property
     def sa_inv(self):
@@ -558,6 +617,124 @@ class OneDVar:
         var = torch.einsum("kj,pji,ki->pk", self._b, s_c, self._b)
         return var.reshape((u.shape[0],) + tuple(self.xa.shape[-2:]))
 
+    # -- the n-form of the update (form="n") -----------------------------------------------------------------------------
+    def _nform_se(self, se_p, k_blocks, y, fx, stream):
+        """``(k_blocks, y, fx, se, w)`` as the n-form entries are given them: the constructor's variances ``[m]``; per-profile
+        variances ``[nprof][m]`` as they are (the entries' se_per_profile; nothing is whitened, w is None); a per-profile full
+        covariance ``[nprof][m][m]`` through ``_whiten``, then variances of 1."""
+        if se_p is not None and se_p.dim() == 2:
+            return k_blocks, y, fx, se_p, None
+        return self._whiten(se_p, k_blocks, y, fx, stream)
+
+    @staticmethod
+    def _nform_lin(nprof, n, m, dev):
+        """The buffers of one n-form linearisation (``mwrt_oe_nform_prepare_device`` writes them)."""
+        f64, u8 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.uint8, device=dev)
+        return dict(h=torch.zeros((nprof, n * (n + 1) // 2), **f64), g=torch.zeros((nprof, n), **f64), rwr=torch.zeros(nprof, **f64),
+                    keep=torch.zeros((nprof, m), **u8), nobs=torch.zeros(nprof, dtype=torch.int32, device=dev),
+                    lin_status=torch.zeros(nprof, **u8))
+
+    def _nform_update(self, k_blocks, u, se, y, fx, stream, post_var, post_cov, lin=None):
+        """The undamped n-form step at the update's state ``u`` on what ``_nform_se`` returned: one prepare (into ``lin``,
+        all profiles) and one solve -> dict(x_new, status, chi2, dfs, nobs, post_var or None[, post_cov [nprof][n][n]]).
+        With a basis ``post_var`` is the level-space diag(B S^_c B^T) from the solve's C^-1 in one contraction."""
+        nprof, n = u.shape[0], u.shape[1] * u.shape[2]
+        lin = self._nform_lin(nprof, n, y.shape[1], u.device) if lin is None else lin
+        _native_oe_nform_prepare(k_blocks, u, self._prior_mean, se, y, fx, lin, None, stream)
+        f64 = dict(dtype=torch.float64, device=u.device)
+        out = dict(x_new=torch.empty_like(u), status=torch.empty(nprof, dtype=torch.uint8, device=u.device),
+                   chi2=torch.empty(nprof, **f64), dfs=torch.empty(nprof, **f64))
+        if post_var and self.basis is None:
+            out["post_var"] = torch.empty_like(u)
+        if post_cov or (post_var and self.basis is not None):
+            out["post_cov"] = torch.empty((nprof, n, n), **f64)
+        _native_oe_nform_solve(u, self._prior_mean, self.sa_inv, lin, None, out, None, stream)
+        out["nobs"] = lin["nobs"]
+        if post_var and self.basis is not None:
+            var = torch.einsum("kj,pji,ki->pk", self._b, out["post_cov"], self._b)
+            out["post_var"] = var.reshape((nprof,) + tuple(self.xa.shape[-2:]))
+        out.setdefault("post_var", None)
+        if not post_cov:
+            out.pop("post_cov", None)
+        return out
+
+    def _step_nform(self, z, p, x, y, post_var, se, post_cov):
+        """``step`` with form="n": K-matrix call -> instrument -> basis -> prepare -> solve."""
+        stream = self._stream(x)
+        nprof = x.shape[0]
+        se_p = self._per_profile_se(se, nprof)
+        u = x.contiguous() if self.basis is None else x.reshape(nprof, 1, self.basis.r).contiguous()
+        tb, valid, k_blocks = self._observe(z, p, self._state(u))
+        fx = tb.reshape(nprof, self.m)
+        k_w, y_w, fx_w, se_w, w = self._nform_se(se_p, k_blocks, y.reshape(nprof, self.m).contiguous(), fx, stream)
+        out = self._fail_whitened(w, self._nform_update(k_w, u, se_w, y_w, fx_w, stream, post_var, post_cov))
+        out["fx"], out["valid"] = fx, valid
+        if w is not None:
+            out["whiten_status"] = w["status"]
+        return out.pop("x_new").reshape(x.shape), out
+
+    def _retrieve_lm_nform(self, z, p, y, x0, max_iter, tol, gamma0, up, down, gamma_max, se):
+        """``retrieve_lm`` with form="n": the same accept / reject logic on ``mwrt_oe_nform_prepare_device`` /
+        ``mwrt_oe_nform_solve_device`` (with gamma) / ``mwrt_oe_nform_cost_device``; the final diagnostics come from one
+        undamped solve on a linearisation of every profile at the final states."""
+        nprof, m = y.shape[0], self.m
+        se_p = self._per_profile_se(se, nprof)
+        se_w, w, y_w = self.se, None, None
+        x = self._start(x0, nprof).contiguous()
+        xa = self._prior_mean
+        dev, stream = x.device, self._stream(x)
+        yv = y.reshape(nprof, m).contiguous()
+        f64, u8 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.uint8, device=dev)
+        lin = self._nform_lin(nprof, x.shape[1] * x.shape[2], m, dev)
+        trial = dict(x_new=torch.zeros_like(x), status=torch.zeros(nprof, **u8))
+        cost = torch.full((nprof,), float("inf"), **f64)
+        cost_try = torch.full((nprof,), float("inf"), **f64)
+        gamma = torch.full((nprof,), float(gamma0), **f64)
+        active = torch.ones(nprof, dtype=torch.bool, device=dev)
+        stale = torch.ones(nprof, dtype=torch.bool, device=dev)          # the state changed since its linearisation
+        converged = torch.zeros(nprof, dtype=torch.bool, device=dev)
+        iters = torch.zeros(nprof, dtype=torch.int32, device=dev)
+        k_blocks = fx = None
+        relin = True
+        for _ in range(int(max_iter)):
+            if relin:
+                k_blocks, fx = self._linearise(z, p, x)
+                k_blocks, y_w, fx, se_w, w = self._nform_se(se_p, k_blocks, yv, fx, stream)
+                mask = (active & stale).to(torch.uint8)
+                _native_oe_nform_prepare(k_blocks, x, xa, se_w, y_w, fx, lin, mask, stream)
+                _native_oe_nform_cost(x, xa, self.sa_inv, se_w, y_w, fx, lin["keep"], cost, mask, stream)
+                stale = torch.zeros_like(stale)
+                active = active & (lin["lin_status"] == 1)
+            mask = active.to(torch.uint8)
+            _native_oe_nform_solve(x, xa, self.sa_inv, lin, gamma, trial, mask, stream)
+            ok = active & (trial["status"] == 1)
+            x_try = self._bound(torch.where(ok[:, None, None], trial["x_new"], x)).contiguous()
+            fx_try = self.forward(z, p, self._state(x_try))[0].reshape(nprof, m)
+            if w is not None:
+                fx_try = _native_obs_whiten_apply(w["l"], w["keep"], 0, fx_try, None, stream)[0]
+            _native_oe_nform_cost(x_try, xa, self.sa_inv, se_w, y_w, fx_try, lin["keep"], cost_try, mask, stream)
+            accept = ok & (cost_try <= cost)
+            move = ((x_try - x).abs() / self._sigma).amax(dim=(1, 2))
+            iters = iters + active.to(torch.int32)
+            x = torch.where(accept[:, None, None], x_try, x).contiguous()
+            cost = torch.where(accept, cost_try, cost)
+            gamma = torch.where(accept, gamma / down, torch.where(active, gamma * up, gamma))
+            done = accept & (move < tol)
+            converged = converged | done
+            stale = stale | accept
+            active = active & ~done & ~(gamma > gamma_max)
+            flag = int((active.any().to(torch.int32) + 2 * stale.any().to(torch.int32)).item())
+            relin = bool(flag & 2)
+            if not flag & 1:
+                break
+        if relin:
+            k_blocks, fx = self._linearise(z, p, x)
+            k_blocks, y_w, fx, se_w, w = self._nform_se(se_p, k_blocks, yv, fx, stream)
+        d = self._fail_whitened(w, self._nform_update(k_blocks, x, se_w, y_w, fx, stream, True, False, lin=lin))
+        return Retrieval(x=self._state(x), chi2=d["chi2"], dfs=d["dfs"], post_var=d["post_var"], status=d["status"],
+                         nobs=d["nobs"], iterations=iters, converged=converged, cost=cost, gamma=gamma,
+                         **({} if self.basis is None else {"coeff": x.reshape(nprof, -1)}))
+
     # -- one Gauss-Newton step ---------------------------------------------------------------------------------------
     def _observe(self, z, p, x, want_rows=True, project=True):
         """One K-matrix call at ``x`` -> (tb [nprof][nang][nf], valid, K blocks in the state's order or None), in what the
@@ -594,7 +771,7 @@ class OneDVar:
     def _stream(x):
         return torch.cuda.current_stream(x.device).cuda_stream if x.is_cuda else None
 
-    def step(self, z, p, x, y, post_var=True, se=None):
+    def step(self, z, p, x, y, post_var=True, se=None, post_cov=False):
         """One K-matrix call at ``x`` plus one update, both queued on torch's current stream -- the stream the change of
         variables and the allocations of this method run on too (use ``torch.cuda.stream(...)`` around the call for another).
         Returns ``(x_new, diagnostics)``: diagnostics holds ``status``, ``chi2``, ``dfs``, ``nobs``, ``post_var`` (None with
@@ -608,7 +785,17 @@ class OneDVar:
         ``se=`` gives every profile its own observation-error covariance, ``[nprof][m]`` or ``[nprof][m][m]`` on the state's
         device, in place of the constructor's: K, y and F are whitened with its factor (behind the instrument and the basis)
         and the update runs with Se = 1.  ``fx`` stays the physical F(x); ``whiten_status`` is added (uint8: 1 ok, 2 Se_p not
-        positive definite -- then ``status`` is 2 and x_new and the diagnostics are NaN --, 3 no row kept)."""
+        positive definite -- then ``status`` is 2 and x_new and the diagnostics are NaN --, 3 no row kept).
+
+        With ``form="n"`` the update is ``mwrt_oe_nform_prepare_device`` + ``mwrt_oe_nform_solve_device``:
+        any m, the same diagnostics; with a basis ``post_var`` comes from the solve's C^-1 in one contraction, with no gain
+        or product call.  ``se=`` as ``[nprof][m]`` goes straight in (nothing is whitened, no ``whiten_status``), as
+        ``[nprof][m][m]`` through the pre-whitening (m <= 140).  ``post_cov=True`` (form="n" only) adds ``post_cov``
+        ``[nprof][n][n]``, the posterior covariance C^-1 in the update's state space (coefficients with a basis)."""
+        if self.form == "n":
+            return self._step_nform(z, p, x, y, post_var, se, post_cov)
+        if post_cov:
+            raise ValueError("step(post_cov=True) needs form='n'; with form='m' characterise(post_cov=True) forms it")
         stream = self._stream(x)
         nprof = x.shape[0]
         se_p = self._per_profile_se(se, nprof)
@@ -646,7 +833,9 @@ class OneDVar:
         With a basis the iteration runs in the coefficients (``x0``: ``[nprof][r]``, default ``c_a``), which are not clamped;
         convergence is max |c_new - c| / sqrt(diag sa_c) < ``tol``.  The steps then skip ``post_var``: the level-space
         diagonal is formed once, at the final states (one K-matrix call, a gain and a product call), so it is the posterior
-        variance at ``Retrieval.x``, not at the state before the last step as ``chi2`` and ``dfs`` are.
+        variance at ``Retrieval.x``, not at the state before the last step as ``chi2`` and ``dfs`` are.  With ``form="n"`` there
+        is no gain or product call: the diagonal comes from one more full ``step`` at the final states (a K-matrix call, the
+        projection, prepare and a solve that returns C^-1), whose x_new is discarded.
 
         ``se=``: a per-profile observation-error covariance as in ``step``; every step whitens its own linearisation.  A
         profile whose Se_p is not positive definite is frozen as failed at its first step: status 2, NaN diagnostics."""
@@ -677,6 +866,10 @@ class OneDVar:
             active = active & ~done
             if not bool(active.any()):
                 break
+        if self.basis is not None and self.form == "n":                  # the level-space diagonal at the final states, too
+            post_var = self.step(z, p, x, y, post_var=True, **({} if se_p is None else {"se": se_p}))[1]["post_var"]
+            return Retrieval(x=self._state(x), chi2=keep["chi2"], dfs=keep["dfs"], post_var=post_var, status=keep["status"],
+                             nobs=keep["nobs"], iterations=iters, converged=converged, coeff=x.reshape(nprof, -1))
         if self.basis is not None:
             k_blocks, fx = self._linearise(z, p, x)
             k_w, y_w, fx_w, se_w, w = self._whiten(se_p, k_blocks, y.reshape(nprof, self.m).contiguous(), fx, self._stream(x))
@@ -701,7 +894,12 @@ class OneDVar:
 
         ``se=``: a per-profile observation-error covariance as in ``step``.  The gain entry and the products run on the
         whitened linearisation; the gain is then un-whitened (``mwrt_obs_whiten_apply_device``, L^-T), so that ``gain`` is
-        d x^ / d y of the physical observations as without ``se=``.  Every other field is the same in both frames."""
+        d x^ / d y of the physical observations as without ``se=``.  Every other field is the same in both frames.
+
+        Not offered with ``form="n"``: the gain matrix is an m-form product."""
+        if self.form == "n":
+            raise ValueError("characterise is not offered with form='n': use form='m' for the gain matrix, the averaging "
+                             "kernel and the error budget, or step(..., post_cov=True) for the posterior covariance")
         if self.basis is not None:
             x = x.reshape(x.shape[0], 1, self.basis.r)
         nprof, n = x.shape[0], x.shape[1] * x.shape[2]
@@ -759,7 +957,13 @@ class OneDVar:
         ``se=``: a per-profile observation-error covariance as in ``step``.  Every linearisation is whitened (the whole
         batch: a profile whose state did not move gets the same factor bit for bit), F(x_trial) is whitened with the factor
         and the rows of the linearisation it is compared on (``mwrt_obs_whiten_apply_device``, L^-1), and J is that of Se_p.
-        A profile whose Se_p is not positive definite is frozen as failed: status 2, NaN diagnostics."""
+        A profile whose Se_p is not positive definite is frozen as failed: status 2, NaN diagnostics.
+
+        With ``form="n"`` the same loop runs on ``mwrt_oe_nform_prepare_device`` / ``mwrt_oe_nform_solve_device`` /
+        ``mwrt_oe_nform_cost_device`` (any m; one n x n solve per trial), and the final diagnostics come from one undamped
+        solve at the final states."""
+        if self.form == "n":
+            return self._retrieve_lm_nform(z, p, y, x0, max_iter, tol, gamma0, up, down, gamma_max, se)
         nprof, m = y.shape[0], self.m
         se_p = self._per_profile_se(se, nprof)
         se_w, w, y_w = self.se, None, None
