@@ -993,6 +993,43 @@ int mwrt_tb_param_jacobian_batch(mwrt_context* ctx, const mwrt_model* model, int
 int mwrt_selftest_math(mwrt_context* ctx, int32_t n, const double* x, const double* y_pos,
                        double* exp_x, double* log_y, double* x_div_y, double* x_div1_y);
 
+/* Diagnostic: one of the kernels' other arithmetic helpers on host arrays of n doubles, so each can be held to a
+ * high-precision reference on its own arguments.  `helper` selects it (MWRT_HELPER_*; the table says what in0..in3 and
+ * out0..out3 mean; arrays a helper does not use may be NULL: unused inputs read as 0, unused outputs are not written);
+ * flag[n] (required) receives the helper's `neg` flag, 0 elsewhere.  The kernel runs with `block` threads per workgroup
+ * (a multiple of 64 in 64..1024), one thread per element (LAYER_VALUE4: one thread per four consecutive elements, n a
+ * multiple of 4); threads past n leave before the helper is called, so the last wave runs its votes with inactive
+ * lanes.  The collectives (BLOCK_SUM .. ROW16_MAX) run one workgroup per `block` elements with every thread in the
+ * call, those past n holding 0.  An unknown helper, n < 0 or a bad `block` returns MWRT_ERR_INVALID_ARGUMENT; n = 0 is
+ * not an error.
+ *   FEXP_SMALL, FTANH_HALF_SMALL   in0 = x: out0 = f(x), out1 = f(x, loop_invariant_vgpr(c0))
+ *   FEXP_TINY, FTANH_HALF_TINY, TWO_ATANH_TAIL, FSQRT   in0: out0
+ *   CRECIP, CSQRT_PRINCIPAL        (in0, in1) = (re, im): (out0, out1)
+ *   CMUL_CDIV                      a = (in0, in1), b = (in2, in3): a b in (out0, out1), a / b in (out2, out3)
+ *   DCERROR_UPPER                  in0 = x, in1 = y: (out0, out1)
+ *   HUI_W_DW                       zh = (in0, in1): w in (out0, out1), dw in (out2, out3)
+ *   PLANCK_B                       in0 = x, in1 = 1/x: out0
+ *   LAYER_VALUE_ZF1 / _ZF0         in0 = x1, in1 = x0, in2 != 0 = live: out0, flag = neg   (layer_value<true / false>)
+ *   LAYER_VALUE4                   in0 = x1, in1 = x0, in2 != 0 = live (read at the thread's first element): out0, flag
+ *   LAYER_VALUE_TL_ZF1 / _ZF0      in0 = x1, in1 = x0: out0 = value, out1 = d/dx1, out2 = d/dx0, flag = neg
+ *   DIV_SMALL                      in0 = n, in1 = d (integers held in doubles; the magic number is magic_of(d)): out0
+ *   BLOCK_SUM, BLOCK_SUFFIX_EXCL   in0: out0;   BLOCK_SCAN   in0: out0 = inclusive prefix, out1 = total
+ *   ROW16_MAX                      in0 (rounded to float): out0
+ *   WAVE_VOTES                     p = in0 != 0, q = in1 != 0: out0 = wave_all(p), out1 = wave_any(p),
+ *                                  out2 = wave_all_of(p, q), as 0 / 1 */
+enum {
+  MWRT_HELPER_FEXP_SMALL = 0, MWRT_HELPER_FEXP_TINY = 1, MWRT_HELPER_FTANH_HALF_SMALL = 2, MWRT_HELPER_FTANH_HALF_TINY = 3,
+  MWRT_HELPER_TWO_ATANH_TAIL = 4, MWRT_HELPER_FSQRT = 5, MWRT_HELPER_CRECIP = 6, MWRT_HELPER_CMUL_CDIV = 7,
+  MWRT_HELPER_CSQRT_PRINCIPAL = 8, MWRT_HELPER_DCERROR_UPPER = 9, MWRT_HELPER_HUI_W_DW = 10, MWRT_HELPER_PLANCK_B = 11,
+  MWRT_HELPER_LAYER_VALUE_ZF1 = 12, MWRT_HELPER_LAYER_VALUE_ZF0 = 13, MWRT_HELPER_LAYER_VALUE4 = 14,
+  MWRT_HELPER_LAYER_VALUE_TL_ZF1 = 15, MWRT_HELPER_LAYER_VALUE_TL_ZF0 = 16, MWRT_HELPER_DIV_SMALL = 17,
+  MWRT_HELPER_BLOCK_SUM = 18, MWRT_HELPER_BLOCK_SCAN = 19, MWRT_HELPER_BLOCK_SUFFIX_EXCL = 20, MWRT_HELPER_ROW16_MAX = 21,
+  MWRT_HELPER_WAVE_VOTES = 22, MWRT_HELPER_COUNT = 23
+};
+int mwrt_selftest_helpers(mwrt_context* ctx, int32_t helper, int32_t n, int32_t block,
+                          const double* in0, const double* in1, const double* in2, const double* in3,
+                          double* out0, double* out1, double* out2, double* out3, uint8_t* flag);
+
 /* Block until everything queued on the context's stream (or `stream`) has finished. */
 int mwrt_synchronize(mwrt_context* ctx, void* stream);
 

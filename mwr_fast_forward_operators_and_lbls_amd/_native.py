@@ -163,6 +163,12 @@ OE_NFORM_MAX_N = 128
 MAX_ANGLES = 64
 
 MWRT_VERSION = 301
+#: MWRT_HELPER_* of include/mwrt.h (mwrt_selftest_helpers), in the header's order
+HELPERS = {name: k for k, name in enumerate((
+    "fexp_small", "fexp_tiny", "ftanh_half_small", "ftanh_half_tiny", "two_atanh_tail", "fsqrt", "crecip", "cmul_cdiv",
+    "csqrt_principal", "dcerror_upper", "hui_w_dw", "planck_b", "layer_value_zf1", "layer_value_zf0", "layer_value4",
+    "layer_value_tl_zf1", "layer_value_tl_zf0", "div_small", "block_sum", "block_scan", "block_suffix_excl", "row16_max",
+    "wave_votes"))}
 
 
 #: every symbol include/mwrt.h declares: (name, restype, argtypes)
@@ -250,6 +256,7 @@ SIGNATURES = {
     "mwrt_set_absorption_mode": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_set_chunk_width": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_selftest_math": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mwrt_selftest_helpers": (ctypes.c_int, [_vp, _i32, _i32, _i32] + [_vp] * 9),
     "mwrt_synchronize": (ctypes.c_int, [_vp, _vp]),
     "mwrt_set_timing": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mwrt_timing_collect": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]),
@@ -1013,6 +1020,22 @@ class Context:
         self._check(self._lib.mwrt_selftest_math(self._handle, x.size, _ptr(x), _ptr(y), *[_ptr(o) for o in outs]),
                     "mwrt_selftest_math")
         return outs
+
+    @_serialised
+    def selftest_helpers(self, helper, inputs, block=256, n=None):
+        """One device helper on host arrays (mwrt_selftest_helpers; ``helper``: a key of HELPERS or its number;
+        ``inputs``: up to four equally long arrays).  Returns (four float64 output arrays, the uint8 flag array)."""
+        helper = HELPERS[helper] if isinstance(helper, str) else int(helper)
+        ins = [_f64(a).ravel() for a in inputs]
+        n = (ins[0].size if ins else 0) if n is None else int(n)
+        if n >= 0 and any(a.size != n for a in ins):
+            raise ValueError("selftest_helpers: every input holds n elements")
+        outs = [np.zeros(max(n, 0)) for _ in range(4)]
+        flag = np.zeros(max(n, 0), dtype=np.uint8)
+        ptrs = [_ptr(a) for a in ins] + [None] * (4 - len(ins))
+        self._check(self._lib.mwrt_selftest_helpers(self._handle, helper, n, int(block), *ptrs, *[_ptr(o) for o in outs],
+                                                    _ptr(flag)), "mwrt_selftest_helpers")
+        return outs, flag
 
     @_serialised
     def synchronize(self, stream=None):

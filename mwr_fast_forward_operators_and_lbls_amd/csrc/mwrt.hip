@@ -1104,6 +1104,48 @@ int mwrt_selftest_math(mwrt_context* c, int32_t n, const double* x, const double
   return MWRT_OK;
 }
 
+int mwrt_selftest_helpers(mwrt_context* c, int32_t helper, int32_t n, int32_t block,
+                          const double* in0, const double* in1, const double* in2, const double* in3,
+                          double* out0, double* out1, double* out2, double* out3, uint8_t* flag) {
+  if (!c) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context");
+  if (helper < 0 || helper >= MWRT_HELPER_COUNT) return fail(MWRT_ERR_INVALID_ARGUMENT, "selftest_helpers: unknown helper");
+  if (n < 0) return fail(MWRT_ERR_INVALID_ARGUMENT, "selftest_helpers: n < 0");
+  if (block < 64 || block > 1024 || block % 64 != 0)
+    return fail(MWRT_ERR_INVALID_ARGUMENT, "selftest_helpers: block must be a multiple of 64 in 64..1024");
+  if (helper == MWRT_HELPER_LAYER_VALUE4 && n % 4 != 0)
+    return fail(MWRT_ERR_INVALID_ARGUMENT, "selftest_helpers: LAYER_VALUE4 takes n in multiples of 4");
+  if (n == 0) return MWRT_OK;
+  if (!flag) return fail(MWRT_ERR_INVALID_ARGUMENT, "selftest_helpers: null flag");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t b = sizeof(double) * (size_t)n;
+  const std::vector<double> zeros((size_t)n, 0.0);
+  std::vector<double> magic;
+  if (helper == MWRT_HELPER_DIV_SMALL) {                // the magic number as the planning code makes it
+    if (!in1) return fail(MWRT_ERR_INVALID_ARGUMENT, "selftest_helpers: DIV_SMALL needs in1 (the divisors)");
+    magic.resize((size_t)n);
+    for (int32_t i = 0; i < n; ++i) magic[i] = (double)magic_of((int)in1[i]);
+    in2 = magic.data();
+  }
+  const double* src[4] = {in0 ? in0 : zeros.data(), in1 ? in1 : zeros.data(), in2 ? in2 : zeros.data(),
+                          in3 ? in3 : zeros.data()};
+  int rc = stage_in(c, c->stream, (size_t)n, src, 4); if (rc) return rc;
+  HIP_TRY(c->d_out.reserve(4 * b + (size_t)n));
+  double* din = c->d_in.as<double>();
+  double* dout = c->d_out.as<double>();
+  HIP_TRY(hipMemsetAsync(dout, 0, 4 * b + (size_t)n, c->stream));
+  HelperArgs a;
+  for (int k = 0; k < 4; ++k) { a.in[k] = din + (size_t)k * n; a.out[k] = dout + (size_t)k * n; }
+  a.flag = reinterpret_cast<uint8_t*>(dout + 4 * (size_t)n);
+  a.n = n; a.helper = helper;
+  HIP_TRY(launch_selftest_helpers(a, block, c->stream));
+  double* dst[4] = {out0, out1, out2, out3};
+  for (int k = 0; k < 4; ++k)
+    if (dst[k]) HIP_TRY(hipMemcpyAsync(dst[k], a.out[k], b, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(flag, a.flag, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));                // (the staged host vectors live until here)
+  return MWRT_OK;
+}
+
 int mwrt_synchronize(mwrt_context* c, void* stream) {
   if (!c) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context");
   HIP_TRY(hipSetDevice(c->device));

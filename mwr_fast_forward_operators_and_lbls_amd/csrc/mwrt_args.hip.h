@@ -146,5 +146,13 @@ hipError_t launch_ray_paths(const double* z, const double* p, const double* t, c
                             const double* elev_deg, int nang, double* amf, uint8_t* duct, hipStream_t st);
 hipError_t launch_selftest_math(const double* x, const double* y, double* out_exp, double* out_log, double* out_div,
                                 double* out_div1, int n, hipStream_t st);
+// mwrt_selftest_helpers: helper = MWRT_HELPER_*, in / out = four device arrays of n doubles each, flag[n]
+struct HelperArgs {
+  const double* in[4];
+  double* out[4];
+  uint8_t* flag;
+  int n, helper;
+};
+hipError_t launch_selftest_helpers(const HelperArgs& a, int block, hipStream_t st);
 
 }  // namespace mwrt

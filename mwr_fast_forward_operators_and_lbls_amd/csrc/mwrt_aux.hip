@@ -1,7 +1,9 @@
 // mwrt_aux.hip -- the kernels that are no templates, in a translation unit of their own, and their launchers: the
-// ray-path pre-kernel of ray_tracing=True (k_ray_paths) and the self-test of the arithmetic helpers (k_selftest_math).
+// ray-path pre-kernel of ray_tracing=True (k_ray_paths) and the self-tests of the arithmetic helpers (k_selftest_math;
+// k_selftest_poly / _cplx / _planck / _layer / _layer4 / _div_small / _block / _votes behind mwrt_selftest_helpers).
 // Declarations: mwrt_args.hip.h.  (The K-matrix kernels are csrc/mwrt_tl.hip.)
 #include "mwrt_absorption.hip.h"
+#include "mwrt_tl_dev.hip.h"          // hui_w_dw, layer_value_tl, the workgroup scans; mwrt_layer.hip.h through it
 
 namespace mwrt {
 
@@ -116,7 +118,135 @@ __global__ void k_selftest_math(const double* x, const double* y, double* out_ex
   out_div1[i] = fdiv1(x[i], y[i]);
 }
 
-hipError_t launch_ray_paths(const double* z, const double* p, const double* t, const double* rh, int64_t nprof, int nlev,
+// diagnostic: the other helpers, each called as shipped on caller-supplied arguments (mwrt_selftest_helpers; the table of
+// selectors is in include/mwrt.h).  One thread per element; a thread past n leaves BEFORE the helper is called, so the
+// last wave takes every vote with inactive lanes.  Several kernels: the polynomial constants ride in SGPR pairs.
+__global__ void __launch_bounds__(1024) k_selftest_poly(HelperArgs a) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  const double x = a.in[0][i];
+  switch (a.helper) {
+    case MWRT_HELPER_FEXP_SMALL:
+      a.out[0][i] = fexp_small(x);
+      a.out[1][i] = fexp_small(x, loop_invariant_vgpr(FEXP_SMALL_C0));
+      break;
+    case MWRT_HELPER_FEXP_TINY: a.out[0][i] = fexp_tiny(x); break;
+    case MWRT_HELPER_FTANH_HALF_SMALL:
+      a.out[0][i] = ftanh_half_small(x);
+      a.out[1][i] = ftanh_half_small(x, loop_invariant_vgpr(FTANH_HALF_SMALL_C0));
+      break;
+    case MWRT_HELPER_FTANH_HALF_TINY: a.out[0][i] = ftanh_half_tiny(x); break;
+    case MWRT_HELPER_TWO_ATANH_TAIL: a.out[0][i] = two_atanh_tail(x); break;
+    default: a.out[0][i] = fsqrt(x); break;
+  }
+}
+
+__global__ void __launch_bounds__(1024) k_selftest_cplx(HelperArgs a) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  const cplx z = {a.in[0][i], a.in[1][i]};
+  cplx r = {0.0, 0.0}, r2 = {0.0, 0.0};
+  switch (a.helper) {
+    case MWRT_HELPER_CRECIP: r = crecip(z); break;
+    case MWRT_HELPER_CMUL_CDIV: {
+      const cplx b = {a.in[2][i], a.in[3][i]};
+      r = cmul(z, b);
+      r2 = cdiv(z, b);
+      break;
+    }
+    case MWRT_HELPER_CSQRT_PRINCIPAL: r = csqrt_principal(z); break;
+    case MWRT_HELPER_DCERROR_UPPER: r = dcerror_upper(z.re, z.im); break;
+    default: hui_w_dw(z, r, r2); break;
+  }
+  a.out[0][i] = r.re; a.out[1][i] = r.im;
+  a.out[2][i] = r2.re; a.out[3][i] = r2.im;
+}
+
+__global__ void __launch_bounds__(1024) k_selftest_planck(HelperArgs a) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  a.out[0][i] = planck_b(a.in[0][i], a.in[1][i]);
+}
+
+__global__ void __launch_bounds__(1024) k_selftest_layer(HelperArgs a) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  const double x1 = a.in[0][i], x0 = a.in[1][i];
+  const bool live = a.in[2][i] != 0.0;
+  bool neg = false;
+  double d1 = 0.0, d0 = 0.0, r;
+  switch (a.helper) {
+    case MWRT_HELPER_LAYER_VALUE_ZF1: r = layer_value<true>(x1, x0, neg, live); break;
+    case MWRT_HELPER_LAYER_VALUE_ZF0: r = layer_value<false>(x1, x0, neg, live); break;
+    case MWRT_HELPER_LAYER_VALUE_TL_ZF1: r = layer_value_tl<true>(x1, x0, d1, d0, neg); break;
+    default: r = layer_value_tl<false>(x1, x0, d1, d0, neg); break;
+  }
+  a.out[0][i] = r; a.out[1][i] = d1; a.out[2][i] = d0;
+  a.flag[i] = neg ? 1 : 0;
+}
+
+// one thread per four consecutive elements (n is a multiple of 4)
+__global__ void __launch_bounds__(1024) k_selftest_layer4(HelperArgs a) {
+  const int64_t i = 4 * (blockIdx.x * (int64_t)blockDim.x + threadIdx.x);
+  if (i >= a.n) return;
+  double x1[4], x0[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { x1[k] = a.in[0][i + k]; x0[k] = a.in[1][i + k]; }
+  bool neg = false;
+  layer_value4(x1, x0, neg, a.in[2][i] != 0.0);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { a.out[0][i + k] = x1[k]; a.flag[i + k] = neg ? 1 : 0; }
+}
+
+__global__ void __launch_bounds__(1024) k_selftest_div_small(HelperArgs a) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  a.out[0][i] = (double)div_small((int)a.in[0][i], (int)a.in[1][i], (unsigned)a.in[2][i]);
+}
+
+// the collectives: one workgroup per blockDim.x elements, every thread in the call (those past n hold 0)
+__global__ void __launch_bounds__(1024) k_selftest_block(HelperArgs a) {
+  __shared__ double wsum[1024 / WAVE];
+  const int tid = threadIdx.x;
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + tid;
+  const bool inside = i < a.n;
+  const double v = inside ? a.in[0][i] : 0.0;
+  const int nwaves = (int)blockDim.x / WAVE;
+  double r, total = 0.0;
+  switch (a.helper) {
+    case MWRT_HELPER_BLOCK_SUM: r = block_sum(v, wsum, tid, (int)blockDim.x); break;
+    case MWRT_HELPER_BLOCK_SCAN: r = block_scan(v, wsum, tid, nwaves, total); break;
+    case MWRT_HELPER_BLOCK_SUFFIX_EXCL: r = block_suffix_excl(v, wsum, tid, nwaves); break;
+    default: r = (double)row16_max((float)v); break;
+  }
+  if (inside) { a.out[0][i] = r; a.out[1][i] = total; }
+}
+
+__global__ void __launch_bounds__(1024) k_selftest_votes(HelperArgs a) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  const bool p = a.in[0][i] != 0.0, q = a.in[1][i] != 0.0;
+  a.out[0][i] = wave_all(p) ? 1.0 : 0.0;
+  a.out[1][i] = wave_any(p) ? 1.0 : 0.0;
+  a.out[2][i] = wave_all_of(p, q) ? 1.0 : 0.0;
+}
+
+hipError_t launch_selftest_helpers(const HelperArgs& a, int block, hipStream_t st) {
+  const int64_t threads = a.helper == MWRT_HELPER_LAYER_VALUE4 ? a.n / 4 : a.n;
+  const dim3 grid((unsigned)((threads + block - 1) / block)), blk((unsigned)block);
+  const int h = a.helper;
+  if (h <= MWRT_HELPER_FSQRT) hipLaunchKernelGGL(k_selftest_poly, grid, blk, 0, st, a);
+  else if (h <= MWRT_HELPER_HUI_W_DW) hipLaunchKernelGGL(k_selftest_cplx, grid, blk, 0, st, a);
+  else if (h == MWRT_HELPER_PLANCK_B) hipLaunchKernelGGL(k_selftest_planck, grid, blk, 0, st, a);
+  else if (h == MWRT_HELPER_LAYER_VALUE4) hipLaunchKernelGGL(k_selftest_layer4, grid, blk, 0, st, a);
+  else if (h <= MWRT_HELPER_LAYER_VALUE_TL_ZF0) hipLaunchKernelGGL(k_selftest_layer, grid, blk, 0, st, a);
+  else if (h == MWRT_HELPER_DIV_SMALL) hipLaunchKernelGGL(k_selftest_div_small, grid, blk, 0, st, a);
+  else if (h <= MWRT_HELPER_ROW16_MAX) hipLaunchKernelGGL(k_selftest_block, grid, blk, 0, st, a);
+  else hipLaunchKernelGGL(k_selftest_votes, grid, blk, 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_ray_paths(const double* z,const double* p, const double* t, const double* rh, int64_t nprof, int nlev,
                             const double* elev_deg, int nang, double* amf, uint8_t* duct, hipStream_t st) {
   hipLaunchKernelGGL(k_ray_paths, dim3((unsigned)nprof), dim3(lanes_for(nlev)), 0, st, z, p, t, rh, nlev, elev_deg, nang, amf,
                      duct);

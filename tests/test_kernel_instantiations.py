@@ -150,7 +150,8 @@ class Call:
     """One GPU call as data.  entry: "tb" (mwrt_tb_batch[_opt]), "multi" (mwrt_tb_batch_multi), "alpha"
     (mwrt_absorption_batch_device -> mwrt_tb_from_absorption_device), "absorption" (mwrt_absorption_batch), "layer_tau"
     (mwrt_layer_tau_batch_device -> mwrt_tb_from_layer_tau_device), "jacobian" (mwrt_tb_jacobian_batch), "jacobian_device"
-    (mwrt_tb_jacobian_batch_device), "selftest" (mwrt_selftest_math).  check: the GPU test that runs it."""
+    (mwrt_tb_jacobian_batch_device), "selftest" (mwrt_selftest_math), "helpers" (mwrt_selftest_helpers, every selector).
+    check: the GPU test that runs it."""
     check: str
     entry: str
     nlev: int
@@ -181,6 +182,8 @@ def route(c, lds_max=LDS_MAX):
     nf = len(frq)
     if c.entry == "selftest":
         return {"k_selftest_math"}, 0
+    if c.entry == "helpers":                                       # launch_selftest_helpers: one kernel per group of selectors
+        return {"k_selftest_" + g for g in ("poly", "cplx", "planck", "layer", "layer4", "div_small", "block", "votes")}, 0
     if c.entry in ("jacobian", "jacobian_device"):
         return {"k_absorb_tl", "k_jac_rte"}, 0
     if c.entry == "absorption":
@@ -294,6 +297,7 @@ def _build_cases():
             add("widths", entry, 1024, frq="f33", options=opts, chunk_width=w, model="R17")
     # one small call each to the remaining kernels, at 1024 levels
     add("misc", "selftest", 2, model="R24")
+    add("helpers", "helpers", 2, model="R24")
     add("misc", "jacobian", 1024, nang=2, model="R24")
     add("misc", "jacobian_device", 1024, nang=2, model="R24")
     add("misc", "tb", 1024, options=("rays",), nang=4, model="R24")
@@ -951,6 +955,28 @@ def test_remaining_kernels_at_1024_levels(gpu_ctx):
     assert valid[0] == 1
     record("rays 1024 TB", np.abs(tb[0].ravel() - r["tbtotal"]).max())
     assert np.abs(tb[0].ravel() - r["tbtotal"]).max() <= TOL_K
+
+
+@pytest.mark.gpu
+def test_helper_selftest_kernels_at_1024_threads(gpu_ctx):
+    """the k_selftest_* kernels behind mwrt_selftest_helpers: every selector once in 1024-thread workgroups, two of them with
+    the last one partly filled (their accuracy is held in test_math_helpers)"""
+    from mwr_fast_forward_operators_and_lbls_amd import _native
+    (c,) = cases_of("helpers")
+    assert len(expected_kernels(c)) == 8
+    n = 2 * 1024 - 100
+    x = np.linspace(0.01, 0.1, n)
+    for name in _native.HELPERS:
+        ins = [np.arange(n) + 0.0, np.full(n, 7.0)] if name == "div_small" else [x, x[::-1].copy(), np.ones(n), x]
+        outs, flag = gpu_ctx.selftest_helpers(name, ins, block=1024)
+        assert all(np.isfinite(o).all() for o in outs) and not flag.any(), name
+        assert np.abs(outs[0]).min() > 0 or name in ("div_small", "block_suffix_excl"), name
+    s = gpu_ctx.selftest_helpers("fsqrt", [x], block=1024)[0][0]
+    assert np.abs(s * s / x - 1).max() < 1e-13
+    v = gpu_ctx.selftest_helpers("layer_value_zf1", [x, x, np.ones(n)], block=1024)[0][0]
+    assert np.array_equal(v, x)
+    q = gpu_ctx.selftest_helpers("div_small", [np.arange(n) + 0.0, np.full(n, 7.0)], block=1024)[0][0]
+    assert np.array_equal(q, np.arange(n) // 7)
 
 
 @pytest.mark.gpu
