@@ -311,7 +311,9 @@ __device__ __forceinline__ unsigned long long lowest_bits(unsigned long long m, 
 // The SD resonant shape costs ~92 VALU per (level, frequency); its DIFFERENCE from the Lorentzian it replaces is small
 // (<= 2 % of it) and smooth across a chunk, so it is evaluated at 9 of the 16 frequencies (slots 0, 2, ..., 14 and 15) and
 // interpolated to the other 7 with host-computed Lagrange weights: error <= 4e-12 of the line's Lorentzian
-// (probe on the oracle's formulas), against the 1e-10 the windowed path works to.  Where a lane is inside 10
+// (probe on the oracle's formulas; 1.8e-12 of the wet absorption at exactly 5 spans, tests/window_reference.py),
+// against the 3e-10 the window plan itself leaves.  The host half-samples only chunks whose own slots interpolate stably
+// (SD_LEBESGUE_MAX, mwrt_plan.h).  Where a lane is inside 10
 // half-widths the odd slots then get Lorentzian + interpolated difference; outside, the plain Lorentzian as always.
 // (SD_NODES, SD_TARGETS, sd_node_slot: mwrt_plan.h)
 

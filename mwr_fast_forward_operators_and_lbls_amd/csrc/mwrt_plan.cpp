@@ -129,6 +129,27 @@ void window_far_sets(const mwrt_model_desc& t, double flo, double fhi, WinDesc* 
   }
 }
 
+// Lagrange weights of the half-sampled speed-dependent shape for one full chunk f[0 .. 15]: w[target][node], the odd slots
+// from slots 0, 2, ..., 14, 15 (w may be null).  False where the chunk cannot be half-sampled: frequencies not increasing,
+// or some target's weights sum to more than SD_LEBESGUE_MAX in absolute value (near-coincident frequencies next to a gap).
+bool sd_half_weights(const double* f, double* w) {
+  for (int j = 1; j < WIN_NFC; ++j) if (!(f[j] > f[j - 1])) return false;
+  bool ok = true;
+  for (int i = 0; i < SD_TARGETS; ++i) {
+    const long double x = f[2 * i + 1];
+    long double lebesgue = 0.0L;
+    for (int n = 0; n < SD_NODES; ++n) {
+      long double wn = 1.0L;
+      for (int q = 0; q < SD_NODES; ++q)
+        if (q != n) wn *= (x - (long double)f[sd_node_slot(q)]) / ((long double)f[sd_node_slot(n)] - (long double)f[sd_node_slot(q)]);
+      lebesgue += fabsl(wn);
+      if (w) w[i * SD_NODES + n] = (double)wn;
+    }
+    if (!(lebesgue <= SD_LEBESGUE_MAX)) ok = false;
+  }
+  return ok;
+}
+
 size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -248,6 +269,8 @@ void chunk_masks(const mwrt_model_desc& t, const double* frq, int nf, int nfc, s
       if (!no_vfar && very_far(t.o2_f[k])) lm.o2_vfar |= 1ull << k;
     }
     if (__builtin_popcountll(lm.o2_vfar) < VF_MIN_LINES) lm.o2_vfar = 0;
+    // half-sampled shape: a full 16-frequency chunk of increasing frequencies whose slots interpolate stably ...
+    const bool half_ok = nfc == 16 && j1 - j0 == 16 && sd_half_weights(frq + j0, nullptr);
     for (int k = 0; k < t.n_h2o; ++k) {
       double dmin = 1e300, smin = 1e300;
       for (int j = j0; j < j1; ++j) { dmin = std::min(dmin, std::fabs(frq[j] - t.h2o_fl[k])); smin = std::min(smin, std::fabs(frq[j] + t.h2o_fl[k])); }
@@ -258,11 +281,9 @@ void chunk_masks(const mwrt_model_desc& t, const double* frq, int nf, int nfc, s
       if (t.h2o_w2[k] > 0.0) {
         lm.h2o_sd |= 1u << k;
         if (10.0 * sd_halfwidth_bound(t, k) < dmin - 1.0) lm.h2o_sdfar |= 1u << k;       // its special shape cannot reach the chunk
-        // half-sampled shape: a full 16-frequency chunk of increasing frequencies, >= 3 GHz and 5 spans from the centre
-        bool inc = nfc == 16 && j1 - j0 == 16;
-        for (int j = j0 + 1; inc && j < j1; ++j) inc = frq[j] > frq[j - 1];
+        // ... >= 3 GHz and 5 spans from the centre
         static const bool no_half = std::getenv("MWRT_NO_SD_HALF") != nullptr;            // diagnostic: time the full sampling
-        if (inc && !no_half && dmin >= 3.0 && dmin >= 5.0 * (frq[j1 - 1] - frq[j0])) lm.h2o_sdint |= 1u << k;
+        if (half_ok && !no_half && dmin >= 3.0 && dmin >= 5.0 * (frq[j1 - 1] - frq[j0])) lm.h2o_sdint |= 1u << k;
       }
     }
     if (__builtin_popcount(lm.h2o_vfar) < VF_MIN_LINES) lm.h2o_vfar = 0;
@@ -318,20 +339,13 @@ void build_windows(const mwrt_model_desc& t, const double* frq, int nf, WindowSe
     };
     std::stable_sort(spans.begin(), spans.end(), [&](const Span& x, const Span& y) { return cost(x) > cost(y); });
   }
-  // Lagrange weights of the half-sampled speed-dependent shape, per chunk (zero for a partial last chunk: never used)
+  // Lagrange weights of the half-sampled speed-dependent shape, per chunk (zero for a partial last chunk and for a chunk
+  // that chunk_masks never half-samples: never used)
   ws->lag_sd.assign((size_t)nchunks * SD_TARGETS * SD_NODES, 0.0);
   for (int ch = 0; ch < nchunks; ++ch) {
     if ((ch + 1) * WIN_NFC > nf) continue;
-    const double* f = frq + (size_t)ch * WIN_NFC;
-    for (int i = 0; i < SD_TARGETS; ++i) {
-      const long double x = f[2 * i + 1];
-      for (int n = 0; n < SD_NODES; ++n) {
-        long double w = 1.0L;
-        for (int q = 0; q < SD_NODES; ++q)
-          if (q != n) w *= (x - (long double)f[sd_node_slot(q)]) / ((long double)f[sd_node_slot(n)] - (long double)f[sd_node_slot(q)]);
-        ws->lag_sd[((size_t)ch * SD_TARGETS + i) * SD_NODES + n] = (double)w;
-      }
-    }
+    double w[SD_TARGETS * SD_NODES];
+    if (sd_half_weights(frq + (size_t)ch * WIN_NFC, w)) std::copy(w, w + SD_TARGETS * SD_NODES, ws->lag_sd.begin() + (size_t)ch * SD_TARGETS * SD_NODES);
   }
   const int nwin = (int)spans.size();
   const int perm = WIN_CHUNKS_MAX * WIN_NFC;

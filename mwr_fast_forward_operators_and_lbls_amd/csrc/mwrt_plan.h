@@ -39,7 +39,7 @@ struct LineMasks {
   unsigned h2o_sd;             // speed-dependent lines (W2 > 0)
   unsigned h2o_sdfar;          // ... of those, the ones whose special shape (inside 10 half-widths) cannot reach any frequency of
                                // the chunk by the host's bound: treated as plain lines, re-checked per level (wave vote)
-  unsigned h2o_sdint;          // speed-dependent lines far enough from the chunk (>= 3 GHz and 5 spans) for the half-sampled shape
+  unsigned h2o_sdint;          // speed-dependent lines far enough from the chunk (>= 3 GHz and 5 spans) for the half-sampled shape (SD_LEBESGUE_MAX)
   unsigned h2o_vfar;           // "very far" lines: summed as ONE Taylor polynomial in f^2 about the chunk's middle (vfar_add)
   unsigned long long o2_vfar;
   double vf_u0, vf_h, vf_invh; // middle and half range of the chunk's f^2 values [GHz^2] (vf_h >= 1), 1 / vf_h
@@ -70,6 +70,10 @@ constexpr int VF_MIN_LINES = 4;              // fewer lines than this do not pay
 // half-sampled speed-dependent shape (mwrt_absorption.hip.h): evaluated at 9 of a chunk's 16 frequencies, interpolated to 7
 constexpr int SD_NODES = 9, SD_TARGETS = 7;
 constexpr int sd_node_slot(int n) { return n < 8 ? 2 * n : 15; }
+// ... where the chunk's own slots interpolate stably: the sum of a target's |weights| (10.3 on an evenly spaced chunk)
+// multiplies every rounding error of the nine sampled values, and 9 weights rounded to doubles still sum to 1 within
+// 9 x 100 x 2^-53 = 1e-13.  Near-coincident frequencies next to a gap reach 1e4 and more: such a chunk is sampled in full.
+constexpr double SD_LEBESGUE_MAX = 100.0;
 
 constexpr int MAX_MULTI = 8;   // absorption models evaluated by one launch (the wrapper runs four)
 

@@ -167,8 +167,13 @@ k_absorb(const AbsorbArgs A) {
 // Lagrange matrix (wave-uniform, from the host: depends on the frequencies only) and adds the remaining lines
 // -- near the window, speed dependent, or failing a per-level vote -- directly.  The per-(level, line) setup of
 // the far lines is paid once per window instead of once per chunk.
-// Interpolation error: <= 1e-10 of the line sum for spans <= 6 GHz (16 nodes, 4 GHz margin; tools/window_probe.py
-// reproduces the bound on the oracle), i.e. invisible against the 1e-6 K parity bar -- and tested against it.
+// Interpolation error: what sets it is a strong isolated line just beyond the margin -- 118.7503 GHz seen from
+// [122.76, 127.76] or [109.74, 114.74] (4.01 GHz beyond a 5-GHz window, 2.6 half-spans from its middle) leaves
+// 2.7e-10 of the dry absorption at the sharp-line top levels, the 6-GHz window [107.95, 113.95] 2.1e-10; inside the
+// 60-GHz band, where many far lines share the sum, 3e-11, out of band 1e-13 (tests/window_reference.py
+// plan_truncation on the oracle's formulas, held under 5e-10 by tests/test_window_plan.py).  On the device the windowed
+// sums then meet the every-line kernel to 3.1e-10 and the oracle to 3.0e-10 relative on those windows (bar 1e-9), TBs to
+// 1.4e-9 K (bar 1e-6 K): tests/test_window_geometry.py, profiles/window_geometry_errors.json.
 //
 // TAU = true: the chunk ends with the layer step (see k_absorb) and writes the zenith layer optical depth,
 // [level][frequency], 8 B per point; the fine-grid TB path is this kernel followed by k_rte_tau.

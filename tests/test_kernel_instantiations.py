@@ -21,13 +21,13 @@ import dataclasses
 import json
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 from mwr_fast_forward_operators_and_lbls_amd import profiles as pr, spectroscopy as sp
+from plan_dump_tool import plan_dump, request as line          # noqa: F401 (plan_dump: the fixture, sanitised build)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mwr_fast_forward_operators_and_lbls_amd", "csrc")
@@ -333,29 +333,9 @@ def seam_frequency_lists():
     return [f, f[:127], f[::-1], np.linspace(20.0, 26.1, 128), np.linspace(20.0, 26.0, 128), f[:129]]
 
 
-@pytest.fixture(scope="module")
-def plan_dump(tmp_path_factory):
-    """tests/plan_dump.cpp + csrc/mwrt_plan.cpp, built with the host C++ compiler under ASan + UBSan; returns
-    ask(request lines) -> one parsed JSON answer per line.  A sanitiser report ends the child with a non-zero status."""
-    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    exe = str(tmp_path_factory.mktemp("plan_dump") / "plan_dump")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    os.path.join(ROOT, "tests", "plan_dump.cpp"), os.path.join(CSRC, "mwrt_plan.cpp"), "-o", exe], check=True)
-
-    def ask(lines):
-        r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True)
-        assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-4000:])
-        out = [json.loads(x) for x in r.stdout.splitlines()]
-        assert len(out) == len(lines)
-        return out
-    return ask
-
-
 def test_mirror_matches_the_planning_code(plan_dump, tmp_path):
     """The Python restatement above against csrc/mwrt_plan.cpp itself, at every seam of test_routing_mirror_at_its_seams and
     for every Call of CASES; the same sanitised run takes the frequency lists through chunk_masks and build_windows"""
-    line = lambda *a: " ".join(repr(float(x)) if isinstance(x, (float, np.floating)) else str(x) for x in a)
     want, asked = [], []
 
     def ask(request, expect):
