@@ -4,9 +4,11 @@ observations per profile; the m-form of the optimal-estimation step holds an m x
 n-form, OneDVar(form="n"), solves an n x n system for the r = 12 + 12 EOF coefficients of examples/reduced_basis_retrieval.py
 instead -- mwrt_oe_nform_prepare_device streams K B once, mwrt_oe_nform_solve_device factorises a 24 x 24 matrix -- and has
 no limit on m.  The example retrieves the 16-elevation scan with form="n" (Levenberg-Marquardt), shows that form="m" is
-refused there, and at 14 x 7 = 98 observations prints both forms side by side.  The n-form takes variances only, so what the
-24 coefficients cannot represent enters Se as the diagonal of its representation error K (Sa - B sa_c B^T) K^T, with K the
-batch mean at the first guess (examples/reduced_basis_retrieval.py carries the full matrix, which the m-form can take).
+refused there, at 14 x 7 = 98 observations prints both forms side by side, and ends with what the extra elevations buy:
+OneDVar.characterise_nform gives the degrees of freedom per block and the temperature averaging kernels at 7
+and at 16 elevations.  The n-form takes variances only, so what the 24 coefficients cannot represent enters Se as the diagonal
+of its representation error K (Sa - B sa_c B^T) K^T, with K the batch mean at the first guess
+(examples/reduced_basis_retrieval.py carries the full matrix, which the m-form can take).
 
     python examples/many_observation_retrieval.py
 """
@@ -104,3 +106,25 @@ print(f"largest difference of the two forms: coefficients {float((res_n.coeff - 
 print(f"16 elevations against 7: T error below 4 km {float(((res16.x[:, 0][:, below] - x_true[:, 0][:, below]) ** 2).mean(dim=1).sqrt().median()):.3f} K "
       f"against {float(((res_n.x[:, 0][:, below] - x_true[:, 0][:, below]) ** 2).mean(dim=1).sqrt().median()):.3f} K, "
       f"dfs {float(res16.dfs.median()):.2f} against {float(res_n.dfs.median()):.2f}")
+
+# ---- what the extra elevations buy: the characterisation of the n-form step ----
+# characterise_nform works in the 24 coefficients: the first 12 are temperature EOFs, the last 12 humidity EOFs, so the
+# degrees of freedom per physical block are the two halves of the averaging-kernel diagonal.  The EOFs are orthonormal, so a
+# temperature row of the level-space averaging kernel is (B_t A_tt B_t^T)[level, :].
+half = R // 2
+ch16 = ov16.characterise_nform(z, p, res16.coeff, y16, gain=False, avk=True)
+ch7 = ov_n.characterise_nform(z, p, res_n.coeff, y7, gain=False, avk=True)
+for name, ch in (("7 elevations ", ch7), ("16 elevations", ch16)):
+    d = ch.avk_diag[:, 0]
+    print(f"{name}: dfs T {float(d[:, :half].sum(dim=1).median()):.2f}, rh {float(d[:, half:].sum(dim=1).median()):.2f}; "
+          f"noise share of the posterior variance of the leading T coefficient "
+          f"{float((ch.noise_var[:, 0, 0] / (ch.noise_var[:, 0, 0] + ch.smooth_var[:, 0, 0])).median()):.2f}")
+b_t = eof_t.b.to("cuda")
+for name, ch in (("7 elevations ", ch7), ("16 elevations", ch16)):
+    rows = (b_t @ ch.avk[:, :half, :half].mean(dim=0) @ b_t.T).cpu().numpy()          # the batch-mean T kernel in level space
+    for target in (0.5, 1.5, 4.0):
+        k = int(np.argmin(np.abs(zm - target)))
+        w = rows[k]
+        above = np.flatnonzero(w >= 0.5 * w.max())
+        print(f"{name}: T averaging kernel of the level at {zm[k]:.2f} km peaks at {zm[int(np.argmax(w))]:.2f} km, "
+              f"half-width {zm[above.max()] - zm[above.min()]:.2f} km, area {w.sum():.2f}")

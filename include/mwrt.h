@@ -905,6 +905,74 @@ int mwrt_oe_nform_cost_device(mwrt_context* ctx, int64_t nprof, int32_t nlev, in
 /* sizeof(mwrt_oe_nform) as compiled into the library (binding self-check). */
 size_t mwrt_oe_nform_size(void);
 
+/* The characterisation of the n-form step (Rodgers 2000, ch. 3): what mwrt_oe_gain_device and
+ * mwrt_oe_product_device give the m-form, from the n x n objects a linearisation already holds and one pass over K.  At
+ * gamma = 0, with H = K^T W K as mwrt_oe_nform_prepare_device wrote it, C = H + Sa^-1 = L L^T and S^ = C^-1:
+ *     A      = S^ H                        [n][n]  averaging kernel (= I - S^ Sa^-1)
+ *     gain^T = W K S^, row i = S^ k_i / se_i [m][n]  contribution functions d x^ / d y_i; 0 in a dropped row
+ *     noise  = diag(S^ H S^) = diag(A S^)  [n]     = diag(gain Se gain^T)
+ *     smooth = diag S^ - noise             [n]     = diag((A - I) Sa (A - I)^T)
+ *     avk_diag = diag A;  dfs_block[b] = sum of avk_diag over block b;  their sum is tr(C^-1 H), the solve's dfs
+ *   mwrt_oe_nform_char_device   S^, A (a row window), avk_diag, dfs_block, noise and smooth from a linearisation
+ *   mwrt_oe_nform_gain_device   the gain from K, the row rule, the variances and S^
+ * These are the diagnostics of the UNDAMPED step: there is no d_gamma, and neither entry reads x, xa, y or fx.  One record,
+ * mwrt_oe_nform_char, serves both (all DEVICE pointers, float64 unless stated; n = nblk * nlev, state index = block *
+ * nlev + level):
+ *   d_k[b]       [nprof][m][nlev], b < nblk   the rows prepare saw                                           (gain)
+ *   d_sa_inv     [n][n]                  Sa^-1, SYMMETRIC, as for mwrt_oe_nform_solve_device                (char)
+ *   d_se         [m], or [nprof][m] with se_per_profile != 0: VARIANCES, as prepare saw them                (gain)
+ *   d_h          [nprof][n (n + 1) / 2]  packed H as prepare wrote it                                       (char)
+ *   d_lin_status [nprof] uint8           as prepare wrote it                                                (char)
+ *   d_keep       [nprof][m] uint8        as prepare wrote it                                                (gain)
+ *   d_active     [nprof] uint8, optional a profile whose flag is 0 is skipped: NONE of its outputs is touched (both)
+ * Outputs of char: d_status [nprof] uint8 required; each of the others optional, but at least one must be given:
+ *   d_post_cov   [nprof][n][n]           S^, full and symmetric
+ *   d_avk        [nprof][rows][n]        rows row_begin .. row_begin + row_count - 1 of A, with the window of
+ *                                        mwrt_oe_product_device: row_count == 0 with row_begin == 0 means all n rows
+ *   d_avk_diag, d_noise_var, d_smooth_var [nprof][nblk][nlev];   d_dfs_block [nprof][nblk]
+ *   status: 1 ok;  0 d_lin_status is 0: every floating-point output of the profile is NaN;  2 d_lin_status is 2 (or
+ *   anything but 0, 1, 3), or a Cholesky pivot fails pivot > 0: every floating-point output is NaN;  3 d_lin_status is 3:
+ *   A, avk_diag, dfs_block and noise_var are exactly 0, S^ is the inverse of Sa^-1 as computed and smooth_var its diagonal
+ *   (both NaN when that factorisation fails; status stays 3, as in the solve).
+ *   Only the rows of A a call needs are formed (the window; all of them for noise_var or smooth_var), and S^ leaves the
+ *   workgroup only when d_post_cov is given: d_avk_diag and d_dfs_block alone cost n^2 per profile behind the inverse.
+ * gain: inputs d_k, d_se, d_keep, d_post_cov and d_status -- those mwrt_oe_nform_char_device wrote, or the d_post_cov and
+ *   d_status mwrt_oe_nform_solve_device wrote at gamma = 0; output d_gain [nprof][m][n], required.  A row whose keep is 0
+ *   is never used and gives exact 0.0 (it may hold NaN: the select comes after the load); a profile whose d_status is 0
+ *   or 2 gets NaN throughout, one whose d_status is 3 gets 0.0 throughout.  A kept row with a variance <= 0 cannot occur
+ *   (its d_lin_status is 2, so its d_status is 2).  The row window is not read.
+ * Determinism: a profile's outputs depend on neither its batch-mates nor nprof, nor on which optional outputs are asked
+ *   for.  An element of A is the same bit for bit in whatever row window it is computed, an element of the gain in whatever
+ *   row tile it falls: every sum is one fixed-order chain of fused multiply-adds (the sums over lanes and blocks a fixed
+ *   tree).  No atomics, no matrix instructions.  No workspace: the calls never allocate and never synchronise; a char launch
+ *   above 64 KiB of dynamic LDS (from n = 89 on) raises the kernel's limit once per device and size, so the entries are
+ *   hipGraph-capturable after one warm-up call.
+ * Refused, checked in this order, nothing written.  MWRT_ERR_INVALID_ARGUMENT: a NULL context or record; struct_size
+ *   smaller than the fixed part (24 bytes); nprof < 0, nlev < 1 or m < 1; nblk outside 1 .. 4; reserved != 0; char:
+ *   row_begin < 0, row_count < 0, a window that runs over n, row_count == 0 with row_begin != 0; a NULL pointer among those
+ *   the call requires (char: d_sa_inv, d_h, d_lin_status, d_status; gain: the first nblk of d_k, d_se, d_keep, d_post_cov,
+ *   d_status, d_gain); char with no output beside d_status; an output pointer equal to an input of the call.
+ *   MWRT_ERR_UNSUPPORTED: n = nblk * nlev > MWRT_OE_NFORM_MAX_N, with the limit in the text; more than 2^31 - 1 workgroups
+ *   in one launch (char: one per profile; gain: nprof * ceil(m / 128) row tiles).  nprof = 0 is MWRT_OK and launches
+ *   nothing.  m is not bounded.  The record starts with its own size: fields at or beyond struct_size (and a field it ends
+ *   inside) are taken as NULL / 0.  Accuracy and timing: DESIGN.md 4.11.1.
+ *   (MWRT_VERSION stays 301: additions.) */
+typedef struct mwrt_oe_nform_char {
+  uint32_t struct_size;        /* sizeof(mwrt_oe_nform_char) of the caller; fields beyond it are not read */
+  int32_t  nblk, se_per_profile, row_begin, row_count, reserved;
+  const double* d_k[4];
+  const double *d_sa_inv, *d_se, *d_h;
+  const uint8_t *d_lin_status, *d_keep, *d_active;
+  uint8_t* d_status;                                   /* out of char, in of gain */
+  double* d_post_cov;                                  /* out of char (optional), in of gain */
+  double *d_avk, *d_avk_diag, *d_noise_var, *d_smooth_var, *d_dfs_block;   /* optional outputs of char */
+  double* d_gain;                                      /* output of gain */
+} mwrt_oe_nform_char;
+int mwrt_oe_nform_char_device(mwrt_context* ctx, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_nform_char* s, void* stream);
+int mwrt_oe_nform_gain_device(mwrt_context* ctx, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_nform_char* s, void* stream);
+/* sizeof(mwrt_oe_nform_char) as compiled into the library (binding self-check). */
+size_t mwrt_oe_nform_char_size(void);
+
 /* The spectroscopic-parameter Jacobian: d TB / d b for entries b of the model's tables -- what the
  * forward-model part K_b S_b K_b^T of an observation-error covariance is built from (Rodgers 2000, section 3.2.2).  The
  * operator is mwrt_tb_jacobian_batch_device's: clear sky, plane-parallel, every line at every frequency; there is no

@@ -87,6 +87,16 @@ class MwrtOeNform(ctypes.Structure):
             "d_cost_obs", "d_cost_prior")]
 
 
+class MwrtOeNformChar(ctypes.Structure):
+    """include/mwrt.h mwrt_oe_nform_char: the record of the n-form's characterisation and gain entries (device pointers)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("nblk", ctypes.c_int32), ("se_per_profile", ctypes.c_int32),
+                ("row_begin", ctypes.c_int32), ("row_count", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("d_k", ctypes.c_void_p * 4)] + [
+        (name, ctypes.c_void_p) for name in (
+            "d_sa_inv", "d_se", "d_h", "d_lin_status", "d_keep", "d_active", "d_status", "d_post_cov", "d_avk", "d_avk_diag",
+            "d_noise_var", "d_smooth_var", "d_dfs_block", "d_gain")]
+
+
 class MwrtOeChar(ctypes.Structure):
     """include/mwrt.h mwrt_oe_char: the record of the gain and product entries (device pointers)."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("nblk", ctypes.c_int32), ("xa_per_profile", ctypes.c_int32),
@@ -238,6 +248,9 @@ SIGNATURES = {
     "mwrt_oe_nform_solve_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeNform), _vp]),
     "mwrt_oe_nform_cost_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeNform), _vp]),
     "mwrt_oe_nform_size": (ctypes.c_size_t, []),
+    "mwrt_oe_nform_char_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeNformChar), _vp]),
+    "mwrt_oe_nform_gain_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeNformChar), _vp]),
+    "mwrt_oe_nform_char_size": (ctypes.c_size_t, []),
     "mwrt_oe_gain_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeChar), _vp]),
     "mwrt_oe_product_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeChar), _vp]),
     "mwrt_oe_char_size": (ctypes.c_size_t, []),
@@ -317,6 +330,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
             raise NativeLibraryMissing("mwrt_oe_lm layout mismatch between libmwrt.so and _native.py")
         if lib.mwrt_oe_nform_size() != ctypes.sizeof(MwrtOeNform):
             raise NativeLibraryMissing("mwrt_oe_nform layout mismatch between libmwrt.so and _native.py")
+        if lib.mwrt_oe_nform_char_size() != ctypes.sizeof(MwrtOeNformChar):
+            raise NativeLibraryMissing("mwrt_oe_nform_char layout mismatch between libmwrt.so and _native.py")
         if lib.mwrt_oe_char_size() != ctypes.sizeof(MwrtOeChar):
             raise NativeLibraryMissing("mwrt_oe_char layout mismatch between libmwrt.so and _native.py")
         if lib.mwrt_obs_apply_size() != ctypes.sizeof(MwrtObsApply):
@@ -818,6 +833,46 @@ class Context:
                        dict(d_x=d_x, d_xa=d_xa, d_sa_inv=d_sa_inv, d_se=d_se, d_y=d_y, d_fx=d_fx, d_keep=d_keep,
                             d_cost=d_cost, d_cost_obs=d_cost_obs, d_cost_prior=d_cost_prior, d_status=d_status,
                             d_active=d_active))
+
+    def _oe_nform_char(self, entry, nprof, nlev, m, d_k, se_per_profile, rows, stream, reserved, struct_size, fields):
+        d_k = list(d_k)
+        rec = MwrtOeNformChar()
+        rec.struct_size = ctypes.sizeof(MwrtOeNformChar) if struct_size is None else int(struct_size)
+        rec.nblk, rec.se_per_profile, rec.reserved = len(d_k), int(bool(se_per_profile)), int(reserved)
+        rec.row_begin, rec.row_count = int(rows[0]), int(rows[1])
+        for b, k in enumerate(d_k[:4]):
+            rec.d_k[b] = int(k) if k is not None else None
+        for name, v in fields.items():
+            setattr(rec, name, int(v) if v is not None else None)
+        self._check(getattr(self._lib, entry)(self._handle, int(nprof), int(nlev), int(m), ctypes.byref(rec), _stream(stream)),
+                    entry)
+
+    @_serialised
+    def oe_nform_char_device(self, nprof, nlev, m, nblk, d_sa_inv, d_h, d_lin_status, d_status, d_post_cov=None, d_avk=None,
+                             d_avk_diag=None, d_dfs_block=None, d_noise_var=None, d_smooth_var=None, d_active=None,
+                             row_begin=0, row_count=0, stream=None, reserved=0, struct_size=None):
+        """The characterisation of the undamped n-form step on a linearisation (include/mwrt.h mwrt_oe_nform_char_device):
+        ``d_h`` and ``d_lin_status`` as ``oe_nform_prepare_device`` wrote them and ``d_sa_inv [n][n]``; ``d_status [nprof]``
+        (uint8) required and at least one of ``d_post_cov [nprof][n][n]``, ``d_avk [nprof][rows][n]`` (rows ``row_begin ..
+        row_begin + row_count - 1``; ``row_count=0`` with ``row_begin=0``: all n), ``d_avk_diag`` / ``d_noise_var`` /
+        ``d_smooth_var [nprof][nblk][nlev]`` and ``d_dfs_block [nprof][nblk]``.  ``nblk`` is the number of state blocks (the
+        call reads no K)."""
+        self._oe_nform_char("mwrt_oe_nform_char_device", nprof, nlev, m, [None] * int(nblk), False, (row_begin, row_count),
+                            stream, reserved, struct_size,
+                            dict(d_sa_inv=d_sa_inv, d_h=d_h, d_lin_status=d_lin_status, d_status=d_status, d_post_cov=d_post_cov,
+                                 d_avk=d_avk, d_avk_diag=d_avk_diag, d_dfs_block=d_dfs_block, d_noise_var=d_noise_var,
+                                 d_smooth_var=d_smooth_var, d_active=d_active))
+
+    @_serialised
+    def oe_nform_gain_device(self, nprof, nlev, m, d_k, d_se, d_keep, d_post_cov, d_status, d_gain, d_active=None,
+                             se_per_profile=False, stream=None, reserved=0, struct_size=None):
+        """The gain matrix of the undamped n-form step (include/mwrt.h mwrt_oe_nform_gain_device) into ``d_gain
+        [nprof][m][n]``: row i is S^ k_i / se_i from the K blocks ``d_k``, the variances ``d_se`` (``[m]`` or, with
+        ``se_per_profile``, ``[nprof][m]``) and ``d_keep`` as prepare saw and wrote them, and ``d_post_cov``, ``d_status`` as
+        ``oe_nform_char_device`` (or ``oe_nform_solve_device`` without ``d_gamma``) wrote them."""
+        self._oe_nform_char("mwrt_oe_nform_gain_device", nprof, nlev, m, d_k, se_per_profile, (0, 0), stream, reserved,
+                            struct_size, dict(d_se=d_se, d_keep=d_keep, d_post_cov=d_post_cov, d_status=d_status,
+                                              d_gain=d_gain, d_active=d_active))
 
     def _oe_char(self, entry, nprof, nlev, m, d_k, xa_per_profile, se_full, stream, reserved, struct_size, fields):
         d_k = list(d_k)

@@ -37,10 +37,13 @@ constexpr Record OBS_WHITEN{"mwrt_obs_whiten", sizeof(mwrt_obs_whiten), offsetof
 // struct_size and four int32, then pointers to the end, as mwrt_oe_lm
 constexpr Record OE_NFORM{"mwrt_oe_nform", sizeof(mwrt_oe_nform), offsetof(mwrt_oe_nform, d_k), FIXED_PART,
                           {{0, I32, 5}, {offsetof(mwrt_oe_nform, d_k), PTR, 27}}};
+// struct_size and five int32, then pointers to the end
+constexpr Record OE_NFORM_CHAR{"mwrt_oe_nform_char", sizeof(mwrt_oe_nform_char), offsetof(mwrt_oe_nform_char, d_k), FIXED_PART,
+                               {{0, I32, 6}, {offsetof(mwrt_oe_nform_char, d_k), PTR, 18}}};
 static_assert(end_of(OE_STEP) == sizeof(mwrt_oe_step) && end_of(OE_LM) == sizeof(mwrt_oe_lm) &&
               end_of(OE_CHAR) == sizeof(mwrt_oe_char) && end_of(OBS_APPLY) == sizeof(mwrt_obs_apply) &&
               end_of(BASIS_APPLY) == sizeof(mwrt_basis_apply) && end_of(OBS_WHITEN) == sizeof(mwrt_obs_whiten) &&
-              end_of(OE_NFORM) == sizeof(mwrt_oe_nform),
+              end_of(OE_NFORM) == sizeof(mwrt_oe_nform) && end_of(OE_NFORM_CHAR) == sizeof(mwrt_oe_nform_char),
               "the runs of a record end where the record ends");
 static_assert(sizeof(int64_t) == PTR, "mwrt_obs_whiten: one run from reserved on");
 
@@ -247,6 +250,47 @@ Refusal oe_nform_args(NfCall call, int64_t nprof, int32_t nlev, int32_t m, const
   if ((int64_t)r->nblk * nlev > MWRT_OE_NFORM_MAX_N)
     return unsupported("n = nblk * nlev > MWRT_OE_NFORM_MAX_N (" + std::to_string(MWRT_OE_NFORM_MAX_N) +
                        " state elements per profile: the packed triangle of C lives in LDS)");
+  if (nprof > GRID_MAX) return unsupported("nprof exceeds grid limit");
+  return {};
+}
+
+// The characterisation of the n-form: the order of oe_nform_args with the row window of oe_char_args before the pointers.
+Refusal oe_nform_char_args(NfCharCall call, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_nform_char* s,
+                           mwrt_oe_nform_char* r) {
+  const bool chr = call == NfCharCall::Char;
+  if (!cut(OE_NFORM_CHAR, s, r)) return too_small(OE_NFORM_CHAR);
+  if (nprof < 0 || nlev < 1 || m < 1) return invalid("nprof < 0, nlev < 1 or m < 1");
+  if (r->nblk < 1 || r->nblk > 4) return invalid("mwrt_oe_nform_char.nblk must be 1 .. 4");
+  if (r->reserved != 0) return invalid("mwrt_oe_nform_char.reserved must be 0");
+  const int64_t n64 = (int64_t)r->nblk * nlev;        // not yet held to its limit here
+  if (chr && (r->row_begin < 0 || r->row_count < 0 || (r->row_count == 0 && r->row_begin != 0) ||
+              (int64_t)r->row_begin + r->row_count > n64))
+    return invalid("mwrt_oe_nform_char: rows row_begin .. row_begin + row_count - 1 must lie in 0 .. n - 1 "
+                   "(row_count 0 with row_begin 0: all rows)");
+  const bool buffers = chr ? r->d_sa_inv && r->d_h && r->d_lin_status && r->d_status
+                           : r->d_se && r->d_keep && r->d_post_cov && r->d_status && r->d_gain && first_blocks(*r);
+  if (!buffers) return invalid("null buffer");
+  const void* outs[7] = {};
+  const void* ins[9] = {};
+  if (chr) {
+    if (!(r->d_post_cov || r->d_avk || r->d_avk_diag || r->d_noise_var || r->d_smooth_var || r->d_dfs_block))
+      return invalid("mwrt_oe_nform_char_device: no output asked for beside d_status");
+    const void* o[7] = {r->d_status, r->d_post_cov, r->d_avk, r->d_avk_diag, r->d_noise_var, r->d_smooth_var, r->d_dfs_block};
+    const void* i[4] = {r->d_sa_inv, r->d_h, r->d_lin_status, r->d_active};
+    for (int k = 0; k < 7; ++k) outs[k] = o[k];
+    for (int k = 0; k < 4; ++k) ins[k] = i[k];
+  } else {
+    outs[0] = r->d_gain;
+    const void* i[5] = {r->d_se, r->d_keep, r->d_post_cov, r->d_status, r->d_active};
+    for (int k = 0; k < 5; ++k) ins[k] = i[k];
+    for (int b = 0; b < r->nblk; ++b) ins[5 + b] = r->d_k[b];
+  }
+  for (const void* o : outs)
+    for (const void* i : ins)
+      if (o && o == i) return invalid("mwrt_oe_nform_char: an output pointer equals an input (nothing is formed in place)");
+  if (n64 > MWRT_OE_NFORM_MAX_N)
+    return unsupported("n = nblk * nlev > MWRT_OE_NFORM_MAX_N (" + std::to_string(MWRT_OE_NFORM_MAX_N) +
+                       " state elements per profile: the packed triangles of C and H live in LDS)");
   if (nprof > GRID_MAX) return unsupported("nprof exceeds grid limit");
   return {};
 }

@@ -30,7 +30,7 @@ struct Record {
   const char* min_what;        // ... "the fixed part (through reserved)"
   Run runs[4];                 // unused ones {0, 0, 0}
 };
-extern const Record OE_STEP, OE_LM, OE_CHAR, OBS_APPLY, BASIS_APPLY, OBS_WHITEN, OE_NFORM;
+extern const Record OE_STEP, OE_LM, OE_CHAR, OBS_APPLY, BASIS_APPLY, OBS_WHITEN, OE_NFORM, OE_NFORM_CHAR;
 
 // The one cut: *out (rec.size bytes) is the caller's record with every field that is not wholly below
 // min(struct_size, rec.size) left zero.  False, *out all zero: struct_size is below rec.min_size.
@@ -46,6 +46,7 @@ enum class LmCall { Prepare, Solve, Cost };      // the three entries of mwrt_oe
 enum class CharCall { Gain, Product };           // the two of mwrt_oe_char
 enum class WhitenCall { Whiten, Apply };         // the two of mwrt_obs_whiten
 enum class NfCall { Prepare, Solve, Cost };      // the three of mwrt_oe_nform
+enum class NfCharCall { Char, Gain };            // the two of mwrt_oe_nform_char
 
 Refusal oe_step_args(int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_step* s, mwrt_oe_step* r);
 Refusal oe_lm_args(LmCall call, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_lm* s, mwrt_oe_lm* r);
@@ -57,6 +58,9 @@ Refusal basis_expand_args(int64_t nprof, const mwrt_basis_apply* s, mwrt_basis_a
 Refusal whiten_args(WhitenCall call, int64_t nprof, int32_t nlev, int32_t m, const mwrt_obs_whiten* s, mwrt_obs_whiten* r);
 // its limit is on n = nblk * nlev (MWRT_OE_NFORM_MAX_N); m is not bounded
 Refusal oe_nform_args(NfCall call, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_nform* s, mwrt_oe_nform* r);
+// the same limit; the row window is held to n for Char alone (Gain does not read it)
+Refusal oe_nform_char_args(NfCharCall call, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_nform_char* s,
+                           mwrt_oe_nform_char* r);
 
 }  // namespace records
 }  // namespace mwrt

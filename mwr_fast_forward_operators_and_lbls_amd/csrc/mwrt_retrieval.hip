@@ -7,7 +7,8 @@
 // limits of the launch geometry and the LDS plan, then launch_tail: an empty batch, the device, the stream, the launches.
 //
 // Host code only: every kernel lives in its own unit (mwrt_oe.hip, mwrt_oe_lm.hip, mwrt_oe_char.hip, mwrt_obs.hip,
-// mwrt_basis.hip, mwrt_whiten.hip, mwrt_nform.hip) and is reached through the launchers the headers below declare.
+// mwrt_basis.hip, mwrt_whiten.hip, mwrt_nform.hip, mwrt_nform_char.hip) and is reached through the launchers the headers
+// below declare.
 #include "mwrt_host.hip.h"
 #include "mwrt_records.h"
 #include "mwrt_oe.hip.h"
@@ -17,6 +18,7 @@
 #include "mwrt_basis.hip.h"
 #include "mwrt_whiten.hip.h"
 #include "mwrt_nform.hip.h"
+#include "mwrt_nform_char.hip.h"
 
 #include <cmath>
 #include <new>
@@ -25,6 +27,7 @@ using namespace mwrt;
 using records::CharCall;
 using records::LmCall;
 using records::NfCall;
+using records::NfCharCall;
 using records::WhitenCall;
 
 struct mwrt_obs : DeviceHandle {    // the blob: w [nnz] | row_ptr [m_out + 1] | col [nnz]
@@ -161,6 +164,30 @@ int oe_nform_call(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const
   }));
 }
 
+// The two entries of the n-form's characterisation (csrc/mwrt_nform_char.hip) share one record.
+int oe_nform_char_call(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_nform_char* s, void* stream,
+                       NfCharCall call) {
+  if (!c || !s) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context or mwrt_oe_nform_char");
+  mwrt_oe_nform_char r;
+  if (const auto no = records::oe_nform_char_args(call, nprof, nlev, m, s, &r)) return refused(no);
+  nfc::CharArgs a{};
+  a.k0 = r.d_k[0]; a.k1 = r.nblk > 1 ? r.d_k[1] : nullptr; a.k2 = r.nblk > 2 ? r.d_k[2] : nullptr;
+  a.k3 = r.nblk > 3 ? r.d_k[3] : nullptr;
+  a.sa_inv = r.d_sa_inv; a.se = r.d_se; a.h = r.d_h; a.lin_status = r.d_lin_status; a.keep = r.d_keep; a.active = r.d_active;
+  a.status = r.d_status; a.post_cov = r.d_post_cov; a.avk = r.d_avk; a.avk_diag = r.d_avk_diag; a.noise_var = r.d_noise_var;
+  a.smooth_var = r.d_smooth_var; a.dfs_block = r.d_dfs_block; a.gain = r.d_gain;
+  a.nblk = r.nblk; a.nlev = nlev; a.m = m; a.n = r.nblk * nlev;
+  a.se_per_profile = r.se_per_profile != 0; a.row_begin = r.row_begin; a.rows = r.row_count == 0 ? a.n : r.row_count;
+  if (call == NfCharCall::Char) {
+    if (const int rc = lds_fits(c, nfc::char_plan(a.n).total_bytes, STEP_LDS)) return rc;
+    return launch_tail(c, nprof, stream, launch([&](hipStream_t st) { return nfc::launch_nfc_char(a, nprof, st); }));
+  }
+  // one workgroup per (profile, nfc::ROWS rows, nfc::COLS columns); the column tiles are the grid's second dimension
+  if (nprof > GRID_MAX / nfc::gain_row_tiles(m))
+    return fail(MWRT_ERR_UNSUPPORTED, "mwrt_oe_nform_gain_device: more than 2147483647 workgroups in one launch (split the batch)");
+  return launch_tail(c, nprof, stream, launch([&](hipStream_t st) { return nfc::launch_nfc_gain(a, nprof, st); }));
+}
+
 // The two entries of the characterisation (csrc/mwrt_oe_char.hip) share one record.
 int oe_char_call(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_char* s, void* stream, CharCall call) {
   if (!c || !s) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context or mwrt_oe_char");
@@ -279,7 +306,17 @@ int mwrt_oe_nform_cost_device(mwrt_context* c, int64_t nprof, int32_t nlev, int3
   return oe_nform_call(c, nprof, nlev, m, s, stream, NfCall::Cost);
 }
 
-/* Its characterisation (csrc/mwrt_oe_char.hip). */
+/* The characterisation of the n-form step (csrc/mwrt_nform_char.hip). */
+size_t mwrt_oe_nform_char_size(void) { return sizeof(mwrt_oe_nform_char); }
+
+int mwrt_oe_nform_char_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_nform_char* s, void* stream) {
+  return oe_nform_char_call(c, nprof, nlev, m, s, stream, NfCharCall::Char);
+}
+int mwrt_oe_nform_gain_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_nform_char* s, void* stream) {
+  return oe_nform_char_call(c, nprof, nlev, m, s, stream, NfCharCall::Gain);
+}
+
+/* The m-form step's characterisation (csrc/mwrt_oe_char.hip). */
 size_t mwrt_oe_char_size(void) { return sizeof(mwrt_oe_char); }
 
 int mwrt_oe_gain_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_char* s, void* stream) {

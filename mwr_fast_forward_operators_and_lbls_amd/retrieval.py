@@ -28,7 +28,8 @@ and ``retrieve_lm`` in the n-form instead (``mwrt_oe_nform_prepa
 ``mwrt_oe_nform_cost_device``): an n x n system for a state of at most 128 elements -- the r coefficients of a basis, or a
 coarse full state -- and any number of observations.  The constructor's ``se`` is then ``[m]`` variances; ``se=`` of a call as
 ``[nprof][m]`` goes straight in, as ``[nprof][m][m]`` through the pre-whitening below.  ``step(..., post_cov=True)`` returns the
-posterior covariance it has formed anyway; ``characterise`` stays with ``form="m"``.
+posterior covariance it has formed anyway; ``characterise`` stays with ``form="m"`` and ``characterise_nform`` returns the
+same ``Characterisation`` for ``form="n"`` (``mwrt_oe_nform_char_device`` / ``mwrt_oe_nform_gain_device``).
 
     ov = OneDVar("R24", frq, elev16, None, se, variables=..., blocks=("t", "h"), xa=xa, basis=eof, form="n")   # m = 224
     res = ov.retrieve(z, p, y)
@@ -179,6 +180,33 @@ def _native_oe_nform_cost(x, xa, sa_inv, se, y, fx, keep, cost, active, stream):
         nprof, nlev, y.shape[1], nblk, x.data_ptr(), xa.data_ptr(), sa_inv.data_ptr(), se.data_ptr(), y.data_ptr(),
         fx.data_ptr(), keep.data_ptr(), cost.data_ptr(), d_active=None if active is None else active.data_ptr(),
         xa_per_profile=xa.dim() == 3, se_per_profile=se.dim() == 2, stream=stream)
+
+
+def _native_oe_nform_char(sa_inv, lin, nblk, out, rows, stream):
+    """One ``mwrt_oe_nform_char_device`` call on the linearisation ``lin`` into ``out`` in place: status, and whichever of
+    post_cov ``[nprof][n][n]``, avk ``[nprof][rows][n]`` (``rows = (begin, count)``, (0, 0): all), avk_diag, noise_var,
+    smooth_var ``[nprof][nblk][nlev]`` and dfs_block ``[nprof][nblk]`` it holds a tensor for.  CPU tests substitute the
+    NumPy reference here."""
+    nprof, n = lin["g"].shape
+    ptr = lambda v: None if v is None else v.data_ptr()   # noqa: E731
+    _native.default_context(sa_inv.device.index or 0).oe_nform_char_device(
+        nprof, n // nblk, lin["keep"].shape[1], nblk, sa_inv.data_ptr(), lin["h"].data_ptr(), lin["lin_status"].data_ptr(),
+        out["status"].data_ptr(), d_post_cov=ptr(out.get("post_cov")), d_avk=ptr(out.get("avk")),
+        d_avk_diag=ptr(out.get("avk_diag")), d_dfs_block=ptr(out.get("dfs_block")), d_noise_var=ptr(out.get("noise_var")),
+        d_smooth_var=ptr(out.get("smooth_var")), row_begin=rows[0], row_count=rows[1], stream=stream)
+
+
+def _native_oe_nform_gain(k_blocks, se, keep, post_cov, status, stream):
+    """One ``mwrt_oe_nform_gain_device`` call -> gain ``[nprof][m][n]`` from the K blocks ``[nprof]...[nlev]``, the
+    variances ``se`` (``[m]`` or ``[nprof][m]``), prepare's ``keep`` and the ``post_cov`` and ``status`` the characterisation
+    wrote.  CPU tests substitute the NumPy reference here."""
+    nprof, m = keep.shape
+    n = post_cov.shape[-1]
+    gain = torch.empty((nprof, m, n), dtype=torch.float64, device=keep.device)
+    _native.default_context(keep.device.index or 0).oe_nform_gain_device(
+        nprof, n // len(k_blocks), m, [k.data_ptr() for k in k_blocks], se.data_ptr(), keep.data_ptr(), post_cov.data_ptr(),
+        status.data_ptr(), gain.data_ptr(), se_per_profile=se.dim() == 2, stream=stream)
+    return gain
 
 
 def _native_oe_gain(k_blocks, x, xa, sa, se, y, fx, stream):
@@ -401,7 +429,8 @@ class Characterisation:
     """What ``OneDVar.characterise`` returns: the undamped step at a state, described (Rodgers 2000, ch. 3; include/mwrt.h
     mwrt_oe_gain_device).  Every field is a tensor on the state's device; n = nblk * nlev, state index = block * nlev + level.
     With a basis the step is the one in the coefficients: n = r and nblk = 1 in every field, ``coeff`` is the state."""
-    gain: torch.Tensor         # [nprof][m][n] row i: the contribution function d x^ / d y_i; 0 in a dropped row
+    gain: Optional[torch.Tensor]   # [nprof][m][n] row i: the contribution function d x^ / d y_i; 0 in a dropped row (None:
+    #                                ``characterise_nform(gain=False)``)
     avk_diag: torch.Tensor     # [nprof][nblk][nlev] diagonal of the averaging kernel
     dfs_block: torch.Tensor    # [nprof][nblk] degrees of freedom for signal per state block; their sum is the step's dfs
     noise_var: torch.Tensor    # [nprof][nblk][nlev] measurement-noise part of the posterior variance
@@ -898,8 +927,9 @@ class OneDVar:
 
         Not offered with ``form="n"``: the gain matrix is an m-form product."""
         if self.form == "n":
-            raise ValueError("characterise is not offered with form='n': use form='m' for the gain matrix, the averaging "
-                             "kernel and the error budget, or step(..., post_cov=True) for the posterior covariance")
+            raise ValueError("characterise is not offered with form='n': use characterise_nform there (or form='m') for the "
+                             "gain matrix, the averaging kernel and the error budget, or step(..., post_cov=True) for the "
+                             "posterior covariance")
         if self.basis is not None:
             x = x.reshape(x.shape[0], 1, self.basis.r)
         nprof, n = x.shape[0], x.shape[1] * x.shape[2]
@@ -926,6 +956,56 @@ class OneDVar:
         return Characterisation(gain=g["gain"], avk_diag=g["avk_diag"], dfs_block=g["dfs_block"], noise_var=g["noise_var"],
                                 smooth_var=g["smooth_var"], status=g["status"], nobs=g["nobs"], keep=g["keep"], **prod,
                                 **({} if self.basis is None else {"coeff": x.reshape(nprof, n)}))
+
+    def characterise_nform(self, z, p, x, y, gain=True, avk=False, post_cov=False, rows=None, se=None) -> Characterisation:
+        """``characterise`` for ``form="n"``: the same fields for the undamped n-form step at ``x``, for any
+        number of observations.  One K-matrix call at ``x``, ``mwrt_oe_nform_prepare_device``, then
+        ``mwrt_oe_nform_char_device`` -- the averaging-kernel diagonal, the degrees of freedom per block, the noise and
+        smoothing variances and, with ``avk`` / ``post_cov``, the averaging kernel and the posterior covariance -- and, with
+        ``gain``, ``mwrt_oe_nform_gain_device``; all on torch's current stream with nothing leaving the device.
+        ``gain=False`` skips the one pass over K (the field is None).  ``rows=(begin, count)`` limits ``avk`` and
+        ``post_cov`` to those rows of the n x n result; ``post_cov`` is sliced from the full S^ when the gain needs it too.
+        Profiles whose status is 0 or 2 hold NaN in every floating-point field.
+
+        With a basis ``x`` holds the coefficients ``[nprof][r]`` and everything returned is in coefficient space: n = r, one
+        block, ``coeff`` is set.  ``se=`` as in ``step``: variances ``[nprof][m]`` go straight in; a full ``[nprof][m][m]``
+        goes through the pre-whitening (m <= 140) and the gain is un-whitened afterwards, as in ``characterise``."""
+        if self.form != "n":
+            raise ValueError("characterise_nform needs form='n'; with form='m' characterise gives the same fields")
+        if self.basis is not None:
+            x = x.reshape(x.shape[0], 1, self.basis.r)
+        nprof, nblk, n = x.shape[0], x.shape[1], x.shape[1] * x.shape[2]
+        if rows is None:
+            win = (0, 0)
+        else:
+            win = (int(rows[0]), int(rows[1]))
+            if win[0] < 0 or win[1] < 1 or win[0] + win[1] > n:
+                raise ValueError(f"rows: expected (begin, count) with count >= 1 inside 0 .. {n - 1}, got {rows}")
+        stream = self._stream(x)
+        u = x.contiguous()
+        k_blocks, fx = self._linearise(z, p, u)
+        k_blocks, y_w, fx, se_w, w = self._nform_se(self._per_profile_se(se, nprof), k_blocks,
+                                                    y.reshape(nprof, self.m).contiguous(), fx, stream)
+        lin = self._nform_lin(nprof, n, self.m, u.device)
+        _native_oe_nform_prepare(k_blocks, u, self._prior_mean, se_w, y_w, fx, lin, None, stream)
+        f64 = dict(dtype=torch.float64, device=u.device)
+        out = dict(status=torch.empty(nprof, dtype=torch.uint8, device=u.device), avk_diag=torch.empty_like(u),
+                   dfs_block=torch.empty((nprof, nblk), **f64), noise_var=torch.empty_like(u), smooth_var=torch.empty_like(u))
+        if avk:
+            out["avk"] = torch.empty((nprof, win[1] or n, n), **f64)
+        if gain or post_cov:
+            out["post_cov"] = torch.empty((nprof, n, n), **f64)
+        _native_oe_nform_char(self.sa_inv, lin, nblk, out, win, stream)
+        out["gain"] = _native_oe_nform_gain(k_blocks, se_w, lin["keep"], out["post_cov"], out["status"], stream) if gain else None
+        if post_cov:
+            out["post_cov"] = out["post_cov"][:, win[0]:win[0] + (win[1] or n)].contiguous()
+        else:
+            out.pop("post_cov", None)
+        out["nobs"], out["keep"] = lin["nobs"], lin["keep"]
+        out = self._fail_whitened(w, out)
+        if w is not None and gain:                          # after everything else: the gain back to d x^ / d y
+            out["gain"] = _native_obs_whiten_apply(w["l"], w["keep"], 1, None, out["gain"], stream)[1]
+        return Characterisation(**out, **({} if self.basis is None else {"coeff": x.reshape(nprof, n)}))
 
     # -- the damped iteration ------------------------------------------------------------------------------------------
     def _linearise(self, z, p, x):

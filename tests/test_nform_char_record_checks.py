@@ -1,0 +1,174 @@
+"""The argument stage of the n-form's characterisation entries (csrc/mwrt_records.cpp oe_nform_char_args) without a GPU:
+tests/nform_char_record_dump.cpp links it as is, built with the host C++ compiler under ASan + UBSan and run as a child
+process -- the pattern, and the helpers, of tests/test_record_checks.py and tests/test_nform_record_checks.py.  The record is
+built from the ctypes mirror of _native.py, so the mirror and the C struct are held against each other too.  Pointer fields
+hold small distinct integers; nothing dereferences them."""
+import ctypes
+import json
+import os
+import shutil
+import subprocess
+
+import pytest
+
+from mwr_fast_forward_operators_and_lbls_amd import _native
+from test_record_checks import CSRC, INVALID, OK, ROOT, UNSUPPORTED, leaves, line, put, record, run
+
+CLS = _native.MwrtOeNformChar
+MINIMUM = 24                                         # the fixed part (through reserved)
+MAX_N = 128                                          # MWRT_OE_NFORM_MAX_N
+SIGNS = "nprof < 0, nlev < 1 or m < 1"
+TOO_SMALL = "mwrt_oe_nform_char.struct_size too small for the fixed part (through reserved)"
+NBLK = "mwrt_oe_nform_char.nblk must be 1 .. 4"
+RESERVED = "mwrt_oe_nform_char.reserved must be 0"
+WINDOW = ("mwrt_oe_nform_char: rows row_begin .. row_begin + row_count - 1 must lie in 0 .. n - 1 "
+          "(row_count 0 with row_begin 0: all rows)")
+NO_OUTPUT = "mwrt_oe_nform_char_device: no output asked for beside d_status"
+ALIASED = "mwrt_oe_nform_char: an output pointer equals an input (nothing is formed in place)"
+N_LIMIT = "n = nblk * nlev > MWRT_OE_NFORM_MAX_N (128 state elements per profile: the packed triangles of C and H live in LDS)"
+OUTPUTS = ("d_post_cov", "d_avk", "d_avk_diag", "d_noise_var", "d_smooth_var", "d_dfs_block")
+#: entry -> (the pointers it requires, pointers it leaves optional)
+ENTRIES = {
+    "nform_char": ("d_sa_inv d_h d_lin_status d_status", "d_k_0 d_se d_keep d_active d_gain " + " ".join(OUTPUTS)),
+    "nform_gain": ("d_se d_keep d_post_cov d_status d_gain d_k_0", "d_sa_inv d_h d_lin_status d_active d_avk d_dfs_block"),
+}
+
+
+@pytest.fixture(scope="module")
+def char_dump(tmp_path_factory):
+    """ask(request lines) -> one parsed JSON answer per line.  A sanitiser report ends the child with a non-zero status."""
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path_factory.mktemp("nform_char_record_dump") / "nform_char_record_dump")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(ROOT, "tests", "nform_char_record_dump.cpp"), os.path.join(CSRC, "mwrt_records.cpp"), "-o", exe],
+                   check=True)
+
+    def ask(lines):
+        r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True)
+        assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-4000:])
+        out = [json.loads(x) for x in r.stdout.splitlines()]
+        assert len(out) == len(lines)
+        return out
+    return ask
+
+
+def rec(**kw):
+    return record(CLS, **kw)
+
+
+def test_the_mirror_is_the_record():
+    assert ctypes.sizeof(CLS) == 168 and CLS.d_k.offset == MINIMUM and CLS.d_sa_inv.offset == 56 and CLS.d_gain.offset == 160
+    assert [name for name, _ in CLS._fields_[:6]] == ["struct_size", "nblk", "se_per_profile", "row_begin", "row_count", "reserved"]
+    assert ctypes.sizeof(_native.MwrtOeNform) == 240                                   # the sibling record has not grown
+
+
+def test_the_cut_at_every_struct_size(char_dump):
+    """Every struct_size from 0 to sizeof + 8 with every field non-zero: below the documented minimum it is refused; from
+    there on a field comes through if and only if it lies wholly below min(struct_size, sizeof), every other byte is zero.
+    The child owns exactly struct_size bytes."""
+    size = ctypes.sizeof(CLS)
+    full = CLS()
+    for k, (field, index, _, width) in enumerate(leaves(CLS)):
+        put(full, field, index, (k + 1) * 0x0101 + (0x01010000 << 8 if width == 8 else 0))
+    full = bytes(full) + b"\xab" * 8
+    assert all(full[off:off + width].count(0) < width for _, _, off, width in leaves(CLS))
+    asked, want = [], []
+    for struct_size in range(size + 9):
+        caller = struct_size.to_bytes(4, "little") + full[4:max(struct_size, 4)]
+        asked.append(f"cut {caller.hex()}")
+        expect = bytearray(size)
+        for _, _, off, width in leaves(CLS):
+            if struct_size >= MINIMUM and off + width <= min(struct_size, size):
+                expect[off:off + width] = caller[off:off + width]
+        want.append((struct_size, OK if struct_size >= MINIMUM else INVALID, bytes(expect).hex()))
+    assert len(asked) == 177
+    for (struct_size, status, expect), got in zip(want, char_dump(asked)):
+        assert (got["status"], got["record"]) == (status, expect), struct_size
+
+
+@pytest.mark.parametrize("entry", sorted(ENTRIES))
+def test_refusals_their_messages_and_their_order(char_dump, entry):
+    required, optional = (s.split() for s in ENTRIES[entry])
+    char = entry == "nform_char"
+    cases = [
+        (line(entry, 3, 2, 3, rec()), OK, None, rec()),
+        (line(entry, 0, 1, 1, rec(nblk=4)), OK, None),
+        (line(entry, 1, 2, 3, rec(se_per_profile=1)), OK, None),
+        # the limit is on n = nblk nlev, not on m
+        (line(entry, 1, MAX_N, 3, rec()), OK, None),
+        (line(entry, 1, 32, 3, rec(nblk=4)), OK, None),
+        (line(entry, 1, 2, 141, rec()), OK, None),
+        (line(entry, 1, 2, 2 ** 31 - 1, rec()), OK, None),
+        (line(entry, 2 ** 31 - 1, 2, 3, rec()), OK, None),
+        (line(entry, 1, MAX_N + 1, 3, rec()), UNSUPPORTED, N_LIMIT),
+        (line(entry, 1, 65, 3, rec(nblk=2)), UNSUPPORTED, N_LIMIT),
+        (line(entry, 1, 2 ** 31 - 1, 3, rec(nblk=4)), UNSUPPORTED, N_LIMIT),
+        (line(entry, 2 ** 31, 2, 3, rec()), UNSUPPORTED, "nprof exceeds grid limit"),
+        (line(entry, 1, 2, 3, rec(struct_size=MINIMUM - 1)), INVALID, TOO_SMALL),
+        (line(entry, 1, 2, 3, rec(struct_size=0)), INVALID, TOO_SMALL),
+        (line(entry, -1, 2, 3, rec()), INVALID, SIGNS),
+        (line(entry, 1, 0, 3, rec()), INVALID, SIGNS),
+        (line(entry, 1, 2, 0, rec()), INVALID, SIGNS),
+        (line(entry, 1, 2, 3, rec(nblk=0)), INVALID, NBLK),
+        (line(entry, 1, 2, 3, rec(nblk=5)), INVALID, NBLK),
+        (line(entry, 1, 2, 3, rec(reserved=1)), INVALID, RESERVED),
+        # two checks would fire: the earlier one is reported
+        (line(entry, -1, 2, 3, rec(struct_size=MINIMUM - 1)), INVALID, TOO_SMALL),
+        (line(entry, -1, 2, 3, rec(nblk=0)), INVALID, SIGNS),
+        (line(entry, 1, 2, 3, rec(nblk=5, reserved=1)), INVALID, NBLK),
+        (line(entry, 1, 2, 3, rec(reserved=1, **{required[0]: None})), INVALID, RESERVED),
+        (line(entry, 1, MAX_N + 1, 3, rec(**{required[0]: None})), INVALID, "null buffer"),
+        (line(entry, 2 ** 31, MAX_N + 1, 3, rec()), UNSUPPORTED, N_LIMIT),
+        # the shortest record: no pointer is read
+        (line(entry, 1, 2, 3, rec(struct_size=MINIMUM)), INVALID, "null buffer"),
+        # a record that ends inside the last required pointer: it reads as NULL
+        (line(entry, 1, 2, 3, rec(struct_size=getattr(CLS, "d_status" if char else "d_gain").offset + 7)), INVALID, "null buffer"),
+    ]
+    cases += [(line(entry, 1, 2, 3, rec(**{p: None})), INVALID, "null buffer") for p in required]
+    cases += [(line(entry, 1, 2, 3, rec(**{p: None})), OK, None) for p in optional]
+    window = [dict(row_begin=-1, row_count=1), dict(row_begin=0, row_count=-1), dict(row_begin=1, row_count=0),
+              dict(row_begin=0, row_count=3), dict(row_begin=1, row_count=2), dict(row_begin=2 ** 31 - 1, row_count=2 ** 31 - 1)]
+    if char:
+        cases += [(line(entry, 1, 2, 3, rec(**w)), INVALID, WINDOW) for w in window]
+        cases += [
+            (line(entry, 1, 2, 3, rec(row_begin=0, row_count=2)), OK, None),
+            (line(entry, 1, 2, 3, rec(row_begin=1, row_count=1)), OK, None),
+            (line(entry, 1, 3, 3, rec(nblk=2, row_begin=5, row_count=1)), OK, None),
+            (line(entry, 1, 2, 3, rec(reserved=1, row_begin=-1)), INVALID, RESERVED),              # the window comes behind it
+            (line(entry, 1, 2, 3, rec(row_begin=-1, d_h=None)), INVALID, WINDOW),                  # ... and before the pointers
+            (line(entry, 1, MAX_N + 1, 3, rec(row_begin=MAX_N, row_count=1)), UNSUPPORTED, N_LIMIT),   # a window inside n > 128
+            (line(entry, 1, 2, 3, rec(nblk=2, d_k_0=None, d_k_1=None)), OK, None),                # char reads no K block
+            (line(entry, 1, 2, 3, rec(**{p: None for p in OUTPUTS})), INVALID, NO_OUTPUT),
+            (line(entry, 1, 2, 3, rec(d_h=None, **{p: None for p in OUTPUTS})), INVALID, "null buffer"),
+            (line(entry, 1, MAX_N + 1, 3, rec(**{p: None for p in OUTPUTS})), INVALID, NO_OUTPUT),
+            # a record that ends before the first optional output: none is read
+            (line(entry, 1, 2, 3, rec(struct_size=CLS.d_post_cov.offset)), INVALID, NO_OUTPUT),
+            (line(entry, 1, 2, 3, rec(struct_size=CLS.d_post_cov.offset + 8)), OK, None),
+        ]
+        cases += [(line(entry, 1, 2, 3, rec(**{p: None for p in OUTPUTS if p != q})), OK, None) for q in OUTPUTS]
+        ins = ("d_sa_inv", "d_h", "d_lin_status", "d_active")
+        cases += [(line(entry, 1, 2, 3, rec(**{o: getattr(rec(), i)})), INVALID, ALIASED)
+                  for o in ("d_status",) + OUTPUTS for i in ins]
+        cases += [
+            (line(entry, 1, MAX_N + 1, 3, rec(d_avk=rec().d_h)), INVALID, ALIASED),                # the limits come last
+            (line(entry, 1, 2, 3, rec(d_avk=rec().d_se)), OK, None),                               # not an input of this entry
+            (line(entry, 1, 2, 3, rec(d_avk=rec().d_post_cov)), OK, None),                         # outputs are not compared
+        ]
+    else:
+        cases += [(line(entry, 1, 2, 3, rec(**w)), OK, None) for w in window]                     # gain does not read the window
+        cases += [
+            (line(entry, 1, 2, 3, rec(nblk=2, d_k_1=None)), INVALID, "null buffer"),
+            (line(entry, 1, 2, 3, rec(nblk=2, d_k_2=None, d_k_3=None)), OK, None),                # beyond nblk: not looked at
+            (line(entry, 1, 2, 3, rec(**{p: None for p in OUTPUTS if p != "d_post_cov"})), OK, None),
+        ]
+        ins = ("d_se", "d_keep", "d_post_cov", "d_status", "d_active", "d_k_0")
+        r0 = rec()
+        cases += [(line(entry, 1, 2, 3, rec(d_gain=r0.d_k[0] if i == "d_k_0" else getattr(r0, i))), INVALID, ALIASED) for i in ins]
+        cases += [
+            (line(entry, 1, 2, 3, rec(nblk=2, d_gain=r0.d_k[1])), INVALID, ALIASED),
+            (line(entry, 1, 2, 3, rec(d_gain=r0.d_k[1])), OK, None),                               # beyond nblk
+            (line(entry, 1, 2, 3, rec(d_gain=r0.d_h)), OK, None),                                  # not an input of this entry
+            (line(entry, 1, MAX_N + 1, 3, rec(d_gain=r0.d_se)), INVALID, ALIASED),
+        ]
+    run(char_dump, cases)
