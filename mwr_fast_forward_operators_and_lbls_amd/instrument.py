@@ -170,13 +170,14 @@ class Instrument:
         return d
 
     # -- on the device --------------------------------------------------------------------------------------------------
-    def native_handle(self, device_index=0):
-        """(context, operator handle) on a device: created on first use, released with the object."""
+    def native_handle(self, device_index=0, ctx=None):
+        """(context, operator handle) on a device: created on first use, released with the object.  ``ctx`` is the context
+        to create it on (default: ``_native.default_context(device_index)``)."""
         hit = self._handles.get(device_index)
-        if hit is None or hit[0]._handle is None:             # first use, or the context was closed since
-            if hit is not None:
+        if hit is None or hit[0]._handle is None or (ctx is not None and hit[0] is not ctx):   # first use, or the context
+            if hit is not None:                                                              # was closed or replaced since
                 hit[0].obs_destroy(hit[1])
-            ctx = _native.default_context(device_index)
+            ctx = _native.default_context(device_index) if ctx is None else ctx
             hit = self._handles[device_index] = (ctx, ctx.obs_create(self.m_in, self.m_out, self.row_ptr, self.col, self.w))
         return hit
 
@@ -188,7 +189,7 @@ class Instrument:
         import torch
         from . import retrieval
         ref = tb if tb is not None else k_blocks[0]
-        stream = torch.cuda.current_stream(ref.device).cuda_stream if ref.is_cuda else None
+        stream = torch.cuda.current_stream(ref.device).cuda_stream if torch.is_tensor(ref) and ref.is_cuda else None
         return retrieval._native_obs_apply(self, tb, k_blocks, stream)
 
     def param_jacobian(self, model, z, p, t, rh, params, relative=False):

@@ -48,7 +48,17 @@ Cholesky factor of the profile's Se_p on the rows it keeps (``mwrt_obs_whiten_de
 and the basis projection) and the unchanged update entries run with Se = 1, which gives exactly the step of Se_p.
 
     se_p = noise[None] + ov.representation_error(z, p, x)            # K S_res K^T of a truncated basis, per profile
-    res = ov.retrieve(z, p, y, se=se_p)"""
+    res = ov.retrieve(z, p, y, se=se_p)
+
+The tensor contract.  The library is handed bare pointers and reads contiguous doubles behind them on the
+GPU, so every tensor argument of this module -- the constructor's ``sa``, ``se``, ``xa``, ``StateBasis``'s ``b``, ``sa_c``,
+``c_a``, and ``z``, ``p``, ``x``, ``x0``, ``y``, ``se=`` of every public method -- must be a float64 ``torch.Tensor`` of the
+stated shape, on the device of ``xa`` (the three of a ``StateBasis`` on one device of their own: the constructor copies
+them to xa's).  Another dtype, a NumPy array or a list, another shape, another device, or a per-profile ``xa`` / ``c_a``
+whose nprof is not the call's is a ``ValueError`` naming the argument: nothing is converted, and nothing has reached the
+library by then.  Any strides are taken (an ``.expand``, a slice of a larger buffer, permuted storage, an offset): each
+argument is made contiguous once, at entry, and a call gives the same bits as on contiguous clones.  With the native
+context only CUDA tensors pass (``_context``).  NaN values are not refused: the kernels answer those with a status."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -62,6 +72,34 @@ from ._native import JacVariables
 from .autodiff import goff_gratch_es
 
 
+def _checked(name, v, *shapes, device=None, want=None):
+    """The one check of a tensor argument of this module: ``v`` must be a float64 tensor in one of ``shapes`` (tuples of
+    sizes; None or a string stands for any size and is printed as ``*`` or as itself) and, with ``device``, on that device.
+    Returns it contiguous: any strides are taken, and made contiguous here, once.  Another dtype is refused, not converted,
+    and so is anything that is not a tensor (``want`` replaces the words after "expected" in the message)."""
+    if want is None:
+        want = "a float64 tensor " + " or ".join(
+            "".join(f"[{'*' if d is None else d}]" for d in s) for s in shapes)
+    if not torch.is_tensor(v):
+        raise ValueError(f"{name}: expected {want}, got {type(v).__name__}")
+    fits = lambda s: len(s) == v.dim() and all(not isinstance(d, int) or d == k for d, k in zip(s, v.shape))   # noqa: E731
+    if v.dtype != torch.float64 or not any(fits(s) for s in shapes):
+        raise ValueError(f"{name}: expected {want}, got {v.dtype} {tuple(v.shape)}")
+    if device is not None and v.device != device:
+        raise ValueError(f"{name}: expected {want} on {device} (the device of xa), got one on {v.device}")
+    return v.contiguous()
+
+
+def _context(ref):
+    """The context whose entries take the pointers of tensors on the device of ``ref``: the one place this module asks
+    for one.  The library reads every pointer on the GPU, so with the native context a tensor anywhere else is refused
+    here; a stand-in context (CPU tests) takes what it is given."""
+    ctx = _native.default_context(ref.device.index or 0)
+    if isinstance(ctx, _native.Context) and not ref.is_cuda:
+        raise ValueError(f"expected CUDA tensors: the native library reads device pointers, got a tensor on {ref.device}")
+    return ctx
+
+
 def _native_k_matrix(model, z, p, t, rh, denliq, denice, frq, elev, variables, want, stream):
     """One ``mwrt_tb_jacobian_batch_vars_device`` call -> (tb [nprof][nang][nf], valid, {block: K rows [nprof][nang][nf][nlev]}).
 
@@ -72,7 +110,7 @@ def _native_k_matrix(model, z, p, t, rh, denliq, denice, frq, elev, variables, w
     rows = {b: torch.empty((nprof, elev.size, frq.size, nlev), **opts) for b in want}
     valid = torch.empty(nprof, dtype=torch.uint8, device=z.device)
     ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
-    _native.default_context(z.device.index or 0).tb_jacobian_batch_vars_device(
+    _context(z).tb_jacobian_batch_vars_device(
         model, nprof, nlev, z.data_ptr(), p.data_ptr(), t.data_ptr(), rh.data_ptr(), frq, elev, tb.data_ptr(),
         rows["t"].data_ptr(), rows["h"].data_ptr(), valid.data_ptr(), d_denliq=ptr(denliq), d_denice=ptr(denice),
         d_dtb_dliq=ptr(rows.get("liq")), d_dtb_dice=ptr(rows.get("ice")), variables=variables, stream=stream)
@@ -88,7 +126,7 @@ def _native_k_matrix_ray(model, z, p, t, rh, denliq, denice, frq, elev, variable
     rows = {b: torch.empty((nprof, elev.size, frq.size, nlev), **opts) for b in want}
     valid = torch.empty(nprof, dtype=torch.uint8, device=z.device)
     ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
-    _native.default_context(z.device.index or 0).tb_jacobian_batch_ray_device(
+    _context(z).tb_jacobian_batch_ray_device(
         model, nprof, nlev, z.data_ptr(), p.data_ptr(), t.data_ptr(), rh.data_ptr(), frq, elev, tb.data_ptr(),
         rows["t"].data_ptr(), rows["h"].data_ptr(), valid.data_ptr(), d_denliq=ptr(denliq), d_denice=ptr(denice),
         d_dtb_dliq=ptr(rows.get("liq")), d_dtb_dice=ptr(rows.get("ice")), variables=variables, stream=stream)
@@ -106,7 +144,7 @@ def _native_oe_step(k_blocks, x, xa, sa, se, y, fx, want_post_var, stream):
                chi2=torch.empty(nprof, **opts), dfs=torch.empty(nprof, **opts),
                nobs=torch.empty(nprof, dtype=torch.int32, device=x.device),
                post_var=torch.empty_like(x) if want_post_var else None)
-    _native.default_context(x.device.index or 0).oe_step_device(
+    _context(x).oe_step_device(
         nprof, nlev, m, [k.data_ptr() for k in k_blocks], x.data_ptr(), xa.data_ptr(), sa.data_ptr(), se.data_ptr(),
         y.data_ptr(), fx.data_ptr(), out["x_new"].data_ptr(), out["status"].data_ptr(), d_chi2=out["chi2"].data_ptr(),
         d_dfs=out["dfs"].data_ptr(), d_post_var=None if out["post_var"] is None else out["post_var"].data_ptr(),
@@ -118,7 +156,7 @@ def _native_oe_lm_prepare(k_blocks, x, xa, sa, se, y, fx, lin, active, stream):
     """One ``mwrt_oe_lm_prepare_device`` call: fills ``lin`` (dict of g0, r, kdx, keep, lin_status) in place for the profiles
     whose ``active`` flag (uint8) is set.  CPU tests substitute the NumPy reference here."""
     nprof, nblk, nlev = x.shape
-    _native.default_context(x.device.index or 0).oe_lm_prepare_device(
+    _context(x).oe_lm_prepare_device(
         nprof, nlev, y.shape[1], [k.data_ptr() for k in k_blocks], x.data_ptr(), xa.data_ptr(), sa.data_ptr(), se.data_ptr(),
         y.data_ptr(), fx.data_ptr(), lin["g0"].data_ptr(), lin["r"].data_ptr(), lin["kdx"].data_ptr(), lin["keep"].data_ptr(),
         lin["lin_status"].data_ptr(), d_active=active.data_ptr(), xa_per_profile=xa.dim() == 3, se_full=se.dim() == 2,
@@ -129,7 +167,7 @@ def _native_oe_lm_solve(k_blocks, x, xa, sa, se, gamma, lin, out, active, stream
     """One ``mwrt_oe_lm_solve_device`` call: the damped trial of every active profile into ``out`` (dict of x_new, status) in
     place.  CPU tests substitute the NumPy reference here."""
     nprof, nblk, nlev = x.shape
-    _native.default_context(x.device.index or 0).oe_lm_solve_device(
+    _context(x).oe_lm_solve_device(
         nprof, nlev, lin["r"].shape[1], [k.data_ptr() for k in k_blocks], x.data_ptr(), xa.data_ptr(), sa.data_ptr(),
         se.data_ptr(), gamma.data_ptr(), lin["g0"].data_ptr(), lin["r"].data_ptr(), lin["kdx"].data_ptr(),
         lin["keep"].data_ptr(), lin["lin_status"].data_ptr(), out["x_new"].data_ptr(), out["status"].data_ptr(),
@@ -140,7 +178,7 @@ def _native_oe_cost(x, xa, se, y, fx, keep, sa_inv, cost, active, stream):
     """One ``mwrt_oe_cost_device`` call: J at ``x`` on the rows ``keep`` names into ``cost`` in place, active profiles only.
     CPU tests substitute the NumPy reference here."""
     nprof, nblk, nlev = x.shape
-    _native.default_context(x.device.index or 0).oe_cost_device(
+    _context(x).oe_cost_device(
         nprof, nlev, y.shape[1], nblk, x.data_ptr(), xa.data_ptr(), se.data_ptr(), y.data_ptr(), fx.data_ptr(),
         keep.data_ptr(), sa_inv.data_ptr(), cost.data_ptr(), d_active=active.data_ptr(), xa_per_profile=xa.dim() == 3,
         se_full=se.dim() == 2, stream=stream)
@@ -151,7 +189,7 @@ def _native_oe_nform_prepare(k_blocks, x, xa, se, y, fx, lin, active, stream):
     profiles whose ``active`` flag (uint8) is set or, with ``active=None``, for all.  ``se`` holds variances, ``[m]`` or
     ``[nprof][m]``.  CPU tests substitute the NumPy reference here."""
     nprof, nblk, nlev = x.shape
-    _native.default_context(x.device.index or 0).oe_nform_prepare_device(
+    _context(x).oe_nform_prepare_device(
         nprof, nlev, y.shape[1], [k.data_ptr() for k in k_blocks], x.data_ptr(), xa.data_ptr(), se.data_ptr(), y.data_ptr(),
         fx.data_ptr(), lin["h"].data_ptr(), lin["g"].data_ptr(), lin["rwr"].data_ptr(), lin["keep"].data_ptr(),
         lin["nobs"].data_ptr(), lin["lin_status"].data_ptr(), d_active=None if active is None else active.data_ptr(),
@@ -164,7 +202,7 @@ def _native_oe_nform_solve(x, xa, sa_inv, lin, gamma, out, active, stream):
     the NumPy reference here."""
     nprof, nblk, nlev = x.shape
     ptr = lambda v: None if v is None else v.data_ptr()   # noqa: E731
-    _native.default_context(x.device.index or 0).oe_nform_solve_device(
+    _context(x).oe_nform_solve_device(
         nprof, nlev, lin["keep"].shape[1], nblk, x.data_ptr(), xa.data_ptr(), sa_inv.data_ptr(), lin["h"].data_ptr(),
         lin["g"].data_ptr(), lin["rwr"].data_ptr(), lin["lin_status"].data_ptr(), out["x_new"].data_ptr(),
         out["status"].data_ptr(), d_gamma=ptr(gamma), d_chi2=ptr(out.get("chi2")), d_dfs=ptr(out.get("dfs")),
@@ -176,7 +214,7 @@ def _native_oe_nform_cost(x, xa, sa_inv, se, y, fx, keep, cost, active, stream):
     """One ``mwrt_oe_nform_cost_device`` call: J at ``x`` on the rows ``keep`` names into ``cost`` in place, active profiles
     only.  CPU tests substitute the NumPy reference here."""
     nprof, nblk, nlev = x.shape
-    _native.default_context(x.device.index or 0).oe_nform_cost_device(
+    _context(x).oe_nform_cost_device(
         nprof, nlev, y.shape[1], nblk, x.data_ptr(), xa.data_ptr(), sa_inv.data_ptr(), se.data_ptr(), y.data_ptr(),
         fx.data_ptr(), keep.data_ptr(), cost.data_ptr(), d_active=None if active is None else active.data_ptr(),
         xa_per_profile=xa.dim() == 3, se_per_profile=se.dim() == 2, stream=stream)
@@ -189,7 +227,7 @@ def _native_oe_nform_char(sa_inv, lin, nblk, out, rows, stream):
     NumPy reference here."""
     nprof, n = lin["g"].shape
     ptr = lambda v: None if v is None else v.data_ptr()   # noqa: E731
-    _native.default_context(sa_inv.device.index or 0).oe_nform_char_device(
+    _context(sa_inv).oe_nform_char_device(
         nprof, n // nblk, lin["keep"].shape[1], nblk, sa_inv.data_ptr(), lin["h"].data_ptr(), lin["lin_status"].data_ptr(),
         out["status"].data_ptr(), d_post_cov=ptr(out.get("post_cov")), d_avk=ptr(out.get("avk")),
         d_avk_diag=ptr(out.get("avk_diag")), d_dfs_block=ptr(out.get("dfs_block")), d_noise_var=ptr(out.get("noise_var")),
@@ -203,7 +241,7 @@ def _native_oe_nform_gain(k_blocks, se, keep, post_cov, status, stream):
     nprof, m = keep.shape
     n = post_cov.shape[-1]
     gain = torch.empty((nprof, m, n), dtype=torch.float64, device=keep.device)
-    _native.default_context(keep.device.index or 0).oe_nform_gain_device(
+    _context(keep).oe_nform_gain_device(
         nprof, n // len(k_blocks), m, [k.data_ptr() for k in k_blocks], se.data_ptr(), keep.data_ptr(), post_cov.data_ptr(),
         status.data_ptr(), gain.data_ptr(), se_per_profile=se.dim() == 2, stream=stream)
     return gain
@@ -222,7 +260,7 @@ def _native_oe_gain(k_blocks, x, xa, sa, se, y, fx, stream):
                dfs_block=torch.empty((nprof, nblk), **f64), noise_var=torch.empty_like(x), smooth_var=torch.empty_like(x),
                status=torch.empty(nprof, dtype=torch.uint8, device=x.device),
                nobs=torch.empty(nprof, dtype=torch.int32, device=x.device))
-    _native.default_context(x.device.index or 0).oe_gain_device(
+    _context(x).oe_gain_device(
         nprof, nlev, m, [k.data_ptr() for k in k_blocks], x.data_ptr(), xa.data_ptr(), sa.data_ptr(), se.data_ptr(),
         y.data_ptr(), fx.data_ptr(), out["status"].data_ptr(), d_gain=out["gain"].data_ptr(), d_ksa=out["ksa"].data_ptr(),
         d_keep=out["keep"].data_ptr(), d_avk_diag=out["avk_diag"].data_ptr(), d_dfs_block=out["dfs_block"].data_ptr(),
@@ -239,7 +277,7 @@ def _native_oe_product(product, gain, keep, k_blocks, ksa, sa, rows, stream):
     nprof, m, n = gain.shape
     nlev = n // len(k_blocks)
     out = torch.empty((nprof, rows[1] or n, n), dtype=torch.float64, device=gain.device)
-    _native.default_context(gain.device.index or 0).oe_product_device(
+    _context(gain).oe_product_device(
         nprof, nlev, m, _native.OE_PRODUCT_AVK if product == "avk" else _native.OE_PRODUCT_POST_COV, gain.data_ptr(),
         keep.data_ptr(), out.data_ptr(), [k.data_ptr() for k in k_blocks], d_ksa=ksa.data_ptr(), d_sa=sa.data_ptr(),
         row_begin=rows[0], row_count=rows[1], stream=stream)
@@ -252,22 +290,31 @@ def _native_obs_apply(instrument, tb, k_blocks, stream):
     quadrature grid.
 
     The single place the instrument's reduction reaches the native library: CPU tests substitute the NumPy reference here."""
-    k_blocks = None if k_blocks is None else [k.contiguous() for k in k_blocks]
+    k_blocks = None if k_blocks is None else list(k_blocks)
     ref = tb if tb is not None else k_blocks[0]
-    nprof = ref.shape[0]
+    named = [("tb", tb)] + [(f"k_blocks[{i}]", k) for i, k in enumerate(k_blocks or [])]
+    for name, v in named:                                     # ``Instrument.apply`` hands over the caller's tensors
+        if v is not None and not torch.is_tensor(v):
+            raise ValueError(f"{name}: expected a float64 tensor, got {type(v).__name__}")
+    if len({v.device for _, v in named if v is not None}) > 1:
+        raise ValueError("tb and k_blocks: expected tensors on one device, got "
+                         + ", ".join(f"{name} on {v.device}" for name, v in named if v is not None))
+    nprof = ref.shape[0] if ref.dim() else 0
     nang, nch = instrument.elev.size, instrument.frq.size
+    grid = f"[{instrument.elev_q.size}][{instrument.frq_q.size}]"
     opts = dict(dtype=torch.float64, device=ref.device)
-    for name, v in [("tb", tb)] + [(f"k_blocks[{i}]", k) for i, k in enumerate(k_blocks or [])]:
-        if v is not None and (v.dtype != torch.float64 or v.shape[0] != nprof or v[0].numel() % instrument.m_in != 0):
-            raise ValueError(f"{name}: expected float64 [{nprof}][{instrument.elev_q.size}][{instrument.frq_q.size}]..., got "
-                             f"{v.dtype} {tuple(v.shape)}")
-    if tb is not None and tb[0].numel() != instrument.m_in:
-        raise ValueError(f"tb: expected [{nprof}][{instrument.m_in}], got {tuple(tb.shape)}")
+    if tb is not None and (tb.dtype != torch.float64 or tb.dim() < 2 or tb[0].numel() != instrument.m_in):
+        raise ValueError(f"tb: expected float64 [nprof]{grid} (or [nprof][{instrument.m_in}]), got {tb.dtype} {tuple(tb.shape)}")
+    nlev = k_blocks[0].shape[-1] if k_blocks and k_blocks[0].dim() else 1
+    for i, k in enumerate(k_blocks or []):
+        if k.dtype != torch.float64 or k.dim() < 3 or k.shape[0] != nprof or k.shape[-1] != nlev or \
+                k[0].numel() != instrument.m_in * nlev:
+            raise ValueError(f"k_blocks[{i}]: expected float64 [{nprof}]{grid}[{nlev}], got {k.dtype} {tuple(k.shape)}")
+    k_blocks = None if k_blocks is None else [k.contiguous() for k in k_blocks]
     tb_in = None if tb is None else tb.contiguous()
     tb_out = None if tb is None else torch.empty((nprof, nang, nch), **opts)
-    nlev = k_blocks[0].shape[-1] if k_blocks else 1
     k_out = None if k_blocks is None else [torch.empty((nprof, nang, nch, nlev), **opts) for _ in k_blocks]
-    ctx, handle = instrument.native_handle(ref.device.index or 0)
+    ctx, handle = instrument.native_handle(ref.device.index or 0, ctx=_context(ref))
     ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
     ctx.obs_apply_device(handle, nprof, nlev, d_tb_in=ptr(tb_in), d_tb_out=ptr(tb_out),
                          d_k_in=[k.data_ptr() for k in k_blocks or []], d_k_out=[k.data_ptr() for k in k_out or []],
@@ -290,7 +337,7 @@ def _native_basis_project(basis, k_blocks, stream):
                          f"{tuple(basis.b.shape)}")
     m = k_blocks[0][0].numel() // nlev
     out = torch.empty((nprof, m, basis.r), dtype=torch.float64, device=k_blocks[0].device)
-    ctx, handle = basis.native_handle(len(k_blocks), k_blocks[0].device.index or 0)
+    ctx, handle = basis.native_handle(len(k_blocks), k_blocks[0].device.index or 0, ctx=_context(k_blocks[0]))
     ctx.basis_project_device(handle, nprof, m, [k.data_ptr() for k in k_blocks], out.data_ptr(), stream=stream)
     return out
 
@@ -308,7 +355,7 @@ def _native_basis_expand(basis, c, x_ref, stream):
                          f"{basis.n}, got {c.dtype} {tuple(c.shape)} and {x_ref.dtype} {tuple(x_ref.shape)}")
     c, x_ref = c.contiguous(), x_ref.contiguous()
     out = torch.empty((nprof, nblk, nlev), dtype=torch.float64, device=c.device)
-    ctx, handle = basis.native_handle(nblk, c.device.index or 0)
+    ctx, handle = basis.native_handle(nblk, c.device.index or 0, ctx=_context(c))
     ctx.basis_expand_device(handle, nprof, c.data_ptr(), x_ref.data_ptr(), out.data_ptr(), x_ref_per_profile=x_ref.dim() == 3,
                             stream=stream)
     return out
@@ -333,7 +380,7 @@ def _native_obs_whiten(k_blocks, se, y, fx, stream):
     out = dict(k=[torch.empty_like(k) for k in k_blocks], y=torch.empty_like(y), fx=torch.empty_like(fx),
                l=torch.empty((nprof, m * (m + 1) // 2), **f64), keep=torch.empty((nprof, m), **u8),
                status=torch.empty(nprof, **u8))
-    _native.default_context(y.device.index or 0).obs_whiten_device(
+    _context(y).obs_whiten_device(
         nprof, nlev, m, se.data_ptr(), y.data_ptr(), fx.data_ptr(), [k.data_ptr() for k in k_blocks], out["l"].data_ptr(),
         out["keep"].data_ptr(), out["status"].data_ptr(), d_y_out=out["y"].data_ptr(), d_fx_out=out["fx"].data_ptr(),
         d_k_out=[k.data_ptr() for k in out["k"]], se_full=se.dim() == 3, stream=stream)
@@ -351,7 +398,7 @@ def _native_obs_whiten_apply(l, keep, mode, vec, block, stream):
     v_out = None if vec is None else torch.empty_like(vec)
     b_out = None if block is None else torch.empty_like(block)
     ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
-    _native.default_context(keep.device.index or 0).obs_whiten_apply_device(
+    _context(keep).obs_whiten_apply_device(
         nprof, 1 if block is None else block.shape[-1], m, l.data_ptr(), keep.data_ptr(), mode=mode, d_y=ptr(vec),
         d_y_out=ptr(v_out), d_k_in=[] if block is None else [block.data_ptr()],
         d_k_out=[] if block is None else [b_out.data_ptr()], stream=stream)
@@ -366,16 +413,16 @@ class StateBasis:
     scales a liquid-water profile shape.  The device copy of B is made once per device and context, on first use."""
 
     def __init__(self, b, sa_c, c_a=None):
-        b, sa_c = torch.as_tensor(b), torch.as_tensor(sa_c)
-        if b.dim() != 2 or b.dtype != torch.float64:
-            raise ValueError(f"b: expected float64 [n][r], got {b.dtype} {tuple(b.shape)}")
+        b = _checked("b", b, ("n", "r"), want="float64 [n][r], a tensor")
         self.n, self.r = int(b.shape[0]), int(b.shape[1])
-        if tuple(sa_c.shape) != (self.r, self.r):
-            raise ValueError(f"sa_c: expected [{self.r}][{self.r}], got {tuple(sa_c.shape)}")
-        c_a = torch.zeros(self.r, dtype=torch.float64, device=b.device) if c_a is None else torch.as_tensor(c_a)
-        if c_a.dim() not in (1, 2) or c_a.shape[-1] != self.r:
-            raise ValueError(f"c_a: expected [{self.r}] or [nprof][{self.r}], got {tuple(c_a.shape)}")
-        self.b, self.sa_c, self.c_a = b.contiguous(), sa_c.to(torch.float64).contiguous(), c_a.to(torch.float64).contiguous()
+        r = self.r
+        sa_c = _checked("sa_c", sa_c, (r, r), want=f"[{r}][{r}], a float64 tensor")
+        c_a = torch.zeros(r, dtype=torch.float64, device=b.device) if c_a is None else c_a
+        c_a = _checked("c_a", c_a, (r,), ("nprof", r), want=f"[{r}] or [nprof][{r}], a float64 tensor")
+        if not b.device == sa_c.device == c_a.device:
+            raise ValueError(f"b, sa_c and c_a: expected on one device, got b on {b.device}, sa_c on {sa_c.device} and c_a "
+                             f"on {c_a.device}")
+        self.b, self.sa_c, self.c_a = b, sa_c, c_a
         self.sa_res = None         # [n][n] what the basis leaves out of the prior covariance (``from_covariance`` sets it)
         self._handles = {}
 
@@ -399,16 +446,17 @@ class StateBasis:
         basis.sa_res = (0.5 * (res + res.T)).contiguous().to(sa.device)
         return basis
 
-    def native_handle(self, nblk, device_index=0):
-        """(context, basis handle) for ``nblk`` blocks on a device: created on first use, released with the object."""
+    def native_handle(self, nblk, device_index=0, ctx=None):
+        """(context, basis handle) for ``nblk`` blocks on a device: created on first use, released with the object.  ``ctx``
+        is the context to create it on (default: ``_native.default_context(device_index)``)."""
         key = (int(nblk), device_index)
         hit = self._handles.get(key)
-        if hit is None or hit[0]._handle is None:             # first use, or the context was closed since
-            if hit is not None:
+        if hit is None or hit[0]._handle is None or (ctx is not None and hit[0] is not ctx):   # first use, or the context
+            if hit is not None:                                                              # was closed or replaced since
                 hit[0].basis_destroy(hit[1])
             if self.n % int(nblk) != 0:
                 raise ValueError(f"basis: b [{self.n}][{self.r}] does not split into {nblk} blocks")
-            ctx = _native.default_context(device_index)
+            ctx = _native.default_context(device_index) if ctx is None else ctx
             hit = self._handles[key] = (ctx, ctx.basis_create(nblk, self.n // int(nblk), self.b.detach().cpu().numpy()))
         return hit
 
@@ -478,7 +526,6 @@ class OneDVar:
             raise ValueError("xa (the prior state) is required")
         if sa is None and basis is None:
             raise ValueError("sa (the prior covariance) is required without a basis")
-        self.sa, self.se, self.xa = None if sa is None else sa.contiguous(), se.contiguous(), xa.contiguous()
         self.m = self.frq.size * self.elev.size
         # with an instrument (instrument.Instrument) the forward operator runs on its quadrature grid and every TB and K row is
         # reduced to channels before the update sees it: se, y and all diagnostics are in channel space, m = instrument.m_out
@@ -489,13 +536,12 @@ class OneDVar:
                                  f"(instrument.frq = {instrument.frq.tolist()}, instrument.elev = {instrument.elev.tolist()})")
             self.m = instrument.m_out
         nblk = len(blocks)
-        if self.xa.dim() not in (2, 3) or self.xa.shape[-2] != nblk:
-            raise ValueError(f"xa: expected [{nblk}][nlev] or [nprof][{nblk}][nlev], got {tuple(self.xa.shape)}")
+        # the tensor contract (module docstring): xa names the device, everything else is checked against it
+        self.xa = _checked("xa", xa, (nblk, "nlev"), ("nprof", nblk, "nlev"))
+        self.device = self.xa.device
         n = nblk * self.xa.shape[-1]
-        if self.sa is not None and tuple(self.sa.shape) != (n, n):
-            raise ValueError(f"sa: expected [{n}][{n}], got {tuple(self.sa.shape)}")
-        if tuple(self.se.shape) not in ((self.m,), (self.m, self.m)):
-            raise ValueError(f"se: expected [{self.m}] or [{self.m}][{self.m}], got {tuple(self.se.shape)}")
+        self.sa = None if sa is None else _checked("sa", sa, (n, n), device=self.device)
+        self.se = _checked("se", se, (self.m,), (self.m, self.m), device=self.device)
         # what the update works in: the state itself, or with a basis the coefficients c ([nprof][1][r] inside this class)
         # with the prior c_a and sa_c.  The coefficients are never clamped: humidity and cloud >= 0 is applied to the
         # physical state clamp(xa + B c) the forward model sees, not to c.
@@ -534,9 +580,46 @@ class OneDVar:
             self._sa_inv = (0.5 * (inv + inv.T)).contiguous()
         return self._sa_inv
 
+    # -- the tensor contract (module docstring) -----------------------------------------------------------------------
+    def _inputs(self, z, p, x=None, y=None, x0=None, se=None, physical=False):
+        """The tensor arguments of a public method, each checked once (``_checked``: a float64 tensor of the stated shape on
+        the device of xa) and contiguous from here on -> ``(z, p, x, y, x0, se)``, None where None was given.  ``x`` and
+        ``x0`` are the update's state: ``[nprof][nblk][nlev]``, or with a basis (and not ``physical``) the coefficients
+        ``[nprof][r]`` (``[nprof][1][r]`` is taken too).  ``y`` comes back as ``[nprof][m]``.  nprof is that of ``x``, else
+        of ``y``; a per-profile xa or c_a of another nprof is refused."""
+        nblk, nlev = self.xa.shape[-2:]
+        dev, nprof = self.device, "nprof"
+        coeff = self.basis is not None and not physical
+        state = lambda n: ((n, self.basis.r), (n, 1, self.basis.r)) if coeff else ((n, nblk, nlev),)   # noqa: E731
+        if x is not None:
+            x = _checked("x", x, *state(nprof), device=dev)
+            nprof = x.shape[0]
+        if y is not None:
+            y = _checked("y", y, (nprof, self.elev.size, self.frq.size), (nprof, self.m), device=dev)
+            nprof = y.shape[0]
+            y = y.reshape(nprof, self.m)
+        if x0 is not None:
+            x0 = _checked("x0", x0, *state(nprof), device=dev)
+        z = _checked("z", z, (nprof, nlev), device=dev)
+        p = _checked("p", p, (nprof, nlev), device=dev)
+        self._batch(nprof)
+        return z, p, x, y, x0, self._per_profile_se(se, nprof)
+
+    def _batch(self, nprof):
+        """A per-profile prior belongs to one batch size: xa ``[nprof][nblk][nlev]`` and c_a ``[nprof][r]`` must have this one."""
+        if self.xa.dim() == 3 and self.xa.shape[0] != nprof:
+            raise ValueError(f"xa: expected [nblk][nlev] or [{nprof}][nblk][nlev] for this batch, got {tuple(self.xa.shape)}")
+        if self.basis is not None and self._prior_mean.dim() == 3 and self._prior_mean.shape[0] != nprof:
+            raise ValueError(f"basis.c_a: expected [{self.basis.r}] or [{nprof}][{self.basis.r}] for this batch, got "
+                             f"{tuple(self.basis.c_a.shape)}")
+
     # -- the state in the operator's inputs -----------------------------------------------------------------------------
     def physical(self, z, p, x):
         """(z, t, rh, denliq, denice) the forward operator takes for the state ``x`` (cloud arrays None when not a block)."""
+        z, p, x = self._inputs(z, p, x=x, physical=True)[:3]
+        return self._physical(z, p, x)
+
+    def _physical(self, z, p, x):
         v = self.variables
         t = x[:, 0].contiguous()
         h = x[:, 1]
@@ -556,6 +639,9 @@ class OneDVar:
 
     def clamp(self, x):
         """Humidity and cloud are kept >= 0 (the linear update knows no such bound)."""
+        return self._clamp(_checked("x", x, ("nprof", len(self.blocks), self.xa.shape[-1]), device=self.device))
+
+    def _clamp(self, x):
         x = x.clone()
         for i, b in enumerate(self.blocks):
             if b != "t":
@@ -565,20 +651,22 @@ class OneDVar:
     # -- the reduced basis -------------------------------------------------------------------------------------------
     def expand(self, c):
         """xa + B c ``[nprof][nblk][nlev]`` for the coefficients ``c [nprof][r]`` (``mwrt_basis_expand_device``), unclamped."""
+        if self.basis is None:
+            raise ValueError("expand needs a basis")
+        c = _checked("c", c, ("nprof", self.basis.r), ("nprof", 1, self.basis.r), device=self.device)
+        self._batch(c.shape[0])
+        return self._expand(c)
+
+    def _expand(self, c):
         return _native_basis_expand(self.basis, c.reshape(c.shape[0], self.basis.r), self.xa, self._stream(c))
 
     def _state(self, u):
         """The physical state the forward model sees for the update's state ``u``: u itself, or clamp(xa + B c)."""
-        if self.basis is None:
-            return u
-        if self._prior_mean.dim() == 3 and self._prior_mean.shape[0] != u.shape[0]:
-            raise ValueError(f"basis.c_a: expected [{self.basis.r}] or [{u.shape[0]}][{self.basis.r}] for this batch, got "
-                             f"{tuple(self.basis.c_a.shape)}")
-        return self.clamp(self.expand(u))
+        return u if self.basis is None else self._clamp(self._expand(u))
 
     def _bound(self, u):
         """The update's state after a move: clamped as ``clamp`` says, except coefficients, which have no bound."""
-        return self.clamp(u) if self.basis is None else u
+        return self._clamp(u) if self.basis is None else u
 
     def _start(self, x0, nprof):
         """The first state of an iteration ([nprof][nblk][nlev], or [nprof][1][r] with a basis): ``x0`` or the prior."""
@@ -592,11 +680,7 @@ class OneDVar:
         """``se=`` of a call, checked: None (the constructor's shared se) or float64 [nprof][m] / [nprof][m][m]."""
         if se is None:
             return None
-        m = self.m
-        if not torch.is_tensor(se) or se.dtype != torch.float64 or tuple(se.shape) not in ((nprof, m), (nprof, m, m)):
-            got = f"{se.dtype} {tuple(se.shape)}" if torch.is_tensor(se) else type(se).__name__
-            raise ValueError(f"se: expected a float64 tensor [{nprof}][{m}] or [{nprof}][{m}][{m}], got {got}")
-        return se.contiguous()
+        return _checked("se", se, (nprof, self.m), (nprof, self.m, self.m), device=self.device)
 
     def _whiten(self, se_p, k_blocks, y, fx, stream):
         """What the update entries are given: ``(k_blocks, y, fx, se, None)`` as they are without a per-profile Se; with one
@@ -632,6 +716,7 @@ class OneDVar:
         products in torch; add it to the noise covariance and pass the sum as ``se=``."""
         if self.basis is None or self.basis.sa_res is None:
             raise ValueError("representation_error needs a basis with sa_res (StateBasis.from_covariance sets it)")
+        z, p, x = self._inputs(z, p, x=x, physical=True)[:3]
         _, _, k_blocks = self._observe(z, p, x, project=False)
         nprof = x.shape[0]
         k = torch.cat([b.reshape(nprof, self.m, -1) for b in k_blocks], dim=2)
@@ -738,7 +823,7 @@ class OneDVar:
             _native_oe_nform_solve(x, xa, self.sa_inv, lin, gamma, trial, mask, stream)
             ok = active & (trial["status"] == 1)
             x_try = self._bound(torch.where(ok[:, None, None], trial["x_new"], x)).contiguous()
-            fx_try = self.forward(z, p, self._state(x_try))[0].reshape(nprof, m)
+            fx_try = self._observe(z, p, self._state(x_try), want_rows=False)[0].reshape(nprof, m)
             if w is not None:
                 fx_try = _native_obs_whiten_apply(w["l"], w["keep"], 0, fx_try, None, stream)[0]
             _native_oe_nform_cost(x_try, xa, self.sa_inv, se_w, y_w, fx_try, lin["keep"], cost_try, mask, stream)
@@ -772,7 +857,7 @@ class OneDVar:
         basis the rows are then contracted with it (``_native_basis_project``, behind the channel reduction, which shrinks
         the rows first): the one block K B.  ``x`` is the physical state.  The one place of this class that runs the forward
         operator."""
-        zz, t, rh, dl, di = self.physical(z, p, x)
+        zz, t, rh, dl, di = self._physical(z, p, x)
         inst = self.instrument
         frq, elev = (self.frq, self.elev) if inst is None else (inst.frq_q, inst.elev_q)
         stream = self._stream(x)
@@ -793,6 +878,7 @@ class OneDVar:
         """The forward model at the state ``x``: ``(tb [nprof][nang][nf], valid [nprof])`` on torch's current stream (the
         K-matrix call's TBs; its rows are discarded).  With an instrument: the channel TBs.  ``x`` is the physical state
         also with a basis (``expand`` gives it for coefficients)."""
+        z, p, x = self._inputs(z, p, x=x, physical=True)[:3]
         tb, valid, _ = self._observe(z, p, x, want_rows=False)
         return tb, valid
 
@@ -821,10 +907,15 @@ class OneDVar:
         or product call.  ``se=`` as ``[nprof][m]`` goes straight in (nothing is whitened, no ``whiten_status``), as
         ``[nprof][m][m]`` through the pre-whitening (m <= 140).  ``post_cov=True`` (form="n" only) adds ``post_cov``
         ``[nprof][n][n]``, the posterior covariance C^-1 in the update's state space (coefficients with a basis)."""
+        if post_cov and self.form != "n":
+            raise ValueError("step(post_cov=True) needs form='n'; with form='m' characterise(post_cov=True) forms it")
+        z, p, x, y, _, se = self._inputs(z, p, x=x, y=y, se=se)
+        return self._step(z, p, x, y, post_var, se, post_cov)
+
+    def _step(self, z, p, x, y, post_var=True, se=None, post_cov=False):
+        """``step`` on arguments ``_inputs`` has checked: what ``retrieve`` iterates."""
         if self.form == "n":
             return self._step_nform(z, p, x, y, post_var, se, post_cov)
-        if post_cov:
-            raise ValueError("step(post_cov=True) needs form='n'; with form='m' characterise(post_cov=True) forms it")
         stream = self._stream(x)
         nprof = x.shape[0]
         se_p = self._per_profile_se(se, nprof)
@@ -868,8 +959,8 @@ class OneDVar:
 
         ``se=``: a per-profile observation-error covariance as in ``step``; every step whitens its own linearisation.  A
         profile whose Se_p is not positive definite is frozen as failed at its first step: status 2, NaN diagnostics."""
+        z, p, _, y, x0, se_p = self._inputs(z, p, y=y, x0=x0, se=se)
         nprof = y.shape[0]
-        se_p = self._per_profile_se(se, nprof)
         x = self._start(x0, nprof)
         dev = x.device
         keys = ("chi2", "dfs", "post_var", "status", "nobs") if self.basis is None else ("chi2", "dfs", "status", "nobs")
@@ -878,7 +969,7 @@ class OneDVar:
         iters = torch.zeros(nprof, dtype=torch.int32, device=dev)
         keep = None
         for _ in range(int(max_iter)):
-            x_new, d = self.step(z, p, x, y, post_var=self.basis is None, **({} if se_p is None else {"se": se_p}))
+            x_new, d = self._step(z, p, x, y, post_var=self.basis is None, se=se_p)
             ok = (d["status"] == 1) | (d["status"] == 3)
             x_new = self._bound(torch.where(ok[:, None, None], x_new, x))
             move = ((x_new - x).abs() / self._sigma).amax(dim=(1, 2))
@@ -896,7 +987,7 @@ class OneDVar:
             if not bool(active.any()):
                 break
         if self.basis is not None and self.form == "n":                  # the level-space diagonal at the final states, too
-            post_var = self.step(z, p, x, y, post_var=True, **({} if se_p is None else {"se": se_p}))[1]["post_var"]
+            post_var = self._step(z, p, x, y, post_var=True, se=se_p)[1]["post_var"]
             return Retrieval(x=self._state(x), chi2=keep["chi2"], dfs=keep["dfs"], post_var=post_var, status=keep["status"],
                              nobs=keep["nobs"], iterations=iters, converged=converged, coeff=x.reshape(nprof, -1))
         if self.basis is not None:
@@ -930,6 +1021,7 @@ class OneDVar:
             raise ValueError("characterise is not offered with form='n': use characterise_nform there (or form='m') for the "
                              "gain matrix, the averaging kernel and the error budget, or step(..., post_cov=True) for the "
                              "posterior covariance")
+        z, p, x, y, _, se = self._inputs(z, p, x=x, y=y, se=se)
         if self.basis is not None:
             x = x.reshape(x.shape[0], 1, self.basis.r)
         nprof, n = x.shape[0], x.shape[1] * x.shape[2]
@@ -972,6 +1064,7 @@ class OneDVar:
         goes through the pre-whitening (m <= 140) and the gain is un-whitened afterwards, as in ``characterise``."""
         if self.form != "n":
             raise ValueError("characterise_nform needs form='n'; with form='m' characterise gives the same fields")
+        z, p, x, y, _, se = self._inputs(z, p, x=x, y=y, se=se)
         if self.basis is not None:
             x = x.reshape(x.shape[0], 1, self.basis.r)
         nprof, nblk, n = x.shape[0], x.shape[1], x.shape[1] * x.shape[2]
@@ -1042,6 +1135,7 @@ class OneDVar:
         With ``form="n"`` the same loop runs on ``mwrt_oe_nform_prepare_device`` / ``mwrt_oe_nform_solve_device`` /
         ``mwrt_oe_nform_cost_device`` (any m; one n x n solve per trial), and the final diagnostics come from one undamped
         solve at the final states."""
+        z, p, _, y, x0, se = self._inputs(z, p, y=y, x0=x0, se=se)
         if self.form == "n":
             return self._retrieve_lm_nform(z, p, y, x0, max_iter, tol, gamma0, up, down, gamma_max, se)
         nprof, m = y.shape[0], self.m
@@ -1077,7 +1171,7 @@ class OneDVar:
             _native_oe_lm_solve(k_blocks, x, xa, sa, se_w, gamma, lin, trial, mask, stream)
             ok = active & (trial["status"] == 1)
             x_try = self._bound(torch.where(ok[:, None, None], trial["x_new"], x)).contiguous()
-            fx_try = self.forward(z, p, self._state(x_try))[0].reshape(nprof, m)
+            fx_try = self._observe(z, p, self._state(x_try), want_rows=False)[0].reshape(nprof, m)
             if w is not None:
                 fx_try = _native_obs_whiten_apply(w["l"], w["keep"], 0, fx_try, None, stream)[0]
             _native_oe_cost(x_try, xa, se_w, y_w, fx_try, lin["keep"], self.sa_inv, cost_try, mask, stream)

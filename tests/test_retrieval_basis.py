@@ -164,7 +164,7 @@ def test_one_column_retrieves_the_scale_of_a_liquid_profile(gpu_ctx):
     b = np.zeros((3 * NLEV, 1))
     b[2 * NLEV:, 0] = shape
     sigma = 2.0
-    basis = lambda sa: StateBasis(torch.as_tensor(b), torch.as_tensor([[sigma ** 2]]), c_a=torch.ones(1, dtype=torch.float64))  # noqa: E731
+    basis = lambda sa: StateBasis(torch.as_tensor(b), torch.as_tensor([[sigma ** 2]]).to(torch.float64), c_a=torch.ones(1, dtype=torch.float64))  # noqa: E731
     ov, z, p, prior, _ = _setup(blocks=("t", "h", "liq"), basis=basis, with_sa=False)
     c_true = _dev(np.array([[0.5], [1.0], [1.5], [2.0]]))
     y, valid = ov.forward(z, p, ov.expand(c_true))

@@ -73,7 +73,7 @@ def test_without_a_basis_the_seams_see_what_they_saw(monkeypatch):
     s = setup()
     ov = make(s)
     assert ov.basis is None
-    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0)
+    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0, dtype=torch.float64)
     x_new, d = ov.step(s["z"], s["p"], s["x_true"], y)
     ov.forward(s["z"], s["p"], s["x_true"])
     res = ov.retrieve(s["z"], s["p"], y, max_iter=2)
@@ -95,7 +95,7 @@ def test_with_a_basis_the_update_sees_one_block_in_coefficients(monkeypatch):
     c_a = torch.as_tensor(np.random.default_rng(2).standard_normal((NPROF, R)) * 0.1)
     sb = eofs(s, c_a=c_a)
     ov = make(s, basis=sb)
-    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0)
+    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0, dtype=torch.float64)
     c = torch.as_tensor(np.random.default_rng(3).standard_normal((NPROF, R)))
     c_new, d = ov.step(s["z"], s["p"], c, y, post_var=False)
     # the forward model ran at clamp(xa + B c): the expansion got c and xa, the K-matrix call its result
@@ -142,7 +142,7 @@ def test_instrument_and_basis_reduce_then_project(monkeypatch):
     inst = Instrument(FRQ, ELEV, beam=3.5, band=[0.23, 0.23, 2.0], n_beam=3, n_band=2)
     sb = eofs(s)
     ov = make(s, instrument=inst, basis=sb)
-    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0)
+    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0, dtype=torch.float64)
     ov.step(s["z"], s["p"], torch.zeros((NPROF, R), dtype=torch.float64), y, post_var=False)
     assert st.order == ["reduce", "project"]
     # the projection got channel rows (m_out of them), not the quadrature grid's
@@ -203,10 +203,10 @@ def test_coefficients_are_not_clamped_but_the_state_is(monkeypatch):
     s = setup()
     b = np.zeros((N, 1))
     b[NLEV:, 0] = 1.0                                                    # one column: a shift of the whole humidity profile
-    sb = StateBasis(torch.as_tensor(b), torch.as_tensor([[4.0]]))
+    sb = StateBasis(torch.as_tensor(b), torch.as_tensor([[4.0]], dtype=torch.float64))
     ov = make(s, basis=sb)
     c = torch.full((NPROF, 1), -5.0, dtype=torch.float64)                # far below zero humidity
-    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0)
+    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0, dtype=torch.float64)
     c_new, d = ov.step(s["z"], s["p"], c, y, post_var=False)
     assert (st.k_calls[0]["args"][4] == 0).all()                         # the forward model saw rh clamped to 0 ...
     assert torch.equal(st.step_calls[0]["args"][0].reshape(NPROF, 1), c)  # ... the update the coefficient as it is
@@ -231,7 +231,7 @@ def test_shape_errors_name_the_expected_shapes(monkeypatch):
     # a per-profile prior of another batch size, and what the seams refuse before they reach the library
     ov = make(s, basis=eofs(s, c_a=torch.zeros((NPROF + 1, R), dtype=torch.float64)))
     with pytest.raises(ValueError, match=r"basis.c_a: expected \[4\] or \[%d\]\[4\]" % NPROF):
-        ov.step(s["z"], s["p"], torch.zeros((NPROF, R), dtype=torch.float64), torch.full((NPROF, M), 255.0))
+        ov.step(s["z"], s["p"], torch.zeros((NPROF, R), dtype=torch.float64), torch.full((NPROF, M), 255.0, dtype=torch.float64))
     sb = eofs(s)
     with pytest.raises(ValueError, match=r"x_ref \[nblk\]\[nlev\] or \[%d\]\[nblk\]\[nlev\]" % NPROF):
         EXPAND(sb, torch.zeros((NPROF, R), dtype=torch.float64), torch.zeros((NPROF + 1, 2, NLEV), dtype=torch.float64), None)

@@ -68,7 +68,7 @@ def test_optional_products_and_rows(monkeypatch):
     s = setup(blocks)
     ov = make(blocks, s)
     n = 2 * NLEV
-    y = torch.full((NPROF, M), 255.0)
+    y = torch.full((NPROF, M), 255.0, dtype=torch.float64)
     full = ov.characterise(s["z"], s["p"], s["x_true"], y, avk=True, post_cov=True)
     assert st.product_calls == [("avk", (0, 0)), ("post_cov", (0, 0))]
     assert full.avk.shape == (NPROF, n, n) and full.post_cov.shape == (NPROF, n, n)
@@ -93,7 +93,7 @@ def test_failed_and_unobserved_profiles(monkeypatch):
     s = setup(blocks)
     ov = make(blocks, s)
     n = 2 * NLEV
-    y = torch.full((NPROF, M), 255.0)
+    y = torch.full((NPROF, M), 255.0, dtype=torch.float64)
     y[1] = float("nan")                                                  # nothing observed: the prior
     y[2, 4] = float("nan")                                               # one observation missing
     x = s["x_true"].clone()

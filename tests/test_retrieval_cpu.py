@@ -84,7 +84,7 @@ def test_blocks_reach_the_update_in_state_order(monkeypatch):
     blocks = ("t", "h", "liq", "ice")
     s = setup(blocks)
     ov = make(blocks, s)
-    y = torch.full((NPROF, NANG, NF), 255.0)
+    y = torch.full((NPROF, NANG, NF), 255.0, dtype=torch.float64)
     x_new, d = ov.step(s["z"], s["p"], s["x_true"], y)
     assert st.calls[0]["want"] == blocks
     for got, b in zip(st.k_seen[0], blocks):                             # K = [K_t | K_h | K_liq | K_ice]
@@ -108,7 +108,7 @@ def test_state_variables_are_changed_to_operator_inputs(monkeypatch):
     x[:, 1] = x[:, 1] * 8000.0                                           # ppmv
     x[:, 2] = 1e-4                                                       # kg/kg
     ov = make(blocks, s, variables=JacVariables.of(humidity="ppmv", cloud="kg/kg", heights="hydrostatic"))
-    ov.step(s["z"], s["p"], x, torch.full((NPROF, M), 255.0))
+    ov.step(s["z"], s["p"], x, torch.full((NPROF, M), 255.0, dtype=torch.float64))
     c = st.calls[0]
     from mwr_fast_forward_operators_and_lbls_amd.autodiff import goff_gratch_es
     t, p = x[:, 0], s["p"]
@@ -148,7 +148,7 @@ def test_humidity_and_cloud_are_clamped_after_every_step(monkeypatch):
     s["xa"][1] = 0.01                                                    # a dry prior with a wide variance ...
     s["xa"][2] = 0.0
     ov = make(blocks, s)
-    y = torch.full((NPROF, M), 200.0)                                    # ... and observations far colder than it explains
+    y = torch.full((NPROF, M), 200.0, dtype=torch.float64)                                    # ... and observations far colder than it explains
     raw, _ = ov.step(s["z"], s["p"], torch.as_tensor(np.broadcast_to(s["xa"], (NPROF, 3, NLEV)).copy()), y)
     assert (raw[:, 1] < 0).any() and (raw[:, 2] < 0).any()               # step returns the raw update
     res = ov.retrieve(s["z"], s["p"], y, max_iter=3, tol=1e-9)

@@ -96,7 +96,7 @@ def test_without_an_instrument_the_seams_see_what_they_saw(monkeypatch):
     s = setup()
     ov = make(s)
     assert ov.instrument is None and ov.m == M
-    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0)
+    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0, dtype=torch.float64)
     x_new, d = ov.step(s["z"], s["p"], s["x_true"], y)
     tb, valid = ov.forward(s["z"], s["p"], s["x_true"])
     k_blocks, fx = ov._linearise(s["z"], s["p"], s["x_true"])
@@ -121,7 +121,7 @@ def test_with_an_instrument_the_update_sees_channel_rows(monkeypatch):
     inst = Instrument(FRQ, ELEV, beam=3.5, band=[0.23, 0.23, 2.0], n_beam=3, n_band=2)
     ov = make(s, instrument=inst)
     assert ov.m == inst.m_out == M and inst.m_in == 6 * 6
-    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0)
+    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0, dtype=torch.float64)
     x_new, d = ov.step(s["z"], s["p"], s["x_true"], y)
     # the K-matrix seam was asked for the quadrature grid, everything else as before
     args = st.k_calls[0]["args"]

@@ -182,7 +182,7 @@ def test_failed_and_unobserved_profiles(monkeypatch):
     NfCharStandins(monkeypatch)
     s = setup()
     ov = make(s, form="n")
-    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0)
+    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0, dtype=torch.float64)
     y[1] = float("nan")                                                  # nothing observed: the prior
     x = s["x_true"].clone()
     x[0, 1, 2] = float("nan")                                            # a state that is not finite

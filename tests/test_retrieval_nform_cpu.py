@@ -285,7 +285,7 @@ def test_constructor_and_call_refusals(monkeypatch):
     coarse = dict(kw, xa=torch.zeros((2, 43), dtype=torch.float64))      # a coarse full state is allowed
     assert retrieval.OneDVar("R24", FRQ, ELEV, torch.eye(86, dtype=torch.float64), torch.as_tensor(s["se"]), form="n", **coarse).form == "n"
     ov = make(s, form="n")
-    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0)
+    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0, dtype=torch.float64)
     with pytest.raises(ValueError) as ei:
         ov.characterise(s["z"], s["p"], s["x_true"], y)
     assert "form='m'" in str(ei.value) and "post_cov=True" in str(ei.value)

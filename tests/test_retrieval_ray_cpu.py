@@ -40,7 +40,7 @@ def test_ray_tracing_reaches_the_ray_seam_only(monkeypatch):
     st = RayStandins(monkeypatch)
     s = tri.setup()
     ov = tri.make(s, ray_tracing=True)
-    y = torch.full((tri.NPROF, tri.ELEV.size, tri.FRQ.size), 255.0)
+    y = torch.full((tri.NPROF, tri.ELEV.size, tri.FRQ.size), 255.0, dtype=torch.float64)
     ov.step(s["z"], s["p"], s["x_true"], y)
     ov.forward(s["z"], s["p"], s["x_true"])
     ov.retrieve(s["z"], s["p"], y, max_iter=2)
@@ -57,7 +57,7 @@ def test_the_default_never_reaches_the_ray_seam(monkeypatch):
     s = tri.setup()
     ov = tri.make(s)
     assert ov.ray_tracing is False
-    y = torch.full((tri.NPROF, tri.ELEV.size, tri.FRQ.size), 255.0)
+    y = torch.full((tri.NPROF, tri.ELEV.size, tri.FRQ.size), 255.0, dtype=torch.float64)
     ov.step(s["z"], s["p"], s["x_true"], y)
     ov.forward(s["z"], s["p"], s["x_true"])
     assert st.ray_calls == [] and len(st.k_calls) == 2
@@ -68,7 +68,7 @@ def test_with_an_instrument_the_ray_seam_is_asked_for_the_quadrature_grid(monkey
     s = tri.setup()
     inst = Instrument(tri.FRQ, tri.ELEV, beam=3.5, band=[0.23, 0.23, 2.0], n_beam=3, n_band=2)
     ov = tri.make(dict(s, se=s["se"][:inst.m_out]), instrument=inst, ray_tracing=True)
-    y = torch.full((tri.NPROF, inst.elev.size, inst.frq.size), 255.0)
+    y = torch.full((tri.NPROF, inst.elev.size, inst.frq.size), 255.0, dtype=torch.float64)
     ov.step(s["z"], s["p"], s["x_true"], y)
     assert st.k_calls == [] and len(st.ray_calls) == 1 and len(st.obs_calls) == 1
     args = st.ray_calls[0]["args"]

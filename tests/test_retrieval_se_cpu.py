@@ -151,7 +151,7 @@ def test_instrument_and_basis_reduce_then_project_then_whiten(monkeypatch):
     inst = Instrument(FRQ, ELEV, beam=3.5, band=[0.23, 0.23, 2.0], n_beam=3, n_band=2)
     sb = eofs(s)
     ov = make(s, instrument=inst, basis=sb)
-    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0)
+    y = torch.full((NPROF, ELEV.size, FRQ.size), 255.0, dtype=torch.float64)
     se_p = se_batch()
     ov.step(s["z"], s["p"], torch.zeros((NPROF, R), dtype=torch.float64), y, post_var=False, se=se_p)
     assert st.order == ["reduce", "project", "whiten"]
