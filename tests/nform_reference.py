@@ -8,7 +8,8 @@ It follows the header literally: dropped observation rows are DELETED, C = H + (
 
 Bars (derived, not measured):
   solve     Cholesky and its solves are backward stable: error <~ c n eps cond with c = 64, n <= 128 and cond <= COND_MAX on
-            the JACOBI-SCALED C (C_ij / sqrt(C_ii C_jj)): Cholesky's error bound is invariant under that scaling (the
+            the JACOBI-SCALED C (C_ij / sqrt(C_ii C_jj)): Cholesky's error bound is invariant under that scaling, and the
+            kernels keep their bits under a change of units (tests/test_oe_scaling.py) (the
             unscaled C reaches 4e6 at four blocks, whose units differ).  TOL = 64 * 128 * eps * 1e4 = 1.8e-8 in the units of
             ``solve_errors``: max |x_ref - xa| per block for x_new, max diag Sa per block for post_var, max |C^-1| for
             post_cov, max(1, |ref|) for dfs, max(1, d^T W d) for chi2 -- the scale at which its formula subtracts.
