@@ -289,7 +289,13 @@ int mwrt_tb_from_absorption_device(mwrt_context* ctx, const mwrt_model* model,
  *   mwrt_tb_from_layer_tau_device RTEquation.planck (from_sat = False) + bright [EXT]: TBs [nprof][nang][nf] from such
  *                                 an array (tau_pitch >= nf), T [nprof][nlev] and d_valid [nprof] (1 = integrate,
  *                                 anything else = that profile's TBs are NaN).  `model` supplies h, k, t_cosmic.
- * DEVICE buffers, asynchronous on `stream`. */
+ * DEVICE buffers, asynchronous on `stream`.
+ * Specified range of the two RTE entries (this one and mwrt_tb_from_absorption_device): every layer optical depth times
+ * every air mass FINITE and at most 1e6 in magnitude (beyond about 700 the layer's transmission is 0 and the path
+ * below it is all that is seen).  Within it the TBs are held to the 50-digit reference (tests/test_rte_columns.py); a
+ * NaN optical depth makes the TBs of its own (profile, frequency) NaN and touches nothing else.  An infinite optical
+ * depth, or a product beyond about 1e40, is outside it: the exponential's range reduction then yields NaN or inf instead
+ * of 0 -- confined to the outputs of that (profile, frequency), but not the opaque-layer answer. */
 int mwrt_layer_tau_pitch(int32_t nf);
 int mwrt_layer_tau_batch_device(mwrt_context* ctx, const mwrt_model* model,
                                 int64_t nprof, int32_t nlev,
