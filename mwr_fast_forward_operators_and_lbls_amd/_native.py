@@ -276,6 +276,14 @@ SIGNATURES = {
     "mwrt_last_kernel_ms": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double)]),
 }
 
+#: (record of include/mwrt.h, its ctypes structure, the file that declares it): ``<record>_size()`` must agree with each
+_RECORD_SIZES = (
+    ("mwrt_model_desc", MwrtModelDesc, "spectroscopy.py"), ("mwrt_oe_step", MwrtOeStep, "_native.py"),
+    ("mwrt_oe_lm", MwrtOeLm, "_native.py"), ("mwrt_oe_nform", MwrtOeNform, "_native.py"),
+    ("mwrt_oe_nform_char", MwrtOeNformChar, "_native.py"), ("mwrt_oe_char", MwrtOeChar, "_native.py"),
+    ("mwrt_obs_apply", MwrtObsApply, "_native.py"), ("mwrt_basis_apply", MwrtBasisApply, "_native.py"),
+    ("mwrt_obs_whiten", MwrtObsWhiten, "_native.py"))
+
 _lib = None
 _lib_lock = threading.Lock()
 _hip_runtime_path = None
@@ -322,24 +330,9 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
-        if lib.mwrt_model_desc_size() != ctypes.sizeof(MwrtModelDesc):
-            raise NativeLibraryMissing("mwrt_model_desc layout mismatch between libmwrt.so and spectroscopy.py")
-        if lib.mwrt_oe_step_size() != ctypes.sizeof(MwrtOeStep):
-            raise NativeLibraryMissing("mwrt_oe_step layout mismatch between libmwrt.so and _native.py")
-        if lib.mwrt_oe_lm_size() != ctypes.sizeof(MwrtOeLm):
-            raise NativeLibraryMissing("mwrt_oe_lm layout mismatch between libmwrt.so and _native.py")
-        if lib.mwrt_oe_nform_size() != ctypes.sizeof(MwrtOeNform):
-            raise NativeLibraryMissing("mwrt_oe_nform layout mismatch between libmwrt.so and _native.py")
-        if lib.mwrt_oe_nform_char_size() != ctypes.sizeof(MwrtOeNformChar):
-            raise NativeLibraryMissing("mwrt_oe_nform_char layout mismatch between libmwrt.so and _native.py")
-        if lib.mwrt_oe_char_size() != ctypes.sizeof(MwrtOeChar):
-            raise NativeLibraryMissing("mwrt_oe_char layout mismatch between libmwrt.so and _native.py")
-        if lib.mwrt_obs_apply_size() != ctypes.sizeof(MwrtObsApply):
-            raise NativeLibraryMissing("mwrt_obs_apply layout mismatch between libmwrt.so and _native.py")
-        if lib.mwrt_basis_apply_size() != ctypes.sizeof(MwrtBasisApply):
-            raise NativeLibraryMissing("mwrt_basis_apply layout mismatch between libmwrt.so and _native.py")
-        if lib.mwrt_obs_whiten_size() != ctypes.sizeof(MwrtObsWhiten):
-            raise NativeLibraryMissing("mwrt_obs_whiten layout mismatch between libmwrt.so and _native.py")
+        for name, struct, where in _RECORD_SIZES:
+            if getattr(lib, name + "_size")() != ctypes.sizeof(struct):
+                raise NativeLibraryMissing(f"{name} layout mismatch between libmwrt.so and {where}")
         if lib.mwrt_version() != MWRT_VERSION:
             raise NativeLibraryMissing(f"libmwrt.so is version {lib.mwrt_version()}, this binding needs {MWRT_VERSION}: "
                                        "rebuild (python -c 'import __graft_entry__ as g; g.build()')")
@@ -397,6 +390,22 @@ def _stream(stream):
         return None
     stream = int(stream)
     return ctypes.c_void_p(STREAM_LEGACY if stream == 0 else stream)
+
+
+def _record(cls, struct_size, ints, ptrs, **blocks):
+    """A record of the structure ``cls`` as every record entry is handed one: ``struct_size`` (None: the whole record), the
+    integer fields ``ints``, the device pointers ``ptrs`` (None: NULL) and, for each pointer array ``blocks`` names, its
+    first four entries.  Whatever is not named stays 0 / NULL."""
+    rec = cls()
+    rec.struct_size = ctypes.sizeof(cls) if struct_size is None else int(struct_size)
+    for name, v in ints.items():
+        setattr(rec, name, int(v or 0))
+    for name, v in ptrs.items():
+        setattr(rec, name, None if v is None else int(v))
+    for name, seq in blocks.items():
+        for b, k in enumerate(list(seq)[:4]):
+            getattr(rec, name)[b] = None if k is None else int(k)
+    return rec
 
 
 def _serialised(method):
@@ -725,28 +734,16 @@ class Context:
         1 .. 4 K-matrix blocks ``[nprof][m][nlev]`` (Jacobian outputs as they were written), the state, prior and
         covariances as the header lays them out; ``d_x_new [nprof][nblk][nlev]`` and ``d_status [nprof]`` (uint8) are
         required, the diagnostics optional.  ``struct_size`` (default: the whole record) is what the record claims."""
-        d_k = list(d_k)
-        rec = MwrtOeStep()
-        rec.struct_size = ctypes.sizeof(MwrtOeStep) if struct_size is None else int(struct_size)
-        rec.nblk, rec.xa_per_profile, rec.se_full, rec.reserved = len(d_k), int(bool(xa_per_profile)), int(bool(se_full)), int(reserved)
-        for b, k in enumerate(d_k[:4]):
-            rec.d_k[b] = int(k) if k is not None else None
-        opt = lambda v: int(v) if v is not None else None   # noqa: E731
-        rec.d_x, rec.d_xa, rec.d_sa, rec.d_se, rec.d_y, rec.d_fx = map(opt, (d_x, d_xa, d_sa, d_se, d_y, d_fx))
-        rec.d_x_new, rec.d_status = opt(d_x_new), opt(d_status)
-        rec.d_chi2, rec.d_dfs, rec.d_post_var, rec.d_nobs = map(opt, (d_chi2, d_dfs, d_post_var, d_nobs))
-        self._check(self._lib.mwrt_oe_step_device(self._handle, int(nprof), int(nlev), int(m), ctypes.byref(rec),
-                                                  _stream(stream)), "mwrt_oe_step_device")
+        self._oe(MwrtOeStep, "mwrt_oe_step_device", nprof, nlev, m, d_k, stream, struct_size,
+                 dict(xa_per_profile=bool(xa_per_profile), se_full=bool(se_full), reserved=reserved),
+                 dict(d_x=d_x, d_xa=d_xa, d_sa=d_sa, d_se=d_se, d_y=d_y, d_fx=d_fx, d_x_new=d_x_new, d_status=d_status,
+                      d_chi2=d_chi2, d_dfs=d_dfs, d_post_var=d_post_var, d_nobs=d_nobs))
 
-    def _oe_lm(self, entry, nprof, nlev, m, d_k, xa_per_profile, se_full, stream, reserved, struct_size, fields):
+    def _oe(self, cls, entry, nprof, nlev, m, d_k, stream, struct_size, ints, ptrs):
+        """The one call of the optimal-estimation entries: a record of ``cls`` (``_record``) with ``nblk = len(d_k)``, the
+        integer fields ``ints`` and the pointers ``ptrs``, handed to ``entry(ctx, nprof, nlev, m, record, stream)``."""
         d_k = list(d_k)
-        rec = MwrtOeLm()
-        rec.struct_size = ctypes.sizeof(MwrtOeLm) if struct_size is None else int(struct_size)
-        rec.nblk, rec.xa_per_profile, rec.se_full, rec.reserved = len(d_k), int(bool(xa_per_profile)), int(bool(se_full)), int(reserved)
-        for b, k in enumerate(d_k[:4]):
-            rec.d_k[b] = int(k) if k is not None else None
-        for name, v in fields.items():
-            setattr(rec, name, int(v) if v is not None else None)
+        rec = _record(cls, struct_size, dict(ints, nblk=len(d_k)), ptrs, d_k=d_k)
         self._check(getattr(self._lib, entry)(self._handle, int(nprof), int(nlev), int(m), ctypes.byref(rec), _stream(stream)),
                     entry)
 
@@ -757,9 +754,10 @@ class Context:
         """The linearisation at x (include/mwrt.h mwrt_oe_lm_prepare_device): the inputs of ``oe_step_device``; writes
         ``d_g0 [nprof][m (m + 1) / 2]``, ``d_r`` and ``d_kdx [nprof][m]``, ``d_keep [nprof][m]`` and ``d_lin_status [nprof]``
         (uint8).  A profile whose ``d_active`` flag (uint8, optional) is 0 is skipped."""
-        self._oe_lm("mwrt_oe_lm_prepare_device", nprof, nlev, m, d_k, xa_per_profile, se_full, stream, reserved, struct_size,
-                    dict(d_x=d_x, d_xa=d_xa, d_sa=d_sa, d_se=d_se, d_y=d_y, d_fx=d_fx, d_g0=d_g0, d_r=d_r, d_kdx=d_kdx,
-                         d_keep=d_keep, d_lin_status=d_lin_status, d_active=d_active))
+        self._oe(MwrtOeLm, "mwrt_oe_lm_prepare_device", nprof, nlev, m, d_k, stream, struct_size,
+                 dict(xa_per_profile=bool(xa_per_profile), se_full=bool(se_full), reserved=reserved),
+                 dict(d_x=d_x, d_xa=d_xa, d_sa=d_sa, d_se=d_se, d_y=d_y, d_fx=d_fx, d_g0=d_g0, d_r=d_r, d_kdx=d_kdx,
+                      d_keep=d_keep, d_lin_status=d_lin_status, d_active=d_active))
 
     @_serialised
     def oe_lm_solve_device(self, nprof, nlev, m, d_k, d_x, d_xa, d_sa, d_se, d_gamma, d_g0, d_r, d_kdx, d_keep,
@@ -767,10 +765,11 @@ class Context:
                            se_full=False, stream=None, reserved=0, struct_size=None):
         """One damped trial on a linearisation (include/mwrt.h mwrt_oe_lm_solve_device) with ``d_gamma [nprof]``:
         ``d_x_new [nprof][nblk][nlev]`` and ``d_status [nprof]`` (uint8) required, ``d_chi2`` and ``d_nobs`` optional."""
-        self._oe_lm("mwrt_oe_lm_solve_device", nprof, nlev, m, d_k, xa_per_profile, se_full, stream, reserved, struct_size,
-                    dict(d_x=d_x, d_xa=d_xa, d_sa=d_sa, d_se=d_se, d_gamma=d_gamma, d_g0=d_g0, d_r=d_r, d_kdx=d_kdx,
-                         d_keep=d_keep, d_lin_status=d_lin_status, d_x_new=d_x_new, d_status=d_status, d_chi2=d_chi2,
-                         d_nobs=d_nobs, d_active=d_active))
+        self._oe(MwrtOeLm, "mwrt_oe_lm_solve_device", nprof, nlev, m, d_k, stream, struct_size,
+                 dict(xa_per_profile=bool(xa_per_profile), se_full=bool(se_full), reserved=reserved),
+                 dict(d_x=d_x, d_xa=d_xa, d_sa=d_sa, d_se=d_se, d_gamma=d_gamma, d_g0=d_g0, d_r=d_r, d_kdx=d_kdx,
+                      d_keep=d_keep, d_lin_status=d_lin_status, d_x_new=d_x_new, d_status=d_status, d_chi2=d_chi2,
+                      d_nobs=d_nobs, d_active=d_active))
 
     @_serialised
     def oe_cost_device(self, nprof, nlev, m, nblk, d_x, d_xa, d_se, d_y, d_fx, d_keep, d_sa_inv, d_cost, d_cost_obs=None,
@@ -778,23 +777,10 @@ class Context:
                        reserved=0, struct_size=None):
         """J = r^T Se^-1 r over the rows ``d_keep`` names + (x - xa)^T Sa^-1 (x - xa) (include/mwrt.h mwrt_oe_cost_device);
         ``nblk`` is the number of state blocks (the call reads no K)."""
-        self._oe_lm("mwrt_oe_cost_device", nprof, nlev, m, [None] * int(nblk), xa_per_profile, se_full, stream, reserved,
-                    struct_size, dict(d_x=d_x, d_xa=d_xa, d_se=d_se, d_y=d_y, d_fx=d_fx, d_keep=d_keep, d_sa_inv=d_sa_inv,
-                                      d_cost=d_cost, d_cost_obs=d_cost_obs, d_cost_prior=d_cost_prior, d_status=d_status,
-                                      d_active=d_active))
-
-    def _oe_nform(self, entry, nprof, nlev, m, d_k, xa_per_profile, se_per_profile, stream, reserved, struct_size, fields):
-        d_k = list(d_k)
-        rec = MwrtOeNform()
-        rec.struct_size = ctypes.sizeof(MwrtOeNform) if struct_size is None else int(struct_size)
-        rec.nblk, rec.xa_per_profile, rec.se_per_profile, rec.reserved = (
-            len(d_k), int(bool(xa_per_profile)), int(bool(se_per_profile)), int(reserved))
-        for b, k in enumerate(d_k[:4]):
-            rec.d_k[b] = int(k) if k is not None else None
-        for name, v in fields.items():
-            setattr(rec, name, int(v) if v is not None else None)
-        self._check(getattr(self._lib, entry)(self._handle, int(nprof), int(nlev), int(m), ctypes.byref(rec), _stream(stream)),
-                    entry)
+        self._oe(MwrtOeLm, "mwrt_oe_cost_device", nprof, nlev, m, [None] * int(nblk), stream, struct_size,
+                 dict(xa_per_profile=bool(xa_per_profile), se_full=bool(se_full), reserved=reserved),
+                 dict(d_x=d_x, d_xa=d_xa, d_se=d_se, d_y=d_y, d_fx=d_fx, d_keep=d_keep, d_sa_inv=d_sa_inv, d_cost=d_cost,
+                      d_cost_obs=d_cost_obs, d_cost_prior=d_cost_prior, d_status=d_status, d_active=d_active))
 
     @_serialised
     def oe_nform_prepare_device(self, nprof, nlev, m, d_k, d_x, d_xa, d_se, d_y, d_fx, d_h, d_g, d_rwr, d_keep, d_nobs,
@@ -804,9 +790,10 @@ class Context:
         ``d_h [nprof][n (n + 1) / 2]`` (K^T W K packed), ``d_g [nprof][n]``, ``d_rwr [nprof]``, ``d_keep [nprof][m]`` (uint8),
         ``d_nobs [nprof]`` (int32) and ``d_lin_status [nprof]`` (uint8).  ``d_se`` holds variances, ``[m]`` or, with
         ``se_per_profile``, ``[nprof][m]``; m is not bounded, n = nblk nlev is (``OE_NFORM_MAX_N``)."""
-        self._oe_nform("mwrt_oe_nform_prepare_device", nprof, nlev, m, d_k, xa_per_profile, se_per_profile, stream, reserved,
-                       struct_size, dict(d_x=d_x, d_xa=d_xa, d_se=d_se, d_y=d_y, d_fx=d_fx, d_h=d_h, d_g=d_g, d_rwr=d_rwr,
-                                         d_keep=d_keep, d_nobs=d_nobs, d_lin_status=d_lin_status, d_active=d_active))
+        self._oe(MwrtOeNform, "mwrt_oe_nform_prepare_device", nprof, nlev, m, d_k, stream, struct_size,
+                 dict(xa_per_profile=bool(xa_per_profile), se_per_profile=bool(se_per_profile), reserved=reserved),
+                 dict(d_x=d_x, d_xa=d_xa, d_se=d_se, d_y=d_y, d_fx=d_fx, d_h=d_h, d_g=d_g, d_rwr=d_rwr, d_keep=d_keep,
+                      d_nobs=d_nobs, d_lin_status=d_lin_status, d_active=d_active))
 
     @_serialised
     def oe_nform_solve_device(self, nprof, nlev, m, nblk, d_x, d_xa, d_sa_inv, d_h, d_g, d_rwr, d_lin_status, d_x_new,
@@ -816,11 +803,11 @@ class Context:
         when it is given: ``d_x_new [nprof][nblk][nlev]`` and ``d_status [nprof]`` (uint8) required; ``d_chi2``, ``d_dfs``,
         ``d_post_var`` and ``d_post_cov [nprof][n][n]`` optional and defined without ``d_gamma`` only.  ``nblk`` is the number
         of state blocks (the call reads no K)."""
-        self._oe_nform("mwrt_oe_nform_solve_device", nprof, nlev, m, [None] * int(nblk), xa_per_profile, False, stream,
-                       reserved, struct_size,
-                       dict(d_x=d_x, d_xa=d_xa, d_sa_inv=d_sa_inv, d_h=d_h, d_g=d_g, d_rwr=d_rwr, d_lin_status=d_lin_status,
-                            d_x_new=d_x_new, d_status=d_status, d_gamma=d_gamma, d_chi2=d_chi2, d_dfs=d_dfs,
-                            d_post_var=d_post_var, d_post_cov=d_post_cov, d_active=d_active))
+        self._oe(MwrtOeNform, "mwrt_oe_nform_solve_device", nprof, nlev, m, [None] * int(nblk), stream, struct_size,
+                 dict(xa_per_profile=bool(xa_per_profile), reserved=reserved),
+                 dict(d_x=d_x, d_xa=d_xa, d_sa_inv=d_sa_inv, d_h=d_h, d_g=d_g, d_rwr=d_rwr, d_lin_status=d_lin_status,
+                      d_x_new=d_x_new, d_status=d_status, d_gamma=d_gamma, d_chi2=d_chi2, d_dfs=d_dfs, d_post_var=d_post_var,
+                      d_post_cov=d_post_cov, d_active=d_active))
 
     @_serialised
     def oe_nform_cost_device(self, nprof, nlev, m, nblk, d_x, d_xa, d_sa_inv, d_se, d_y, d_fx, d_keep, d_cost,
@@ -828,24 +815,10 @@ class Context:
                              se_per_profile=False, stream=None, reserved=0, struct_size=None):
         """J = sum over the rows ``d_keep`` names of (y - fx)^2 / se + (x - xa)^T Sa^-1 (x - xa) (include/mwrt.h
         mwrt_oe_nform_cost_device); ``nblk`` is the number of state blocks (the call reads no K)."""
-        self._oe_nform("mwrt_oe_nform_cost_device", nprof, nlev, m, [None] * int(nblk), xa_per_profile, se_per_profile,
-                       stream, reserved, struct_size,
-                       dict(d_x=d_x, d_xa=d_xa, d_sa_inv=d_sa_inv, d_se=d_se, d_y=d_y, d_fx=d_fx, d_keep=d_keep,
-                            d_cost=d_cost, d_cost_obs=d_cost_obs, d_cost_prior=d_cost_prior, d_status=d_status,
-                            d_active=d_active))
-
-    def _oe_nform_char(self, entry, nprof, nlev, m, d_k, se_per_profile, rows, stream, reserved, struct_size, fields):
-        d_k = list(d_k)
-        rec = MwrtOeNformChar()
-        rec.struct_size = ctypes.sizeof(MwrtOeNformChar) if struct_size is None else int(struct_size)
-        rec.nblk, rec.se_per_profile, rec.reserved = len(d_k), int(bool(se_per_profile)), int(reserved)
-        rec.row_begin, rec.row_count = int(rows[0]), int(rows[1])
-        for b, k in enumerate(d_k[:4]):
-            rec.d_k[b] = int(k) if k is not None else None
-        for name, v in fields.items():
-            setattr(rec, name, int(v) if v is not None else None)
-        self._check(getattr(self._lib, entry)(self._handle, int(nprof), int(nlev), int(m), ctypes.byref(rec), _stream(stream)),
-                    entry)
+        self._oe(MwrtOeNform, "mwrt_oe_nform_cost_device", nprof, nlev, m, [None] * int(nblk), stream, struct_size,
+                 dict(xa_per_profile=bool(xa_per_profile), se_per_profile=bool(se_per_profile), reserved=reserved),
+                 dict(d_x=d_x, d_xa=d_xa, d_sa_inv=d_sa_inv, d_se=d_se, d_y=d_y, d_fx=d_fx, d_keep=d_keep, d_cost=d_cost,
+                      d_cost_obs=d_cost_obs, d_cost_prior=d_cost_prior, d_status=d_status, d_active=d_active))
 
     @_serialised
     def oe_nform_char_device(self, nprof, nlev, m, nblk, d_sa_inv, d_h, d_lin_status, d_status, d_post_cov=None, d_avk=None,
@@ -857,11 +830,11 @@ class Context:
         row_begin + row_count - 1``; ``row_count=0`` with ``row_begin=0``: all n), ``d_avk_diag`` / ``d_noise_var`` /
         ``d_smooth_var [nprof][nblk][nlev]`` and ``d_dfs_block [nprof][nblk]``.  ``nblk`` is the number of state blocks (the
         call reads no K)."""
-        self._oe_nform_char("mwrt_oe_nform_char_device", nprof, nlev, m, [None] * int(nblk), False, (row_begin, row_count),
-                            stream, reserved, struct_size,
-                            dict(d_sa_inv=d_sa_inv, d_h=d_h, d_lin_status=d_lin_status, d_status=d_status, d_post_cov=d_post_cov,
-                                 d_avk=d_avk, d_avk_diag=d_avk_diag, d_dfs_block=d_dfs_block, d_noise_var=d_noise_var,
-                                 d_smooth_var=d_smooth_var, d_active=d_active))
+        self._oe(MwrtOeNformChar, "mwrt_oe_nform_char_device", nprof, nlev, m, [None] * int(nblk), stream, struct_size,
+                 dict(row_begin=row_begin, row_count=row_count, reserved=reserved),
+                 dict(d_sa_inv=d_sa_inv, d_h=d_h, d_lin_status=d_lin_status, d_status=d_status, d_post_cov=d_post_cov,
+                      d_avk=d_avk, d_avk_diag=d_avk_diag, d_dfs_block=d_dfs_block, d_noise_var=d_noise_var,
+                      d_smooth_var=d_smooth_var, d_active=d_active))
 
     @_serialised
     def oe_nform_gain_device(self, nprof, nlev, m, d_k, d_se, d_keep, d_post_cov, d_status, d_gain, d_active=None,
@@ -870,21 +843,9 @@ class Context:
         [nprof][m][n]``: row i is S^ k_i / se_i from the K blocks ``d_k``, the variances ``d_se`` (``[m]`` or, with
         ``se_per_profile``, ``[nprof][m]``) and ``d_keep`` as prepare saw and wrote them, and ``d_post_cov``, ``d_status`` as
         ``oe_nform_char_device`` (or ``oe_nform_solve_device`` without ``d_gamma``) wrote them."""
-        self._oe_nform_char("mwrt_oe_nform_gain_device", nprof, nlev, m, d_k, se_per_profile, (0, 0), stream, reserved,
-                            struct_size, dict(d_se=d_se, d_keep=d_keep, d_post_cov=d_post_cov, d_status=d_status,
-                                              d_gain=d_gain, d_active=d_active))
-
-    def _oe_char(self, entry, nprof, nlev, m, d_k, xa_per_profile, se_full, stream, reserved, struct_size, fields):
-        d_k = list(d_k)
-        rec = MwrtOeChar()
-        rec.struct_size = ctypes.sizeof(MwrtOeChar) if struct_size is None else int(struct_size)
-        rec.nblk, rec.xa_per_profile, rec.se_full, rec.reserved = len(d_k), int(bool(xa_per_profile)), int(bool(se_full)), int(reserved)
-        for b, k in enumerate(d_k[:4]):
-            rec.d_k[b] = int(k) if k is not None else None
-        for name, v in fields.items():
-            setattr(rec, name, int(v) if v is not None else (0 if name in ("product", "row_begin", "row_count", "reserved2") else None))
-        self._check(getattr(self._lib, entry)(self._handle, int(nprof), int(nlev), int(m), ctypes.byref(rec), _stream(stream)),
-                    entry)
+        self._oe(MwrtOeNformChar, "mwrt_oe_nform_gain_device", nprof, nlev, m, d_k, stream, struct_size,
+                 dict(se_per_profile=bool(se_per_profile), reserved=reserved),
+                 dict(d_se=d_se, d_keep=d_keep, d_post_cov=d_post_cov, d_status=d_status, d_gain=d_gain, d_active=d_active))
 
     @_serialised
     def oe_gain_device(self, nprof, nlev, m, d_k, d_x, d_xa, d_sa, d_se, d_y, d_fx, d_status, d_gain=None, d_ksa=None,
@@ -894,10 +855,11 @@ class Context:
         ``oe_step_device``; ``d_status [nprof]`` (uint8) required, and at least one of ``d_gain`` and ``d_ksa``
         ``[nprof][m][n]``, ``d_keep [nprof][m]`` (uint8), ``d_avk_diag`` / ``d_noise_var`` / ``d_smooth_var``
         ``[nprof][nblk][nlev]``, ``d_dfs_block [nprof][nblk]`` and ``d_nobs [nprof]`` (int32)."""
-        self._oe_char("mwrt_oe_gain_device", nprof, nlev, m, d_k, xa_per_profile, se_full, stream, reserved, struct_size,
-                      dict(d_x=d_x, d_xa=d_xa, d_sa=d_sa, d_se=d_se, d_y=d_y, d_fx=d_fx, d_status=d_status, d_gain=d_gain,
-                           d_ksa=d_ksa, d_keep=d_keep, d_avk_diag=d_avk_diag, d_dfs_block=d_dfs_block,
-                           d_noise_var=d_noise_var, d_smooth_var=d_smooth_var, d_nobs=d_nobs, reserved2=reserved2))
+        self._oe(MwrtOeChar, "mwrt_oe_gain_device", nprof, nlev, m, d_k, stream, struct_size,
+                 dict(xa_per_profile=bool(xa_per_profile), se_full=bool(se_full), reserved=reserved, reserved2=reserved2),
+                 dict(d_x=d_x, d_xa=d_xa, d_sa=d_sa, d_se=d_se, d_y=d_y, d_fx=d_fx, d_status=d_status, d_gain=d_gain,
+                      d_ksa=d_ksa, d_keep=d_keep, d_avk_diag=d_avk_diag, d_dfs_block=d_dfs_block, d_noise_var=d_noise_var,
+                      d_smooth_var=d_smooth_var, d_nobs=d_nobs))
 
     @_serialised
     def oe_product_device(self, nprof, nlev, m, product, d_gain, d_keep, d_out, d_k, d_ksa=None, d_sa=None, row_begin=0,
@@ -906,9 +868,9 @@ class Context:
         reads ``d_ksa`` and ``d_sa``; ``d_k`` then only tells the number of blocks and may hold None) from a gain entry's
         ``d_gain`` and ``d_keep`` (include/mwrt.h mwrt_oe_product_device), rows ``row_begin .. row_begin + row_count - 1``
         into ``d_out [nprof][row_count][n]``; ``row_count=0`` with ``row_begin=0`` is all n rows."""
-        self._oe_char("mwrt_oe_product_device", nprof, nlev, m, d_k, False, False, stream, reserved, struct_size,
-                      dict(d_gain=d_gain, d_keep=d_keep, d_out=d_out, d_ksa=d_ksa, d_sa=d_sa, product=product,
-                           row_begin=row_begin, row_count=row_count, reserved2=reserved2))
+        self._oe(MwrtOeChar, "mwrt_oe_product_device", nprof, nlev, m, d_k, stream, struct_size,
+                 dict(product=product, row_begin=row_begin, row_count=row_count, reserved=reserved, reserved2=reserved2),
+                 dict(d_gain=d_gain, d_keep=d_keep, d_out=d_out, d_ksa=d_ksa, d_sa=d_sa))
 
     @_serialised
     def obs_create(self, m_in, m_out, row_ptr, col, w) -> ctypes.c_void_p:
@@ -938,16 +900,9 @@ class Context:
         ``d_tb_out [nprof][m_out]`` (optional, as a pair) and, for each of up to four blocks, ``d_k_in[b]
         [nprof][m_in][nlev]`` -> ``d_k_out[b] [nprof][m_out][nlev]``.  ``nblk`` (default: ``len(d_k_in)``) and
         ``struct_size`` (default: the whole record) are what the record claims."""
-        d_k_in, d_k_out = list(d_k_in), list(d_k_out)
-        rec = MwrtObsApply()
-        rec.struct_size = ctypes.sizeof(MwrtObsApply) if struct_size is None else int(struct_size)
-        rec.nblk, rec.reserved = len(d_k_in) if nblk is None else int(nblk), int(reserved)
-        opt = lambda v: int(v) if v is not None else None   # noqa: E731
-        rec.d_tb_in, rec.d_tb_out = opt(d_tb_in), opt(d_tb_out)
-        for b, k in enumerate(d_k_in[:4]):
-            rec.d_k_in[b] = opt(k)
-        for b, k in enumerate(d_k_out[:4]):
-            rec.d_k_out[b] = opt(k)
+        d_k_in = list(d_k_in)
+        rec = _record(MwrtObsApply, struct_size, dict(nblk=len(d_k_in) if nblk is None else nblk, reserved=reserved),
+                      dict(d_tb_in=d_tb_in, d_tb_out=d_tb_out), d_k_in=d_k_in, d_k_out=d_k_out)
         self._check(self._lib.mwrt_obs_apply_device(self._handle, handle, int(nprof), int(nlev), ctypes.byref(rec),
                                                     _stream(stream)), "mwrt_obs_apply_device")
 
@@ -973,12 +928,8 @@ class Context:
     def basis_project_device(self, handle, nprof, m, d_k_in, d_k_out, stream=None, reserved=0, struct_size=None, reserved2=0):
         """K B (include/mwrt.h mwrt_basis_project_device): the blocks ``d_k_in[b] [nprof][m][nlev]`` of the basis' nblk ->
         ``d_k_out [nprof][m][r]``.  ``struct_size`` (default: the whole record) is what the record claims."""
-        rec = MwrtBasisApply()
-        rec.struct_size = ctypes.sizeof(MwrtBasisApply) if struct_size is None else int(struct_size)
-        rec.reserved, rec.reserved2 = int(reserved), int(reserved2)
-        for b, k in enumerate(list(d_k_in)[:4]):
-            rec.d_k_in[b] = int(k) if k is not None else None
-        rec.d_k_out = int(d_k_out) if d_k_out is not None else None
+        rec = _record(MwrtBasisApply, struct_size, dict(reserved=reserved, reserved2=reserved2), dict(d_k_out=d_k_out),
+                      d_k_in=d_k_in)
         self._check(self._lib.mwrt_basis_project_device(self._handle, handle, int(nprof), int(m), ctypes.byref(rec),
                                                         _stream(stream)), "mwrt_basis_project_device")
 
@@ -987,32 +938,20 @@ class Context:
                             struct_size=None, reserved2=0):
         """x_ref + B c (include/mwrt.h mwrt_basis_expand_device): ``d_c [nprof][r]`` and ``d_x_ref [n]`` (``[nprof][n]``
         with ``x_ref_per_profile``) -> ``d_x [nprof][n]``."""
-        rec = MwrtBasisApply()
-        rec.struct_size = ctypes.sizeof(MwrtBasisApply) if struct_size is None else int(struct_size)
-        rec.reserved, rec.reserved2 = int(reserved), int(reserved2)
-        opt = lambda v: int(v) if v is not None else None   # noqa: E731
-        rec.d_c, rec.d_x_ref, rec.d_x = opt(d_c), opt(d_x_ref), opt(d_x)
-        rec.x_ref_per_profile = int(bool(x_ref_per_profile))
+        rec = _record(MwrtBasisApply, struct_size,
+                      dict(reserved=reserved, reserved2=reserved2, x_ref_per_profile=bool(x_ref_per_profile)),
+                      dict(d_c=d_c, d_x_ref=d_x_ref, d_x=d_x))
         self._check(self._lib.mwrt_basis_expand_device(self._handle, handle, int(nprof), ctypes.byref(rec),
                                                        _stream(stream)), "mwrt_basis_expand_device")
 
     @staticmethod
     def _whiten_record(d_se, d_y, d_fx, d_k_in, d_l, d_keep, d_status, d_y_out, d_fx_out, d_k_out, se_full, mode, reserved,
                        struct_size, nblk):
-        d_k_in, d_k_out = list(d_k_in), list(d_k_out)
-        rec = MwrtObsWhiten()
-        rec.struct_size = ctypes.sizeof(MwrtObsWhiten) if struct_size is None else int(struct_size)
-        rec.nblk = len(d_k_in) if nblk is None else int(nblk)
-        rec.se_full, rec.mode, rec.reserved = int(bool(se_full)), int(mode), int(reserved)
-        opt = lambda v: int(v) if v is not None else None   # noqa: E731
-        rec.d_se, rec.d_y, rec.d_fx = opt(d_se), opt(d_y), opt(d_fx)
-        rec.d_l, rec.d_keep, rec.d_status = opt(d_l), opt(d_keep), opt(d_status)
-        rec.d_y_out, rec.d_fx_out = opt(d_y_out), opt(d_fx_out)
-        for b, k in enumerate(d_k_in[:4]):
-            rec.d_k_in[b] = opt(k)
-        for b, k in enumerate(d_k_out[:4]):
-            rec.d_k_out[b] = opt(k)
-        return rec
+        d_k_in = list(d_k_in)
+        return _record(MwrtObsWhiten, struct_size,
+                       dict(nblk=len(d_k_in) if nblk is None else nblk, se_full=bool(se_full), mode=mode, reserved=reserved),
+                       dict(d_se=d_se, d_y=d_y, d_fx=d_fx, d_l=d_l, d_keep=d_keep, d_status=d_status, d_y_out=d_y_out,
+                            d_fx_out=d_fx_out), d_k_in=d_k_in, d_k_out=d_k_out)
 
     @_serialised
     def obs_whiten_device(self, nprof, nlev, m, d_se, d_y, d_fx, d_k_in, d_l, d_keep, d_status, d_y_out=None, d_fx_out=None,

@@ -100,37 +100,34 @@ def _context(ref):
     return ctx
 
 
-def _native_k_matrix(model, z, p, t, rh, denliq, denice, frq, elev, variables, want, stream):
-    """One ``mwrt_tb_jacobian_batch_vars_device`` call -> (tb [nprof][nang][nf], valid, {block: K rows [nprof][nang][nf][nlev]}).
-
-    The single place the K-matrix of this module reaches the native library: CPU tests substitute a stand-in here."""
+def _k_matrix(entry, model, z, p, t, rh, denliq, denice, frq, elev, variables, want, stream):
+    """The body of the two K-matrix seams: one call of ``entry(context, ...)``, the context method either of them names."""
     nprof, nlev = z.shape
     opts = dict(dtype=torch.float64, device=z.device)
     tb = torch.empty((nprof, elev.size, frq.size), **opts)
     rows = {b: torch.empty((nprof, elev.size, frq.size, nlev), **opts) for b in want}
     valid = torch.empty(nprof, dtype=torch.uint8, device=z.device)
     ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
-    _context(z).tb_jacobian_batch_vars_device(
-        model, nprof, nlev, z.data_ptr(), p.data_ptr(), t.data_ptr(), rh.data_ptr(), frq, elev, tb.data_ptr(),
+    entry(
+        _context(z), model, nprof, nlev, z.data_ptr(), p.data_ptr(), t.data_ptr(), rh.data_ptr(), frq, elev, tb.data_ptr(),
         rows["t"].data_ptr(), rows["h"].data_ptr(), valid.data_ptr(), d_denliq=ptr(denliq), d_denice=ptr(denice),
         d_dtb_dliq=ptr(rows.get("liq")), d_dtb_dice=ptr(rows.get("ice")), variables=variables, stream=stream)
     return tb, valid, rows
+
+
+def _native_k_matrix(model, z, p, t, rh, denliq, denice, frq, elev, variables, want, stream):
+    """One ``mwrt_tb_jacobian_batch_vars_device`` call -> (tb [nprof][nang][nf], valid, {block: K rows [nprof][nang][nf][nlev]}).
+
+    The single place the K-matrix of this module reaches the native library: CPU tests substitute a stand-in here."""
+    entry = lambda ctx, *args, **kw: ctx.tb_jacobian_batch_vars_device(*args, **kw)   # noqa: E731
+    return _k_matrix(entry, model, z, p, t, rh, denliq, denice, frq, elev, variables, want, stream)
 
 
 def _native_k_matrix_ray(model, z, p, t, rh, denliq, denice, frq, elev, variables, want, stream):
     """One ``mwrt_tb_jacobian_batch_ray_device`` call: ``_native_k_matrix`` along refracted spherical ray paths, what
     ``OneDVar(..., ray_tracing=True)`` runs instead.  CPU tests substitute a stand-in here."""
-    nprof, nlev = z.shape
-    opts = dict(dtype=torch.float64, device=z.device)
-    tb = torch.empty((nprof, elev.size, frq.size), **opts)
-    rows = {b: torch.empty((nprof, elev.size, frq.size, nlev), **opts) for b in want}
-    valid = torch.empty(nprof, dtype=torch.uint8, device=z.device)
-    ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
-    _context(z).tb_jacobian_batch_ray_device(
-        model, nprof, nlev, z.data_ptr(), p.data_ptr(), t.data_ptr(), rh.data_ptr(), frq, elev, tb.data_ptr(),
-        rows["t"].data_ptr(), rows["h"].data_ptr(), valid.data_ptr(), d_denliq=ptr(denliq), d_denice=ptr(denice),
-        d_dtb_dliq=ptr(rows.get("liq")), d_dtb_dice=ptr(rows.get("ice")), variables=variables, stream=stream)
-    return tb, valid, rows
+    entry = lambda ctx, *args, **kw: ctx.tb_jacobian_batch_ray_device(*args, **kw)   # noqa: E731
+    return _k_matrix(entry, model, z, p, t, rh, denliq, denice, frq, elev, variables, want, stream)
 
 
 def _native_oe_step(k_blocks, x, xa, sa, se, y, fx, want_post_var, stream):
@@ -507,6 +504,100 @@ class Retrieval:
     coeff: Optional[torch.Tensor] = None   # [nprof][r] the retrieved coefficients (with a basis; x = clamp(xa + B coeff))
 
 
+class _MForm:
+    """What the m-form of the update does its own way (an m x m system per profile: ``mwrt_oe_step_device`` and the
+    ``mwrt_oe_lm_*`` split): how ``se=`` of a call is prepared, the buffers of a linearisation, prepare / cost / solve on
+    them, and the undamped update with its diagnostics.  ``OneDVar`` holds one of ``_MForm`` and ``_NForm`` as ``_form``;
+    everything around these five -- the step, the damped loop, the iteration -- is written once."""
+
+    def __init__(self, ov):
+        self.ov = ov
+
+    def se(self, se_p, k_blocks, y, fx, stream):
+        """``(k_blocks, y, fx, se, w)`` as the entries are given them: a per-profile Se is always pre-whitened."""
+        return self.ov._whiten(se_p, k_blocks, y, fx, stream)
+
+    @staticmethod
+    def lin(nprof, n, m, dev):
+        """The buffers of one linearisation (``mwrt_oe_lm_prepare_device`` writes them)."""
+        f64, u8 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.uint8, device=dev)
+        return dict(g0=torch.zeros((nprof, m * (m + 1) // 2), **f64), r=torch.zeros((nprof, m), **f64),
+                    kdx=torch.zeros((nprof, m), **f64), keep=torch.zeros((nprof, m), **u8), lin_status=torch.zeros(nprof, **u8))
+
+    def prepare(self, k_blocks, x, se, y, fx, lin, active, stream):
+        _native_oe_lm_prepare(k_blocks, x, self.ov._prior_mean, self.ov._prior_cov, se, y, fx, lin, active, stream)
+
+    def cost(self, x, se, y, fx, keep, cost, active, stream):
+        _native_oe_cost(x, self.ov._prior_mean, se, y, fx, keep, self.ov.sa_inv, cost, active, stream)
+
+    def solve(self, k_blocks, x, se, gamma, lin, out, active, stream):
+        _native_oe_lm_solve(k_blocks, x, self.ov._prior_mean, self.ov._prior_cov, se, gamma, lin, out, active, stream)
+
+    def update(self, k_blocks, u, se, y, fx, stream, post_var, post_cov=False, lin=None):
+        """The undamped step at the update's state ``u`` on what ``se`` returned -> dict(x_new, status, chi2, dfs, nobs,
+        post_var or None): one ``_native_oe_step`` call; with a basis ``post_var`` is ``_post_var_levels``.  ``post_cov``
+        and ``lin`` are the n-form's."""
+        ov = self.ov
+        out = _native_oe_step(k_blocks, u, ov._prior_mean, ov._prior_cov, se, y, fx, post_var and ov.basis is None, stream)
+        if post_var and ov.basis is not None:
+            out["post_var"] = ov._post_var_levels(k_blocks, u, y, fx, stream, se)
+        return out
+
+
+class _NForm(_MForm):
+    """The same five for the n-form (an n x n system per profile, any m; ``mwrt_oe_nform_*_device``)."""
+
+    def se(self, se_p, k_blocks, y, fx, stream):
+        """The constructor's variances ``[m]``; per-profile variances ``[nprof][m]`` as they are (the entries'
+        se_per_profile; nothing is whitened, w is None); a per-profile full covariance ``[nprof][m][m]`` through the
+        pre-whitening, then variances of 1."""
+        if se_p is not None and se_p.dim() == 2:
+            return k_blocks, y, fx, se_p, None
+        return self.ov._whiten(se_p, k_blocks, y, fx, stream)
+
+    @staticmethod
+    def lin(nprof, n, m, dev):
+        """The buffers of one n-form linearisation (``mwrt_oe_nform_prepare_device`` writes them)."""
+        f64, u8 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.uint8, device=dev)
+        return dict(h=torch.zeros((nprof, n * (n + 1) // 2), **f64), g=torch.zeros((nprof, n), **f64), rwr=torch.zeros(nprof, **f64),
+                    keep=torch.zeros((nprof, m), **u8), nobs=torch.zeros(nprof, dtype=torch.int32, device=dev),
+                    lin_status=torch.zeros(nprof, **u8))
+
+    def prepare(self, k_blocks, x, se, y, fx, lin, active, stream):
+        _native_oe_nform_prepare(k_blocks, x, self.ov._prior_mean, se, y, fx, lin, active, stream)
+
+    def cost(self, x, se, y, fx, keep, cost, active, stream):
+        _native_oe_nform_cost(x, self.ov._prior_mean, self.ov.sa_inv, se, y, fx, keep, cost, active, stream)
+
+    def solve(self, k_blocks, x, se, gamma, lin, out, active, stream):
+        _native_oe_nform_solve(x, self.ov._prior_mean, self.ov.sa_inv, lin, gamma, out, active, stream)
+
+    def update(self, k_blocks, u, se, y, fx, stream, post_var, post_cov=False, lin=None):
+        """The undamped n-form step at ``u``: one prepare (into ``lin``, all profiles) and one solve -> dict(x_new, status,
+        chi2, dfs, nobs, post_var or None[, post_cov [nprof][n][n]]).  With a basis ``post_var`` is the level-space
+        diag(B S^_c B^T) from the solve's C^-1 in one contraction."""
+        ov = self.ov
+        nprof, n = u.shape[0], u.shape[1] * u.shape[2]
+        lin = self.lin(nprof, n, y.shape[1], u.device) if lin is None else lin
+        self.prepare(k_blocks, u, se, y, fx, lin, None, stream)
+        f64 = dict(dtype=torch.float64, device=u.device)
+        out = dict(x_new=torch.empty_like(u), status=torch.empty(nprof, dtype=torch.uint8, device=u.device),
+                   chi2=torch.empty(nprof, **f64), dfs=torch.empty(nprof, **f64))
+        if post_var and ov.basis is None:
+            out["post_var"] = torch.empty_like(u)
+        if post_cov or (post_var and ov.basis is not None):
+            out["post_cov"] = torch.empty((nprof, n, n), **f64)
+        self.solve(k_blocks, u, se, None, lin, out, None, stream)
+        out["nobs"] = lin["nobs"]
+        if post_var and ov.basis is not None:
+            var = torch.einsum("kj,pji,ki->pk", ov._b, out["post_cov"], ov._b)
+            out["post_var"] = var.reshape((nprof,) + tuple(ov.xa.shape[-2:]))
+        out.setdefault("post_var", None)
+        if not post_cov:
+            out.pop("post_cov", None)
+        return out
+
+
 class OneDVar:
     def __init__(self, model, frq, elev, sa, se, variables: Optional[JacVariables] = None, blocks=("t", "h"), xa=None,
                  instrument=None, ray_tracing=False, basis: Optional[StateBasis] = None, form="m"):
@@ -560,6 +651,7 @@ class OneDVar:
             self._prior_cov = basis.sa_c.to(dev).contiguous()
             self._sigma = torch.sqrt(torch.diagonal(self._prior_cov)).reshape(1, -1)
         self._sa_inv = None
+        self._form = _NForm(self) if form == "n" else _MForm(self)
         if form == "n":
             # the n-form entries (include/mwrt.h mwrt_oe_nform_*_device): an n x n system per profile, any m, variances only
             size = n if basis is None else basis.r
@@ -722,132 +814,14 @@ class OneDVar:
         k = torch.cat([b.reshape(nprof, self.m, -1) for b in k_blocks], dim=2)
         return k @ self.basis.sa_res.to(k.device) @ k.transpose(1, 2)
 
-    def _post_var_levels(self, k_blocks, u, y, fx, stream, se=None):
+    def _post_var_levels(self, k_blocks, u, y, fx, stream, se):
         """diag(B S^_c B^T) ``[nprof][nblk][nlev]``: the posterior variance of the physical state from the posterior covariance
         of the coefficients (``mwrt_oe_gain_device`` + ``mwrt_oe_product_device``, [r][r] per profile) and one contraction."""
-        g = _native_oe_gain(k_blocks, u, self._prior_mean, self._prior_cov, self.se if se is None else se, y, fx, stream)
+        g = _native_oe_gain(k_blocks, u, self._prior_mean, self._prior_cov, se, y, fx, stream)
         s_c = _native_oe_product("post_cov", g["gain"], g["keep"], k_blocks, g["ksa"], self._prior_cov, (0, 0), stream)
         s_c = s_c.masked_fill(((g["status"] == 0) | (g["status"] == 2))[:, None, None], float("nan"))
         var = torch.einsum("kj,pji,ki->pk", self._b, s_c, self._b)
         return var.reshape((u.shape[0],) + tuple(self.xa.shape[-2:]))
-
-    # -- the n-form of the update (form="n") -----------------------------------------------------------------------------
-    def _nform_se(self, se_p, k_blocks, y, fx, stream):
-        """``(k_blocks, y, fx, se, w)`` as the n-form entries are given them: the constructor's variances ``[m]``; per-profile
-        variances ``[nprof][m]`` as they are (the entries' se_per_profile; nothing is whitened, w is None); a per-profile full
-        covariance ``[nprof][m][m]`` through ``_whiten``, then variances of 1."""
-        if se_p is not None and se_p.dim() == 2:
-            return k_blocks, y, fx, se_p, None
-        return self._whiten(se_p, k_blocks, y, fx, stream)
-
-    @staticmethod
-    def _nform_lin(nprof, n, m, dev):
-        """The buffers of one n-form linearisation (``mwrt_oe_nform_prepare_device`` writes them)."""
-        f64, u8 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.uint8, device=dev)
-        return dict(h=torch.zeros((nprof, n * (n + 1) // 2), **f64), g=torch.zeros((nprof, n), **f64), rwr=torch.zeros(nprof, **f64),
-                    keep=torch.zeros((nprof, m), **u8), nobs=torch.zeros(nprof, dtype=torch.int32, device=dev),
-                    lin_status=torch.zeros(nprof, **u8))
-
-    def _nform_update(self, k_blocks, u, se, y, fx, stream, post_var, post_cov, lin=None):
-        """The undamped n-form step at the update's state ``u`` on what ``_nform_se`` returned: one prepare (into ``lin``,
-        all profiles) and one solve -> dict(x_new, status, chi2, dfs, nobs, post_var or None[, post_cov [nprof][n][n]]).
-        With a basis ``post_var`` is the level-space diag(B S^_c B^T) from the solve's C^-1 in one contraction."""
-        nprof, n = u.shape[0], u.shape[1] * u.shape[2]
-        lin = self._nform_lin(nprof, n, y.shape[1], u.device) if lin is None else lin
-        _native_oe_nform_prepare(k_blocks, u, self._prior_mean, se, y, fx, lin, None, stream)
-        f64 = dict(dtype=torch.float64, device=u.device)
-        out = dict(x_new=torch.empty_like(u), status=torch.empty(nprof, dtype=torch.uint8, device=u.device),
-                   chi2=torch.empty(nprof, **f64), dfs=torch.empty(nprof, **f64))
-        if post_var and self.basis is None:
-            out["post_var"] = torch.empty_like(u)
-        if post_cov or (post_var and self.basis is not None):
-            out["post_cov"] = torch.empty((nprof, n, n), **f64)
-        _native_oe_nform_solve(u, self._prior_mean, self.sa_inv, lin, None, out, None, stream)
-        out["nobs"] = lin["nobs"]
-        if post_var and self.basis is not None:
-            var = torch.einsum("kj,pji,ki->pk", self._b, out["post_cov"], self._b)
-            out["post_var"] = var.reshape((nprof,) + tuple(self.xa.shape[-2:]))
-        out.setdefault("post_var", None)
-        if not post_cov:
-            out.pop("post_cov", None)
-        return out
-
-    def _step_nform(self, z, p, x, y, post_var, se, post_cov):
-        """``step`` with form="n": K-matrix call -> instrument -> basis -> prepare -> solve."""
-        stream = self._stream(x)
-        nprof = x.shape[0]
-        se_p = self._per_profile_se(se, nprof)
-        u = x.contiguous() if self.basis is None else x.reshape(nprof, 1, self.basis.r).contiguous()
-        tb, valid, k_blocks = self._observe(z, p, self._state(u))
-        fx = tb.reshape(nprof, self.m)
-        k_w, y_w, fx_w, se_w, w = self._nform_se(se_p, k_blocks, y.reshape(nprof, self.m).contiguous(), fx, stream)
-        out = self._fail_whitened(w, self._nform_update(k_w, u, se_w, y_w, fx_w, stream, post_var, post_cov))
-        out["fx"], out["valid"] = fx, valid
-        if w is not None:
-            out["whiten_status"] = w["status"]
-        return out.pop("x_new").reshape(x.shape), out
-
-    def _retrieve_lm_nform(self, z, p, y, x0, max_iter, tol, gamma0, up, down, gamma_max, se):
-        """``retrieve_lm`` with form="n": the same accept / reject logic on ``mwrt_oe_nform_prepare_device`` /
-        ``mwrt_oe_nform_solve_device`` (with gamma) / ``mwrt_oe_nform_cost_device``; the final diagnostics come from one
-        undamped solve on a linearisation of every profile at the final states."""
-        nprof, m = y.shape[0], self.m
-        se_p = self._per_profile_se(se, nprof)
-        se_w, w, y_w = self.se, None, None
-        x = self._start(x0, nprof).contiguous()
-        xa = self._prior_mean
-        dev, stream = x.device, self._stream(x)
-        yv = y.reshape(nprof, m).contiguous()
-        f64, u8 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.uint8, device=dev)
-        lin = self._nform_lin(nprof, x.shape[1] * x.shape[2], m, dev)
-        trial = dict(x_new=torch.zeros_like(x), status=torch.zeros(nprof, **u8))
-        cost = torch.full((nprof,), float("inf"), **f64)
-        cost_try = torch.full((nprof,), float("inf"), **f64)
-        gamma = torch.full((nprof,), float(gamma0), **f64)
-        active = torch.ones(nprof, dtype=torch.bool, device=dev)
-        stale = torch.ones(nprof, dtype=torch.bool, device=dev)          # the state changed since its linearisation
-        converged = torch.zeros(nprof, dtype=torch.bool, device=dev)
-        iters = torch.zeros(nprof, dtype=torch.int32, device=dev)
-        k_blocks = fx = None
-        relin = True
-        for _ in range(int(max_iter)):
-            if relin:
-                k_blocks, fx = self._linearise(z, p, x)
-                k_blocks, y_w, fx, se_w, w = self._nform_se(se_p, k_blocks, yv, fx, stream)
-                mask = (active & stale).to(torch.uint8)
-                _native_oe_nform_prepare(k_blocks, x, xa, se_w, y_w, fx, lin, mask, stream)
-                _native_oe_nform_cost(x, xa, self.sa_inv, se_w, y_w, fx, lin["keep"], cost, mask, stream)
-                stale = torch.zeros_like(stale)
-                active = active & (lin["lin_status"] == 1)
-            mask = active.to(torch.uint8)
-            _native_oe_nform_solve(x, xa, self.sa_inv, lin, gamma, trial, mask, stream)
-            ok = active & (trial["status"] == 1)
-            x_try = self._bound(torch.where(ok[:, None, None], trial["x_new"], x)).contiguous()
-            fx_try = self._observe(z, p, self._state(x_try), want_rows=False)[0].reshape(nprof, m)
-            if w is not None:
-                fx_try = _native_obs_whiten_apply(w["l"], w["keep"], 0, fx_try, None, stream)[0]
-            _native_oe_nform_cost(x_try, xa, self.sa_inv, se_w, y_w, fx_try, lin["keep"], cost_try, mask, stream)
-            accept = ok & (cost_try <= cost)
-            move = ((x_try - x).abs() / self._sigma).amax(dim=(1, 2))
-            iters = iters + active.to(torch.int32)
-            x = torch.where(accept[:, None, None], x_try, x).contiguous()
-            cost = torch.where(accept, cost_try, cost)
-            gamma = torch.where(accept, gamma / down, torch.where(active, gamma * up, gamma))
-            done = accept & (move < tol)
-            converged = converged | done
-            stale = stale | accept
-            active = active & ~done & ~(gamma > gamma_max)
-            flag = int((active.any().to(torch.int32) + 2 * stale.any().to(torch.int32)).item())
-            relin = bool(flag & 2)
-            if not flag & 1:
-                break
-        if relin:
-            k_blocks, fx = self._linearise(z, p, x)
-            k_blocks, y_w, fx, se_w, w = self._nform_se(se_p, k_blocks, yv, fx, stream)
-        d = self._fail_whitened(w, self._nform_update(k_blocks, x, se_w, y_w, fx, stream, True, False, lin=lin))
-        return Retrieval(x=self._state(x), chi2=d["chi2"], dfs=d["dfs"], post_var=d["post_var"], status=d["status"],
-                         nobs=d["nobs"], iterations=iters, converged=converged, cost=cost, gamma=gamma,
-                         **({} if self.basis is None else {"coeff": x.reshape(nprof, -1)}))
 
     # -- one Gauss-Newton step ---------------------------------------------------------------------------------------
     def _observe(self, z, p, x, want_rows=True, project=True):
@@ -861,12 +835,9 @@ class OneDVar:
         inst = self.instrument
         frq, elev = (self.frq, self.elev) if inst is None else (inst.frq_q, inst.elev_q)
         stream = self._stream(x)
-        if self.ray_tracing:
-            tb, valid, rows = _native_k_matrix_ray(self.model, zz.contiguous(), p.contiguous(), t, rh, dl, di, frq, elev,
-                                                   self.variables, self.blocks, stream)
-        else:
-            tb, valid, rows = _native_k_matrix(self.model, zz.contiguous(), p.contiguous(), t, rh, dl, di, frq, elev,
-                                               self.variables, self.blocks, stream)
+        k_matrix = _native_k_matrix_ray if self.ray_tracing else _native_k_matrix
+        tb, valid, rows = k_matrix(self.model, zz.contiguous(), p.contiguous(), t, rh, dl, di, frq, elev, self.variables,
+                                   self.blocks, stream)
         k_blocks = [rows[b] for b in self.blocks] if want_rows else None
         if inst is not None:
             tb, k_blocks = _native_obs_apply(inst, tb, k_blocks, stream)
@@ -913,35 +884,20 @@ class OneDVar:
         return self._step(z, p, x, y, post_var, se, post_cov)
 
     def _step(self, z, p, x, y, post_var=True, se=None, post_cov=False):
-        """``step`` on arguments ``_inputs`` has checked: what ``retrieve`` iterates."""
-        if self.form == "n":
-            return self._step_nform(z, p, x, y, post_var, se, post_cov)
+        """``step`` on arguments ``_inputs`` has checked, what ``retrieve`` iterates: K-matrix call -> instrument -> basis ->
+        the call's se -> the form's update."""
         stream = self._stream(x)
         nprof = x.shape[0]
         se_p = self._per_profile_se(se, nprof)
-        if self.basis is not None:
-            u = x.reshape(nprof, 1, self.basis.r).contiguous()
-            tb, valid, k_blocks = self._observe(z, p, self._state(u))
-            fx = tb.reshape(nprof, self.m)
-            yv = y.reshape(nprof, self.m).contiguous()
-            k_w, y_w, fx_w, se_w, w = self._whiten(se_p, k_blocks, yv, fx, stream)
-            out = _native_oe_step(k_w, u, self._prior_mean, self._prior_cov, se_w, y_w, fx_w, False, stream)
-            if post_var:
-                out["post_var"] = self._post_var_levels(k_w, u, y_w, fx_w, stream, se=se_w)
-            out = self._fail_whitened(w, out)
-            out["fx"], out["valid"] = fx, valid
-            if w is not None:
-                out["whiten_status"] = w["status"]
-            return out.pop("x_new").reshape(x.shape), out
-        tb, valid, k_blocks = self._observe(z, p, x)
+        u = x.contiguous() if self.basis is None else x.reshape(nprof, 1, self.basis.r).contiguous()
+        tb, valid, k_blocks = self._observe(z, p, self._state(u))
         fx = tb.reshape(nprof, self.m)
-        k_w, y_w, fx_w, se_w, w = self._whiten(se_p, k_blocks, y.reshape(nprof, self.m).contiguous(), fx, stream)
-        out = self._fail_whitened(w, _native_oe_step(k_w, x.contiguous(), self.xa, self.sa, se_w, y_w, fx_w, post_var, stream))
-        x_new = out.pop("x_new")
+        k_w, y_w, fx_w, se_w, w = self._form.se(se_p, k_blocks, y.reshape(nprof, self.m).contiguous(), fx, stream)
+        out = self._fail_whitened(w, self._form.update(k_w, u, se_w, y_w, fx_w, stream, post_var, post_cov))
         out["fx"], out["valid"] = fx, valid
         if w is not None:
             out["whiten_status"] = w["status"]
-        return x_new, out
+        return out.pop("x_new").reshape(x.shape), out
 
     def retrieve(self, z, p, y, x0=None, max_iter=10, tol=0.05, se=None) -> Retrieval:
         """Iterates ``step`` from ``x0`` (default: the prior).  After every step humidity and cloud are clamped to >= 0.  A
@@ -986,21 +942,43 @@ class OneDVar:
             active = active & ~done
             if not bool(active.any()):
                 break
-        if self.basis is not None and self.form == "n":                  # the level-space diagonal at the final states, too
+        if self.basis is None:
+            post_var = keep["post_var"]
+        elif self.form == "n":                                           # the level-space diagonal at the final states, too
             post_var = self._step(z, p, x, y, post_var=True, se=se_p)[1]["post_var"]
-            return Retrieval(x=self._state(x), chi2=keep["chi2"], dfs=keep["dfs"], post_var=post_var, status=keep["status"],
-                             nobs=keep["nobs"], iterations=iters, converged=converged, coeff=x.reshape(nprof, -1))
-        if self.basis is not None:
+        else:
             k_blocks, fx = self._linearise(z, p, x)
             k_w, y_w, fx_w, se_w, w = self._whiten(se_p, k_blocks, y.reshape(nprof, self.m).contiguous(), fx, self._stream(x))
-            post_var = self._post_var_levels(k_w, x.contiguous(), y_w, fx_w, self._stream(x), se=None if w is None else se_w)
+            post_var = self._post_var_levels(k_w, x.contiguous(), y_w, fx_w, self._stream(x), se_w)
             post_var = self._fail_whitened(w, dict(post_var=post_var))["post_var"]
-            return Retrieval(x=self._state(x), chi2=keep["chi2"], dfs=keep["dfs"], post_var=post_var, status=keep["status"],
-                             nobs=keep["nobs"], iterations=iters, converged=converged, coeff=x.reshape(nprof, -1))
-        return Retrieval(x=x, chi2=keep["chi2"], dfs=keep["dfs"], post_var=keep["post_var"], status=keep["status"],
-                         nobs=keep["nobs"], iterations=iters, converged=converged)
+        return Retrieval(x=self._state(x), chi2=keep["chi2"], dfs=keep["dfs"], post_var=post_var, status=keep["status"],
+                         nobs=keep["nobs"], iterations=iters, converged=converged,
+                         **({} if self.basis is None else {"coeff": x.reshape(nprof, -1)}))
 
     # -- what the step says about itself --------------------------------------------------------------------------------
+    @staticmethod
+    def _rows(rows, n):
+        """``rows=(begin, count)`` of a characterisation as the window the entries take; None is all n rows, (0, 0)."""
+        if rows is None:
+            return 0, 0
+        win = (int(rows[0]), int(rows[1]))
+        if win[0] < 0 or win[1] < 1 or win[0] + win[1] > n:
+            raise ValueError(f"rows: expected (begin, count) with count >= 1 inside 0 .. {n - 1}, got {rows}")
+        return win
+
+    def _linearised(self, z, p, x, y, rows, se):
+        """What both characterisations begin with: the checked arguments, the update's state u (``[nprof][1][r]`` with a
+        basis), the rows window, one linearisation at u and the call's se on it -> ``(u, win, k_blocks, y, fx, se, w,
+        stream)``, the middle five as the form's ``se`` returns them."""
+        z, p, x, y, _, se = self._inputs(z, p, x=x, y=y, se=se)
+        nprof = x.shape[0]
+        u = (x if self.basis is None else x.reshape(nprof, 1, self.basis.r)).contiguous()
+        win = self._rows(rows, u.shape[1] * u.shape[2])
+        stream = self._stream(u)
+        k_blocks, fx = self._linearise(z, p, u)
+        seen = self._form.se(self._per_profile_se(se, nprof), k_blocks, y.reshape(nprof, self.m).contiguous(), fx, stream)
+        return (u, win, *seen, stream)
+
     def characterise(self, z, p, x, y, avk=False, post_cov=False, rows=None, se=None) -> Characterisation:
         """The gain matrix, the averaging-kernel diagonal, the degrees of freedom per block and the split of the posterior
         variance into noise and smoothing error of the undamped step at ``x`` (e.g. ``Retrieval.x``): one K-matrix call at
@@ -1021,22 +999,8 @@ class OneDVar:
             raise ValueError("characterise is not offered with form='n': use characterise_nform there (or form='m') for the "
                              "gain matrix, the averaging kernel and the error budget, or step(..., post_cov=True) for the "
                              "posterior covariance")
-        z, p, x, y, _, se = self._inputs(z, p, x=x, y=y, se=se)
-        if self.basis is not None:
-            x = x.reshape(x.shape[0], 1, self.basis.r)
-        nprof, n = x.shape[0], x.shape[1] * x.shape[2]
-        if rows is None:
-            win = (0, 0)
-        else:
-            win = (int(rows[0]), int(rows[1]))
-            if win[0] < 0 or win[1] < 1 or win[0] + win[1] > n:
-                raise ValueError(f"rows: expected (begin, count) with count >= 1 inside 0 .. {n - 1}, got {rows}")
-        stream = self._stream(x)
-        k_blocks, fx = self._linearise(z, p, x)
-        k_blocks, y_w, fx, se_w, w = self._whiten(self._per_profile_se(se, nprof), k_blocks,
-                                                  y.reshape(nprof, self.m).contiguous(), fx, stream)
-        g = self._fail_whitened(w, _native_oe_gain(k_blocks, x.contiguous(), self._prior_mean, self._prior_cov, se_w, y_w, fx,
-                                                   stream))
+        u, win, k_blocks, y_w, fx, se_w, w, stream = self._linearised(z, p, x, y, rows, se)
+        g = self._fail_whitened(w, _native_oe_gain(k_blocks, u, self._prior_mean, self._prior_cov, se_w, y_w, fx, stream))
         failed = ((g["status"] == 0) | (g["status"] == 2))[:, None, None]
         prod = {}
         for name, want in (("avk", avk), ("post_cov", post_cov)):
@@ -1047,7 +1011,7 @@ class OneDVar:
             g["gain"] = _native_obs_whiten_apply(w["l"], w["keep"], 1, None, g["gain"], stream)[1]
         return Characterisation(gain=g["gain"], avk_diag=g["avk_diag"], dfs_block=g["dfs_block"], noise_var=g["noise_var"],
                                 smooth_var=g["smooth_var"], status=g["status"], nobs=g["nobs"], keep=g["keep"], **prod,
-                                **({} if self.basis is None else {"coeff": x.reshape(nprof, n)}))
+                                **({} if self.basis is None else {"coeff": u.reshape(u.shape[0], -1)}))
 
     def characterise_nform(self, z, p, x, y, gain=True, avk=False, post_cov=False, rows=None, se=None) -> Characterisation:
         """``characterise`` for ``form="n"``: the same fields for the undamped n-form step at ``x``, for any
@@ -1064,23 +1028,10 @@ class OneDVar:
         goes through the pre-whitening (m <= 140) and the gain is un-whitened afterwards, as in ``characterise``."""
         if self.form != "n":
             raise ValueError("characterise_nform needs form='n'; with form='m' characterise gives the same fields")
-        z, p, x, y, _, se = self._inputs(z, p, x=x, y=y, se=se)
-        if self.basis is not None:
-            x = x.reshape(x.shape[0], 1, self.basis.r)
-        nprof, nblk, n = x.shape[0], x.shape[1], x.shape[1] * x.shape[2]
-        if rows is None:
-            win = (0, 0)
-        else:
-            win = (int(rows[0]), int(rows[1]))
-            if win[0] < 0 or win[1] < 1 or win[0] + win[1] > n:
-                raise ValueError(f"rows: expected (begin, count) with count >= 1 inside 0 .. {n - 1}, got {rows}")
-        stream = self._stream(x)
-        u = x.contiguous()
-        k_blocks, fx = self._linearise(z, p, u)
-        k_blocks, y_w, fx, se_w, w = self._nform_se(self._per_profile_se(se, nprof), k_blocks,
-                                                    y.reshape(nprof, self.m).contiguous(), fx, stream)
-        lin = self._nform_lin(nprof, n, self.m, u.device)
-        _native_oe_nform_prepare(k_blocks, u, self._prior_mean, se_w, y_w, fx, lin, None, stream)
+        u, win, k_blocks, y_w, fx, se_w, w, stream = self._linearised(z, p, x, y, rows, se)
+        nprof, nblk, n = u.shape[0], u.shape[1], u.shape[1] * u.shape[2]
+        lin = self._form.lin(nprof, n, self.m, u.device)
+        self._form.prepare(k_blocks, u, se_w, y_w, fx, lin, None, stream)
         f64 = dict(dtype=torch.float64, device=u.device)
         out = dict(status=torch.empty(nprof, dtype=torch.uint8, device=u.device), avk_diag=torch.empty_like(u),
                    dfs_block=torch.empty((nprof, nblk), **f64), noise_var=torch.empty_like(u), smooth_var=torch.empty_like(u))
@@ -1098,7 +1049,7 @@ class OneDVar:
         out = self._fail_whitened(w, out)
         if w is not None and gain:                          # after everything else: the gain back to d x^ / d y
             out["gain"] = _native_obs_whiten_apply(w["l"], w["keep"], 1, None, out["gain"], stream)[1]
-        return Characterisation(**out, **({} if self.basis is None else {"coeff": x.reshape(nprof, n)}))
+        return Characterisation(**out, **({} if self.basis is None else {"coeff": u.reshape(nprof, n)}))
 
     # -- the damped iteration ------------------------------------------------------------------------------------------
     def _linearise(self, z, p, x):
@@ -1136,18 +1087,15 @@ class OneDVar:
         ``mwrt_oe_nform_cost_device`` (any m; one n x n solve per trial), and the final diagnostics come from one undamped
         solve at the final states."""
         z, p, _, y, x0, se = self._inputs(z, p, y=y, x0=x0, se=se)
-        if self.form == "n":
-            return self._retrieve_lm_nform(z, p, y, x0, max_iter, tol, gamma0, up, down, gamma_max, se)
+        form = self._form
         nprof, m = y.shape[0], self.m
         se_p = self._per_profile_se(se, nprof)
         se_w, w, y_w = self.se, None, None
         x = self._start(x0, nprof).contiguous()
-        xa, sa = self._prior_mean, self._prior_cov
         dev, stream = x.device, self._stream(x)
         yv = y.reshape(nprof, m).contiguous()
         f64, u8 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.uint8, device=dev)
-        lin = dict(g0=torch.zeros((nprof, m * (m + 1) // 2), **f64), r=torch.zeros((nprof, m), **f64),
-                   kdx=torch.zeros((nprof, m), **f64), keep=torch.zeros((nprof, m), **u8), lin_status=torch.zeros(nprof, **u8))
+        lin = form.lin(nprof, x.shape[1] * x.shape[2], m, dev)
         trial = dict(x_new=torch.zeros_like(x), status=torch.zeros(nprof, **u8))
         cost = torch.full((nprof,), float("inf"), **f64)
         cost_try = torch.full((nprof,), float("inf"), **f64)
@@ -1161,20 +1109,20 @@ class OneDVar:
         for _ in range(int(max_iter)):
             if relin:
                 k_blocks, fx = self._linearise(z, p, x)
-                k_blocks, y_w, fx, se_w, w = self._whiten(se_p, k_blocks, yv, fx, stream)
+                k_blocks, y_w, fx, se_w, w = form.se(se_p, k_blocks, yv, fx, stream)
                 mask = (active & stale).to(torch.uint8)
-                _native_oe_lm_prepare(k_blocks, x, xa, sa, se_w, y_w, fx, lin, mask, stream)
-                _native_oe_cost(x, xa, se_w, y_w, fx, lin["keep"], self.sa_inv, cost, mask, stream)
+                form.prepare(k_blocks, x, se_w, y_w, fx, lin, mask, stream)
+                form.cost(x, se_w, y_w, fx, lin["keep"], cost, mask, stream)
                 stale = torch.zeros_like(stale)
                 active = active & (lin["lin_status"] == 1)
             mask = active.to(torch.uint8)
-            _native_oe_lm_solve(k_blocks, x, xa, sa, se_w, gamma, lin, trial, mask, stream)
+            form.solve(k_blocks, x, se_w, gamma, lin, trial, mask, stream)
             ok = active & (trial["status"] == 1)
             x_try = self._bound(torch.where(ok[:, None, None], trial["x_new"], x)).contiguous()
             fx_try = self._observe(z, p, self._state(x_try), want_rows=False)[0].reshape(nprof, m)
             if w is not None:
                 fx_try = _native_obs_whiten_apply(w["l"], w["keep"], 0, fx_try, None, stream)[0]
-            _native_oe_cost(x_try, xa, se_w, y_w, fx_try, lin["keep"], self.sa_inv, cost_try, mask, stream)
+            form.cost(x_try, se_w, y_w, fx_try, lin["keep"], cost_try, mask, stream)
             accept = ok & (cost_try <= cost)
             move = ((x_try - x).abs() / self._sigma).amax(dim=(1, 2))
             iters = iters + active.to(torch.int32)
@@ -1191,14 +1139,8 @@ class OneDVar:
                 break
         if relin:
             k_blocks, fx = self._linearise(z, p, x)
-            k_blocks, y_w, fx, se_w, w = self._whiten(se_p, k_blocks, yv, fx, stream)
-        d = _native_oe_step(k_blocks, x, xa, sa, se_w, y_w, fx, self.basis is None, stream)
-        if self.basis is not None:
-            d["post_var"] = self._post_var_levels(k_blocks, x, y_w, fx, stream, se=None if w is None else se_w)
-        d = self._fail_whitened(w, d)
-        if self.basis is not None:
-            return Retrieval(x=self._state(x), chi2=d["chi2"], dfs=d["dfs"],
-                             post_var=d["post_var"], status=d["status"], nobs=d["nobs"],
-                             iterations=iters, converged=converged, cost=cost, gamma=gamma, coeff=x.reshape(nprof, -1))
-        return Retrieval(x=x, chi2=d["chi2"], dfs=d["dfs"], post_var=d["post_var"], status=d["status"], nobs=d["nobs"],
-                         iterations=iters, converged=converged, cost=cost, gamma=gamma)
+            k_blocks, y_w, fx, se_w, w = form.se(se_p, k_blocks, yv, fx, stream)
+        d = self._fail_whitened(w, form.update(k_blocks, x, se_w, y_w, fx, stream, True, lin=lin))
+        return Retrieval(x=self._state(x), chi2=d["chi2"], dfs=d["dfs"], post_var=d["post_var"], status=d["status"],
+                         nobs=d["nobs"], iterations=iters, converged=converged, cost=cost, gamma=gamma,
+                         **({} if self.basis is None else {"coeff": x.reshape(nprof, -1)}))
