@@ -979,6 +979,65 @@ int mwrt_oe_nform_gain_device(mwrt_context* ctx, int64_t nprof, int32_t nlev, in
 /* sizeof(mwrt_oe_nform_char) as compiled into the library (binding self-check). */
 size_t mwrt_oe_nform_char_size(void);
 
+/* Observation selection by information content (Rodgers 2000, section 2.5 and ch. 3; the sequential
+ * channel selection of Rabier et al. 2002): which observations of a scan carry the information.  Per profile, with the
+ * rows k_i [n] of [K0 | K1 | ...] (n = nblk * nlev), the variances se_i, a start covariance S0 [n][n] (Sa, the sa_c of a
+ * basis, or the posterior of an earlier selection) and a candidate set:
+ *     q_i = k_i^T S0 k_i / se_i                         the SNR^2 of observation i in the metric of the current posterior
+ *   round t = 0 .. nsel - 1:
+ *     j = argmax of q_i over the unchosen candidates; ties go to the LOWEST index; stop when the best q is not > 0
+ *     v = S k_j;  d = se_j + k_j^T v;  order[t] = j;  q_pick[t] = q_j;  rank[j] = t
+ *     dfs_gain[t] = v^T Sa^-1 v / d                     only when d_sa_inv and d_dfs_gain are given
+ *     S <- S - v v^T / d                                the posterior after assimilating j
+ *     q_i <- max(0, q_i - k_i^T v squared / (d se_i))   for every unchosen candidate, one pass over K
+ * The largest q is the largest entropy reduction log2(1 + q) / 2; the bits are formed by the caller from q_pick.  The
+ * incremental form of q is the specified one (m n per round instead of m n^2); by Cauchy-Schwarz in the metric of S the
+ * term taken off never exceeds q_i.  Row i is a candidate when every element of k_i and se_i is finite, its d_keep flag is
+ * 1 and its d_candidate flag is 1 (an absent flag array counts as all 1).  The select comes after the load: a row that is
+ * no candidate may hold NaN.  The record (all DEVICE pointers, float64 unless stated):
+ *   d_k[b]       [nprof][m][nlev], b < nblk   as for mwrt_oe_nform
+ *   d_s0         [n][n], or [nprof][n][n] with s0_per_profile != 0: SYMMETRIC (the lower triangle is the one used)
+ *   d_se         [m], or [nprof][m] with se_per_profile != 0: VARIANCES
+ *   d_sa_inv     [n][n], optional        Sa^-1, SYMMETRIC; read only together with d_dfs_gain
+ *   d_keep       [nprof][m] uint8, optional;   d_candidate [m] uint8, optional;   d_active [nprof] uint8, optional: a
+ *                profile whose flag is 0 is skipped and NONE of its outputs is touched
+ * Outputs, required: d_order [nprof][nsel] int32 and d_q_pick [nprof][nsel] (unused slots, when fewer than nsel rows are
+ *   picked: -1 and 0.0); d_rank [nprof][m] int32 (-1 for a row not chosen); d_q [nprof][m], also the kernel's work vector:
+ *   at the end what each unchosen candidate would still add, its q_pick for a chosen row, exact 0.0 for a row that is no
+ *   candidate; d_count [nprof] int32, the picks made; d_status [nprof] uint8.  Optional: d_dfs_gain [nprof][nsel] (unused
+ *   slots 0.0), d_post_cov [nprof][n][n] the last S, full and symmetric, d_post_var [nprof][nblk][nlev] its diagonal.
+ *   status: 1 ok;  0 S0 (or Sa^-1 when read) is not finite: every floating-point output of the profile is NaN, order and
+ *   rank are -1, count is 0;  2 a candidate's variance is <= 0, or some d is not > 0 or not finite: the same outputs as 0;
+ *   3 no candidate: count is 0, order is -1, post_cov is S0 exactly and post_var its diagonal.
+ * Determinism: a profile's outputs depend on neither its batch-mates nor nprof, nor on which optional outputs are asked
+ *   for.  Every sum has one fixed order; no atomics, no matrix instructions.  Two bit-identical rows with
+ *   bit-identical variances have bit-identical q in every round, whatever their indices, which is what makes the
+ *   lowest-index rule observable.  No workspace: the call never allocates and never synchronises; a launch above 64 KiB of
+ *   dynamic LDS (from n = 125 on) raises the kernel's limit once per device and size, so the entry is hipGraph-capturable
+ *   after one warm-up call.  K is read nsel + 1 times.
+ * Refused, checked in this order, nothing written.  MWRT_ERR_INVALID_ARGUMENT: a NULL context or record; struct_size
+ *   smaller than the fixed part (24 bytes); nprof < 0, nlev < 1 or m < 1; nblk outside 1 .. 4; reserved != 0; nsel < 1 or
+ *   nsel > m; a NULL pointer among those required (the first nblk of d_k, d_s0, d_se, d_order, d_q_pick, d_rank, d_q,
+ *   d_count, d_status); d_dfs_gain without d_sa_inv; an output pointer equal to an input.  MWRT_ERR_UNSUPPORTED: n = nblk *
+ *   nlev > MWRT_OE_NFORM_MAX_N, with the limit in the text; more than 2^31 - 1 profiles.  nprof = 0 is MWRT_OK and launches
+ *   nothing.  m is not bounded.  The record starts with its own size: fields at or beyond struct_size (and a field it ends
+ *   inside) are taken as NULL / 0.  Accuracy and timing: DESIGN.md 4.12.
+ *   (MWRT_VERSION stays 301: additions.) */
+typedef struct mwrt_oe_select {
+  uint32_t struct_size;        /* sizeof(mwrt_oe_select) of the caller; fields beyond it are not read */
+  int32_t  nblk, se_per_profile, s0_per_profile, nsel, reserved;
+  const double* d_k[4];
+  const double *d_s0, *d_se, *d_sa_inv;
+  const uint8_t *d_keep, *d_candidate, *d_active;
+  int32_t* d_order;  double* d_q_pick;                 /* [nprof][nsel], required */
+  int32_t* d_rank;   double* d_q;                      /* [nprof][m], required */
+  int32_t* d_count;  uint8_t* d_status;                /* [nprof], required */
+  double *d_dfs_gain, *d_post_cov, *d_post_var;        /* optional */
+} mwrt_oe_select;
+int mwrt_oe_select_device(mwrt_context* ctx, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_select* s, void* stream);
+/* sizeof(mwrt_oe_select) as compiled into the library (binding self-check). */
+size_t mwrt_oe_select_size(void);
+
 /* The spectroscopic-parameter Jacobian: d TB / d b for entries b of the model's tables -- what the
  * forward-model part K_b S_b K_b^T of an observation-error covariance is built from (Rodgers 2000, section 3.2.2).  The
  * operator is mwrt_tb_jacobian_batch_device's: clear sky, plane-parallel, every line at every frequency; there is no

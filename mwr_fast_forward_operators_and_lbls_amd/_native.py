@@ -97,6 +97,16 @@ class MwrtOeNformChar(ctypes.Structure):
             "d_noise_var", "d_smooth_var", "d_dfs_block", "d_gain")]
 
 
+class MwrtOeSelect(ctypes.Structure):
+    """include/mwrt.h mwrt_oe_select: the record of the observation selection (device pointers)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("nblk", ctypes.c_int32), ("se_per_profile", ctypes.c_int32),
+                ("s0_per_profile", ctypes.c_int32), ("nsel", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("d_k", ctypes.c_void_p * 4)] + [
+        (name, ctypes.c_void_p) for name in (
+            "d_s0", "d_se", "d_sa_inv", "d_keep", "d_candidate", "d_active", "d_order", "d_q_pick", "d_rank", "d_q", "d_count",
+            "d_status", "d_dfs_gain", "d_post_cov", "d_post_var")]
+
+
 class MwrtOeChar(ctypes.Structure):
     """include/mwrt.h mwrt_oe_char: the record of the gain and product entries (device pointers)."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("nblk", ctypes.c_int32), ("xa_per_profile", ctypes.c_int32),
@@ -251,6 +261,8 @@ SIGNATURES = {
     "mwrt_oe_nform_char_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeNformChar), _vp]),
     "mwrt_oe_nform_gain_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeNformChar), _vp]),
     "mwrt_oe_nform_char_size": (ctypes.c_size_t, []),
+    "mwrt_oe_select_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeSelect), _vp]),
+    "mwrt_oe_select_size": (ctypes.c_size_t, []),
     "mwrt_oe_gain_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeChar), _vp]),
     "mwrt_oe_product_device": (ctypes.c_int, [_vp, _i64, _i32, _i32, ctypes.POINTER(MwrtOeChar), _vp]),
     "mwrt_oe_char_size": (ctypes.c_size_t, []),
@@ -280,7 +292,8 @@ SIGNATURES = {
 _RECORD_SIZES = (
     ("mwrt_model_desc", MwrtModelDesc, "spectroscopy.py"), ("mwrt_oe_step", MwrtOeStep, "_native.py"),
     ("mwrt_oe_lm", MwrtOeLm, "_native.py"), ("mwrt_oe_nform", MwrtOeNform, "_native.py"),
-    ("mwrt_oe_nform_char", MwrtOeNformChar, "_native.py"), ("mwrt_oe_char", MwrtOeChar, "_native.py"),
+    ("mwrt_oe_nform_char", MwrtOeNformChar, "_native.py"), ("mwrt_oe_select", MwrtOeSelect, "_native.py"),
+    ("mwrt_oe_char", MwrtOeChar, "_native.py"),
     ("mwrt_obs_apply", MwrtObsApply, "_native.py"), ("mwrt_basis_apply", MwrtBasisApply, "_native.py"),
     ("mwrt_obs_whiten", MwrtObsWhiten, "_native.py"))
 
@@ -846,6 +859,24 @@ class Context:
         self._oe(MwrtOeNformChar, "mwrt_oe_nform_gain_device", nprof, nlev, m, d_k, stream, struct_size,
                  dict(se_per_profile=bool(se_per_profile), reserved=reserved),
                  dict(d_se=d_se, d_keep=d_keep, d_post_cov=d_post_cov, d_status=d_status, d_gain=d_gain, d_active=d_active))
+
+    @_serialised
+    def oe_select_device(self, nprof, nlev, m, d_k, d_s0, d_se, nsel, d_order, d_q_pick, d_rank, d_q, d_count, d_status,
+                         d_sa_inv=None, d_keep=None, d_candidate=None, d_active=None, d_dfs_gain=None, d_post_cov=None,
+                         d_post_var=None, se_per_profile=False, s0_per_profile=False, stream=None, reserved=0,
+                         struct_size=None):
+        """Observation selection by information content (include/mwrt.h mwrt_oe_select_device): the greedy order of the
+        ``nsel`` rows of the K blocks ``d_k`` that reduce the entropy of ``d_s0`` (``[n][n]`` or, with ``s0_per_profile``,
+        ``[nprof][n][n]``) most, under the variances ``d_se`` (``[m]`` or, with ``se_per_profile``, ``[nprof][m]``).  Writes
+        ``d_order`` (int32) and ``d_q_pick [nprof][nsel]``, ``d_rank`` (int32) and ``d_q [nprof][m]``, ``d_count`` (int32)
+        and ``d_status [nprof]`` (uint8); optional ``d_dfs_gain [nprof][nsel]`` (needs ``d_sa_inv [n][n]``), ``d_post_cov
+        [nprof][n][n]`` and ``d_post_var [nprof][nblk][nlev]``.  ``d_keep [nprof][m]``, ``d_candidate [m]`` and ``d_active
+        [nprof]`` (uint8) narrow the candidates and the batch."""
+        self._oe(MwrtOeSelect, "mwrt_oe_select_device", nprof, nlev, m, d_k, stream, struct_size,
+                 dict(se_per_profile=bool(se_per_profile), s0_per_profile=bool(s0_per_profile), nsel=nsel, reserved=reserved),
+                 dict(d_s0=d_s0, d_se=d_se, d_sa_inv=d_sa_inv, d_keep=d_keep, d_candidate=d_candidate, d_active=d_active,
+                      d_order=d_order, d_q_pick=d_q_pick, d_rank=d_rank, d_q=d_q, d_count=d_count, d_status=d_status,
+                      d_dfs_gain=d_dfs_gain, d_post_cov=d_post_cov, d_post_var=d_post_var))
 
     @_serialised
     def oe_gain_device(self, nprof, nlev, m, d_k, d_x, d_xa, d_sa, d_se, d_y, d_fx, d_status, d_gain=None, d_ksa=None,

@@ -28,6 +28,7 @@ BASIS = os.path.join(CSRC, "mwrt_basis.hip")
 WHITEN = os.path.join(CSRC, "mwrt_whiten.hip")
 NFORM = os.path.join(CSRC, "mwrt_nform.hip")
 NFORM_CHAR = os.path.join(CSRC, "mwrt_nform_char.hip")
+SELECT = os.path.join(CSRC, "mwrt_select.hip")
 AUX = os.path.join(CSRC, "mwrt_aux.hip")
 PLAN = os.path.join(CSRC, "mwrt_plan.cpp")
 RETRIEVAL = os.path.join(CSRC, "mwrt_retrieval.hip")
@@ -35,7 +36,7 @@ RECORDS = os.path.join(CSRC, "mwrt_records.cpp")
 INST_WIDTHS = (8, 14, 16)
 #: the translation units of the library: (source, extra defines)
 UNITS = [(SRC, []), (RETRIEVAL, [])] + [(INST, [f"-DMWRT_INST_NFC={n}"]) for n in INST_WIDTHS] + [
-    (unit, []) for unit in (TL, RAY, PAR, OE, OE_LM, OE_CHAR, OBS, BASIS, WHITEN, NFORM, NFORM_CHAR, AUX, PLAN, RECORDS)]
+    (unit, []) for unit in (TL, RAY, PAR, OE, OE_LM, OE_CHAR, OBS, BASIS, WHITEN, NFORM, NFORM_CHAR, SELECT, AUX, PLAN, RECORDS)]
 #: the units that hold the C entry points: host code only
 HOST_UNITS = (SRC, RETRIEVAL)
 MAX_COMPILE_WORKERS = 16

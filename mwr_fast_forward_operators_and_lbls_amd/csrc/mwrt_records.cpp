@@ -40,10 +40,14 @@ constexpr Record OE_NFORM{"mwrt_oe_nform", sizeof(mwrt_oe_nform), offsetof(mwrt_
 // struct_size and five int32, then pointers to the end
 constexpr Record OE_NFORM_CHAR{"mwrt_oe_nform_char", sizeof(mwrt_oe_nform_char), offsetof(mwrt_oe_nform_char, d_k), FIXED_PART,
                                {{0, I32, 6}, {offsetof(mwrt_oe_nform_char, d_k), PTR, 18}}};
+// struct_size and five int32, then pointers to the end, as mwrt_oe_nform_char
+constexpr Record OE_SELECT{"mwrt_oe_select", sizeof(mwrt_oe_select), offsetof(mwrt_oe_select, d_k), FIXED_PART,
+                           {{0, I32, 6}, {offsetof(mwrt_oe_select, d_k), PTR, 19}}};
 static_assert(end_of(OE_STEP) == sizeof(mwrt_oe_step) && end_of(OE_LM) == sizeof(mwrt_oe_lm) &&
               end_of(OE_CHAR) == sizeof(mwrt_oe_char) && end_of(OBS_APPLY) == sizeof(mwrt_obs_apply) &&
               end_of(BASIS_APPLY) == sizeof(mwrt_basis_apply) && end_of(OBS_WHITEN) == sizeof(mwrt_obs_whiten) &&
-              end_of(OE_NFORM) == sizeof(mwrt_oe_nform) && end_of(OE_NFORM_CHAR) == sizeof(mwrt_oe_nform_char),
+              end_of(OE_NFORM) == sizeof(mwrt_oe_nform) && end_of(OE_NFORM_CHAR) == sizeof(mwrt_oe_nform_char) &&
+              end_of(OE_SELECT) == sizeof(mwrt_oe_select),
               "the runs of a record end where the record ends");
 static_assert(sizeof(int64_t) == PTR, "mwrt_obs_whiten: one run from reserved on");
 
@@ -291,6 +295,32 @@ Refusal oe_nform_char_args(NfCharCall call, int64_t nprof, int32_t nlev, int32_t
   if (n64 > MWRT_OE_NFORM_MAX_N)
     return unsupported("n = nblk * nlev > MWRT_OE_NFORM_MAX_N (" + std::to_string(MWRT_OE_NFORM_MAX_N) +
                        " state elements per profile: the packed triangles of C and H live in LDS)");
+  if (nprof > GRID_MAX) return unsupported("nprof exceeds grid limit");
+  return {};
+}
+
+// The observation selection: the order of oe_nform_char_args with nsel where that has its row window.
+Refusal oe_select_args(int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_select* s, mwrt_oe_select* r) {
+  if (!cut(OE_SELECT, s, r)) return too_small(OE_SELECT);
+  if (nprof < 0 || nlev < 1 || m < 1) return invalid("nprof < 0, nlev < 1 or m < 1");
+  if (r->nblk < 1 || r->nblk > 4) return invalid("mwrt_oe_select.nblk must be 1 .. 4");
+  if (r->reserved != 0) return invalid("mwrt_oe_select.reserved must be 0");
+  if (r->nsel < 1 || r->nsel > m) return invalid("mwrt_oe_select.nsel must be 1 .. m");
+  const bool buffers = r->d_s0 && r->d_se && r->d_order && r->d_q_pick && r->d_rank && r->d_q && r->d_count && r->d_status &&
+                       first_blocks(*r);
+  if (!buffers) return invalid("null buffer");
+  if (r->d_dfs_gain && !r->d_sa_inv)
+    return invalid("mwrt_oe_select: d_dfs_gain needs d_sa_inv (the degrees of freedom are taken against the prior)");
+  const void* outs[9] = {r->d_order, r->d_q_pick, r->d_rank, r->d_q, r->d_count, r->d_status, r->d_dfs_gain, r->d_post_cov,
+                         r->d_post_var};
+  const void* ins[10] = {r->d_s0, r->d_se, r->d_sa_inv, r->d_keep, r->d_candidate, r->d_active};
+  for (int b = 0; b < r->nblk; ++b) ins[6 + b] = r->d_k[b];
+  for (const void* o : outs)
+    for (const void* i : ins)
+      if (o && o == i) return invalid("mwrt_oe_select: an output pointer equals an input (nothing is formed in place)");
+  if ((int64_t)r->nblk * nlev > MWRT_OE_NFORM_MAX_N)
+    return unsupported("n = nblk * nlev > MWRT_OE_NFORM_MAX_N (" + std::to_string(MWRT_OE_NFORM_MAX_N) +
+                       " state elements per profile: the packed triangle of S lives in LDS)");
   if (nprof > GRID_MAX) return unsupported("nprof exceeds grid limit");
   return {};
 }

@@ -30,7 +30,7 @@ struct Record {
   const char* min_what;        // ... "the fixed part (through reserved)"
   Run runs[4];                 // unused ones {0, 0, 0}
 };
-extern const Record OE_STEP, OE_LM, OE_CHAR, OBS_APPLY, BASIS_APPLY, OBS_WHITEN, OE_NFORM, OE_NFORM_CHAR;
+extern const Record OE_STEP, OE_LM, OE_CHAR, OBS_APPLY, BASIS_APPLY, OBS_WHITEN, OE_NFORM, OE_NFORM_CHAR, OE_SELECT;
 
 // The one cut: *out (rec.size bytes) is the caller's record with every field that is not wholly below
 // min(struct_size, rec.size) left zero.  False, *out all zero: struct_size is below rec.min_size.
@@ -61,6 +61,8 @@ Refusal oe_nform_args(NfCall call, int64_t nprof, int32_t nlev, int32_t m, const
 // the same limit; the row window is held to n for Char alone (Gain does not read it)
 Refusal oe_nform_char_args(NfCharCall call, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_nform_char* s,
                            mwrt_oe_nform_char* r);
+// the same limit; nsel is held to 1 .. m between the reserved field and the pointers
+Refusal oe_select_args(int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_select* s, mwrt_oe_select* r);
 
 }  // namespace records
 }  // namespace mwrt

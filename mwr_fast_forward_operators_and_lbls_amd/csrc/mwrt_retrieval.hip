@@ -7,7 +7,7 @@
 // limits of the launch geometry and the LDS plan, then launch_tail: an empty batch, the device, the stream, the launches.
 //
 // Host code only: every kernel lives in its own unit (mwrt_oe.hip, mwrt_oe_lm.hip, mwrt_oe_char.hip, mwrt_obs.hip,
-// mwrt_basis.hip, mwrt_whiten.hip, mwrt_nform.hip, mwrt_nform_char.hip) and is reached through the launchers the headers
+// mwrt_basis.hip, mwrt_whiten.hip, mwrt_nform.hip, mwrt_nform_char.hip, mwrt_select.hip) and is reached through the launchers the headers
 // below declare.
 #include "mwrt_host.hip.h"
 #include "mwrt_records.h"
@@ -19,6 +19,7 @@
 #include "mwrt_whiten.hip.h"
 #include "mwrt_nform.hip.h"
 #include "mwrt_nform_char.hip.h"
+#include "mwrt_select.hip.h"
 
 #include <cmath>
 #include <new>
@@ -111,6 +112,7 @@ template <class R> oe::OeArgs oe_kernel_args(const R& r, int32_t nlev, int32_t m
 
 constexpr const char* STEP_LDS = "the optimal-estimation step needs more LDS than this device has per workgroup";
 constexpr const char* GAIN_LDS = "the optimal-estimation gain needs more LDS than this device has per workgroup";
+constexpr const char* SELECT_LDS = "the observation selection needs more LDS than this device has per workgroup";
 int lds_fits(const mwrt_context* c, size_t bytes, const char* or_else) {
   return bytes <= (size_t)c->lds_max ? MWRT_OK : fail(MWRT_ERR_UNSUPPORTED, or_else);
 }
@@ -186,6 +188,23 @@ int oe_nform_char_call(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, 
   if (nprof > GRID_MAX / nfc::gain_row_tiles(m))
     return fail(MWRT_ERR_UNSUPPORTED, "mwrt_oe_nform_gain_device: more than 2147483647 workgroups in one launch (split the batch)");
   return launch_tail(c, nprof, stream, launch([&](hipStream_t st) { return nfc::launch_nfc_gain(a, nprof, st); }));
+}
+
+// The observation selection (csrc/mwrt_select.hip): one entry, one kernel.
+int oe_select_call(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_select* s, void* stream) {
+  if (!c || !s) return fail(MWRT_ERR_INVALID_ARGUMENT, "null context or mwrt_oe_select");
+  mwrt_oe_select r;
+  if (const auto no = records::oe_select_args(nprof, nlev, m, s, &r)) return refused(no);
+  sel::SelArgs a{};
+  a.k0 = r.d_k[0]; a.k1 = r.nblk > 1 ? r.d_k[1] : nullptr; a.k2 = r.nblk > 2 ? r.d_k[2] : nullptr;
+  a.k3 = r.nblk > 3 ? r.d_k[3] : nullptr;
+  a.s0 = r.d_s0; a.se = r.d_se; a.sa_inv = r.d_sa_inv; a.keep = r.d_keep; a.candidate = r.d_candidate; a.active = r.d_active;
+  a.order = r.d_order; a.q_pick = r.d_q_pick; a.rank = r.d_rank; a.q = r.d_q; a.count = r.d_count; a.status = r.d_status;
+  a.dfs_gain = r.d_dfs_gain; a.post_cov = r.d_post_cov; a.post_var = r.d_post_var;
+  a.nblk = r.nblk; a.nlev = nlev; a.m = m; a.n = r.nblk * nlev; a.nsel = r.nsel;
+  a.se_per_profile = r.se_per_profile != 0; a.s0_per_profile = r.s0_per_profile != 0;
+  if (const int rc = lds_fits(c, sel::sel_plan(a.n).total_bytes, SELECT_LDS)) return rc;
+  return launch_tail(c, nprof, stream, launch([&](hipStream_t st) { return sel::launch_select(a, nprof, st); }));
 }
 
 // The two entries of the characterisation (csrc/mwrt_oe_char.hip) share one record.
@@ -304,6 +323,13 @@ int mwrt_oe_nform_solve_device(mwrt_context* c, int64_t nprof, int32_t nlev, int
 }
 int mwrt_oe_nform_cost_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_nform* s, void* stream) {
   return oe_nform_call(c, nprof, nlev, m, s, stream, NfCall::Cost);
+}
+
+/* The observation selection by information content (csrc/mwrt_select.hip). */
+size_t mwrt_oe_select_size(void) { return sizeof(mwrt_oe_select); }
+
+int mwrt_oe_select_device(mwrt_context* c, int64_t nprof, int32_t nlev, int32_t m, const mwrt_oe_select* s, void* stream) {
+  return oe_select_call(c, nprof, nlev, m, s, stream);
 }
 
 /* The characterisation of the n-form step (csrc/mwrt_nform_char.hip). */

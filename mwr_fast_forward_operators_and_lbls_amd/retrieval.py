@@ -50,6 +50,10 @@ and the basis projection) and the unchanged update entries run with Se = 1, whic
     se_p = noise[None] + ov.representation_error(z, p, x)            # K S_res K^T of a truncated basis, per profile
     res = ov.retrieve(z, p, y, se=se_p)
 
+Which observations of a scan carry the information -- the greedy order by entropy reduction, the degrees of freedom along
+it and the posterior after the picks -- is the business of the module ``selection`` (DESIGN.md 4.12;
+``mwrt_oe_select_device``): ``selection.rank_observations(ov, z, p, x)`` takes a ``OneDVar`` of either form.
+
 The tensor contract.  The library is handed bare pointers and reads contiguous doubles behind them on the
 GPU, so every tensor argument of this module -- the constructor's ``sa``, ``se``, ``xa``, ``StateBasis``'s ``b``, ``sa_c``,
 ``c_a``, and ``z``, ``p``, ``x``, ``x0``, ``y``, ``se=`` of every public method -- must be a float64 ``torch.Tensor`` of the
