@@ -60,6 +60,12 @@ def is_stale() -> bool:
     return any(os.path.getmtime(d) > t for d in DEPS)
 
 
+def compile_command(src: str, obj: str, defs=(), extra=()) -> list:
+    """The command that compiles one translation unit of the library, a row of UNITS, for gfx950 into ``obj``."""
+    return [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
+            *extra, *defs, "-c", src, "-o", obj]
+
+
 def build_native(force: bool = False, verbose: bool = False, extra_flags=(), out: str = None) -> str:
     """Compile the translation units for gfx950 and link libmwrt.so (or ``out``).  Returns the library path."""
     lib = out or LIB
@@ -68,14 +74,12 @@ def build_native(force: bool = False, verbose: bool = False, extra_flags=(), out
     hipcc = hipcc_path()
     os.makedirs(OBJ_DIR, exist_ok=True)
     tag = str(os.getpid())
-    common = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
-              *extra_flags]
     jobs = [(src, os.path.join(OBJ_DIR, f"{os.path.splitext(os.path.basename(src))[0]}.{i}.{tag}.o"), defs)
             for i, (src, defs) in enumerate(UNITS)]
 
     def compile_one(job):
         src, obj, defs = job
-        cmd = common + defs + ["-c", src, "-o", obj]
+        cmd = compile_command(src, obj, defs, extra_flags)
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.run(cmd, check=True)

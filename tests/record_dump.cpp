@@ -1,10 +1,12 @@
 // record_dump -- what the argument stage of the record entries (csrc/mwrt_records.cpp, linked as is) answers, as JSON: one
 // object {"status", "message", "record"} per request line on stdin, `record` being the cut record as hex.  Built and run by
-// tests/test_record_checks.py under ASan + UBSan; needs no GPU.  HEX is the caller's record: the bytes are copied to a heap
-// block of exactly their length, so a read beyond what the caller owns is a sanitiser report.
+// tests/record_kit.py under ASan + UBSan for the four tests/test_*record_checks.py; needs no GPU.  HEX is the caller's
+// record: the bytes are copied to a heap block of exactly their length, so a read beyond what the caller owns is a
+// sanitiser report.
 //
 //   cut RECORD HEX                                    RECORD: mwrt_oe_step, ... -- the cut alone (status -1: below the minimum)
 //   oe_step | oe_lm_prepare | oe_lm_solve | oe_cost | oe_gain | oe_product | whiten | whiten_apply   NPROF NLEV M HEX
+//   nform_prepare | nform_solve | nform_cost | nform_char | nform_gain | select                      NPROF NLEV M HEX
 //   obs_apply NPROF NLEV HEX
 //   basis_project BASIS_NBLK NPROF M HEX
 //   basis_expand NPROF HEX
@@ -40,8 +42,10 @@ int main() {
     auto as = [&](auto* r) { return reinterpret_cast<decltype(r)>(caller.data()); };
     const size_t nargs = w.size() - 2;
     mwrt_oe_step step; mwrt_oe_lm lm; mwrt_oe_char ch; mwrt_obs_apply ob; mwrt_basis_apply ba; mwrt_obs_whiten wh;
+    mwrt_oe_nform nf; mwrt_oe_nform_char nc; mwrt_oe_select sel;
     if (cmd == "cut" && nargs == 1) {
-      const Record* recs[] = {&OE_STEP, &OE_LM, &OE_CHAR, &OBS_APPLY, &BASIS_APPLY, &OBS_WHITEN};
+      const Record* recs[] = {&OE_STEP, &OE_LM, &OE_CHAR, &OBS_APPLY, &BASIS_APPLY, &OBS_WHITEN, &OE_NFORM, &OE_NFORM_CHAR,
+                              &OE_SELECT};
       const Record* rec = nullptr;
       for (const Record* r : recs) if (w[1] == r->name) rec = r;
       if (!rec) { std::fprintf(stderr, "record_dump: unknown record '%s'\n", w[1].c_str()); return 2; }
@@ -59,6 +63,14 @@ int main() {
     } else if ((cmd == "whiten" || cmd == "whiten_apply") && nargs == 3) {
       const WhitenCall call = cmd == "whiten" ? WhitenCall::Whiten : WhitenCall::Apply;
       answer(whiten_args(call, num(1), (int32_t)num(2), (int32_t)num(3), as(&wh), &wh), &wh, sizeof wh);
+    } else if ((cmd == "nform_prepare" || cmd == "nform_solve" || cmd == "nform_cost") && nargs == 3) {
+      const NfCall call = cmd == "nform_prepare" ? NfCall::Prepare : cmd == "nform_solve" ? NfCall::Solve : NfCall::Cost;
+      answer(oe_nform_args(call, num(1), (int32_t)num(2), (int32_t)num(3), as(&nf), &nf), &nf, sizeof nf);
+    } else if ((cmd == "nform_char" || cmd == "nform_gain") && nargs == 3) {
+      const NfCharCall call = cmd == "nform_char" ? NfCharCall::Char : NfCharCall::Gain;
+      answer(oe_nform_char_args(call, num(1), (int32_t)num(2), (int32_t)num(3), as(&nc), &nc), &nc, sizeof nc);
+    } else if (cmd == "select" && nargs == 3) {
+      answer(oe_select_args(num(1), (int32_t)num(2), (int32_t)num(3), as(&sel), &sel), &sel, sizeof sel);
     } else if (cmd == "obs_apply" && nargs == 2) {
       answer(obs_apply_args(num(1), (int32_t)num(2), as(&ob), &ob), &ob, sizeof ob);
     } else if (cmd == "basis_project" && nargs == 3) {

@@ -5,12 +5,12 @@ the tile constants of the plan header as the code has them."""
 import ctypes
 import os
 import re
-import subprocess
 
 import basis_reference as bar
+from kernel_unit import MWRT_H, check_record, library_kernels, resource_usage
 from mwr_fast_forward_operators_and_lbls_amd import _native, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMESPACE = "basis"            # the kernels live in mwrt::basis
 KERNELS = {"k_project", "k_expand"}
 SYMBOLS = ("mwrt_basis_create", "mwrt_basis_destroy", "mwrt_basis_project_device", "mwrt_basis_expand_device",
            "mwrt_basis_apply_size")
@@ -26,25 +26,8 @@ def plan():
     return out
 
 
-def resource_usage(tmp_path):
-    cmd = [build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
-           "-Rpass-analysis=kernel-resource-usage", "-c", build.BASIS, "-o", str(tmp_path / "basis.o")]
-    text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-    out, name = {}, None
-    for line in text.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            s = re.search(r"\d+(k_project|k_expand)E", m.group(1))
-            name = s.group(1) if s else m.group(1)
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name is not None:
-            out.setdefault(name, {})[m.group(1).split(" ")[0]] = int(m.group(2))
-    return out
-
-
-def test_basis_kernels_keep_their_budgets(tmp_path):
-    use = resource_usage(tmp_path)
+def test_basis_kernels_keep_their_budgets():
+    use = resource_usage(build.BASIS)
     assert set(use) == KERNELS, use                                      # the unit holds these kernels and no other
     t = plan()
     u = use["k_project"]
@@ -58,17 +41,7 @@ def test_basis_kernels_keep_their_budgets(tmp_path):
 
 
 def test_library_holds_exactly_the_basis_kernels(native_lib):
-    out = subprocess.run(["nm", "-C", "--defined-only", _native.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    found = set()
-    for line in out.splitlines():
-        if "__device_stub__" in line:
-            continue
-        m = re.search(r"mwrt::basis::(?:\(anonymous namespace\)::)?(k_\w+(?:<[^>()]*>)?)\(", line)
-        if m:
-            found.add(m.group(1))
-    assert found == KERNELS, found
-    # and nothing of the unit leaks into the inventories the other tests pin
-    assert not re.search(r"mwrt::(?:oe::|lm::|oec::|obs::|par::|ray::)?(?:\(anonymous namespace\)::)?k_(?:project|expand)", out)
+    assert library_kernels(_native.LIB_PATH)[NAMESPACE] == KERNELS
 
 
 def test_host_unit_carries_no_basis_device_code():
@@ -80,23 +53,17 @@ def test_host_unit_carries_no_basis_device_code():
 
 
 def test_abi_surface_of_the_reduced_basis(native_lib):
-    header = open(os.path.join(ROOT, "include", "mwrt.h")).read()
+    header = open(MWRT_H).read()
     for sym in SYMBOLS:
         assert re.search(r"\b%s\s*\(" % sym, header) and sym in _native.SIGNATURES and hasattr(native_lib, sym), sym
     rec = _native.MwrtBasisApply
-    assert native_lib.mwrt_basis_apply_size() == ctypes.sizeof(rec) == 80
-    # the record in the header, field by field and in order, is the ctypes mirror
-    body = re.search(r"typedef struct mwrt_basis_apply \{(.*?)\} mwrt_basis_apply;", header, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = [n for decl in body.split(";") for n in re.findall(r"\*?\s*(\w+)(?:\[\d+\])?\s*(?:,|$)", decl.strip())]
-    assert names == [f[0] for f in rec._fields_] == ["struct_size", "reserved", "d_k_in", "d_k_out", "d_c", "d_x_ref", "d_x",
-                                                     "x_ref_per_profile", "reserved2"]
+    check_record(native_lib, "mwrt_basis_apply", rec, 80, offsets=[0, 4, 8, 40, 48, 56, 64, 72, 76],
+                 names=["struct_size", "reserved", "d_k_in", "d_k_out", "d_c", "d_x_ref", "d_x", "x_ref_per_profile", "reserved2"])
     kinds = {f[0]: f[1] for f in rec._fields_}
     assert kinds["struct_size"] is ctypes.c_uint32 and kinds["reserved"] is ctypes.c_int32
     assert kinds["x_ref_per_profile"] is ctypes.c_int32 and kinds["reserved2"] is ctypes.c_int32
     assert ctypes.sizeof(kinds["d_k_in"]) == 4 * ctypes.sizeof(ctypes.c_void_p)
     assert all(kinds[k] is ctypes.c_void_p for k in ("d_k_out", "d_c", "d_x_ref", "d_x"))
-    assert [getattr(rec, f[0]).offset for f in rec._fields_] == [0, 4, 8, 40, 48, 56, 64, 72, 76]
     assert native_lib.mwrt_version() == 301 == _native.MWRT_VERSION
 
 

@@ -6,17 +6,17 @@ than it had before them -- 64 B per lane in the commit before the groups, read f
 The groups alone took it to 96 B.  Two changes to the OPT code brought it back under: z, T, p and the ozone column are
 read again after the line loops instead of riding through them (72 B), and cloud_level builds its record from scalars, which
 frees the 16-byte stack slot the zero-initialised struct had left behind (52 B)."""
-from test_fused_kernel_resources import resource_usage
+from kernel_unit import resource_usage
+from mwr_fast_forward_operators_and_lbls_amd import build
 
-OPT_HEADLINE = "k_tb_fusedILi14ELi8ELi256ELb1ELb0ELb0EE"      # <NFC 14, NFK 8, MAXT 256, OPT, no EXTRAS, no ALPHA>
+OPT_HEADLINE = "k_tb_fused<14, 8, 256, true, false, false>"   # <NFC 14, NFK 8, MAXT 256, OPT, no EXTRAS, no ALPHA>
 PARENT_SCRATCH = 64                                            # bytes per lane, the commit before the far-line groups
 
 
-def test_opt_fused_kernel_keeps_its_third_wave_and_its_scratch(tmp_path):
-    use = resource_usage(tmp_path)
-    mine = [v for k, v in use.items() if OPT_HEADLINE in k]
-    assert len(mine) == 1, sorted(use)
-    u = mine[0]
+def test_opt_fused_kernel_keeps_its_third_wave_and_its_scratch():
+    use = resource_usage(build.INST, ("-DMWRT_INST_NFC=14",))     # the compile test_fused_kernel_resources.py asks for
+    assert OPT_HEADLINE in use, sorted(use)
+    u = use[OPT_HEADLINE]
     print(u)
     assert u["Occupancy"] >= 3, u
     assert u["ScratchSize"] <= PARENT_SCRATCH, u

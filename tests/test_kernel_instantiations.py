@@ -8,6 +8,8 @@ picks exactly one per stage from the frequency count (chunk width 8 / 14 / 16), 
 CPU part (unmarked): ``kernel_inventory`` lists the kernels of the built library with ``nm``; ``expected_kernels``
 restates the routing in a few lines of Python; the union over the case table ``CASES`` must equal the inventory, in both
 directions, so a new instantiation without a covering case, or a case claiming a kernel that does not exist, fails here.
+The kernels in namespaces of their own (mwrt::oe, mwrt::nf, ...) are pinned by the tests of their units; the whole library,
+namespace by namespace, is held against those sets and the union above in one test.
 The restatement is held to the library's own planning code: ``tests/plan_dump.cpp`` links ``csrc/mwrt_plan.cpp`` as is
 (a host-only unit), is built with the host compiler under ASan + UBSan and answers every seam and every case.
 
@@ -21,13 +23,22 @@ import dataclasses
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from mwr_fast_forward_operators_and_lbls_amd import profiles as pr, spectroscopy as sp
+from kernel_unit import library_kernels
 from plan_dump_tool import plan_dump, request as line          # noqa: F401 (plan_dump: the fixture, sanitised build)
+# the kernel units with a namespace of their own: each test module names it (NAMESPACE) and pins its kernels (KERNELS)
+import test_basis_kernel_resources, test_nform_char_kernel_resources, test_nform_kernel_resources    # noqa: E401
+import test_obs_kernel_resources, test_oe_char_kernel_resources, test_oe_kernel_resources          # noqa: E401
+import test_oe_lm_kernel_resources, test_param_kernel_resources, test_ray_kernel_resources         # noqa: E401
+import test_select_kernel_resources, test_whiten_kernel_resources                                   # noqa: E401
+
+KERNEL_UNITS = (test_basis_kernel_resources, test_nform_char_kernel_resources, test_nform_kernel_resources,
+                test_obs_kernel_resources, test_oe_char_kernel_resources, test_oe_kernel_resources, test_oe_lm_kernel_resources,
+                test_param_kernel_resources, test_ray_kernel_resources, test_select_kernel_resources, test_whiten_kernel_resources)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mwr_fast_forward_operators_and_lbls_amd", "csrc")
@@ -227,9 +238,9 @@ def normalise_kernel_name(symbol):
 
 
 def kernel_inventory(lib_path):
-    """The kernels compiled into `lib_path`: the host handles of mwrt::k_* (anonymous-namespace ones included)."""
-    out = subprocess.run(["nm", "-C", "--defined-only", lib_path], capture_output=True, text=True, check=True).stdout
-    return {k for k in (normalise_kernel_name(line) for line in out.splitlines()) if k}
+    """The kernels compiled into `lib_path` directly in mwrt: the host handles of mwrt::k_* (anonymous-namespace ones
+    included).  The units' own namespaces are beside them in library_kernels(lib_path)."""
+    return library_kernels(lib_path)[""]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -320,6 +331,17 @@ def test_case_table_covers_every_compiled_kernel(native_lib):
     assert inventory, "nm found no mwrt::k_* kernel in the library"
     assert not inventory - claimed, "compiled kernels no case reaches: %s" % sorted(inventory - claimed)
     assert not claimed - inventory, "cases claim kernels that are not compiled: %s" % sorted(claimed - inventory)
+
+
+def test_the_library_holds_the_units_kernels_and_no_other(native_lib):
+    """Every kernel of libmwrt.so, namespace by namespace, against what the tests of the units pin: a kernel in a namespace
+    no unit lists, or in a unit's namespace under another unit's name, fails here."""
+    table = {unit.NAMESPACE: unit.KERNELS for unit in KERNEL_UNITS}
+    assert len(table) == len(KERNEL_UNITS)
+    table[""] = set().union(*(expected_kernels(c) for c in CASES))
+    found = library_kernels(native_lib._name)
+    assert found == table, {ns: sorted(found.get(ns, set()) ^ table.get(ns, set())) for ns in set(found) | set(table)
+                            if found.get(ns) != table.get(ns)}
 
 
 # what test_routing_mirror_at_its_seams pins, as inputs: the planning code is asked the same questions

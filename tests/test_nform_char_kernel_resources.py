@@ -5,15 +5,15 @@ recipe, one record layout on both sides; and the guard of the GPU tests' shape l
 import ctypes
 import os
 import re
-import subprocess
 
+from kernel_unit import MWRT_H, check_record, library_kernels, plan_rows, resource_usage
 from mwr_fast_forward_operators_and_lbls_amd import _native, build
 
 import nform_char_reference as ncr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(build.CSRC, "mwrt_nform_char.hip.h")
 SYMBOLS = ("mwrt_oe_nform_char_device", "mwrt_oe_nform_gain_device", "mwrt_oe_nform_char_size")
+NAMESPACE = "nfc"            # the kernels live in mwrt::nfc
 KERNELS = {"k_nfc_char", "k_nfc_gain"}
 # (VGPRs at most, waves per SIMD at least), from the remark of the build this test was written against (38 and 128 VGPRs,
 # rounded up to a multiple of 8; occupancy as shown): k_nfc_char must not be held back by registers (its LDS block is what
@@ -37,25 +37,8 @@ def char_lds_bytes(n, c):
     return 8 * (2 * even(n * (n + 1) // 2) + even(n) + c["THREADS"])
 
 
-def resource_usage(tmp_path):
-    cmd = [build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
-           "-Rpass-analysis=kernel-resource-usage", "-c", build.NFORM_CHAR, "-o", str(tmp_path / "nform_char.o")]
-    text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-    out, name = {}, None
-    for line in text.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            s = re.search(r"\d+(k_nfc_char|k_nfc_gain)E", m.group(1))
-            name = s.group(1) if s else m.group(1)
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name is not None:
-            out.setdefault(name, {})[m.group(1).split(" ")[0]] = int(m.group(2))
-    return out
-
-
-def test_the_kernels_keep_their_register_budget(tmp_path):
-    use = resource_usage(tmp_path)
+def test_the_kernels_keep_their_register_budget():
+    use = resource_usage(build.NFORM_CHAR)
     assert set(use) == KERNELS, use                                      # every kernel of the unit is one of the two
     for name, u in use.items():
         assert u["ScratchSize"] == 0 and u["AGPRs"] == 0, (name, u)
@@ -71,15 +54,9 @@ def test_the_lds_plan_follows_its_formula(tmp_path):
     c = constants()
     assert c == dict(ROWS=128, COLS=32, KCHUNK=16, MR=4, NC=4, THREADS=256)
     assert c["THREADS"] // 8 * c["MR"] == c["ROWS"] and 8 * c["NC"] == c["COLS"] and 2 * c["THREADS"] == c["KCHUNK"] * c["COLS"]
-    src = tmp_path / "plans.hip"
-    src.write_text('#include <cstdio>\n#include "%s"\nint main() {\n  for (int n = 1; n <= MWRT_OE_NFORM_MAX_N; ++n)\n'
-                   '    std::printf("%%d %%zu %%zu %%zu %%d %%d\\n", n, mwrt::nfc::char_plan(n).total_bytes, mwrt::nfc::char_plan(n).s,\n'
-                   '                mwrt::nfc::char_plan(n).dg, mwrt::nfc::cols_per_lane(n), mwrt::nfc::gain_col_tiles(n));\n'
-                   '  return 0;\n}\n' % HEADER)
-    exe = str(tmp_path / "plans")
-    subprocess.run([build.hipcc_path(), "--offload-arch=gfx950", "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                    str(src), "-o", exe], check=True, capture_output=True)
-    rows = [tuple(map(int, ln.split())) for ln in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines()]
+    rows = plan_rows(HEADER, '    std::printf("%d %zu %zu %zu %d %d\\n", n, mwrt::nfc::char_plan(n).total_bytes, mwrt::nfc::char_plan(n).s,\n'
+                             '                mwrt::nfc::char_plan(n).dg, mwrt::nfc::cols_per_lane(n), mwrt::nfc::gain_col_tiles(n));',
+                     tmp_path)
     assert [r[0] for r in rows] == list(range(1, _native.OE_NFORM_MAX_N + 1))
     for n, total, s, dg, cpl, ctiles in rows:
         nte = (n * (n + 1) // 2 + 1) & ~1
@@ -90,34 +67,18 @@ def test_the_lds_plan_follows_its_formula(tmp_path):
 
 
 def test_library_holds_exactly_the_nform_char_kernels(native_lib):
-    out = subprocess.run(["nm", "-C", "--defined-only", _native.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    found = set()
-    for line in out.splitlines():
-        if "__device_stub__" in line:
-            continue
-        m = re.search(r"mwrt::nfc::(?:\(anonymous namespace\)::)?(k_\w+(?:<[^>()]*>)?)\(", line)
-        if m:
-            found.add(m.group(1))
-    assert found == KERNELS, found
-    # and nothing of the unit leaks into the inventories the other tests pin
-    assert not re.search(r"mwrt::(?:oe::|lm::|nf::|oec::|basis::)?(?:\(anonymous namespace\)::)?k_nfc", out)
+    assert library_kernels(_native.LIB_PATH)[NAMESPACE] == KERNELS
     assert not any(name.startswith("k_nf_") for name in KERNELS)
 
 
 def test_abi_surface_of_the_nform_char(native_lib):
-    header = open(os.path.join(ROOT, "include", "mwrt.h")).read()
+    header = open(MWRT_H).read()
     for sym in SYMBOLS:
         assert re.search(r"\b%s\s*\(" % sym, header) and sym in _native.SIGNATURES and hasattr(native_lib, sym), sym
     rec = _native.MwrtOeNformChar
-    assert native_lib.mwrt_oe_nform_char_size() == ctypes.sizeof(rec) == 168
     assert native_lib.mwrt_oe_nform_size() == ctypes.sizeof(_native.MwrtOeNform) == 240
     # the record in the header, field by field and in order, is the ctypes mirror; every pointer 8 bytes after the last
-    body = re.search(r"typedef struct mwrt_oe_nform_char \{(.*?)\} mwrt_oe_nform_char;", header, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = [n for decl in body.split(";") for n in re.findall(r"\*?\s*(\w+)(?:\[\d+\])?\s*(?:,|$)", decl.strip())]
-    assert names == [f[0] for f in rec._fields_], names
-    assert [getattr(rec, n).offset for n in names[:7]] == [0, 4, 8, 12, 16, 20, 24]
-    assert [getattr(rec, n).offset for n in names[7:]] == list(range(56, 168, 8))
+    check_record(native_lib, "mwrt_oe_nform_char", rec, 168, offsets=[0, 4, 8, 12, 16, 20, 24] + list(range(56, 168, 8)))
     assert native_lib.mwrt_version() == 301
     # the unit is in the build recipe, its entries in the host unit that holds no device code
     assert (build.NFORM_CHAR, []) in build.UNITS and len(build.HOST_UNITS) == 2

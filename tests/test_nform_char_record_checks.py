@@ -1,18 +1,14 @@
 """The argument stage of the n-form's characterisation entries (csrc/mwrt_records.cpp oe_nform_char_args) without a GPU:
-tests/nform_char_record_dump.cpp links it as is, built with the host C++ compiler under ASan + UBSan and run as a child
-process -- the pattern, and the helpers, of tests/test_record_checks.py and tests/test_nform_record_checks.py.  The record is
-built from the ctypes mirror of _native.py, so the mirror and the C struct are held against each other too.  Pointer fields
-hold small distinct integers; nothing dereferences them."""
+tests/record_dump.cpp links it as is, built with the host C++ compiler under ASan + UBSan and run as a child process
+(tests/record_kit.py: the fixture and the helpers; the cut of the record at every struct_size is held with the other
+records' by tests/test_record_checks.py).  The record is built from the ctypes mirror of _native.py, so the mirror and the C
+struct are held against each other too.  Pointer fields hold small distinct integers; nothing dereferences them."""
 import ctypes
-import json
-import os
-import shutil
-import subprocess
 
 import pytest
 
 from mwr_fast_forward_operators_and_lbls_amd import _native
-from test_record_checks import CSRC, INVALID, OK, ROOT, UNSUPPORTED, leaves, line, put, record, run
+from record_kit import INVALID, OK, UNSUPPORTED, line, record, record_dump, run      # noqa: F401 (record_dump: the fixture)
 
 CLS = _native.MwrtOeNformChar
 MINIMUM = 24                                         # the fixed part (through reserved)
@@ -34,25 +30,6 @@ ENTRIES = {
 }
 
 
-@pytest.fixture(scope="module")
-def char_dump(tmp_path_factory):
-    """ask(request lines) -> one parsed JSON answer per line.  A sanitiser report ends the child with a non-zero status."""
-    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    exe = str(tmp_path_factory.mktemp("nform_char_record_dump") / "nform_char_record_dump")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    os.path.join(ROOT, "tests", "nform_char_record_dump.cpp"), os.path.join(CSRC, "mwrt_records.cpp"), "-o", exe],
-                   check=True)
-
-    def ask(lines):
-        r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True)
-        assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-4000:])
-        out = [json.loads(x) for x in r.stdout.splitlines()]
-        assert len(out) == len(lines)
-        return out
-    return ask
-
-
 def rec(**kw):
     return record(CLS, **kw)
 
@@ -63,32 +40,8 @@ def test_the_mirror_is_the_record():
     assert ctypes.sizeof(_native.MwrtOeNform) == 240                                   # the sibling record has not grown
 
 
-def test_the_cut_at_every_struct_size(char_dump):
-    """Every struct_size from 0 to sizeof + 8 with every field non-zero: below the documented minimum it is refused; from
-    there on a field comes through if and only if it lies wholly below min(struct_size, sizeof), every other byte is zero.
-    The child owns exactly struct_size bytes."""
-    size = ctypes.sizeof(CLS)
-    full = CLS()
-    for k, (field, index, _, width) in enumerate(leaves(CLS)):
-        put(full, field, index, (k + 1) * 0x0101 + (0x01010000 << 8 if width == 8 else 0))
-    full = bytes(full) + b"\xab" * 8
-    assert all(full[off:off + width].count(0) < width for _, _, off, width in leaves(CLS))
-    asked, want = [], []
-    for struct_size in range(size + 9):
-        caller = struct_size.to_bytes(4, "little") + full[4:max(struct_size, 4)]
-        asked.append(f"cut {caller.hex()}")
-        expect = bytearray(size)
-        for _, _, off, width in leaves(CLS):
-            if struct_size >= MINIMUM and off + width <= min(struct_size, size):
-                expect[off:off + width] = caller[off:off + width]
-        want.append((struct_size, OK if struct_size >= MINIMUM else INVALID, bytes(expect).hex()))
-    assert len(asked) == 177
-    for (struct_size, status, expect), got in zip(want, char_dump(asked)):
-        assert (got["status"], got["record"]) == (status, expect), struct_size
-
-
 @pytest.mark.parametrize("entry", sorted(ENTRIES))
-def test_refusals_their_messages_and_their_order(char_dump, entry):
+def test_refusals_their_messages_and_their_order(record_dump, entry):
     required, optional = (s.split() for s in ENTRIES[entry])
     char = entry == "nform_char"
     cases = [
@@ -171,4 +124,4 @@ def test_refusals_their_messages_and_their_order(char_dump, entry):
             (line(entry, 1, 2, 3, rec(d_gain=r0.d_h)), OK, None),                                  # not an input of this entry
             (line(entry, 1, MAX_N + 1, 3, rec(d_gain=r0.d_se)), INVALID, ALIASED),
         ]
-    run(char_dump, cases)
+    run(record_dump, cases)

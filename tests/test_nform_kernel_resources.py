@@ -5,15 +5,15 @@ sides; and the guard of the tests' shape list against the plan constants as buil
 import ctypes
 import os
 import re
-import subprocess
 
+from kernel_unit import MWRT_H, check_record, library_kernels, plan_rows, resource_usage
 from mwr_fast_forward_operators_and_lbls_amd import _native, build
 
 import nform_reference as nfr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(build.CSRC, "mwrt_nform.hip.h")
 SYMBOLS = ("mwrt_oe_nform_prepare_device", "mwrt_oe_nform_solve_device", "mwrt_oe_nform_cost_device", "mwrt_oe_nform_size")
+NAMESPACE = "nf"            # the kernels live in mwrt::nf
 KERNELS = {"k_nf_normal<1>", "k_nf_normal<2>", "k_nf_normal<3>", "k_nf_solve", "k_nf_cost"}
 # (VGPRs at most, waves per SIMD at least), from the remark of the build this test was written against (146 / 232 / 230,
 # 88 and 28 VGPRs): k_nf_normal<TT> holds TT 4 x 4 tiles of accumulators and one chunk of K in flight and must keep two
@@ -41,26 +41,8 @@ def solve_lds_bytes(n, c):
     return 8 * (even(n * (n + 1) // 2) + 4 * even(n) + c["THREADS"])
 
 
-def resource_usage(tmp_path):
-    cmd = [build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
-           "-Rpass-analysis=kernel-resource-usage", "-c", build.NFORM, "-o", str(tmp_path / "nform.o")]
-    text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-    out, name = {}, None
-    for line in text.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            k = re.search(r"k_nf_normalILi(\d+)E", m.group(1))
-            s = re.search(r"\d+(k_nf_solve|k_nf_cost)E", m.group(1))
-            name = f"k_nf_normal<{k.group(1)}>" if k else s.group(1) if s else m.group(1)
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name is not None:
-            out.setdefault(name, {})[m.group(1).split(" ")[0]] = int(m.group(2))
-    return out
-
-
-def test_nform_kernels_keep_their_register_budget(tmp_path):
-    use = resource_usage(tmp_path)
+def test_nform_kernels_keep_their_register_budget():
+    use = resource_usage(build.NFORM)
     assert set(use) == KERNELS, use                                      # every kernel of the unit is one of the three
     for name, u in use.items():
         assert u["ScratchSize"] == 0 and u["AGPRs"] == 0, (name, u)
@@ -76,15 +58,9 @@ def test_the_lds_plans_follow_their_formulas(tmp_path):
     assert c == dict(ROW_CHUNK=16, TILE=4, MAX_TILES=3, THREADS=256)
     assert c["ROW_CHUNK"] % (c["THREADS"] // 64) == 0                    # whole rows per wave
     assert tiles_per_thread(_native.OE_NFORM_MAX_N, c) == c["MAX_TILES"]
-    src = tmp_path / "plans.hip"
-    src.write_text('#include <cstdio>\n#include "%s"\nint main() {\n  for (int n = 1; n <= MWRT_OE_NFORM_MAX_N; ++n)\n'
-                   '    std::printf("%%d %%d %%d %%zu %%zu %%zu\\n", n, mwrt::nf::tiles_per_thread(n), mwrt::nf::normal_plan(n).pitch,\n'
-                   '                mwrt::nf::normal_plan(n).total_bytes, mwrt::nf::solve_plan(n).total_bytes,\n'
-                   '                mwrt::nf::cost_plan(n).total_bytes);\n  return 0;\n}\n' % HEADER)
-    exe = str(tmp_path / "plans")
-    subprocess.run([build.hipcc_path(), "--offload-arch=gfx950", "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                    str(src), "-o", exe], check=True, capture_output=True)
-    rows = [tuple(map(int, ln.split())) for ln in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines()]
+    rows = plan_rows(HEADER, '    std::printf("%d %d %d %zu %zu %zu\\n", n, mwrt::nf::tiles_per_thread(n), mwrt::nf::normal_plan(n).pitch,\n'
+                             '                mwrt::nf::normal_plan(n).total_bytes, mwrt::nf::solve_plan(n).total_bytes,\n'
+                             '                mwrt::nf::cost_plan(n).total_bytes);', tmp_path)
     assert [r[0] for r in rows] == list(range(1, _native.OE_NFORM_MAX_N + 1))
     for n, tt, pitch, normal, solve, cost in rows:
         assert tt == tiles_per_thread(n, c) and 1 <= tt <= c["MAX_TILES"], n
@@ -97,33 +73,17 @@ def test_the_lds_plans_follow_their_formulas(tmp_path):
 
 
 def test_library_holds_exactly_the_nform_kernels(native_lib):
-    out = subprocess.run(["nm", "-C", "--defined-only", _native.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    found = set()
-    for line in out.splitlines():
-        if "__device_stub__" in line:
-            continue
-        m = re.search(r"mwrt::nf::(?:\(anonymous namespace\)::)?(k_\w+(?:<[^>()]*>)?)\(", line)
-        if m:
-            found.add(m.group(1))
-    assert found == KERNELS, found
-    # and nothing of the unit leaks into the inventories the other tests pin
-    assert not re.search(r"mwrt::(?:oe::|lm::)?(?:\(anonymous namespace\)::)?k_nf", out)
+    assert library_kernels(_native.LIB_PATH)[NAMESPACE] == KERNELS
 
 
 def test_abi_surface_of_the_nform(native_lib):
-    header = open(os.path.join(ROOT, "include", "mwrt.h")).read()
+    header = open(MWRT_H).read()
     for sym in SYMBOLS:
         assert re.search(r"\b%s\s*\(" % sym, header) and sym in _native.SIGNATURES and hasattr(native_lib, sym), sym
     rec = _native.MwrtOeNform
-    assert native_lib.mwrt_oe_nform_size() == ctypes.sizeof(rec) == 240
     assert re.search(r"#define MWRT_OE_NFORM_MAX_N %d\b" % _native.OE_NFORM_MAX_N, header) and _native.OE_NFORM_MAX_N == 128
     # the record in the header, field by field and in order, is the ctypes mirror; every pointer 8 bytes after the last
-    body = re.search(r"typedef struct mwrt_oe_nform \{(.*?)\} mwrt_oe_nform;", header, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = [n for decl in body.split(";") for n in re.findall(r"\*?\s*(\w+)(?:\[\d+\])?\s*(?:,|$)", decl.strip())]
-    assert names == [f[0] for f in rec._fields_], names
-    assert [getattr(rec, n).offset for n in names[:6]] == [0, 4, 8, 12, 16, 24]
-    assert [getattr(rec, n).offset for n in names[6:]] == list(range(56, 240, 8))
+    check_record(native_lib, "mwrt_oe_nform", rec, 240, offsets=[0, 4, 8, 12, 16, 24] + list(range(56, 240, 8)))
     assert native_lib.mwrt_version() == 301
     # the unit is in the build recipe, its entries in the host unit that holds no device code
     assert (build.NFORM, []) in build.UNITS and len(build.HOST_UNITS) == 2

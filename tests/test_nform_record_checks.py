@@ -1,17 +1,14 @@
-"""The argument stage of the n-form entries (csrc/mwrt_records.cpp oe_nform_args) without a GPU: tests/nform_record_dump.cpp
-links it as is, built with the host C++ compiler under ASan + UBSan and run as a child process -- the pattern, and the
-helpers, of tests/test_record_checks.py.  The record is built from the ctypes mirror of _native.py, so the mirror and the C
-struct are held against each other too.  Pointer fields hold small distinct integers; nothing dereferences them."""
+"""The argument stage of the n-form entries (csrc/mwrt_records.cpp oe_nform_args) without a GPU: tests/record_dump.cpp links
+it as is, built with the host C++ compiler under ASan + UBSan and run as a child process (tests/record_kit.py: the fixture
+and the helpers; the cut of the record at every struct_size is held with the other records' by tests/test_record_checks.py).
+The record is built from the ctypes mirror of _native.py, so the mirror and the C struct are held against each other too.
+Pointer fields hold small distinct integers; nothing dereferences them."""
 import ctypes
-import json
-import os
-import shutil
-import subprocess
 
 import pytest
 
 from mwr_fast_forward_operators_and_lbls_amd import _native
-from test_record_checks import CSRC, INVALID, OK, ROOT, UNSUPPORTED, leaves, line, put, record, run
+from record_kit import INVALID, OK, UNSUPPORTED, line, record, record_dump, run      # noqa: F401 (record_dump: the fixture)
 
 CLS = _native.MwrtOeNform
 MINIMUM = 24                                         # the fixed part (through reserved, with its padding)
@@ -31,24 +28,6 @@ ENTRIES = {
 DIAGNOSTICS = ("d_chi2", "d_dfs", "d_post_var", "d_post_cov")
 
 
-@pytest.fixture(scope="module")
-def nform_dump(tmp_path_factory):
-    """ask(request lines) -> one parsed JSON answer per line.  A sanitiser report ends the child with a non-zero status."""
-    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    exe = str(tmp_path_factory.mktemp("nform_record_dump") / "nform_record_dump")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    os.path.join(ROOT, "tests", "nform_record_dump.cpp"), os.path.join(CSRC, "mwrt_records.cpp"), "-o", exe], check=True)
-
-    def ask(lines):
-        r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True)
-        assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-4000:])
-        out = [json.loads(x) for x in r.stdout.splitlines()]
-        assert len(out) == len(lines)
-        return out
-    return ask
-
-
 def rec(gamma=False, **kw):
     """A record the three entries accept: every pointer given but d_gamma, which excludes the diagnostics."""
     return record(CLS, **dict({} if gamma else {"d_gamma": None}, **kw))
@@ -59,32 +38,8 @@ def test_the_mirror_is_the_record():
     assert [name for name, _ in CLS._fields_[:5]] == ["struct_size", "nblk", "xa_per_profile", "se_per_profile", "reserved"]
 
 
-def test_the_cut_at_every_struct_size(nform_dump):
-    """Every struct_size from 0 to sizeof + 8 with every field non-zero: below the documented minimum it is refused; from
-    there on a field comes through if and only if it lies wholly below min(struct_size, sizeof), every other byte is zero.
-    The child owns exactly struct_size bytes."""
-    size = ctypes.sizeof(CLS)
-    full = CLS()
-    for k, (field, index, _, width) in enumerate(leaves(CLS)):
-        put(full, field, index, (k + 1) * 0x0101 + (0x01010000 << 8 if width == 8 else 0))
-    full = bytes(full) + b"\xab" * 8
-    assert all(full[off:off + width].count(0) < width for _, _, off, width in leaves(CLS))
-    asked, want = [], []
-    for struct_size in range(size + 9):
-        caller = struct_size.to_bytes(4, "little") + full[4:max(struct_size, 4)]
-        asked.append(f"cut {caller.hex()}")
-        expect = bytearray(size)
-        for _, _, off, width in leaves(CLS):
-            if struct_size >= MINIMUM and off + width <= min(struct_size, size):
-                expect[off:off + width] = caller[off:off + width]
-        want.append((struct_size, OK if struct_size >= MINIMUM else INVALID, bytes(expect).hex()))
-    assert len(asked) == 249
-    for (struct_size, status, expect), got in zip(want, nform_dump(asked)):
-        assert (got["status"], got["record"]) == (status, expect), struct_size
-
-
 @pytest.mark.parametrize("entry", sorted(ENTRIES))
-def test_refusals_their_messages_and_their_order(nform_dump, entry):
+def test_refusals_their_messages_and_their_order(record_dump, entry):
     required, optional = (s.split() for s in ENTRIES[entry])
     cases = [
         (line(entry, 3, 2, 3, rec()), OK, None, rec()),
@@ -139,4 +94,4 @@ def test_refusals_their_messages_and_their_order(nform_dump, entry):
         ]
     else:                                                                            # d_gamma and the diagnostics: not looked at
         cases.append((line(entry, 1, 2, 3, rec(gamma=True)), OK, None))
-    run(nform_dump, cases)
+    run(record_dump, cases)

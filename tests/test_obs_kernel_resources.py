@@ -4,34 +4,17 @@ cross-compiled for gfx950 with the library's flags; the inventory of mwrt::obs k
 import ctypes
 import os
 import re
-import subprocess
 
+from kernel_unit import MWRT_H, check_record, library_kernels, resource_usage
 from mwr_fast_forward_operators_and_lbls_amd import _native, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMESPACE = "obs"            # the kernels live in mwrt::obs
 KERNELS = {"k_obs_apply"}
 SYMBOLS = ("mwrt_obs_create", "mwrt_obs_destroy", "mwrt_obs_apply_device", "mwrt_obs_apply_size")
 
 
-def resource_usage(tmp_path):
-    cmd = [build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
-           "-Rpass-analysis=kernel-resource-usage", "-c", build.OBS, "-o", str(tmp_path / "obs.o")]
-    text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-    out, name = {}, None
-    for line in text.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            s = re.search(r"\d+(k_obs_\w+?)E", m.group(1))
-            name = s.group(1) if s else m.group(1)
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name is not None:
-            out.setdefault(name, {})[m.group(1).split(" ")[0]] = int(m.group(2))
-    return out
-
-
-def test_obs_kernel_streams_from_registers_alone(tmp_path):
-    use = resource_usage(tmp_path)
+def test_obs_kernel_streams_from_registers_alone():
+    use = resource_usage(build.OBS)
     assert set(use) == KERNELS, use                                      # the unit holds this kernel and no other
     u = use["k_obs_apply"]
     assert u["ScratchSize"] == 0 and u["AGPRs"] == 0, u
@@ -41,17 +24,7 @@ def test_obs_kernel_streams_from_registers_alone(tmp_path):
 
 
 def test_library_holds_exactly_the_obs_kernel(native_lib):
-    out = subprocess.run(["nm", "-C", "--defined-only", _native.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    found = set()
-    for line in out.splitlines():
-        if "__device_stub__" in line:
-            continue
-        m = re.search(r"mwrt::obs::(?:\(anonymous namespace\)::)?(k_\w+(?:<[^>()]*>)?)\(", line)
-        if m:
-            found.add(m.group(1))
-    assert found == KERNELS, found
-    # and nothing of the unit leaks into the inventories the other tests pin
-    assert not re.search(r"mwrt::(?:oe::|lm::|oec::)?(?:\(anonymous namespace\)::)?k_obs", out)
+    assert library_kernels(_native.LIB_PATH)[NAMESPACE] == KERNELS
 
 
 def test_host_unit_carries_no_obs_device_code():
@@ -64,16 +37,12 @@ def test_host_unit_carries_no_obs_device_code():
 
 
 def test_abi_surface_of_the_instrument_operator(native_lib):
-    header = open(os.path.join(ROOT, "include", "mwrt.h")).read()
+    header = open(MWRT_H).read()
     for sym in SYMBOLS:
         assert re.search(r"\b%s\s*\(" % sym, header) and sym in _native.SIGNATURES and hasattr(native_lib, sym), sym
     rec = _native.MwrtObsApply
-    assert native_lib.mwrt_obs_apply_size() == ctypes.sizeof(rec) == 96
-    # the record in the header, field by field and in order, is the ctypes mirror
-    body = re.search(r"typedef struct mwrt_obs_apply \{(.*?)\} mwrt_obs_apply;", header, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = [n for decl in body.split(";") for n in re.findall(r"\*?\s*(\w+)(?:\[\d+\])?\s*(?:,|$)", decl.strip())]
-    assert names == [f[0] for f in rec._fields_] == ["struct_size", "nblk", "reserved", "d_tb_in", "d_tb_out", "d_k_in", "d_k_out"]
+    check_record(native_lib, "mwrt_obs_apply", rec, 96,
+                 names=["struct_size", "nblk", "reserved", "d_tb_in", "d_tb_out", "d_k_in", "d_k_out"])
     kinds = {f[0]: f[1] for f in rec._fields_}
     assert kinds["struct_size"] is ctypes.c_uint32 and kinds["nblk"] is ctypes.c_int32 and kinds["reserved"] is ctypes.c_int32
     assert kinds["d_tb_in"] is ctypes.c_void_p and kinds["d_tb_out"] is ctypes.c_void_p

@@ -4,45 +4,27 @@ and the new ABI surface -- declared, exported, bound, and one record layout on b
 import ctypes
 import os
 import re
-import subprocess
 
+from kernel_unit import MWRT_H, check_record, library_kernels, resource_usage
 from mwr_fast_forward_operators_and_lbls_amd import _native, build
 from test_oe_kernel_resources import BUDGET
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
+NAMESPACE = "oec"            # the kernels live in mwrt::oec
 # k_char_gain<MR> is steps 1-4 and 7 of k_oe_step<MR> with one more triangular product: it is held to that kernel's VGPR
 # and occupancy budget
 KERNELS = {f"k_char_gain<{mr}>" for mr in BUDGET} | {"k_char_product"}
 
 
-def resource_usage(tmp_path):
-    cmd = [build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
-           "-Rpass-analysis=kernel-resource-usage", "-c", build.OE_CHAR, "-o", str(tmp_path / "oe_char.o")]
-    text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-    out, name = {}, None
-    for line in text.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            k = re.search(r"k_char_gainILi(\d+)E", m.group(1))
-            s = re.search(r"\d+(k_char_product)E", m.group(1))
-            name = int(k.group(1)) if k else s.group(1) if s else m.group(1)
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name is not None:
-            out.setdefault(name, {})[m.group(1).split(" ")[0]] = int(m.group(2))
-    return out
-
-
-def test_char_kernels_keep_their_register_budget(tmp_path):
-    use = resource_usage(tmp_path)
-    assert set(use) == set(BUDGET) | {"k_char_product"}, use             # every kernel of the unit is one of the two
+def test_char_kernels_keep_their_register_budget():
+    use = resource_usage(build.OE_CHAR)
+    assert set(use) == KERNELS, use                                      # every kernel of the unit is one of the two
     for name, u in use.items():
         assert u["ScratchSize"] == 0, (name, u)
         assert u["AGPRs"] == 0, (name, u)                                # the register cap spills nowhere, AGPRs included
         assert u["LDS"] <= 256, (name, u)                                # static LDS: nothing but the dynamic block's stub
     for mr, (vgprs, waves) in BUDGET.items():
-        assert use[mr]["VGPRs"] <= vgprs and use[mr]["Occupancy"] >= waves, (mr, use[mr])
+        u = use[f"k_char_gain<{mr}>"]
+        assert u["VGPRs"] <= vgprs and u["Occupancy"] >= waves, (mr, u)
     # the product keeps two workgroups (8 waves) per CU resident at least: registers must allow it
     assert use["k_char_product"]["Occupancy"] >= 2, use
 
@@ -69,30 +51,15 @@ def test_lds_plan_fits_and_is_aligned():
 
 
 def test_library_holds_exactly_the_char_kernels(native_lib):
-    out = subprocess.run(["nm", "-C", "--defined-only", _native.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    found = set()
-    for line in out.splitlines():
-        if "__device_stub__" in line:
-            continue
-        m = re.search(r"mwrt::oec::(?:\(anonymous namespace\)::)?(k_\w+(?:<[^>()]*>)?)\(", line)
-        if m:
-            found.add(m.group(1))
-    assert found == KERNELS, found
-    # and nothing of the unit leaks into the inventories the other tests pin
-    assert not re.search(r"mwrt::(?:oe::|lm::)?(?:\(anonymous namespace\)::)?k_char", out)
+    assert library_kernels(_native.LIB_PATH)[NAMESPACE] == KERNELS
 
 
 def test_abi_surface_of_the_characterisation(native_lib):
-    header = open(os.path.join(ROOT, "include", "mwrt.h")).read()
+    header = open(MWRT_H).read()
     for sym in ("mwrt_oe_gain_device", "mwrt_oe_product_device", "mwrt_oe_char_size"):
         assert re.search(r"\b%s\s*\(" % sym, header) and sym in _native.SIGNATURES and hasattr(native_lib, sym), sym
     rec = _native.MwrtOeChar
-    assert native_lib.mwrt_oe_char_size() == ctypes.sizeof(rec) == 200
-    # the record in the header, field by field and in order, is the ctypes mirror
-    body = re.search(r"typedef struct mwrt_oe_char \{(.*?)\} mwrt_oe_char;", header, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = [n for decl in body.split(";") for n in re.findall(r"\*?\s*(\w+)(?:\[\d+\])?\s*(?:,|$)", decl.strip())]
-    assert names == [f[0] for f in rec._fields_], names
+    names = check_record(native_lib, "mwrt_oe_char", rec, 200)
     kinds = {f[0]: f[1] for f in rec._fields_}
     assert all(kinds[k] is ctypes.c_int32 for k in ("product", "row_begin", "row_count", "reserved2", "nblk", "reserved"))
     assert all(kinds[k] is ctypes.c_void_p for k in names if k.startswith("d_") and k != "d_k")

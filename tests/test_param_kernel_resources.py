@@ -4,34 +4,17 @@ ABI surface -- declared, exported, bound, and the record laid out alike on both 
 import ctypes
 import os
 import re
-import subprocess
 
+from kernel_unit import MWRT_H, library_kernels, resource_usage
 from mwr_fast_forward_operators_and_lbls_amd import _native, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMESPACE = "par"            # the kernels live in mwrt::par
 KERNELS = {"k_par_tangent", "k_par_contract"}
 SYMBOLS = ("mwrt_tb_param_jacobian_batch_device", "mwrt_tb_param_jacobian_batch")
 
 
-def resource_usage(tmp_path):
-    cmd = [build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
-           "-Rpass-analysis=kernel-resource-usage", "-c", build.PAR, "-o", str(tmp_path / "par.o")]
-    text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-    out, name = {}, None
-    for line in text.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            s = re.search(r"\d+(k_par_\w+?)E", m.group(1))
-            name = s.group(1) if s else m.group(1)
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name is not None:
-            out.setdefault(name, {})[m.group(1).split(" ")[0]] = int(m.group(2))
-    return out
-
-
-def test_parameter_kernels_keep_their_register_budget(tmp_path):
-    use = resource_usage(tmp_path)
+def test_parameter_kernels_keep_their_register_budget():
+    use = resource_usage(build.PAR)
     assert set(use) == KERNELS, use                                      # the unit holds these kernels and no others
     for u in use.values():
         assert u["ScratchSize"] == 0 and u["AGPRs"] == 0, use
@@ -44,17 +27,7 @@ def test_parameter_kernels_keep_their_register_budget(tmp_path):
 
 
 def test_library_holds_exactly_the_parameter_kernels(native_lib):
-    out = subprocess.run(["nm", "-C", "--defined-only", _native.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    found = set()
-    for line in out.splitlines():
-        if "__device_stub__" in line:
-            continue
-        m = re.search(r"mwrt::par::(?:\(anonymous namespace\)::)?(k_\w+(?:<[^>()]*>)?)\(", line)
-        if m:
-            found.add(m.group(1))
-    assert found == KERNELS, found
-    # and nothing of the unit leaks into the inventories the other tests pin
-    assert not re.search(r"mwrt::(?:oe::|lm::|oec::|obs::)?(?:\(anonymous namespace\)::)?k_par", out)
+    assert library_kernels(_native.LIB_PATH)[NAMESPACE] == KERNELS
 
 
 def test_host_unit_carries_no_parameter_device_code():
@@ -74,7 +47,7 @@ def test_host_unit_carries_no_parameter_device_code():
 
 
 def test_abi_surface_of_the_parameter_jacobian(native_lib):
-    header = open(os.path.join(ROOT, "include", "mwrt.h")).read()
+    header = open(MWRT_H).read()
     for sym in SYMBOLS:
         assert re.search(r"\b%s\s*\(" % sym, header) and sym in _native.SIGNATURES and hasattr(native_lib, sym), sym
     rec = _native.MwrtParam

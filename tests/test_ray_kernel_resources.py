@@ -4,38 +4,21 @@ ABI surface -- declared, exported, bound, in the build recipe."""
 import inspect
 import os
 import re
-import subprocess
 
+from kernel_unit import MWRT_H, library_kernels, resource_usage
 from mwr_fast_forward_operators_and_lbls_amd import _native, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMESPACE = "ray"            # the kernels live in mwrt::ray
 KERNELS = {"k_ray_paths_tl", "k_jac_rte_ray"}
 SYMBOLS = ("mwrt_tb_jacobian_batch_ray_device", "mwrt_tb_jacobian_batch_ray")
 
 
-def resource_usage(tmp_path):
-    cmd = [build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
-           "-Rpass-analysis=kernel-resource-usage", "-c", build.RAY, "-o", str(tmp_path / "ray.o")]
-    text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-    out, name = {}, None
-    for line in text.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            s = re.search(r"\d+(k_\w+?)ENS", m.group(1))
-            name = s.group(1) if s else m.group(1)
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name is not None:
-            out.setdefault(name, {})[m.group(1).split(" ")[0]] = int(m.group(2))
-    return out
-
-
-def test_ray_kernels_keep_what_they_achieved(tmp_path):
+def test_ray_kernels_keep_what_they_achieved():
     """What the compiler gives today, as bounds (the same figures stand in DESIGN 4.5.4).  k_jac_rte_ray is the loop that
     runs per (profile, frequency): no scratch, four waves per SIMD (a 1024-lane workgroup's ceiling is 128 VGPRs).
     k_ray_paths_tl runs once per profile and carries a five-direction tangent through the ray tracer: it sits at that
     ceiling and spills."""
-    use = resource_usage(tmp_path)
+    use = resource_usage(build.RAY)
     assert set(use) == KERNELS, use
     rte, path = use["k_jac_rte_ray"], use["k_ray_paths_tl"]
     assert rte["ScratchSize"] == 0 and rte["VGPRs"] <= 105 and rte["Occupancy"] >= 4, rte
@@ -45,17 +28,7 @@ def test_ray_kernels_keep_what_they_achieved(tmp_path):
 
 
 def test_library_holds_exactly_the_ray_kernels(native_lib):
-    out = subprocess.run(["nm", "-C", "--defined-only", _native.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    found = set()
-    for line in out.splitlines():
-        if "__device_stub__" in line:
-            continue
-        m = re.search(r"mwrt::ray::(?:\(anonymous namespace\)::)?(k_\w+(?:<[^>()]*>)?)\(", line)
-        if m:
-            found.add(m.group(1))
-    assert found == KERNELS, found
-    # and nothing of the unit leaks into the inventory tests/test_kernel_instantiations.py pins
-    assert not re.search(r"mwrt::(?:\(anonymous namespace\)::)?k_(?:ray_paths_tl|jac_rte_ray)", out)
+    assert library_kernels(_native.LIB_PATH)[NAMESPACE] == KERNELS
 
 
 def test_unit_layout_and_build_recipe():
@@ -71,7 +44,7 @@ def test_unit_layout_and_build_recipe():
 
 
 def test_abi_surface_of_the_ray_entries(native_lib):
-    header = open(os.path.join(ROOT, "include", "mwrt.h")).read()
+    header = open(MWRT_H).read()
     for s in SYMBOLS:
         assert re.search(r"\bint %s\(" % s, header) and hasattr(native_lib, s) and s in _native.SIGNATURES, s
     assert native_lib.mwrt_version() == 301 == _native.MWRT_VERSION

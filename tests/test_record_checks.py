@@ -1,20 +1,15 @@
 """The argument stage of the record entries (csrc/mwrt_records.cpp) without a GPU: tests/record_dump.cpp links it as is,
-built with the host C++ compiler under ASan + UBSan and run as a child process.  The records are built from the ctypes
-mirrors of _native.py, so the mirrors and the C structs are held against each other too.  Pointer fields hold small
-distinct integers; nothing dereferences them."""
+built with the host C++ compiler under ASan + UBSan and run as a child process (tests/record_kit.py: the fixture and the
+helpers).  The cut of all nine records is held here; the entries of the three newest have modules of their own.  The
+records are built from the ctypes mirrors of _native.py, so the mirrors and the C structs are held against each other too.
+Pointer fields hold small distinct integers; nothing dereferences them."""
 import ctypes
-import json
-import os
-import shutil
-import subprocess
 
 import pytest
 
 from mwr_fast_forward_operators_and_lbls_amd import _native
+from record_kit import INVALID, OK, UNSUPPORTED, leaves, line, put, record, record_dump, run      # noqa: F401 (the fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mwr_fast_forward_operators_and_lbls_amd", "csrc")
-OK, INVALID, UNSUPPORTED = 0, -1, -5                 # include/mwrt.h mwrt_status
 MAX_LEVELS, MAX_M = 1024, 140                        # MWRT_MAX_LEVELS, MWRT_OE_MAX_M
 
 #: record -> (ctypes mirror, documented minimum struct_size: include/mwrt.h)
@@ -25,100 +20,40 @@ RECORDS = {
     "mwrt_obs_apply": (_native.MwrtObsApply, 12),
     "mwrt_basis_apply": (_native.MwrtBasisApply, 8),
     "mwrt_obs_whiten": (_native.MwrtObsWhiten, 24),
+    "mwrt_oe_nform": (_native.MwrtOeNform, 24),      # these three: the fixed part (through reserved, with its padding)
+    "mwrt_oe_nform_char": (_native.MwrtOeNformChar, 24),
+    "mwrt_oe_select": (_native.MwrtOeSelect, 24),
 }
+#: sizeof + 9 requests each: struct_size 0 .. sizeof + 8
+CUT_REQUESTS = {"mwrt_oe_step": 161, "mwrt_oe_lm": 233, "mwrt_oe_char": 209, "mwrt_obs_apply": 105, "mwrt_basis_apply": 89,
+                "mwrt_obs_whiten": 161, "mwrt_oe_nform": 249, "mwrt_oe_nform_char": 177, "mwrt_oe_select": 185}
 
 
-@pytest.fixture(scope="module")
-def record_dump(tmp_path_factory):
-    """ask(request lines) -> one parsed JSON answer per line.  A sanitiser report ends the child with a non-zero status."""
-    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    exe = str(tmp_path_factory.mktemp("record_dump") / "record_dump")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    os.path.join(ROOT, "tests", "record_dump.cpp"), os.path.join(CSRC, "mwrt_records.cpp"), "-o", exe], check=True)
-
-    def ask(lines):
-        r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True)
-        assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-4000:])
-        out = [json.loads(x) for x in r.stdout.splitlines()]
-        assert len(out) == len(lines)
-        return out
-    return ask
-
-
-def leaves(cls):
-    """(name, element index or None, offset, size) of every field, an array counted element by element."""
-    out = []
-    for name, kind in cls._fields_:
-        off = getattr(cls, name).offset
-        if issubclass(kind, ctypes.Array):
-            out += [(name, i, off + i * ctypes.sizeof(kind._type_), ctypes.sizeof(kind._type_)) for i in range(kind._length_)]
-        else:
-            out.append((name, None, off, ctypes.sizeof(kind)))
-    return out
-
-
-def put(rec, name, index, value):
-    if index is None:
-        setattr(rec, name, value)
-    else:
-        getattr(rec, name)[index] = value
-
-
-def record(cls, struct_size=None, **fields):
-    """A record every entry of its family accepts: every pointer given and distinct (0x1000 + its offset), every integer 0
-    but nblk = 1, struct_size = sizeof; then `fields` (an array element as name_i=value, None for a NULL pointer)."""
-    rec = cls()
-    for name, index, off, _ in leaves(cls):
-        if name.startswith("d_"):
-            put(rec, name, index, 0x1000 + off)
-    rec.struct_size = ctypes.sizeof(cls) if struct_size is None else struct_size
-    if hasattr(rec, "nblk"):
-        rec.nblk = 1
-    for key, value in fields.items():
-        name, _, index = key.rpartition("_") if key[-1].isdigit() and key[-2] == "_" else (key, "", None)
-        put(rec, name, None if index is None else int(index), value)
-    return rec
-
-
-def line(entry, *scalars_and_record):
-    *scalars, rec = scalars_and_record
-    return " ".join([entry, *map(str, scalars), bytes(rec).hex()])
-
-
-def test_the_cut_at_every_struct_size(record_dump):
-    """Every record at every struct_size from 0 to sizeof + 8 with every field non-zero: below the documented minimum it is
+@pytest.mark.parametrize("name", sorted(RECORDS))
+def test_the_cut_at_every_struct_size(record_dump, name):
+    """The record at every struct_size from 0 to sizeof + 8 with every field non-zero: below the documented minimum it is
     refused; from there on a field comes through if and only if it lies wholly below min(struct_size, sizeof), every other
-    byte is zero.  The expectation is built from the ctypes offsets and sizes.  The child owns exactly struct_size bytes."""
+    byte is zero (a field beyond the cut reads as NULL / 0).  The expectation is built from the ctypes offsets and sizes.
+    The child owns exactly struct_size bytes."""
+    cls, minimum = RECORDS[name]
+    size = ctypes.sizeof(cls)
+    rec = cls()
+    for k, (field, index, _, width) in enumerate(leaves(cls)):
+        put(rec, field, index, (k + 1) * 0x0101 + (0x01010000 << 8 if width == 8 else 0))
+    full = bytes(rec) + b"\xab" * 8
+    assert all(full[off:off + width].count(0) < width for _, _, off, width in leaves(cls))
     asked, want = [], []
-    for name, (cls, minimum) in RECORDS.items():
-        size = ctypes.sizeof(cls)
-        rec = cls()
-        for k, (field, index, _, width) in enumerate(leaves(cls)):
-            put(rec, field, index, (k + 1) * 0x0101 + (0x01010000 << 8 if width == 8 else 0))
-        full = bytes(rec) + b"\xab" * 8
-        assert all(full[off:off + width].count(0) < width for _, _, off, width in leaves(cls))
-        for struct_size in range(size + 9):
-            caller = struct_size.to_bytes(4, "little") + full[4:max(struct_size, 4)]
-            asked.append(f"cut {name} {caller.hex()}")
-            expect = bytearray(size)
-            for _, _, off, width in leaves(cls):
-                if struct_size >= minimum and off + width <= min(struct_size, size):
-                    expect[off:off + width] = caller[off:off + width]
-            want.append((name, struct_size, OK if struct_size >= minimum else INVALID, bytes(expect).hex()))
-    assert len(asked) > 900
-    for (name, struct_size, status, expect), got in zip(want, record_dump(asked)):
-        assert (got["status"], got["record"]) == (status, expect), (name, struct_size)
-
-
-def run(record_dump, cases):
-    """cases: (request line, status, message or None for 'accepted'[, record that comes out])"""
-    got = record_dump([c[0] for c in cases])
-    for case, g in zip(cases, got):
-        request, status, message = case[:3]
-        assert (g["status"], g["message"]) == (status, message or ""), request[:60]
-        if len(case) > 3:
-            assert g["record"] == bytes(case[3]).hex(), request[:60]
+    for struct_size in range(size + 9):
+        caller = struct_size.to_bytes(4, "little") + full[4:max(struct_size, 4)]
+        asked.append(f"cut {name} {caller.hex()}")
+        expect = bytearray(size)
+        for _, _, off, width in leaves(cls):
+            if struct_size >= minimum and off + width <= min(struct_size, size):
+                expect[off:off + width] = caller[off:off + width]
+        want.append((struct_size, OK if struct_size >= minimum else INVALID, bytes(expect).hex()))
+    assert len(asked) == CUT_REQUESTS[name] == size + 9 and sorted(CUT_REQUESTS) == sorted(RECORDS)
+    for (struct_size, status, expect), got in zip(want, record_dump(asked)):
+        assert (got["status"], got["record"]) == (status, expect), struct_size
 
 
 NLEV_LIMIT = "nlev > MWRT_MAX_LEVELS (1024)"

@@ -5,15 +5,15 @@ record layout on both sides; and the guard of the GPU tests' shape list against 
 import ctypes
 import os
 import re
-import subprocess
 
+from kernel_unit import MWRT_H, check_record, library_kernels, plan_rows, resource_usage
 from mwr_fast_forward_operators_and_lbls_amd import _native, build
 
 import select_reference as sr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(build.CSRC, "mwrt_select.hip.h")
 SYMBOLS = ("mwrt_oe_select_device", "mwrt_oe_select_size")
+NAMESPACE = "sel"            # the kernels live in mwrt::sel
 KERNELS = {"k_sel_select"}
 # (VGPRs at most, waves per SIMD at least), from the remark of the build this test was written against (110 VGPRs, rounded up
 # to a multiple of 8; occupancy as shown).  One workgroup is four waves, one per SIMD, so four waves per SIMD let four
@@ -35,20 +35,8 @@ def lds_bytes(n, c):
     return 8 * (even(n * (n + 1) // 2) + 3 * even(n) + c["WAVES"] + c["WAVES"])
 
 
-def test_the_kernel_keeps_its_register_budget(tmp_path):
-    cmd = [build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
-           "-Rpass-analysis=kernel-resource-usage", "-c", build.SELECT, "-o", str(tmp_path / "select.o")]
-    text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-    use, name = {}, None
-    for line in text.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            s = re.search(r"\d+(k_sel_\w+?)E", m.group(1))
-            name = s.group(1) if s else m.group(1)
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name is not None:
-            use.setdefault(name, {})[m.group(1).split(" ")[0]] = int(m.group(2))
+def test_the_kernel_keeps_its_register_budget():
+    use = resource_usage(build.SELECT)
     assert set(use) == KERNELS, use
     for name, u in use.items():
         assert u["ScratchSize"] == 0 and u["AGPRs"] == 0, (name, u)
@@ -62,15 +50,9 @@ def test_the_lds_plan_follows_its_formula(tmp_path):
     hipcc and held against the formula of DESIGN 4.12, written out again from the constants."""
     c = constants()
     assert c == dict(THREADS=256, WAVES=4)
-    src = tmp_path / "plans.hip"
-    src.write_text('#include <cstdio>\n#include "%s"\nint main() {\n  for (int n = 1; n <= MWRT_OE_NFORM_MAX_N; ++n) {\n'
-                   '    const mwrt::sel::SelPlan p = mwrt::sel::sel_plan(n);\n'
-                   '    std::printf("%%d %%zu %%zu %%zu %%zu %%zu %%zu %%d\\n", n, p.total_bytes, p.v, p.u, p.kj, p.best, p.ints,\n'
-                   '                mwrt::sel::cols_per_lane(n));\n  }\n  return 0;\n}\n' % HEADER)
-    exe = str(tmp_path / "plans")
-    subprocess.run([build.hipcc_path(), "--offload-arch=gfx950", "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                    str(src), "-o", exe], check=True, capture_output=True)
-    rows = [tuple(map(int, ln.split())) for ln in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines()]
+    rows = plan_rows(HEADER, '    const mwrt::sel::SelPlan p = mwrt::sel::sel_plan(n);\n'
+                             '    std::printf("%d %zu %zu %zu %zu %zu %zu %d\\n", n, p.total_bytes, p.v, p.u, p.kj, p.best, p.ints,\n'
+                             '                mwrt::sel::cols_per_lane(n));', tmp_path)
     assert [r[0] for r in rows] == list(range(1, _native.OE_NFORM_MAX_N + 1))
     for n, total, v, u, kj, best, ints, cpl in rows:
         nte, np_ = (n * (n + 1) // 2 + 1) & ~1, (n + 1) & ~1
@@ -82,34 +64,18 @@ def test_the_lds_plan_follows_its_formula(tmp_path):
 
 
 def test_library_holds_exactly_the_select_kernels(native_lib):
-    out = subprocess.run(["nm", "-C", "--defined-only", _native.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    found = set()
-    for line in out.splitlines():
-        if "__device_stub__" in line:
-            continue
-        m = re.search(r"mwrt::sel::(?:\(anonymous namespace\)::)?(k_\w+(?:<[^>()]*>)?)\(", line)
-        if m:
-            found.add(m.group(1))
-    assert found == KERNELS, found
-    # and nothing of the unit leaks into the inventories the other tests pin: no k_sel_ outside mwrt::sel, none directly in mwrt
-    assert not re.search(r"mwrt::(?:oe::|lm::|nf::|nfc::|oec::|basis::)?(?:\(anonymous namespace\)::)?k_sel_", out)
+    assert library_kernels(_native.LIB_PATH)[NAMESPACE] == KERNELS
     assert all(name.startswith("k_sel_") for name in KERNELS)
 
 
 def test_abi_surface_of_the_selection(native_lib):
-    header = open(os.path.join(ROOT, "include", "mwrt.h")).read()
+    header = open(MWRT_H).read()
     for sym in SYMBOLS:
         assert re.search(r"\b%s\s*\(" % sym, header) and sym in _native.SIGNATURES and hasattr(native_lib, sym), sym
     rec = _native.MwrtOeSelect
-    assert native_lib.mwrt_oe_select_size() == ctypes.sizeof(rec) == 176
     assert ("mwrt_oe_select", rec, "_native.py") in _native._RECORD_SIZES
     # the record in the header, field by field and in order, is the ctypes mirror; every pointer 8 bytes after the last
-    body = re.search(r"typedef struct mwrt_oe_select \{(.*?)\} mwrt_oe_select;", header, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = [n for decl in body.split(";") for n in re.findall(r"\*?\s*(\w+)(?:\[\d+\])?\s*(?:,|$)", decl.strip())]
-    assert names == [f[0] for f in rec._fields_], names
-    assert [getattr(rec, n).offset for n in names[:7]] == [0, 4, 8, 12, 16, 20, 24]
-    assert [getattr(rec, n).offset for n in names[7:]] == list(range(56, 176, 8))
+    check_record(native_lib, "mwrt_oe_select", rec, 176, offsets=[0, 4, 8, 12, 16, 20, 24] + list(range(56, 176, 8)))
     assert native_lib.mwrt_version() == 301
     # the unit is in the build recipe, its entry in the host unit that holds no device code
     assert (build.SELECT, []) in build.UNITS and len(build.HOST_UNITS) == 2

@@ -1,18 +1,12 @@
 """The argument stage of the observation selection (csrc/mwrt_records.cpp oe_select_args) without a GPU:
-tests/select_record_dump.cpp links it as is, built with the host C++ compiler under ASan + UBSan and run as a child process
--- the pattern, and the helpers, of tests/test_record_checks.py and tests/test_nform_char_record_checks.py.  The record is
-built from the ctypes mirror of _native.py, so the mirror and the C struct are held against each other too.  Pointer fields
-hold small distinct integers; nothing dereferences them."""
+tests/record_dump.cpp links it as is, built with the host C++ compiler under ASan + UBSan and run as a child process
+(tests/record_kit.py: the fixture and the helpers; the cut of the record at every struct_size is held with the other
+records' by tests/test_record_checks.py).  The record is built from the ctypes mirror of _native.py, so the mirror and the C
+struct are held against each other too.  Pointer fields hold small distinct integers; nothing dereferences them."""
 import ctypes
-import json
-import os
-import shutil
-import subprocess
-
-import pytest
 
 from mwr_fast_forward_operators_and_lbls_amd import _native
-from test_record_checks import CSRC, INVALID, OK, ROOT, UNSUPPORTED, leaves, line, put, record, run
+from record_kit import INVALID, OK, UNSUPPORTED, line, record, record_dump, run      # noqa: F401 (record_dump: the fixture)
 
 CLS = _native.MwrtOeSelect
 MINIMUM = 24                                         # the fixed part (through reserved)
@@ -29,25 +23,6 @@ REQUIRED = "d_k_0 d_s0 d_se d_order d_q_pick d_rank d_q d_count d_status".split(
 OPTIONAL = "d_keep d_candidate d_active d_dfs_gain d_post_cov d_post_var".split()
 INPUTS = "d_s0 d_se d_sa_inv d_keep d_candidate d_active d_k_0".split()
 OUTPUTS = "d_order d_q_pick d_rank d_q d_count d_status d_dfs_gain d_post_cov d_post_var".split()
-
-
-@pytest.fixture(scope="module")
-def select_dump(tmp_path_factory):
-    """ask(request lines) -> one parsed JSON answer per line.  A sanitiser report ends the child with a non-zero status."""
-    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    exe = str(tmp_path_factory.mktemp("select_record_dump") / "select_record_dump")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    os.path.join(ROOT, "tests", "select_record_dump.cpp"), os.path.join(CSRC, "mwrt_records.cpp"), "-o", exe],
-                   check=True)
-
-    def ask(lines):
-        r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True)
-        assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-4000:])
-        out = [json.loads(x) for x in r.stdout.splitlines()]
-        assert len(out) == len(lines)
-        return out
-    return ask
 
 
 def rec(**kw):
@@ -69,31 +44,7 @@ def test_the_mirror_is_the_record():
     assert ctypes.sizeof(_native.MwrtOeNform) == 240 and ctypes.sizeof(_native.MwrtOeNformChar) == 168
 
 
-def test_the_cut_at_every_struct_size(select_dump):
-    """Every struct_size from 0 to sizeof + 8 with every field non-zero: below the documented minimum it is refused; from
-    there on a field comes through if and only if it lies wholly below min(struct_size, sizeof), every other byte is zero
-    (a field beyond the cut reads as NULL / 0).  The child owns exactly struct_size bytes."""
-    size = ctypes.sizeof(CLS)
-    full = CLS()
-    for k, (field, index, _, width) in enumerate(leaves(CLS)):
-        put(full, field, index, (k + 1) * 0x0101 + (0x01010000 << 8 if width == 8 else 0))
-    full = bytes(full) + b"\xab" * 8
-    assert all(full[off:off + width].count(0) < width for _, _, off, width in leaves(CLS))
-    asked, want = [], []
-    for struct_size in range(size + 9):
-        caller = struct_size.to_bytes(4, "little") + full[4:max(struct_size, 4)]
-        asked.append(f"cut {caller.hex()}")
-        expect = bytearray(size)
-        for _, _, off, width in leaves(CLS):
-            if struct_size >= MINIMUM and off + width <= min(struct_size, size):
-                expect[off:off + width] = caller[off:off + width]
-        want.append((struct_size, OK if struct_size >= MINIMUM else INVALID, bytes(expect).hex()))
-    assert len(asked) == 185
-    for (struct_size, status, expect), got in zip(want, select_dump(asked)):
-        assert (got["status"], got["record"]) == (status, expect), struct_size
-
-
-def test_refusals_their_messages_and_their_order(select_dump):
+def test_refusals_their_messages_and_their_order(record_dump):
     e = "select"
     r0 = rec()
     cases = [
@@ -154,4 +105,4 @@ def test_refusals_their_messages_and_their_order(select_dump):
         (line(e, 1, 2, 3, rec(d_q=r0.d_k[1])), OK, None),                                      # beyond nblk
         (line(e, 1, 2, 3, rec(d_post_cov=r0.d_post_var)), OK, None),                           # outputs are not compared
     ]
-    run(select_dump, cases)
+    run(record_dump, cases)

@@ -5,12 +5,12 @@ the plan constants of the header as the code has them."""
 import ctypes
 import os
 import re
-import subprocess
 
 import whiten_reference as whr
+from kernel_unit import MWRT_H, check_record, library_kernels, resource_usage
 from mwr_fast_forward_operators_and_lbls_amd import _native, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMESPACE = "wh"            # the kernels live in mwrt::wh
 KERNELS = {"k_wh_factor", "k_wh_apply"}
 SYMBOLS = ("mwrt_obs_whiten_device", "mwrt_obs_whiten_apply_device", "mwrt_obs_whiten_size")
 HEADER = os.path.join(os.path.dirname(build.WHITEN), "mwrt_whiten.hip.h")
@@ -24,25 +24,8 @@ def plan():
             for name in ("FACTOR_THREADS", "COLS", "ROW_BLOCK", "LOAD_BATCH", "KEEP_WORDS")}
 
 
-def resource_usage(tmp_path):
-    cmd = [build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
-           "-Rpass-analysis=kernel-resource-usage", "-c", build.WHITEN, "-o", str(tmp_path / "whiten.o")]
-    text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-    out, name = {}, None
-    for line in text.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            s = re.search(r"\d+(k_wh_[a-z]+)E", m.group(1))
-            name = s.group(1) if s else m.group(1)
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name is not None:
-            out.setdefault(name, {})[m.group(1).split(" ")[0]] = int(m.group(2))
-    return out
-
-
-def test_whiten_kernels_keep_their_budgets(tmp_path):
-    use = resource_usage(tmp_path)
+def test_whiten_kernels_keep_their_budgets():
+    use = resource_usage(build.WHITEN)
     assert set(use) == KERNELS, use                                      # the unit holds these kernels and no other
     t = plan()
     for u in use.values():
@@ -65,18 +48,7 @@ def test_whiten_kernels_keep_their_budgets(tmp_path):
 
 
 def test_library_holds_exactly_the_whiten_kernels(native_lib):
-    out = subprocess.run(["nm", "-C", "--defined-only", _native.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    found, elsewhere = set(), []
-    for line in out.splitlines():
-        if "__device_stub__" in line:
-            continue
-        m = re.search(r"^\S+ \S (?:mwrt::wh::(?:\(anonymous namespace\)::)?)(k_\w+(?:<[^>()]*>)?)\(", line)
-        if m:
-            found.add(m.group(1))
-        elif re.search(r"^\S+ \S mwrt::(?!wh::)(?:\w+::)*(?:\(anonymous namespace\)::)?k_wh_\w+\(", line):
-            elsewhere.append(line)
-    assert found == KERNELS, found
-    assert not elsewhere, elsewhere                                       # none of the names in another namespace
+    assert library_kernels(_native.LIB_PATH)[NAMESPACE] == KERNELS
 
 
 def test_host_unit_carries_no_whiten_device_code():
@@ -88,23 +60,18 @@ def test_host_unit_carries_no_whiten_device_code():
 
 
 def test_abi_surface_of_the_pre_whitening(native_lib):
-    header = open(os.path.join(ROOT, "include", "mwrt.h")).read()
+    header = open(MWRT_H).read()
     for sym in SYMBOLS:
         assert re.search(r"\b%s\s*\(" % sym, header) and sym in _native.SIGNATURES and hasattr(native_lib, sym), sym
     rec = _native.MwrtObsWhiten
-    assert native_lib.mwrt_obs_whiten_size() == ctypes.sizeof(rec) == 152
-    # the record in the header, field by field and in order, is the ctypes mirror
-    body = re.search(r"typedef struct mwrt_obs_whiten \{(.*?)\} mwrt_obs_whiten;", header, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = [n for decl in body.split(";") for n in re.findall(r"\*?\s*(\w+)(?:\[\d+\])?\s*(?:,|$)", decl.strip())]
-    assert names == [f[0] for f in rec._fields_] == ["struct_size", "nblk", "se_full", "mode", "reserved", "d_se", "d_y", "d_fx",
-                                                     "d_k_in", "d_l", "d_keep", "d_status", "d_y_out", "d_fx_out", "d_k_out"]
+    check_record(native_lib, "mwrt_obs_whiten", rec, 152, offsets=[0, 4, 8, 12, 16, 24, 32, 40, 48, 80, 88, 96, 104, 112, 120],
+                 names=["struct_size", "nblk", "se_full", "mode", "reserved", "d_se", "d_y", "d_fx", "d_k_in", "d_l", "d_keep",
+                        "d_status", "d_y_out", "d_fx_out", "d_k_out"])
     kinds = {f[0]: f[1] for f in rec._fields_}
     assert kinds["struct_size"] is ctypes.c_uint32 and kinds["reserved"] is ctypes.c_int64
     assert all(kinds[k] is ctypes.c_int32 for k in ("nblk", "se_full", "mode"))
     assert all(ctypes.sizeof(kinds[k]) == 4 * ctypes.sizeof(ctypes.c_void_p) for k in ("d_k_in", "d_k_out"))
     assert all(kinds[k] is ctypes.c_void_p for k in ("d_se", "d_y", "d_fx", "d_l", "d_keep", "d_status", "d_y_out", "d_fx_out"))
-    assert [getattr(rec, f[0]).offset for f in rec._fields_] == [0, 4, 8, 12, 16, 24, 32, 40, 48, 80, 88, 96, 104, 112, 120]
     assert native_lib.mwrt_version() == 301 == _native.MWRT_VERSION
     assert (_native.WHITEN_FORWARD, _native.WHITEN_TRANSPOSED) == (0, 1)
 
